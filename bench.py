@@ -9,10 +9,17 @@ by all ranks per second of wall time (barrier + synchronize on both sides, max o
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          one process per GPU (torch.distributed.run for N > 1)
     python bench.py --gpus N --single-process                    one host process driving N devices (shard.ShardedOTW)
+    python bench.py ... --full                                   also cpu_baseline, parity and secondary (below)
+    python bench.py ... --dump-outputs DIR                       write what the last timed step computed to DIR/*.npy
+
+A plain run sets up, warms up, times the steps and prints the line (with roofline, which comes from the timed steps'
+own HIP events).  --dump-outputs DIR writes, after the timed steps, what a caller of the timed path receives for each
+stream of this process (see dump_outputs); the inputs are seeded, so two builds can be compared file for file.
 
 Extra JSON objects (see the task contract):
   roofline      dominant kernel (otw_advance_kernel): algorithmic bytes per launch / mean launch
                 duration from HIP events recorded on the launch stream, against HBM 8 TB/s.
+With --full only:
   cpu_baseline  N = 1 only: timed on this box's host cores on the same streams, before the GPU is touched (the
                 worker processes are forked while the process is still GPU-free): the C port of otw_eran.py's insert
                 loop (oracle/) on 1 core and on all usable cores (one stream per task), and the numpy
@@ -352,6 +359,47 @@ def secondary_gpu(inp, cpu, dev, head_ref, head_lives, head_paths, c, mrc, only=
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6   # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, eng, states, c, first_stream=0, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as float64 arrays
+    out_dir/<name><suffix>.npy, for the streams of this process (eng: BatchedOTW or ShardedOTW, states: its states()):
+      streams       (k,)       global index of every stream written, ascending
+      path_lengths  (k,)       length of its alignment path
+      paths         (sum, 2)   the paths as eng.path(b) returns them, concatenated in the order of `streams`
+      end_state     (k, 10)    t, j, direction, previous, run_count, status, first_insert, n_path, consumed, path_truncated
+      row_band, col_band (k, c + 1)  the accumulated-cost bands of eng.bands(b) (NaN where the index is < 0)
+    Every stream is written while the total stays within DUMP_BUDGET_BYTES (the default batch is ~5 MB); past that, the
+    streams taken are a fixed seeded sample.  Returns {"streams": k, "bytes": total}."""
+    from real_time_audio_sync_amd import _native as nat
+    cols = [nat.ST_T, nat.ST_J, nat.ST_DIRECTION, nat.ST_PREVIOUS, nat.ST_RUN_COUNT, nat.ST_STATUS, nat.ST_FIRST_INSERT,
+            nat.ST_N_PATH, nat.ST_CONSUMED, nat.ST_PATH_TRUNCATED]
+    n = len(states)
+    taken, total = {}, 0
+    for b in np.random.RandomState(0).permutation(n):
+        p = eng.path(int(b))
+        rb, cb = eng.bands(int(b))
+        nbytes = 8 * (p.size + rb.size + cb.size + len(cols) + 2)
+        if total + nbytes > DUMP_BUDGET_BYTES:
+            break
+        taken[int(b)] = (p, rb, cb)
+        total += nbytes
+    order = sorted(taken)
+    arrays = {
+        "streams": np.array([first_stream + b for b in order], dtype=np.float64),
+        "path_lengths": np.array([len(taken[b][0]) for b in order], dtype=np.float64),
+        "paths": np.concatenate([taken[b][0] for b in order] + [np.empty((0, 2))]).astype(np.float64),
+        "end_state": states[order][:, cols].astype(np.float64).reshape(len(order), len(cols)),
+        "row_band": np.array([taken[b][1] for b in order], dtype=np.float64).reshape(len(order), c + 1),
+        "col_band": np.array([taken[b][2] for b in order], dtype=np.float64).reshape(len(order), c + 1),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return {"streams": len(order), "bytes": total}
+
+
 # ------------------------------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -364,12 +412,16 @@ def main():
     ap.add_argument("--max-run-count", type=int, default=3)
     ap.add_argument("--waves", type=int, default=0, help="waves per stream workgroup (0 = library default)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"], help="feature dtype in HBM")
+    ap.add_argument("--full", action="store_true", help="also cpu_baseline, the parity gate and the secondary workloads "
+                    "(a plain run does only the timed headline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/*.npy (see dump_outputs)")
     ap.add_argument("--cpu-streams", type=int, default=-1, help="streams timed on the CPU oracle (-1 = all on rank 0)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip cpu_baseline / parity gate / secondary (profiling runs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip cpu_baseline / parity gate / secondary")
     ap.add_argument("--no-numpy", action="store_true", help="skip the (slow) numpy leg of cpu_baseline")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads")
     ap.add_argument("--secondary-only", default="", help="comma-separated secondary entry keys (dtw322, dtw1289, otw_b1, "
-                    "otw_b64_f64, chroma, wtw20, wtw100, wtw10k): run only those (profiling, one entry per rocprofv3 run)")
+                    "otw_b64_f64, chroma, wtw20, wtw100, wtw10k): with --full, run only those (profiling, one entry per rocprofv3 run)")
     ap.add_argument("--no-fork", action="store_true", help="CPU legs without worker processes (1-core leg only): safe "
                     "under rocprofv3, whose preloaded runtime must not be forked")
     ap.add_argument("--single-process", action="store_true",
@@ -413,9 +465,10 @@ def main():
     # ---- CPU side, before the GPU is initialised (the workers are forked): at N = 1 the cpu_baseline legs, whose paths
     # are also the parity checker; at N > 1 every rank computes the C port's paths of its own shard
     cpu = opaths = sec_inp = sec_cpu = None
-    want_secondary = (n_gpus == 1 and rank == 0 and not args.no_cpu and not args.no_secondary and B == 64
+    cpu_side = args.full and not args.no_cpu
+    want_secondary = (cpu_side and n_gpus == 1 and rank == 0 and not args.no_secondary and B == 64
                       and args.c == 500 and args.n_ref == 2200 and args.dtype == "f32")
-    if not args.no_cpu:
+    if cpu_side:
         if n_gpus == 1:
             n_cpu = B if args.cpu_streams < 0 else min(B, args.cpu_streams)
             cpu = cpu_legs(ref, lives, args.c, args.max_run_count, n_cpu, numpy_leg=not args.no_numpy, allow_fork=not args.no_fork)
@@ -514,6 +567,11 @@ def main():
     st0 = eng0.states()                       # the slice the HIP events bracket (one device's launch)
     alg_bytes = _otw_alg_bytes(st0, nat)[0]
 
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, eng, states, args.c, first_stream=lo,
+                              suffix="_rank%d" % rank if world > 1 else "")
+        note("outputs written: %s" % dumped)
+
     # ---- parity (outside the timed region): every stream of this rank's shard against the C port's path
     mism = checked = 0
     if opaths is not None:
@@ -594,7 +652,7 @@ def main():
                           "%d host cores; legs: the same on 1 core, and the numpy restatement on 1 core"
                           % (len(opaths), frames // B, main_leg["cores"]),
                 "legs": legs, "host_cpus": os.cpu_count(), "usable_cpus": usable_cpus()}
-        if not args.no_cpu:
+        if cpu_side:
             result["parity"] = {"streams_checked": checked_total, "streams_total": B * n_gpus,
                                 "path_mismatches": mism_total,
                                 "how": "every rank checks every stream of its own shard against the C port's path"}

@@ -3,6 +3,11 @@ or fails to load, importing this module raises."""
 import ctypes
 import os
 
+# torch before the library: torch's ROCm build ships its own HIP runtime (soname libamdhip64.so.7).  Loaded first, it is
+# the one librtsync.so's libamdhip64.so.7 dependency resolves to; loaded after, it would sit beside a second runtime from
+# the system ROCm, and the library's runtime would not see the devices torch holds.
+import torch  # noqa: F401
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSYNC_LIB selects another build of the same library (A/B measurements of kernel variants in one process tree)
 SO_PATH = os.environ.get("RTSYNC_LIB") or os.path.join(_HERE, "librtsync.so")

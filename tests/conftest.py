@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -31,9 +32,14 @@ def wtw_window_golden():
 
 @pytest.fixture(scope="session")
 def chopin_audio():
-    z = np.load(os.path.join(GOLDEN, "chopin_20b_audio.npz"))
+    # stored as parts of under 1 MiB each (tests/golden/make_golden.py): every array is its parts' pieces in order
+    pieces = {}
+    for fn in sorted(glob.glob(os.path.join(GOLDEN, "chopin_20b_audio.part*.npz"))):
+        z = np.load(fn)
+        for k in z.files:
+            pieces.setdefault(k, []).append(z[k])
     # librosa.load semantics for these PCM16 stereo files: (L + R) / 65536 exactly, float32
-    return {k.replace("_lr_sum", ""): (z[k].astype(np.float32) / np.float32(65536.0)) for k in z.files}
+    return {k.replace("_lr_sum", ""): (np.concatenate(v).astype(np.float32) / np.float32(65536.0)) for k, v in pieces.items()}
 
 
 @pytest.fixture(scope="session")

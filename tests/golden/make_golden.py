@@ -309,7 +309,12 @@ def main():
             raw = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, w.getnchannels())
         # mono float32 sample = (L + R) / 65536 exactly (librosa.load semantics); store L + R
         aud[key + "_lr_sum"] = raw.astype(np.int32).sum(axis=1).astype(np.int32)
-    np.savez_compressed(os.path.join(HERE, "chopin_20b_audio.npz"), **aud)
+    # committed as parts of under 1 MiB each, every array cut in two (tests/conftest.py joins them)
+    part = 0
+    for key in ("ref_lr_sum", "live_lr_sum"):
+        for piece in np.array_split(aud[key], 2):
+            np.savez_compressed(os.path.join(HERE, "chopin_20b_audio.part%d.npz" % part), **{key: piece})
+            part += 1
 
     # ---- accuracy metric (tests.py:29-137): the reference's test_simple class, cut out of tests.py as
     # text (the module itself runs a whole evaluation at import, tests.py:278-283), on the chopin

@@ -24,6 +24,8 @@ static int fails = 0;
 
 int main(void) {
     void *fake = (void *)(uintptr_t)4096; /* never dereferenced on the paths below */
+    /* unbuffered: a LeakSanitizer report at exit ends the process without flushing stdio */
+    setvbuf(stdout, NULL, _IONBF, 0);
     printf("version %d, gfx950 devices %d\n", rts_version(), rts_device_count());
 
     /* ---- OTW ---- */

@@ -50,3 +50,55 @@ def test_bench_line_contract():
         assert sec[k]["parity"]["path_mismatches"] == 0 and sec[k]["parity"]["streams_checked"] >= 1
     assert sec["chroma"]["parity"]["ok"] and sec["wtw10k"]["parity"]["equal_to_fixture"]
     assert r["secondary_wall_s"] < 60
+
+
+def test_dump_outputs_layout_and_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs on a stand-in engine: float64 files, streams in ascending global order, paths concatenated in
+    that order; past the byte budget a fixed seeded subset of the streams, the same one on every call."""
+    import sys
+
+    import numpy as np
+
+    import __graft_entry__ as ge
+    ge.build()                                    # dump_outputs reads the state layout from the native binding
+    sys.path.insert(0, ROOT)
+    import bench
+    from real_time_audio_sync_amd import _native as nat
+
+    c, B = 5, 12
+    rs = np.random.RandomState(3)
+    paths = [rs.randint(0, 50, size=(20 + 3 * b, 2)).astype(np.int32) for b in range(B)]
+    bands = [(rs.rand(c + 1), rs.rand(c + 1)) for b in range(B)]
+    states = rs.randint(-1, 100, size=(B, nat.STATE_LEN)).astype(np.int32)
+
+    class Eng:
+        def path(self, b):
+            return paths[b]
+
+        def bands(self, b):
+            return bands[b]
+
+    def load(d):
+        return {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+
+    info = bench.dump_outputs(str(tmp_path / "all"), Eng(), states, c, first_stream=100)
+    got = load(tmp_path / "all")
+    assert info["streams"] == B and all(a.dtype == np.float64 for a in got.values())
+    assert list(got["streams"]) == list(range(100, 100 + B))
+    assert np.array_equal(got["paths"], np.concatenate(paths)) and list(got["path_lengths"]) == [len(p) for p in paths]
+    assert np.array_equal(got["end_state"][:, 7], states[:, nat.ST_N_PATH]) and got["end_state"].shape == (B, 10)
+    assert np.array_equal(got["row_band"], np.array([rb for rb, _ in bands]))
+    assert np.array_equal(got["col_band"], np.array([cb for _, cb in bands]))
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", info["bytes"] // 2)
+    subsets = []
+    for k in range(2):
+        info = bench.dump_outputs(str(tmp_path / ("part%d" % k)), Eng(), states, c)
+        part = load(tmp_path / ("part%d" % k))
+        assert 0 < info["streams"] < B and info["bytes"] <= bench.DUMP_BUDGET_BYTES
+        sel = [int(s) for s in part["streams"]]
+        assert sel == sorted(sel)
+        assert np.array_equal(part["paths"], np.concatenate([paths[s] for s in sel]))
+        assert np.array_equal(part["end_state"], got["end_state"][sel])
+        subsets.append(sel)
+    assert subsets[0] == subsets[1]

@@ -1,10 +1,10 @@
 """bench.py's N>1 branch (BASELINE configs[3]: streams sharded 64 per GPU, no data-path collective).
 
   * test_bench_two_ranks_on_one_device: ALWAYS runs -- a fresh child `python -m torch.distributed.run --nproc-per-node 2
-    bench.py --gpus 2`, both ranks on device 0 (BENCH_SINGLE_DEVICE=1) with the report reductions over gloo
+    bench.py --gpus 2 --full`, both ranks on device 0 (BENCH_SINGLE_DEVICE=1) with the report reductions over gloo
     (BENCH_DIST_BACKEND=gloo; RCCL refuses two ranks on one device).  Everything else is the driver's N>1 path: contiguous
     partition, per-rank engines, barrier / max-clock, and the parity gate over EVERY stream of EVERY rank.
-  * test_bench_single_process_shards: ALWAYS runs -- `bench.py --gpus 2 --single-process` (shard.ShardedOTW), same line.
+  * test_bench_single_process_shards: ALWAYS runs -- `bench.py --gpus 2 --single-process --full` (shard.ShardedOTW), same line.
   * test_bench_over_rccl_on_all_devices: the same over RCCL on however many gfx950 devices the box has (skipped on a
     one-GPU box)."""
 import json
@@ -52,13 +52,13 @@ def test_bench_two_ranks_on_one_device():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BENCH_SINGLE_DEVICE="1", BENCH_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16", "--n-ref", "600", "--c", "100"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16", "--n-ref", "600", "--c", "100", "--full"]
     r = _bench_line(cmd, env)
     _check_sharded_line(r, 2, 16)
     assert "gloo" in r["config"]["launcher"]
     # the frames of the two shards add up to what one process counts for the same 32 streams
     one = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                       "--batch", "32", "--n-ref", "600", "--c", "100", "--no-numpy"], dict(os.environ))
+                       "--batch", "32", "--n-ref", "600", "--c", "100", "--full", "--no-numpy"], dict(os.environ))
     assert one["config"]["frames_per_step"] == r["config"]["frames_per_step"]
     assert one["parity"]["streams_checked"] == 32 and one["parity"]["path_mismatches"] == 0
 
@@ -69,7 +69,7 @@ def test_bench_single_process_shards():
         pytest.skip("no GPU")
     env = dict(os.environ, BENCH_SINGLE_DEVICE="1")
     r = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-process", "--steps", "3",
-                     "--warmup", "1", "--batch", "16", "--n-ref", "600", "--c", "100"], env)
+                     "--warmup", "1", "--batch", "16", "--n-ref", "600", "--c", "100", "--full"], env)
     _check_sharded_line(r, 2, 16)
     assert "ShardedOTW" in r["config"]["launcher"]
 
@@ -86,7 +86,7 @@ def test_bench_over_rccl_on_all_devices():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(n), "--steps", "3", "--warmup", "1", "--batch", "8", "--n-ref", "500", "--c", "100"]
+           "--gpus", str(n), "--steps", "3", "--warmup", "1", "--batch", "8", "--n-ref", "500", "--c", "100", "--full"]
     r = _bench_line(cmd, env, timeout=600)
     _check_sharded_line(r, n, 8)
 

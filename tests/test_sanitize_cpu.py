@@ -9,6 +9,7 @@ UndefinedBehaviorSanitizer on everything that runs on the host (GPU sanitizers a
     symbols are satisfied by empty stubs) driven by tests/sanitize/shim_driver.c, which asserts every return code.
 Leak detection is on: the error paths must free what they allocated."""
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -27,9 +28,19 @@ def _run(cmd, **kw):
     return p.returncode, p.stdout, p.stderr
 
 
-def _clean_report(err):
-    for bad in ("ERROR: AddressSanitizer", "ERROR: LeakSanitizer", "runtime error:"):
+def _clean_report(err, allowed_leaks=()):
+    """No sanitizer error in `err`; leak records equal to one of `allowed_leaks` (see _leaks) are let through."""
+    for bad in ("ERROR: AddressSanitizer", "runtime error:"):
         assert bad not in err, err[-4000:]
+    assert not [l for l in _leaks(err) if l not in allowed_leaks], err[-4000:]
+    if not allowed_leaks:
+        assert "ERROR: LeakSanitizer" not in err, err[-4000:]
+
+
+def _leaks(err):
+    """The leak records of a LeakSanitizer report (size, object count, allocation stack), addresses stripped."""
+    return [re.sub(r"0x[0-9a-f]+", "0x", b.strip()) for b in re.split(r"\n\s*\n", err)
+            if re.match(r"\s*(Direct|Indirect) leak of", b)]
 
 
 def _fnv(h, a):
@@ -104,7 +115,8 @@ def test_oracle_under_asan_ubsan(tmp_path):
 
 def test_host_shim_validation_paths_under_asan_ubsan():
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    clang = "/opt/rocm/lib/llvm/bin/clang"
+    rocm = "/opt/rocm"
+    clang = os.path.join(rocm, "lib", "llvm", "bin", "clang")
     if not (os.path.exists(hipcc) and os.path.exists(clang)):
         pytest.skip("no ROCm toolchain")
     os.makedirs(OUT, exist_ok=True)
@@ -128,6 +140,19 @@ def test_host_shim_validation_paths_under_asan_ubsan():
     assert rc == 0, err[-3000:]
     # hide any GPU: this test is about the host paths (and must behave the same on the GPU box)
     env = dict(ENV, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    # Where a GPU driver is present, the HIP runtime's own start-up leaves allocations LeakSanitizer reports, even with
+    # every device hidden; their stacks end in libstdc++'s operator new (the runtime keeps no frame pointers), so no
+    # suppression can name them.  A program that only starts the runtime shows exactly those records: the driver may
+    # have them and no other (and then exits with the same leak status as that program).
+    probe = os.path.join(OUT, "runtime_probe")
+    with open(probe + ".c", "w") as g:
+        g.write("#include <hip/hip_runtime_api.h>\nint main(void) { int n = 0; (void)hipGetDeviceCount(&n); return 0; }\n")
+    rc, out, err = _run([clang] + FLAGS + ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), probe + ".c",
+                                           "-o", probe, "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
+                                           "-Wl,-rpath," + os.path.join(rocm, "lib")])
+    assert rc == 0, err[-3000:]
+    probe_rc, _, probe_err = _run([probe], env=env, timeout=120)
+    _clean_report(probe_err, allowed_leaks=_leaks(probe_err))
     rc, out, err = _run([exe], env=env, timeout=300)
-    _clean_report(err)
-    assert rc == 0 and "ok (0 mismatches)" in out, (out, err[-3000:])
+    _clean_report(err, allowed_leaks=_leaks(probe_err))
+    assert rc == probe_rc and "ok (0 mismatches)" in out, (out, err[-3000:])

@@ -12,7 +12,7 @@ tail -5 $OUT/collect.log
 for B in 128 256 512 1024 4096; do
   timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-cpu --batch $B >> $OUT/${TAG}_batch_sweep.jsonl
 done
-timeout -k 10 300 python3 bench.py --dtype f64 --no-numpy > $OUT/${TAG}_bench_f64.json
+timeout -k 10 300 python3 bench.py --full --dtype f64 --no-numpy > $OUT/${TAG}_bench_f64.json
 timeout -k 10 300 python3 bench.py --dtype f64 --no-cpu --batch 4096 --steps 5 --warmup 2 >> $OUT/${TAG}_batch_sweep.jsonl
 timeout -k 10 600 python3 tools/bench_secondary.py > $OUT/${TAG}_secondary_kernels.jsonl 2> $OUT/secondary.err || { tail -20 $OUT/secondary.err; exit 1; }
 timeout -k 10 300 python3 tools/bench_live.py 120 > $OUT/${TAG}_live.jsonl 2> $OUT/live.err || { tail -20 $OUT/live.err; exit 1; }

@@ -3,11 +3,11 @@
 
     python3 tools/collect_profile.py TAG        -> gpurun_out/profile_TAG/
 
-  1. bench.py (default flags)                                   -> TAG_bench_final.json
+  1. bench.py --full                                            -> TAG_bench_final.json
   2. rocprofv3 --kernel-trace --stats -- python3 bench.py ...   -> TAG_otw_kernel_stats.csv, TAG_bench_under_rocprof.json
   3. rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ_* (separate passes, --no-cpu, 3 steps)
                                                                 -> TAG_pmc.json, otw_traffic.json (with the sha of csrc/otw.hip)
-  4. per secondary entry of the bench line: rocprofv3 --kernel-trace --stats -- python3 bench.py --secondary-only KEY ...
+  4. per secondary entry of the bench line: rocprofv3 --kernel-trace --stats -- python3 bench.py --full --secondary-only KEY
                                                                 -> TAG_secondary_kernel_stats.json
 Every profiler pass is its own child process with the program right after `--` (no shell, no env wrapper).
 Everything is written under gpurun_out/profile_TAG/ only; copy what should be judged into profiles/ by hand
@@ -101,7 +101,7 @@ def main():
     # roofline.traffic from profiles/otw_traffic.json), so that the two files agree
     with open(os.path.join(out, "otw_traffic.json"), "w") as f:
         json.dump(traffic, f, indent=1)
-    final = run(["python3", "bench.py", "--traffic-json", os.path.join(out, "otw_traffic.json")],
+    final = run(["python3", "bench.py", "--full", "--traffic-json", os.path.join(out, "otw_traffic.json")],
                 os.path.join(out, tag + "_bench_final.json"))
     print("bench: %.3f ms/step, %.3e frames/s" % (final["ms_per_step"], final["value"]), flush=True)
     summary = {"kernel": krow["Name"], "kernel_trace": {k: krow[k] for k in ("Calls", "AverageNs", "MinNs", "MaxNs", "StdDev")},
@@ -123,7 +123,7 @@ def bench_secondary(tag, out, final):
     for key in ("dtw322", "dtw1289", "otw_b1", "otw_b64_f64", "chroma", "wtw20", "wtw100", "wtw10k"):
         d = os.path.join(out, "trace_sec_" + key)
         line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", "python3", "bench.py",
-                    "--no-fork", "--no-numpy", "--steps", "2", "--warmup", "1", "--secondary-only", key],
+                    "--full", "--no-fork", "--no-numpy", "--steps", "2", "--warmup", "1", "--secondary-only", key],
                    os.path.join(out, "sec_%s.json" % key))
         entry = [e for e in line["secondary"] if e["key"] == key][0]
         want = [k.split(" ")[0] for k in entry["kernels"]]
