@@ -87,7 +87,7 @@ int rts_version(void);
 int rts_device_count(void);
 
 /* ------------------------------------------------------------------------------------------
- * Online time warping, batched over B independent live streams against one reference.
+ * Online time warping, batched over B independent live streams against one reference (or one each).
  * ------------------------------------------------------------------------------------------ */
 typedef struct rts_otw rts_otw;
 
@@ -102,6 +102,17 @@ typedef struct rts_otw rts_otw;
  * RTS_ERR_UNSUPPORTED with a message. */
 int rts_otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, int c, int max_run_count,
                    int variant, int cost_kind, rts_otw **out);
+/* The same for B streams that each follow their own reference (one piece per microphone): stream b behaves exactly like
+ * stream 0 of an rts_otw_create handle made with ref_dev = frames [first_host[b], first_host[b] + len_host[b]) of
+ * `refs_dev` ([n_ref_frames][F] frame-major, dtype `ref_dtype`, held by reference) and N = len_host[b]; every limit the
+ * reference derives from N (live capacity 2N_b, the stop at j + 1 >= N_b) is the stream's own.  The host tables are
+ * copied at create; ranges may overlap or repeat.  Buffers are sized by the longest reference N_max (path capacity
+ * 3 N_max + 8, insert history [B][2 N_max][F]); every getter is unchanged.  RTS_ERR_INVALID for a NULL pointer, len < 1,
+ * first < 0 or a range past n_ref_frames (the message names the stream); the rules of rts_otw_create apply otherwise.
+ * The dense mirror (rts_otw_set_dense, rts_otw_replay_dense) returns RTS_ERR_UNSUPPORTED on such a handle. */
+int rts_otw_create_refs(const void *refs_dev, int ref_dtype, int F, long long n_ref_frames,
+                        const long long *first_host, const int32_t *len_host, int B, int c, int max_run_count,
+                        int variant, int cost_kind, rts_otw **out);
 int rts_otw_destroy(rts_otw *h);
 /* Back to the freshly-constructed state (all streams). */
 int rts_otw_reset(rts_otw *h, void *stream);
@@ -232,7 +243,7 @@ int rts_chroma_project(rts_chroma *h, const double *spec_dev, int n_frames, int 
 int rts_chroma_diff(const void *chroma_dev, int dtype, int n_frames, void *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * Windowed time warping, batched over B live streams against one reference chroma.
+ * Windowed time warping, batched over B live streams against one reference chroma (or one each).
  * ------------------------------------------------------------------------------------------ */
 typedef struct rts_wtw rts_wtw;
 
@@ -257,6 +268,14 @@ typedef struct rts_wtw rts_wtw;
  * wtw.py:105). */
 int rts_wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win_frames, int hop_frames,
                    int keep_last_d, rts_wtw **out);
+/* The same for B streams that each follow their own reference chroma: stream b behaves exactly like stream 0 of an
+ * rts_wtw_create handle made with chroma_ref_dev = frames [first_host[b], first_host[b] + len_host[b]) of
+ * `chroma_refs_dev` ([n_ref_frames][F] float64) and M = len_host[b], so its N = 2 M_b, its boundary checks and the
+ * truncation of its reference windows are its own.  Tables copied at create, ranges may overlap or repeat; the live
+ * history is [B][2 M_max][F] (rts_wtw_device_views reports 2 M_max).  Errors as for rts_otw_create_refs. */
+int rts_wtw_create_refs(const double *chroma_refs_dev, int F, long long n_ref_frames,
+                        const long long *first_host, const int32_t *len_host, int B, int win_frames,
+                        int hop_frames, int keep_last_d, rts_wtw **out);
 int rts_wtw_destroy(rts_wtw *h);
 int rts_wtw_reset(rts_wtw *h, void *stream);
 
@@ -289,7 +308,8 @@ typedef struct rts_live rts_live;
  *                             `while len(data) >= 4096: col = wav_to_chroma_col(data[:4096]); ln.insert(col); data = data[2048:]`
  *   wtw.py:71-93              WTW.insert(list): self.buf += list; `while len(self.buf) >= fft_len:` one column per hop
  * Binds a chroma plan (its fft_len / hop; un-padded framing, chroma.py:35-42) and exactly one of `otw` (created with
- * the same B; columns go through rts_otw_push) or `wtw` (rts_wtw_push with precheck, i.e. wtw.py:76-77 once per feed).
+ * the same B; columns go through rts_otw_push) or `wtw` (rts_wtw_push with precheck, i.e. wtw.py:76-77 once per feed);
+ * a tracker created for another number of streams is refused with RTS_ERR_INVALID.
  * The plan and the tracker must outlive the handle and live on the current device.  max_pending: capacity in samples of
  * each stream's pending buffer (>= fft_len + hop); a feed that would exceed it is refused with RTS_ERR_INVALID.
  * All calls of one handle must use the same `stream`. */

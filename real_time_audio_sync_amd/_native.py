@@ -57,6 +57,8 @@ _decl("rts_last_error", ctypes.c_char_p, [])
 _decl("rts_version", _i32, [])
 _decl("rts_device_count", _i32, [])
 _decl("rts_otw_create", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)])
+_i64 = ctypes.c_longlong
+_decl("rts_otw_create_refs", _i32, [_vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)])
 _decl("rts_otw_destroy", _i32, [_vp])
 _decl("rts_otw_reset", _i32, [_vp, _vp])
 _decl("rts_otw_run", _i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp])
@@ -71,7 +73,6 @@ _decl("rts_otw_set_waves", _i32, [_vp, _i32])
 _decl("rts_otw_set_dense", _i32, [_vp, _vp, _vp, _vp])
 _decl("rts_otw_replay_dense", _i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp])
 _decl("rts_otw_kernel_name", ctypes.c_char_p, [_vp])
-_i64 = ctypes.c_longlong
 _decl("rts_dtw_workspace_bytes", _i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_size_t)])
 _decl("rts_dtw", _i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                         ctypes.c_size_t, _vp])
@@ -88,6 +89,7 @@ _decl("rts_chroma_diff", _i32, [_vp, _i32, _i32, _vp, _vp])
 
 
 _decl("rts_wtw_create", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)])
+_decl("rts_wtw_create_refs", _i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)])
 _decl("rts_wtw_destroy", _i32, [_vp])
 _decl("rts_wtw_reset", _i32, [_vp, _vp])
 _decl("rts_wtw_push", _i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp])

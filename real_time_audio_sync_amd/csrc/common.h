@@ -11,6 +11,10 @@ namespace rts {
 char *last_error_buf();  // thread-local, 512 bytes
 int set_error(int code, const char *fmt, ...);
 
+// Streams of a tracker handle (rts_live_create checks that it binds one of its own size).  Library-internal.
+__attribute__((visibility("hidden"))) int otw_batch(const rts_otw *h);
+__attribute__((visibility("hidden"))) int wtw_batch(const rts_wtw *h);
+
 #define RTS_HIP(call)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \

@@ -174,6 +174,9 @@ int rts_live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max
     if (!plan) return set_error(RTS_ERR_INVALID, "plan is NULL");
     if ((otw == nullptr) == (wtw == nullptr)) return set_error(RTS_ERR_INVALID, "exactly one of otw / wtw must be given");
     if (B < 1) return set_error(RTS_ERR_INVALID, "B must be >= 1");
+    if ((otw ? otw_batch(otw) : wtw_batch(wtw)) != B)
+        return set_error(RTS_ERR_INVALID, "the tracker was created for %d streams, not B = %d",
+                         otw ? otw_batch(otw) : wtw_batch(wtw), B);
     int fft_len = 0, hop = 0;
     if (int rc = rts_chroma_plan_info(plan, &fft_len, &hop); rc != RTS_OK) return rc;
     if (max_pending < fft_len + hop || (long long)max_pending * B > 0x7fffffffLL)

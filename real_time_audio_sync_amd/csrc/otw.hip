@@ -44,7 +44,7 @@ constexpr int kF = 12;
 constexpr int kFetch = 8;  // frames fetched per ring refill
 
 struct OtwArgs {
-    const void *ref;          // [N][F]
+    const void *ref;          // [N][F]; with per-stream references [n_ref_frames][F], stream b at ref_first[b]
     const void *live;         // [B][live_stride][F]
     const int32_t *live_len;  // [B]
     int32_t *state;           // [B][RTS_STATE_LEN]
@@ -52,13 +52,18 @@ struct OtwArgs {
     double *bands;            // [B][2][c+1]
     long long live_stride;    // frames between consecutive streams in `live`
     int N, c, max_run_count, variant, cost_kind, mode;
-    int path_cap, live_cap;   // live_cap = 2N (otw_eran.py:14)
+    int path_cap, live_cap;   // live_cap = 2N (otw_eran.py:14); the history stride is live_stride
     int ref_f64, live_f64;
     int clamp_len;            // run mode: never read past live_stride frames
     long long *debug;         // diagnostic builds only (-DRTS_OTW_STAMPS): [B][16] cycle sums
     int spec;                 // 1: the pipelined kernel was selected (host-side choice; the kernel does not read it)
     double *dense_acc;        // optional [B][2N][N]: the reference's dense acc_cost (otw_eran.py:27), NULL = off
     double *dense_cost;       // optional [B][2N][N]: the reference's dense cost (otw_eran.py:23)
+    // per-stream references (rts_otw_create_refs), NULL for a single-reference handle: stream b follows frames
+    // [ref_first[b], ref_first[b] + ref_len[b]) of `ref`, and its N is ref_len[b].  The kernel reads every reference
+    // quantity from OtwEnv (e.ref, e.N, e.live_cap), which the prologue fills from these or from ref / N / live_cap.
+    const long long *ref_first;
+    const int32_t *ref_len;
 };
 
 // RT = element type of the feature rings: double, or float when both inputs are float32 (their values
@@ -1362,8 +1367,6 @@ otw_advance_kernel(OtwArgs a) {
     e.b = blockIdx.x;
     e.lane = lane;
     e.c = a.c;
-    e.N = a.N;
-    e.live_cap = a.live_cap;
     e.euclid = a.cost_kind == RTS_COST_EUCLID;
     e.variant = a.variant;
     e.mode = a.mode;
@@ -1373,11 +1376,20 @@ otw_advance_kernel(OtwArgs a) {
     e.ref_f64 = a.ref_f64;
     e.live_base = (long long)e.b * a.live_stride * kF;
     e.live = a.live;
-    e.ref = a.ref;
+    if (a.ref_first) {  // this stream's own reference: plain loads of a uniform address, once per launch
+        const int nb = a.ref_len[e.b];
+        e.N = nb;
+        e.live_cap = 2 * nb;  // otw_eran.py:14 for this stream; the history stride stays live_stride
+        e.ref = static_cast<const char *>(a.ref) + a.ref_first[e.b] * (long long)kF * (a.ref_f64 ? 8 : 4);
+    } else {
+        e.N = a.N;
+        e.live_cap = a.live_cap;
+        e.ref = a.ref;
+    }
     e.path = a.path;
     // LiveNote's set_live applies the run-count update at the bottom of its loop (livenote_v2.py:149-155)
     e.deferred_update = (a.mode == RTS_MODE_SET_LIVE) && (a.variant != RTS_VARIANT_OTW);
-    const int c = a.c, N = a.N;
+    const int c = a.c, N = e.N;
     int32_t *st = a.state + (size_t)e.b * RTS_STATE_LEN;
     int live_len_raw = a.live_len[e.b];
     if (a.clamp_len && live_len_raw > (int)a.live_stride) live_len_raw = (int)a.live_stride;
@@ -1452,7 +1464,7 @@ otw_advance_kernel(OtwArgs a) {
         if constexpr (kRefRing) {
             for (int idx = tid; idx < (k.ref_hi - lo_r + 1) * kF; idx += NT) {
                 const int fr = lo_r + idx / kF, f = idx % kF;
-                S.refw[f][fr & (W - 1)] = (typename RingElem<RT>::type)otw_load_feat(a.ref, a.ref_f64, (long long)fr * kF + f);
+                S.refw[f][fr & (W - 1)] = (typename RingElem<RT>::type)otw_load_feat(e.ref, a.ref_f64, (long long)fr * kF + f);
             }
         }
         if (!k.first) {
@@ -1484,8 +1496,8 @@ otw_advance_kernel(OtwArgs a) {
                 S.R[swz<W>(0)] = d;
                 S.C[swz<W>(0)] = d;
                 if (DENSE) {
-                    a.dense_acc[(long long)e.b * a.live_cap * N] = d;
-                    a.dense_cost[(long long)e.b * a.live_cap * N] = d;
+                    a.dense_acc[(long long)e.b * e.live_cap * N] = d;
+                    a.dense_cost[(long long)e.b * e.live_cap * N] = d;
                 }
             }
             k.first = 0;
@@ -1600,7 +1612,7 @@ otw_advance_kernel(OtwArgs a) {
                                                        Rsh[swz<W>(j0 > 0 ? j0 - 1 : 0)], SP.row[sp].d, sentinel);
                     if (lane == 0) R[swz<W>(j0)] = av;
                 }
-                if (!(pflags & kPlanStop) && pt + 1 < live_len && pt + 1 < a.live_cap)  // row pt+1 over [.., jn-1]
+                if (!(pflags & kPlanStop) && pt + 1 < live_len && pt + 1 < e.live_cap)  // row pt+1 over [.., jn-1]
                     otw_spec_strip<W, false>(S.Dr[(pt + 1) & 1], R, Rsh, jn, c, lane, sentinel, &SP.row[sp ^ 1], RTS_ROUNDS_ACC);
                 RTS_LW_END(pflags & kPlanHit);
                 RTS_STEP_BARRIER();
@@ -1821,7 +1833,7 @@ otw_advance_kernel(OtwArgs a) {
             if (do_row && wave == 0) {
                 const double x_in = (k1r > 0) ? sentinel : inf;  // (t, k1r-1) was never evaluated
                 const int lo_arg = (jn - c + 1 > 0) ? jn - c + 1 : 0;  // row band's lower end at decide()
-                const long long dro = ((long long)e.b * a.live_cap + pt) * N + k1r;  // cell (pt, k1r)
+                const long long dro = ((long long)e.b * e.live_cap + pt) * N + k1r;  // cell (pt, k1r)
                 strip_chain<W, DENSE>(Dr, S.R, S.R, k1r, nr, x_in, lane, lo_arg, rf_min, rf_idx, DENSE ? a.dense_acc + dro : nullptr,
                                       DENSE ? a.dense_cost + dro : nullptr, 1);
                 if (lane == 0 && k1r > 0) S.R[swz<W>(k1r - 1)] = sentinel;
@@ -1834,7 +1846,7 @@ otw_advance_kernel(OtwArgs a) {
                 // the corner's diagonal term needs column jn-1 at row t-1, which the chain is about to overwrite
                 const double dcorner = Dc[swz<W>(pt)];
                 const double pa = (do_row && pt > 0) ? S.C[swz<W>(pt - 1)] + 2 * dcorner : inf;
-                const long long dco = ((long long)e.b * a.live_cap + k1c) * N + jn;  // cell (k1c, jn)
+                const long long dco = ((long long)e.b * e.live_cap + k1c) * N + jn;  // cell (k1c, jn)
                 strip_chain<W, DENSE>(Dc, S.C, S.C, k1c, ncc, x_in, lane, k1c, fm, fi, DENSE ? a.dense_acc + dco : nullptr,
                                       DENSE ? a.dense_cost + dco : nullptr, N);
                 if (lane == 0) {
@@ -1881,7 +1893,7 @@ otw_advance_kernel(OtwArgs a) {
                         if (lane == 0) {
                             S.C[swz<W>(pt)] = cl;
                             if (DENSE) {
-                                const long long o = ((long long)e.b * a.live_cap + pt) * N + jn;
+                                const long long o = ((long long)e.b * e.live_cap + pt) * N + jn;
                                 a.dense_acc[o] = cl;
                                 a.dense_cost[o] = d;
                             }
@@ -1918,7 +1930,7 @@ otw_advance_kernel(OtwArgs a) {
     {
         int te = S.t, je = S.j;
         const int t_state = te;
-        if (te > a.live_cap - 1) te = a.live_cap - 1;
+        if (te > e.live_cap - 1) te = e.live_cap - 1;
         if (je > N - 1) je = N - 1;
         double *bb = a.bands + (size_t)e.b * 2 * (c + 1);
         const double qnan = __longlong_as_double(0x7ff8000000000000LL);
@@ -1926,7 +1938,7 @@ otw_advance_kernel(OtwArgs a) {
         const double *Rf = (SPEC && (fl & kPlanRi)) ? SP.ShR : S.R, *Cf = (SPEC && (fl & kPlanCi)) ? SP.ShC : S.C;
         // set_live that ran out of live frames stops with t one past the last frame (otw_eran.py:113-116): row t was
         // never evaluated and reads as the matrix's initial value
-        const bool row_missing = (t_state >= e.live_len) && (t_state <= a.live_cap - 1);
+        const bool row_missing = (t_state >= e.live_len) && (t_state <= e.live_cap - 1);
         const double sentinel = (e.variant == RTS_VARIANT_OTW) ? 1e10 : (double)INFINITY;
         for (int i = tid; i <= c; i += NT) {
             const int y = je - c + i, x = te - c + i;
@@ -2034,11 +2046,14 @@ __global__ void otw_append_many_kernel(double *hist, int32_t *hist_len, const vo
 struct rts_otw {
     const void *ref;
     int ref_dtype, F, N, B, c, max_run_count, variant, cost_kind;
-    int W, waves, path_cap, live_cap;
+    int W, waves, path_cap;
+    int hist_stride;    // frames per stream in `hist`: 2N (2 N_max with per-stream references)
     int32_t *state;     // [B][16]
     int32_t *path;      // [B][path_cap][2]
     double *bands;      // [B][2][c+1]
-    double *hist;       // [B][live_cap][F], allocated on first insert
+    double *hist;       // [B][hist_stride][F], allocated on first insert
+    long long *ref_first;  // per-stream references (rts_otw_create_refs): [B] first frames, device; NULL otherwise
+    int32_t *ref_len;      // [B] lengths N_b, device
     int32_t *hist_len;  // [B]
     long long *debug;   // diagnostic builds only
     double *dense_acc, *dense_cost;  // caller-owned, optional
@@ -2161,7 +2176,9 @@ static OtwArgs base_args(const rts_otw *h) {
     a.variant = h->variant;
     a.cost_kind = h->cost_kind;
     a.path_cap = h->path_cap;
-    a.live_cap = h->live_cap;
+    a.live_cap = 2 * h->N;  // per-stream references: the kernel takes 2 N_b from ref_len instead
+    a.ref_first = h->ref_first;
+    a.ref_len = h->ref_len;
     a.ref_f64 = h->ref_dtype == RTS_F64;
     a.debug = h->debug;
     a.spec = h->spec;
@@ -2170,16 +2187,10 @@ static OtwArgs base_args(const rts_otw *h) {
     return a;
 }
 
-}  // namespace rts
-
-extern "C" {
-
-int rts_otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, int c, int max_run_count,
-                   int variant, int cost_kind, rts_otw **out) {
-    using namespace rts;
-    if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!ref_dev) return set_error(RTS_ERR_INVALID, "ref_dev is NULL");
+// The constructor behind rts_otw_create (first_host == NULL: one reference of N frames) and rts_otw_create_refs (N =
+// N_max, per-stream tables of B entries, already checked).  Every argument is checked before the first HIP call.
+static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, int c, int max_run_count, int variant,
+                      int cost_kind, const long long *first_host, const int32_t *len_host, rts_otw **out) {
     if (F < 1) return set_error(RTS_ERR_INVALID, "F must be >= 1 (got %d)", F);
     if (F != kF) return set_error(RTS_ERR_UNSUPPORTED, "F must be 12 chroma bins (got %d)", F);
     if (N < 1 || B < 1) return set_error(RTS_ERR_INVALID, "N and B must be >= 1 (got N=%d B=%d)", N, B);
@@ -2217,7 +2228,7 @@ int rts_otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, int 
         const char *tp = getenv("RTS_OTW_TP_FROM");  // tests: 0 selects the residency-oriented flavour at any batch size
         h->tp_from = tp ? atoi(tp) : 2;
     }
-    h->live_cap = 2 * N;
+    h->hist_stride = 2 * N;
     h->path_cap = 3 * N + 8;  // one point per decide(); decides <= row strips + column strips <= 2N + N
     hipError_t e;
     if ((e = hipGetDevice(&h->device)) != hipSuccess ||
@@ -2228,7 +2239,11 @@ int rts_otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, int 
     if ((e = hipMalloc((void **)&h->state, sizeof(int32_t) * RTS_STATE_LEN * (size_t)B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->path, sizeof(int32_t) * 2 * (size_t)h->path_cap * B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->bands, sizeof(double) * 2 * (size_t)(c + 1) * B)) != hipSuccess ||
-        (e = hipMalloc((void **)&h->hist_len, sizeof(int32_t) * (size_t)B)) != hipSuccess) {
+        (e = hipMalloc((void **)&h->hist_len, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
+        (first_host && (e = hipMalloc((void **)&h->ref_first, sizeof(long long) * (size_t)B)) != hipSuccess) ||
+        (first_host && (e = hipMalloc((void **)&h->ref_len, sizeof(int32_t) * (size_t)B)) != hipSuccess) ||
+        (first_host && (e = hipMemcpy(h->ref_first, first_host, sizeof(long long) * (size_t)B, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (first_host && (e = hipMemcpy(h->ref_len, len_host, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice)) != hipSuccess)) {
         rts_otw_destroy(h);
         return set_error(RTS_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
     }
@@ -2245,6 +2260,42 @@ int rts_otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, int 
     return RTS_OK;
 }
 
+int otw_batch(const rts_otw *h) { return h->B; }
+
+}  // namespace rts
+
+extern "C" {
+
+int rts_otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, int c, int max_run_count,
+                   int variant, int cost_kind, rts_otw **out) {
+    using namespace rts;
+    if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!ref_dev) return set_error(RTS_ERR_INVALID, "ref_dev is NULL");
+    return otw_create(ref_dev, ref_dtype, F, N, B, c, max_run_count, variant, cost_kind, nullptr, nullptr, out);
+}
+
+int rts_otw_create_refs(const void *refs_dev, int ref_dtype, int F, long long n_ref_frames,
+                        const long long *first_host, const int32_t *len_host, int B, int c, int max_run_count,
+                        int variant, int cost_kind, rts_otw **out) {
+    using namespace rts;
+    if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!refs_dev) return set_error(RTS_ERR_INVALID, "refs_dev is NULL");
+    if (!first_host || !len_host) return set_error(RTS_ERR_INVALID, "first_host / len_host is NULL");
+    if (B < 1) return set_error(RTS_ERR_INVALID, "B must be >= 1 (got %d)", B);
+    int n_max = 0;
+    for (int b = 0; b < B; b++) {
+        if (len_host[b] < 1) return set_error(RTS_ERR_INVALID, "stream %d: len must be >= 1 (got %d)", b, len_host[b]);
+        if (first_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: first must be >= 0 (got %lld)", b, first_host[b]);
+        if (first_host[b] > n_ref_frames - len_host[b])
+            return set_error(RTS_ERR_INVALID, "stream %d: frames [%lld, %lld) lie outside the %lld reference frames", b,
+                             first_host[b], first_host[b] + len_host[b], n_ref_frames);
+        if (len_host[b] > n_max) n_max = len_host[b];
+    }
+    return otw_create(refs_dev, ref_dtype, F, n_max, B, c, max_run_count, variant, cost_kind, first_host, len_host, out);
+}
+
 int rts_otw_destroy(rts_otw *h) {
     if (!h) return RTS_OK;
     if (h->state) (void)hipFree(h->state);
@@ -2252,6 +2303,8 @@ int rts_otw_destroy(rts_otw *h) {
     if (h->bands) (void)hipFree(h->bands);
     if (h->hist) (void)hipFree(h->hist);
     if (h->hist_len) (void)hipFree(h->hist_len);
+    if (h->ref_first) (void)hipFree(h->ref_first);
+    if (h->ref_len) (void)hipFree(h->ref_len);
     if (h->rp_state) (void)hipFree(h->rp_state);
     if (h->rp_path) (void)hipFree(h->rp_path);
     if (h->rp_bands) (void)hipFree(h->rp_bands);
@@ -2269,7 +2322,7 @@ int rts_otw_reset(rts_otw *h, void *stream) {
     RTS_HIP(hipGetLastError());
     RTS_HIP(hipMemsetAsync(h->hist_len, 0, sizeof(int32_t) * (size_t)h->B, s));
     if (h->dense_acc) {  // otw_eran.py:23,27 / livenote_v2.py:21-23
-        const long long n = (long long)h->B * h->live_cap * h->N;
+        const long long n = (long long)h->B * 2 * h->N * h->N;
         const double sentinel = (h->variant == RTS_VARIANT_OTW) ? 1e10 : (double)INFINITY;
         hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, h->dense_acc, n, sentinel);
         hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, h->dense_cost, n, -1.0);
@@ -2281,6 +2334,8 @@ int rts_otw_reset(rts_otw *h, void *stream) {
 int rts_otw_set_dense(rts_otw *h, double *acc_dev, double *cost_dev, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (h->ref_first)
+        return set_error(RTS_ERR_UNSUPPORTED, "the dense mirror is not available on a handle with per-stream references");
     if ((acc_dev == nullptr) != (cost_dev == nullptr))
         return set_error(RTS_ERR_INVALID, "acc_dev and cost_dev must both be given or both be NULL");
     h->dense_acc = acc_dev;
@@ -2292,6 +2347,8 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
                          double *acc_dev, double *cost_dev, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (h->ref_first)
+        return set_error(RTS_ERR_UNSUPPORTED, "the dense replay is not available on a handle with per-stream references");
     if (!acc_dev || !cost_dev) return set_error(RTS_ERR_INVALID, "acc_dev / cost_dev is NULL");
     if (int rc = check_device(h); rc != RTS_OK) return rc;
     if (h->src_kind == 3)
@@ -2308,7 +2365,7 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
         return set_error(RTS_ERR_INVALID, "the handle's frames came through rts_otw_insert / rts_otw_push (or it is fresh): live_dev must be NULL");
     }
     hipStream_t s = (hipStream_t)stream;
-    const long long n = (long long)h->B * h->live_cap * h->N;
+    const long long n = (long long)h->B * 2 * h->N * h->N;
     const double sentinel = (h->variant == RTS_VARIANT_OTW) ? 1e10 : (double)INFINITY;
     hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, acc_dev, n, sentinel);
     hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, cost_dev, n, -1.0);
@@ -2343,7 +2400,7 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
     } else {
         a.live = h->hist;
         a.live_len = h->hist_len;
-        a.live_stride = h->live_cap;
+        a.live_stride = h->hist_stride;
         a.live_f64 = 1;
         a.mode = RTS_MODE_INSERT_LOOP;
     }
@@ -2397,16 +2454,16 @@ int rts_otw_insert(rts_otw *h, const void *frames_dev, int frames_dtype, const u
     hipStream_t s = (hipStream_t)stream;
     if (int rc = check_device(h); rc != RTS_OK) return rc;
     if (!h->hist) {
-        RTS_HIP(hipMalloc((void **)&h->hist, sizeof(double) * kF * (size_t)h->live_cap * h->B));
+        RTS_HIP(hipMalloc((void **)&h->hist, sizeof(double) * kF * (size_t)h->hist_stride * h->B));
     }
     h->src_kind = (h->src_kind == 0 || h->src_kind == 2) ? 2 : 3;
     hipLaunchKernelGGL(otw_append_kernel, dim3(h->B), dim3(64), 0, s, h->hist, h->hist_len, frames_dev,
-                       frames_dtype == RTS_F64, active_dev, h->B, h->live_cap);
+                       frames_dtype == RTS_F64, active_dev, h->B, h->hist_stride);
     RTS_HIP(hipGetLastError());
     OtwArgs a = base_args(h);
     a.live = h->hist;
     a.live_len = h->hist_len;
-    a.live_stride = h->live_cap;
+    a.live_stride = h->hist_stride;
     a.live_f64 = 1;
     a.mode = RTS_MODE_INSERT_LOOP;
     return launch(h, a, s);
@@ -2423,16 +2480,16 @@ int rts_otw_push(rts_otw *h, const void *frames_dev, int frames_dtype, int n_max
     hipStream_t s = (hipStream_t)stream;
     if (int rc = check_device(h); rc != RTS_OK) return rc;
     if (!h->hist) {
-        RTS_HIP(hipMalloc((void **)&h->hist, sizeof(double) * kF * (size_t)h->live_cap * h->B));
+        RTS_HIP(hipMalloc((void **)&h->hist, sizeof(double) * kF * (size_t)h->hist_stride * h->B));
     }
     h->src_kind = (h->src_kind == 0 || h->src_kind == 2) ? 2 : 3;
     hipLaunchKernelGGL(otw_append_many_kernel, dim3(h->B), dim3(128), 0, s, h->hist, h->hist_len, frames_dev,
-                       frames_dtype == RTS_F64, n_new_dev, n_max, n_max, h->B, h->live_cap);
+                       frames_dtype == RTS_F64, n_new_dev, n_max, n_max, h->B, h->hist_stride);
     RTS_HIP(hipGetLastError());
     OtwArgs a = base_args(h);
     a.live = h->hist;
     a.live_len = h->hist_len;
-    a.live_stride = h->live_cap;
+    a.live_stride = h->hist_stride;
     a.live_f64 = 1;
     a.mode = RTS_MODE_INSERT_LOOP;
     return launch(h, a, s);

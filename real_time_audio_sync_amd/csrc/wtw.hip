@@ -39,8 +39,8 @@ constexpr int kWtwStripFrom = 64;  // windows above this many frames use the str
 constexpr int kWtwMaxW = 16384;
 
 struct WtwArgs {
-    const double *ref;    // [M][F]
-    double *live;         // [B][N][F]  (N = 2M)
+    const double *ref;    // [M][F]; with per-stream references [n_ref_frames][F], stream b at ref_first[b]
+    double *live;         // [B][live_stride][F]  (live_stride = 2M, 2 M_max with per-stream references)
     int32_t *appended;    // [B] columns written to `live` so far
     int32_t *state;       // [B][8]: chroma_ptr, live_ptr, ref_ptr, status, n_path, n_windows, cells_lo, cells_hi
     int32_t *path;        // [B][path_cap][2]
@@ -58,9 +58,32 @@ struct WtwArgs {
     int32_t *err;
     int32_t *ticket;           // [B] next row group of the pending window (sdp::for_each_rowgroup); zeroed by the control step
     int n_rg, n_strips_wg;
-    int M, N, W, hopf, path_cap;
+    int M, live_stride, W, hopf, path_cap;
     int fill_separate;         // long windows: the hand-over's fill and column records by wtw_big_fill_kernel
+    // per-stream references (rts_wtw_create_refs), NULL for a single-reference handle: stream b follows frames
+    // [ref_first[b], ref_first[b] + ref_len[b]) of `ref`.  The kernels take every reference quantity from wtw_ref().
+    const long long *ref_first;
+    const int32_t *ref_len;
 };
+
+// Stream b's reference: its frames, its length M and its live capacity N = 2M (wtw.py:52).  Plain loads of a uniform
+// address; every kernel resolves this once, at its start.
+struct WtwRef {
+    const double *ref;
+    int M, N;
+};
+__device__ __forceinline__ WtwRef wtw_ref(const WtwArgs &g, int b) {
+    WtwRef r;
+    if (g.ref_first) {
+        r.ref = g.ref + g.ref_first[b] * kWF;
+        r.M = g.ref_len[b];
+    } else {
+        r.ref = g.ref;
+        r.M = g.M;
+    }
+    r.N = 2 * r.M;
+    return r;
+}
 
 __device__ __forceinline__ double wtw_dot_chain(const double *x, const double *y) {
     double s = 0.0;
@@ -101,7 +124,8 @@ __global__ void __launch_bounds__(256) wtw_advance_kernel(WtwArgs g) {
     __shared__ long long s_cells;
 
     int32_t *st = g.state + (size_t)b * 8;
-    const double *live = g.live + (size_t)b * g.N * kWF;
+    const double *live = g.live + (size_t)b * g.live_stride * kWF;
+    const WtwRef sr = wtw_ref(g, b);
     auto Bm = [&]() {
         if constexpr (BL)
             return bl;
@@ -111,7 +135,7 @@ __global__ void __launch_bounds__(256) wtw_advance_kernel(WtwArgs g) {
     // `appended` may exceed the capacity N: the excess columns were dropped by the append kernel and mean
     // "the next column does not fit" (wtw.py:92 would raise IndexError) once the stored ones are consumed
     const int appended_raw = g.appended[b];
-    const int appended = appended_raw < g.N ? appended_raw : g.N;
+    const int appended = appended_raw < sr.N ? appended_raw : sr.N;
 
     if (tid == 0) {
         s_chroma_ptr = st[0];
@@ -130,7 +154,7 @@ __global__ void __launch_bounds__(256) wtw_advance_kernel(WtwArgs g) {
             int go = 0;
             if (s_status == RTS_RUNNING && s_chroma_ptr < appended) {
                 s_chroma_ptr += 1;
-                if (s_ref_ptr >= (g.M - 1 - W) || s_live_ptr >= (g.N - 1 - W))
+                if (s_ref_ptr >= (sr.M - 1 - W) || s_live_ptr >= (sr.N - 1 - W))
                     s_status = RTS_STOP_REF_END;
                 else
                     go = 1;
@@ -144,10 +168,10 @@ __global__ void __launch_bounds__(256) wtw_advance_kernel(WtwArgs g) {
             const int lp = s_live_ptr, rp = s_ref_ptr;
             const int n = W;
             int m = W;
-            if (rp + m > g.M) m = g.M - rp;  // numpy slice truncation of chroma_ref[:, rp:rp+W]
+            if (rp + m > sr.M) m = sr.M - rp;  // numpy slice truncation of chroma_ref[:, rp:rp+W]
             if (m <= 0) break;
             for (int idx = tid; idx < n * kWF; idx += kWtwNT) xs_l[idx] = live[(size_t)lp * kWF + idx];
-            for (int idx = tid; idx < m * kWF; idx += kWtwNT) ys_l[idx] = g.ref[(size_t)rp * kWF + idx];
+            for (int idx = tid; idx < m * kWF; idx += kWtwNT) ys_l[idx] = sr.ref[(size_t)rp * kWF + idx];
             const double *xs = xs_l, *ys = ys_l;
             __syncthreads();
             for (int i = tid; i < n; i += kWtwNT) nx[i] = sqrt(wtw_dot_chain(xs + i * kWF, xs + i * kWF));
@@ -248,7 +272,7 @@ __global__ void __launch_bounds__(256) wtw_advance_kernel(WtwArgs g) {
     }
     __syncthreads();
     if (tid == 0) {
-        if (s_status == RTS_RUNNING && s_chroma_ptr >= g.N && appended_raw > g.N) s_status = RTS_LIVE_OVERFLOW;
+        if (s_status == RTS_RUNNING && s_chroma_ptr >= sr.N && appended_raw > sr.N) s_status = RTS_LIVE_OVERFLOW;
         st[0] = s_chroma_ptr;
         st[1] = s_live_ptr;
         st[2] = s_ref_ptr;
@@ -403,10 +427,11 @@ __global__ void __launch_bounds__(R == 1 ? 256 : 512) wtw_win_kernel(WtwArgs g) 
     double *nypre = ypre + kWinPrefN * kWF;                                       // [kWinPrefN] their norms
 
     int32_t *st = g.state + (size_t)b * 8;
-    const double *live = g.live + (size_t)b * g.N * kWF;
+    const double *live = g.live + (size_t)b * g.live_stride * kWF;
     int32_t *path = g.path + (size_t)b * g.path_cap * 2;
+    const WtwRef sr = wtw_ref(g, b);
     const int appended_raw = g.appended[b];
-    const int appended = appended_raw < g.N ? appended_raw : g.N;
+    const int appended = appended_raw < sr.N ? appended_raw : sr.N;
     // state in registers (uniform: every thread computes the same values; n_path is kept by wave 0 only)
     int chroma_ptr = st[0], live_ptr = st[1], ref_ptr = st[2], status = st[3], n_path = st[4], n_windows = st[5];
     long long cells = ((long long)(uint32_t)st[7] << 32) | (uint32_t)st[6];
@@ -420,13 +445,13 @@ __global__ void __launch_bounds__(R == 1 ? 256 : 512) wtw_win_kernel(WtwArgs g) 
         int pending = 0, m = 0;
         const int n = W;
         if (status == RTS_RUNNING && chroma_ptr < appended) {
-            if (ref_ptr >= (g.M - 1 - W) || live_ptr >= (g.N - 1 - W)) {
+            if (ref_ptr >= (sr.M - 1 - W) || live_ptr >= (sr.N - 1 - W)) {
                 chroma_ptr += 1;
                 status = RTS_STOP_REF_END;
             } else if (live_ptr + W <= appended) {
                 chroma_ptr = live_ptr + W;
                 m = W;
-                if (ref_ptr + m > g.M) m = g.M - ref_ptr;
+                if (ref_ptr + m > sr.M) m = sr.M - ref_ptr;
                 pending = m > 0 ? 1 : 0;
                 if (!pending) chroma_ptr = appended;
             } else {
@@ -506,8 +531,8 @@ __global__ void __launch_bounds__(R == 1 ? 256 : 512) wtw_win_kernel(WtwArgs g) 
                 ny0 = nypre[off];
             } else {
                 // my columns' reference frames first (their latency hides behind the staging of the rows)
-                sdp::load_frame(g.ref, 1, (long long)rp + (lane < m ? lane : m - 1), y0);
-                if (m > 64) sdp::load_frame(g.ref, 1, (long long)rp + (64 + lane < m ? 64 + lane : m - 1), y1);
+                sdp::load_frame(sr.ref, 1, (long long)rp + (lane < m ? lane : m - 1), y0);
+                if (m > 64) sdp::load_frame(sr.ref, 1, (long long)rp + (64 + lane < m ? 64 + lane : m - 1), y1);
                 // my rows (cwv, cwv + NCW, ...) into my slice of xs / nx: wave-private, no barrier
                 for (int q = lane; q < nrows * kWF; q += 64) {
                     const int row = cwv + NCW * (q / kWF);
@@ -591,7 +616,7 @@ __global__ void __launch_bounds__(R == 1 ? 256 : 512) wtw_win_kernel(WtwArgs g) 
             const int nrows = (n - cwv + NCW - 1) / NCW;
             for (int q = lane; q < nrows * kWF; q += 64) {
                 const int row = cwv + NCW * (q / kWF);
-                const int fr = (nlp + row < g.N) ? nlp + row : g.N - 1;
+                const int fr = (nlp + row < sr.N) ? nlp + row : sr.N - 1;
                 xs[row * kWF + q % kWF] = live[(size_t)fr * kWF + q % kWF];
             }
             for (int q = lane; q < nrows; q += 64) {
@@ -604,7 +629,7 @@ __global__ void __launch_bounds__(R == 1 ? 256 : 512) wtw_win_kernel(WtwArgs g) 
             if (wave <= 2) {  // waves 1 and 2: 64 reference frames each
                 const int slot = 64 * (wave - 1) + lane;
                 double yv[kWF];
-                sdp::load_frame(g.ref, 1, (long long)((rp + slot < g.M) ? rp + slot : g.M - 1), yv);
+                sdp::load_frame(sr.ref, 1, (long long)((rp + slot < sr.M) ? rp + slot : sr.M - 1), yv);
 #pragma unroll
                 for (int f = 0; f < kWF; f++) ypre[slot * kWF + f] = yv[f];
                 nypre[slot] = sdp::WtwPolicy::norm(yv);
@@ -674,7 +699,7 @@ __global__ void __launch_bounds__(R == 1 ? 256 : 512) wtw_win_kernel(WtwArgs g) 
         if (b == 0 && tid == 0) g_win_stamps[5] += 1;
 #endif
     }
-    if (status == RTS_RUNNING && chroma_ptr >= g.N && appended_raw > g.N) status = RTS_LIVE_OVERFLOW;
+    if (status == RTS_RUNNING && chroma_ptr >= sr.N && appended_raw > sr.N) status = RTS_LIVE_OVERFLOW;
     if (tid == 0) {
         st[0] = chroma_ptr;
         st[1] = live_ptr;
@@ -698,7 +723,7 @@ __global__ void __launch_bounds__(H == 2 ? 384 : 256) wtw_big_dp_kernel(WtwArgs 
     if (ctl[0] == 0) return;  // no window pending for this stream
     const int lp = ctl[1];
     sdp::Problem pb;
-    pb.x = g.live + ((size_t)b * g.N + lp) * kWF;  // rows: the live window (wtw.py:101)
+    pb.x = g.live + ((size_t)b * g.live_stride + lp) * kWF;  // rows: the live window (wtw.py:101)
     pb.x_f64 = 1;
     pb.yrec = g.yrec + (size_t)b * g.W * sdp::kYRec;  // columns: the reference window (wtw.py:102), prepared by ctl
     pb.M = ctl[3];
@@ -741,11 +766,12 @@ __global__ void __launch_bounds__(64) wtw_big_segment_kernel(WtwArgs g) {
 // become float64 records with their norms.  `tid` of `nt` threads share the work.
 __device__ __forceinline__ void wtw_window_handover(const WtwArgs &g, int b, int ref_ptr, int nm, size_t tid, size_t nt) {
     const int W = g.W;
+    const WtwRef sr = wtw_ref(g, b);
     unsigned long long *bnd = g.bnd + (size_t)b * sdp::n_strips(W) * W;
     const size_t words = (size_t)(g.n_rg > 1 ? g.n_rg - 1 : 0) * nm;
     for (size_t k = tid; k < words; k += nt) bnd[k] = sdp::kSentinel;
     for (size_t col = tid; col < (size_t)nm; col += nt)
-        sdp::prep_column<sdp::WtwPolicy>(g.ref, 1, (long long)ref_ptr + (long long)col,
+        sdp::prep_column<sdp::WtwPolicy>(sr.ref, 1, (long long)ref_ptr + (long long)col,
                                          g.yrec + (size_t)b * W * sdp::kYRec - (size_t)ref_ptr * sdp::kYRec);
 }
 
@@ -804,8 +830,9 @@ __device__ __forceinline__ void wtw_ctl_body(const WtwArgs &g) {
     }
     __syncthreads();
     // ---- bookkeeping up to the next event (uniform across the workgroup: everything below depends on state only)
+    const WtwRef sr = wtw_ref(g, b);
     const int appended_raw = g.appended[b];
-    const int appended = appended_raw < g.N ? appended_raw : g.N;
+    const int appended = appended_raw < sr.N ? appended_raw : sr.N;
     int chroma_ptr = st[0], status = st[3], n_windows = st[5];
     long long cells = ((long long)(uint32_t)st[7] << 32) | (uint32_t)st[6];
     if (pending) {
@@ -814,21 +841,21 @@ __device__ __forceinline__ void wtw_ctl_body(const WtwArgs &g) {
     }
     int next_pending = 0, nn = 0, nm = 0;
     if (status == RTS_RUNNING && chroma_ptr < appended) {
-        if (ref_ptr >= (g.M - 1 - W) || live_ptr >= (g.N - 1 - W)) {
+        if (ref_ptr >= (sr.M - 1 - W) || live_ptr >= (sr.N - 1 - W)) {
             chroma_ptr += 1;  // wtw.py:92-97: the next column trips the boundary check
             status = RTS_STOP_REF_END;
         } else if (live_ptr + W <= appended) {
             chroma_ptr = live_ptr + W;  // the column that completes the window (wtw.py:100)
             nn = W;
             nm = W;
-            if (ref_ptr + nm > g.M) nm = g.M - ref_ptr;  // numpy slice truncation of chroma_ref[:, rp:rp+W]
+            if (ref_ptr + nm > sr.M) nm = sr.M - ref_ptr;  // numpy slice truncation of chroma_ref[:, rp:rp+W]
             next_pending = nm > 0 ? 1 : 0;
             if (!next_pending) chroma_ptr = appended;  // unreachable (wtw.py:96 stops first); never stall
         } else {
             chroma_ptr = appended;
         }
     }
-    if (!next_pending && status == RTS_RUNNING && chroma_ptr >= g.N && appended_raw > g.N) status = RTS_LIVE_OVERFLOW;
+    if (!next_pending && status == RTS_RUNNING && chroma_ptr >= sr.N && appended_raw > sr.N) status = RTS_LIVE_OVERFLOW;
     if (next_pending && !g.fill_separate) wtw_window_handover(g, b, ref_ptr, nm, tid, NT);
     __syncthreads();
     if (tid == 0) {
@@ -865,11 +892,12 @@ __global__ void __launch_bounds__(64 * sdp::kTailStrips) wtw_big_tail_ctl_kernel
 }
 
 // wtw.py:76-77: the check made at the top of insert(), before any column is processed.
-__global__ void wtw_precheck_kernel(int32_t *state, int B, int M, int N) {
+__global__ void wtw_precheck_kernel(int32_t *state, int B, int M, const int32_t *ref_len) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    const int Mb = ref_len ? ref_len[b] : M, Nb = 2 * Mb;  // this stream's M and N = 2M (wtw.py:52)
     int32_t *st = state + (size_t)b * 8;
-    if (st[3] == RTS_RUNNING && (st[2] >= M - 1 || st[1] >= N - 1)) st[3] = RTS_STOP_REF_END;
+    if (st[3] == RTS_RUNNING && (st[2] >= Mb - 1 || st[1] >= Nb - 1)) st[3] = RTS_STOP_REF_END;
 }
 
 // Append n_new[b] columns from cols [B][n_max][F] to the live history; columns beyond the 2M capacity
@@ -877,7 +905,8 @@ __global__ void wtw_precheck_kernel(int32_t *state, int B, int M, int N) {
 // LIVE_OVERFLOW by the advance kernel once it has walked the columns that did fit.
 // grid (B, slices): a push of a whole recording is 200 KB per stream, so several workgroups share a stream's copy.  Every
 // slice reads the old count from `appended`; slice 0 writes the new one to `appended_next`, and the host swaps the two
-// arrays after the launch (the kernels that follow read the new one).
+// arrays after the launch (the kernels that follow read the new one).  N is the history stride: with per-stream references
+// 2 M_max, and the kernels that walk the columns apply a stream's own capacity 2 M_b.
 constexpr int kWtwAppendSlices = 8;
 __global__ void wtw_append_kernel(double *live, int32_t *appended, int32_t *appended_next, int32_t *state, const void *cols,
                                   int cols_f64, const int32_t *n_new, int n_uniform, int n_max, int B, int N) {
@@ -908,7 +937,10 @@ __global__ void wtw_append_kernel(double *live, int32_t *appended, int32_t *appe
 
 struct rts_wtw {
     const double *ref;
-    int M, N, B, W, hopf, path_cap;
+    int M, B, W, hopf, path_cap;
+    int live_stride;  // frames per stream in `live`: 2M (2 M_max with per-stream references)
+    long long *ref_first;  // per-stream references (rts_wtw_create_refs): [B] first frames, device; NULL otherwise
+    int32_t *ref_len;      // [B] lengths M_b, device
     double *live;
     int32_t *appended, *appended_next, *state, *path;
     int8_t *bwork;
@@ -937,12 +969,14 @@ static int wtw_check_device(const rts_wtw *h) {
 
 extern "C" {
 
-int rts_wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win_frames, int hop_frames, int keep_last_d,
-                   rts_wtw **out) {
-    using namespace rts;
-    if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!chroma_ref_dev) return set_error(RTS_ERR_INVALID, "chroma_ref_dev is NULL");
+}  // extern "C"
+
+namespace rts {
+
+// The constructor behind rts_wtw_create (first_host == NULL: one reference of M frames) and rts_wtw_create_refs (M =
+// M_max, per-stream tables of B entries, already checked).  Every argument is checked before the first HIP call.
+static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win_frames, int hop_frames, int keep_last_d,
+                      const long long *first_host, const int32_t *len_host, rts_wtw **out) {
     if (F < 1) return set_error(RTS_ERR_INVALID, "F must be >= 1 (got %d)", F);
     if (F != kWF) return set_error(RTS_ERR_UNSUPPORTED, "F must be 12 chroma bins (got %d)", F);
     if (M < 1 || B < 1) return set_error(RTS_ERR_INVALID, "M and B must be >= 1");
@@ -959,11 +993,11 @@ int rts_wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win_fr
         return set_error(RTS_ERR_HIP, "hipGetDevice failed: %s", hipGetErrorString(ed));
     }
     h->M = M;
-    h->N = 2 * M;  // wtw.py:52
+    h->live_stride = 2 * M;  // wtw.py:52
     h->B = B;
     h->W = win_frames;
     h->hopf = hop_frames;
-    h->path_cap = (h->N / hop_frames + 2) * (win_frames + hop_frames + 2);
+    h->path_cap = (h->live_stride / hop_frames + 2) * (win_frames + hop_frames + 2);
     const int W = win_frames;
     // Windows of more than one strip (64 rows) take the strip-DP path: measured on 64 streams at wtw_live.py's W = 100 /
     // hop = 50 it is twice as fast as the single-workgroup sweep despite its five launches per window.
@@ -1009,7 +1043,11 @@ int rts_wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win_fr
                   (W <= kWtwLdsB ? (size_t)W * W : 0) + 64;
     }
     hipError_t e;
-    if ((e = hipMalloc((void **)&h->live, sizeof(double) * kWF * (size_t)h->N * B)) != hipSuccess ||
+    if ((e = hipMalloc((void **)&h->live, sizeof(double) * kWF * (size_t)h->live_stride * B)) != hipSuccess ||
+        (first_host && (e = hipMalloc((void **)&h->ref_first, sizeof(long long) * (size_t)B)) != hipSuccess) ||
+        (first_host && (e = hipMalloc((void **)&h->ref_len, sizeof(int32_t) * (size_t)B)) != hipSuccess) ||
+        (first_host && (e = hipMemcpy(h->ref_first, first_host, sizeof(long long) * (size_t)B, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (first_host && (e = hipMemcpy(h->ref_len, len_host, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice)) != hipSuccess) ||
         (e = hipMalloc((void **)&h->appended, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->appended_next, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->state, sizeof(int32_t) * 8 * (size_t)B)) != hipSuccess ||
@@ -1063,9 +1101,46 @@ int rts_wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win_fr
     return RTS_OK;
 }
 
+int wtw_batch(const rts_wtw *h) { return h->B; }
+
+}  // namespace rts
+
+extern "C" {
+
+int rts_wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win_frames, int hop_frames, int keep_last_d,
+                   rts_wtw **out) {
+    using namespace rts;
+    if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!chroma_ref_dev) return set_error(RTS_ERR_INVALID, "chroma_ref_dev is NULL");
+    return wtw_create(chroma_ref_dev, F, M, B, win_frames, hop_frames, keep_last_d, nullptr, nullptr, out);
+}
+
+int rts_wtw_create_refs(const double *chroma_refs_dev, int F, long long n_ref_frames, const long long *first_host,
+                        const int32_t *len_host, int B, int win_frames, int hop_frames, int keep_last_d, rts_wtw **out) {
+    using namespace rts;
+    if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!chroma_refs_dev) return set_error(RTS_ERR_INVALID, "chroma_refs_dev is NULL");
+    if (!first_host || !len_host) return set_error(RTS_ERR_INVALID, "first_host / len_host is NULL");
+    if (B < 1) return set_error(RTS_ERR_INVALID, "B must be >= 1 (got %d)", B);
+    int m_max = 0;
+    for (int b = 0; b < B; b++) {
+        if (len_host[b] < 1) return set_error(RTS_ERR_INVALID, "stream %d: len must be >= 1 (got %d)", b, len_host[b]);
+        if (first_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: first must be >= 0 (got %lld)", b, first_host[b]);
+        if (first_host[b] > n_ref_frames - len_host[b])
+            return set_error(RTS_ERR_INVALID, "stream %d: frames [%lld, %lld) lie outside the %lld reference frames", b,
+                             first_host[b], first_host[b] + len_host[b], n_ref_frames);
+        if (len_host[b] > m_max) m_max = len_host[b];
+    }
+    return wtw_create(chroma_refs_dev, F, m_max, B, win_frames, hop_frames, keep_last_d, first_host, len_host, out);
+}
+
 int rts_wtw_destroy(rts_wtw *h) {
     if (!h) return RTS_OK;
     if (h->live) (void)hipFree(h->live);
+    if (h->ref_first) (void)hipFree(h->ref_first);
+    if (h->ref_len) (void)hipFree(h->ref_len);
     if (h->appended) (void)hipFree(h->appended);
     if (h->appended_next) (void)hipFree(h->appended_next);
     if (h->state) (void)hipFree(h->state);
@@ -1097,7 +1172,7 @@ int rts_wtw_reset(rts_wtw *h, void *stream) {
     RTS_HIP(hipMemsetAsync(h->appended, 0, sizeof(int32_t) * (size_t)h->B, s));
     RTS_HIP(hipMemsetAsync(h->state, 0, sizeof(int32_t) * 8 * (size_t)h->B, s));
     // wtw.py:55: chroma_live starts as zeros
-    RTS_HIP(hipMemsetAsync(h->live, 0, sizeof(double) * kWF * (size_t)h->N * h->B, s));
+    RTS_HIP(hipMemsetAsync(h->live, 0, sizeof(double) * kWF * (size_t)h->live_stride * h->B, s));
     if (h->ctl) RTS_HIP(hipMemsetAsync(h->ctl, 0, sizeof(int32_t) * 8 * (size_t)h->B, s));
     if (h->err) RTS_HIP(hipMemsetAsync(h->err, 0, 16, s));
     if (h->ticket) RTS_HIP(hipMemsetAsync(h->ticket, 0, sizeof(int32_t) * (size_t)h->B, s));
@@ -1114,12 +1189,12 @@ int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, co
     if (int rc = wtw_check_device(h); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (precheck) {
-        hipLaunchKernelGGL(wtw_precheck_kernel, dim3((h->B + 63) / 64), dim3(64), 0, s, h->state, h->B, h->M, h->N);
+        hipLaunchKernelGGL(wtw_precheck_kernel, dim3((h->B + 63) / 64), dim3(64), 0, s, h->state, h->B, h->M, h->ref_len);
         RTS_HIP(hipGetLastError());
     }
     if (n_max == 0) return RTS_OK;
     hipLaunchKernelGGL(wtw_append_kernel, dim3(h->B, n_max >= 64 ? kWtwAppendSlices : 1), dim3(256), 0, s, h->live, h->appended,
-                       h->appended_next, h->state, cols_dev, cols_dtype == RTS_F64, n_new_dev, n_max, n_max, h->B, h->N);
+                       h->appended_next, h->state, cols_dev, cols_dtype == RTS_F64, n_new_dev, n_max, n_max, h->B, h->live_stride);
     {
         int32_t *t = h->appended;
         h->appended = h->appended_next;
@@ -1149,7 +1224,9 @@ int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, co
     g.fill_separate = ((size_t)(h->n_rg > 1 ? h->n_rg - 1 : 0) * h->W > (1u << 16)) ? 1 : 0;  // more than 0.5 MB of boundary words
     g.n_strips_wg = h->big_waves;
     g.M = h->M;
-    g.N = h->N;
+    g.live_stride = h->live_stride;
+    g.ref_first = h->ref_first;
+    g.ref_len = h->ref_len;
     g.W = h->W;
     g.hopf = h->hopf;
     g.path_cap = h->path_cap;
@@ -1265,7 +1342,7 @@ int rts_wtw_device_views(rts_wtw *h, double **live_chroma_dev, int *live_capacit
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (live_chroma_dev) *live_chroma_dev = h->live;
-    if (live_capacity) *live_capacity = h->N;
+    if (live_capacity) *live_capacity = h->live_stride;
     if (last_d_dev) *last_d_dev = h->dlast;
     return RTS_OK;
 }

@@ -1,4 +1,4 @@
-"""Many live audio streams followed against one reference, entirely on the device.
+"""Many live audio streams followed against one reference (or one reference each), entirely on the device.
 
 This is the batched form of the reference's microphone loops (livenote_live.py:161-209 for the OTW family,
 wtw.py:71-93 for WTW): audio arrives in buffers of arbitrary size; whenever a stream has at least ``fft_len``
@@ -24,22 +24,43 @@ _KINDS = {np.dtype(np.float32): nat.F32, np.dtype(np.int16): nat.I16}
 class LiveSession(object):
     def __init__(self, ref_chroma, batch, c=500, max_run_count=3, variant="otw", fft_len=4096, hop_size=2048,
                  fs=22050, max_pending=1 << 16, device="cuda:0", wtw_params=None):
-        """``ref_chroma``: (12, N) reference chroma (e.g. chroma.wav_to_chroma(ref_path)).  With ``wtw_params``
-        ({'dtw_win_size', 'dtw_hop_size'} in samples, like wtw.py:29-30) the streams are followed by windowed time
-        warping instead of ``variant`` ('otw' | 'livenote' | 'livenote_v2')."""
+        """``ref_chroma``: (12, N) reference chroma (e.g. chroma.wav_to_chroma(ref_path)), or a list of ``batch`` such
+        arrays, one per stream (one piece per microphone; a list entry that repeats is uploaded once).  With
+        ``wtw_params`` ({'dtw_win_size', 'dtw_hop_size'} in samples, like wtw.py:29-30) the streams are followed by
+        windowed time warping instead of ``variant`` ('otw' | 'livenote' | 'livenote_v2')."""
         self.plan = ChromaPlan(fft_len, hop_size, fs, device)
         self.dev = self.device = self.plan.device
         self.B, self.L, self.H = int(batch), int(fft_len), int(hop_size)
         self.cap = int(max_pending)
-        ref = np.asarray(ref_chroma, dtype=np.float64)
+        per_stream = isinstance(ref_chroma, (list, tuple))
+        if per_stream:
+            if len(ref_chroma) != self.B:
+                raise ValueError("%d references for %d streams" % (len(ref_chroma), self.B))
+            conv = {}
+            refs = [conv.setdefault(id(r), np.asarray(r, dtype=np.float64)) for r in ref_chroma]
+        else:
+            ref = np.asarray(ref_chroma, dtype=np.float64)
         self.otw = self.wtw = None
         if wtw_params is None:
-            self.otw = BatchedOTW(ref, c, max_run_count, batch=batch, variant=variant, device=device, dtype=torch.float64)
+            if per_stream:
+                self.otw = BatchedOTW.with_references(refs, c, max_run_count, variant=variant, device=device,
+                                                      dtype=torch.float64)
+            else:
+                self.otw = BatchedOTW(ref, c, max_run_count, batch=batch, variant=variant, device=device,
+                                      dtype=torch.float64)
         else:
             from .wtw import BatchedWTW
-            self._ref_dev = torch.from_numpy(np.ascontiguousarray(ref.T)).to(self.dev)
-            self.wtw = BatchedWTW(self._ref_dev, wtw_params['dtw_win_size'] // self.H, wtw_params['dtw_hop_size'] // self.H,
-                                  batch)
+            win, hopf = wtw_params['dtw_win_size'] // self.H, wtw_params['dtw_hop_size'] // self.H
+            if per_stream:
+                devs = {}
+                for r in refs:
+                    if id(r) not in devs:
+                        devs[id(r)] = torch.from_numpy(np.ascontiguousarray(r.T)).to(self.dev)
+                self._ref_dev = [devs[id(r)] for r in refs]
+                self.wtw = BatchedWTW.with_references(self._ref_dev, win, hopf)
+            else:
+                self._ref_dev = torch.from_numpy(np.ascontiguousarray(ref.T)).to(self.dev)
+                self.wtw = BatchedWTW(self._ref_dev, win, hopf, batch)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.dev):
             nat.check(nat.lib.rts_live_create(self.plan._h, self.otw._h if self.otw else None,

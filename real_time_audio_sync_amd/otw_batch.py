@@ -1,4 +1,5 @@
-"""Batched online time warping on one MI355X: B independent live streams against one reference.
+"""Batched online time warping on one MI355X: B independent live streams against one reference, or each against its
+own (``BatchedOTW.with_references``).
 
 This is the host-side object behind the drop-in classes (otw_eran.OnlineTimeWarping,
 livenote.LiveNote, livenote_v2.LiveNoteV2) and behind bench.py.  torch supplies device memory and
@@ -33,29 +34,78 @@ def frames_tensor(x, device, dtype=None):
 _on_device = nat.on_device
 
 
+def _concat_refs(refs, to_frames):
+    """Per-stream references -> (one device tensor [n_ref_frames][12], int64 first frames [B], int32 lengths [B]).  A
+    reference object that appears more than once is converted and uploaded once; its range is reused."""
+    if len(refs) < 1:
+        raise ValueError("at least one reference is needed")
+    parts, seen, first, lens, off = [], {}, [], [], 0
+    for r in refs:
+        if id(r) not in seen:
+            t = to_frames(r)
+            if parts and t.dtype != parts[0].dtype:
+                raise TypeError("all references must have the same dtype (%s, %s)" % (parts[0].dtype, t.dtype))
+            seen[id(r)] = (off, int(t.shape[0]))
+            parts.append(t)
+            off += int(t.shape[0])
+        f, n = seen[id(r)]
+        first.append(f)
+        lens.append(n)
+    return torch.cat(parts).contiguous(), np.array(first, dtype=np.int64), np.array(lens, dtype=np.int32)
+
+
 class BatchedOTW:
     """``ref``: (12, N) feature-major array/tensor, or a device tensor already [N][12] with
     ``frame_major=True``.  ``variant``: 'otw' | 'livenote' | 'livenote_v2'."""
 
     def __init__(self, ref, c, max_run_count, batch=1, variant="otw", euclid=False, device="cuda:0",
                  dtype=None, frame_major=False, waves=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("BatchedOTW needs a ROCm GPU (no CPU fallback)")
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        torch.cuda.set_device(self.device)
+        self._set_device(device)
         if frame_major:
             self.ref = ref.to(self.device).contiguous()
         else:
             self.ref = frames_tensor(ref, self.device, dtype)
         self.N, F = self.ref.shape
+        self.ref_lens = None
         self.B, self.c = int(batch), int(c)
         self.variant = variant
         h = ctypes.c_void_p()
         nat.check(nat.lib.rts_otw_create(self.ref.data_ptr(), _np_dtype_code(self.ref.dtype), F, self.N, self.B,
                                          self.c, int(max_run_count), _VARIANTS[variant],
                                          nat.COST_EUCLID if euclid else nat.COST_DOT, ctypes.byref(h)))
+        self._finish(h, waves)
+
+    @classmethod
+    def with_references(cls, refs, c, max_run_count, variant="otw", euclid=False, device="cuda:0", dtype=None,
+                        waves=None):
+        """One reference per stream (one piece per microphone): ``refs`` is a list of ``batch`` (12, N_b) arrays or
+        tensors.  Stream b behaves exactly like stream 0 of ``BatchedOTW(refs[b], ...)``.  A reference object that
+        appears more than once is uploaded once.  ``N`` is the longest N_b, ``ref_lens`` holds them all.  The dense
+        mirror is not available on such a handle (``enable_dense`` / ``replay_dense`` raise)."""
+        self = cls.__new__(cls)
+        self._set_device(device)
+        self.ref, first, lens = _concat_refs(refs, lambda r: frames_tensor(r, self.device, dtype))
+        F = self.ref.shape[1]
+        self.N, self.ref_lens = int(lens.max()), lens
+        self.B, self.c = len(refs), int(c)
+        self.variant = variant
+        h = ctypes.c_void_p()
+        nat.check(nat.lib.rts_otw_create_refs(self.ref.data_ptr(), _np_dtype_code(self.ref.dtype), F, self.ref.shape[0],
+                                              first.ctypes.data, lens.ctypes.data, self.B, self.c, int(max_run_count),
+                                              _VARIANTS[variant], nat.COST_EUCLID if euclid else nat.COST_DOT,
+                                              ctypes.byref(h)))
+        self._finish(h, waves)
+        return self
+
+    def _set_device(self, device):
+        if not torch.cuda.is_available():
+            raise RuntimeError("BatchedOTW needs a ROCm GPU (no CPU fallback)")
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        torch.cuda.set_device(self.device)
+
+    def _finish(self, h, waves):
         self._h = h
         if waves is not None:
             nat.check(nat.lib.rts_otw_set_waves(self._h, int(waves)))
@@ -161,6 +211,8 @@ class BatchedOTW:
     def enable_dense(self):
         """Allocate and attach the reference's dense (2N x N) acc_cost / cost matrices per stream
         (float64 device tensors [B][2N][N]); every evaluated cell is mirrored into them."""
+        if self.ref_lens is not None:   # refused by the library: one [2N][N] layout per handle
+            nat.check(nat.lib.rts_otw_set_dense(self._h, None, None, self._stream()))
         self.dense_acc = torch.empty((self.B, 2 * self.N, self.N), dtype=torch.float64, device=self.device)
         self.dense_cost = torch.empty((self.B, 2 * self.N, self.N), dtype=torch.float64, device=self.device)
         nat.check(nat.lib.rts_otw_set_dense(self._h, self.dense_acc.data_ptr(), self.dense_cost.data_ptr(),
@@ -172,6 +224,8 @@ class BatchedOTW:
         """The reference's dense (2N x N) acc_cost / cost matrices (float64 device tensors [B][2N][N]) for
         everything consumed since the last reset, recomputed on demand by a second pass over the kept frames
         (rts_otw_replay_dense); the tracker itself never pays for them."""
+        if self.ref_lens is not None:   # refused by the library, before anything is allocated
+            nat.check(nat.lib.rts_otw_replay_dense(self._h, None, nat.F64, 0, None, None, None, self._stream()))
         acc = torch.empty((self.B, 2 * self.N, self.N), dtype=torch.float64, device=self.device)
         cost = torch.empty((self.B, 2 * self.N, self.N), dtype=torch.float64, device=self.device)
         if self._keep is not None:   # the frames of the last run(): handed in again, the library keeps no pointer to them

@@ -22,12 +22,35 @@ class BatchedWTW(object):
         torch.cuda.set_device(self.device)
         self.ref = chroma_ref_dev
         self.M = chroma_ref_dev.shape[0]
+        self.ref_lens = None
         self.B, self.W, self.hopf = int(batch), int(win_frames), int(hop_frames)
         h = ctypes.c_void_p()
         nat.check(nat.lib.rts_wtw_create(self.ref.data_ptr(), 12, self.M, self.B, self.W, self.hopf,
                                          int(bool(keep_last_d)), ctypes.byref(h)))
         self._h = h
         self._keep_d = keep_last_d
+
+    @classmethod
+    def with_references(cls, chroma_refs, win_frames, hop_frames, keep_last_d=False):
+        """One reference chroma per stream: ``chroma_refs`` is a list of ``batch`` device tensors [M_b][12] float64
+        (one device).  Stream b behaves exactly like stream 0 of ``BatchedWTW(chroma_refs[b], ...)``; a tensor that
+        appears more than once is copied once.  ``M`` is the longest M_b, ``ref_lens`` holds them all."""
+        from .otw_batch import _concat_refs
+        for r in chroma_refs:
+            assert r.dtype == torch.float64 and r.dim() == 2 and r.shape[1] == 12
+        self = cls.__new__(cls)
+        self.device = chroma_refs[0].device
+        torch.cuda.set_device(self.device)
+        self.ref, first, lens = _concat_refs(chroma_refs, lambda r: r.to(self.device))
+        self.M, self.ref_lens = int(lens.max()), lens
+        self.B, self.W, self.hopf = len(chroma_refs), int(win_frames), int(hop_frames)
+        h = ctypes.c_void_p()
+        nat.check(nat.lib.rts_wtw_create_refs(self.ref.data_ptr(), 12, self.ref.shape[0], first.ctypes.data,
+                                              lens.ctypes.data, self.B, self.W, self.hopf, int(bool(keep_last_d)),
+                                              ctypes.byref(h)))
+        self._h = h
+        self._keep_d = keep_last_d
+        return self
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

@@ -1,0 +1,319 @@
+"""Per-stream references (rts_otw_create_refs / rts_wtw_create_refs, BatchedOTW.with_references,
+BatchedWTW.with_references, LiveSession with a list of references): stream b must behave bit for bit like stream 0 of a
+single-reference handle made with its own reference, including every limit the reference derives from its length."""
+import ctypes
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+PARAMS = {'fft_len': 4096, 'hop_size': 2048, 'dtw_win_size': 4096 * 10, 'dtw_hop_size': 2048 * 10}  # tests.py:174
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+
+
+def _otw_batch(seed=0):
+    """16 streams, references of 150..900 frames, ragged lives.  Stream 1: a slow rendition that runs past its own 2N_b
+    (LIVE_OVERFLOW) while 2N_max is far away; stream 2: runs into its reference's end (stop); stream 3: one frame;
+    stream 4: no frame at all."""
+    from real_time_audio_sync_amd import synth
+    rs = np.random.RandomState(seed)
+    lens = [900, 150, 160, 300, 220] + [int(x) for x in rs.randint(150, 901, size=11)]
+    refs = [synth.synth_ref(n, seed=seed * 100 + b) for b, n in enumerate(lens)]
+    lives = [synth.synth_live(r, seed=seed * 100 + 50 + b) for b, r in enumerate(refs)]
+    lives[1] = synth.synth_live(refs[1], seed=7, lo=0.3, hi=0.45)           # ~2.7 N_b frames
+    assert 2 * lens[1] < lives[1].shape[1] < 2 * max(lens)
+    lives[2] = np.concatenate([lives[2], np.repeat(refs[2][:, -1:], 60, axis=1)], axis=1)
+    lives[3] = lives[3][:, :1]
+    lives[4] = lives[4][:, :0]
+    return refs, lives
+
+
+def _oracle_run(oracle, ref, live, c, variant, euclid):
+    o = oracle.OtwOracle(ref, c, 3, variant=variant, cost=oracle.COST_EUCLID if euclid else oracle.COST_DOT)
+    n = o.run(live) if live.shape[1] else 0
+    return o, n
+
+
+def _check_vs_oracle(eng, b, o, n, tag):
+    st, so = eng.state(b), o.state
+    assert np.array_equal(eng.path(b), o.path), tag
+    for k in ("t", "j", "direction", "previous", "run_count", "status"):
+        assert st[k] == so[k], (tag, k, st[k], so[k])
+    assert st["consumed"] == n, tag
+    cnt = o.counters
+    assert (st["cells"], st["row_strips"], st["col_strips"]) == (cnt["cells"], cnt["row_strips"], cnt["col_strips"]), tag
+    if n:  # (a stream that never received a frame has no bands on the device yet)
+        rb, cb = eng.bands(b)
+        orb, ocb = o.bands()
+        assert np.array_equal(rb, orb, equal_nan=True) and np.array_equal(cb, ocb, equal_nan=True), tag
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_otw_per_stream_references_vs_oracle(dtype):
+    import oracle
+    from real_time_audio_sync_amd import _native as nat
+    from real_time_audio_sync_amd.otw_batch import BatchedOTW
+    tdt = torch.float32 if dtype == "f32" else torch.float64
+    refs, lives = _otw_batch()
+    variants = {"otw": oracle.OTW, "livenote": oracle.LIVENOTE, "livenote_v2": oracle.LIVENOTE_V2}
+    for variant, ov in variants.items():
+        for euclid in (False, True):
+            c = 50
+            eng = BatchedOTW.with_references(refs, c, 3, variant=variant, euclid=euclid, dtype=tdt)
+            assert eng.N == 900 and list(eng.ref_lens) == [r.shape[1] for r in refs]
+            lv, ln = eng.pack(lives, dtype=tdt)
+            eng.run(lv, ln)
+            statuses = [eng.state(b)["status"] for b in range(eng.B)]
+            assert statuses[1] == nat.LIVE_OVERFLOW and statuses[2] == nat.STOP_REF_END, statuses
+            for b in range(eng.B):
+                o, n = _oracle_run(oracle, refs[b], lives[b], c, ov, euclid)
+                _check_vs_oracle(eng, b, o, n, (variant, euclid, dtype, b))
+            eng.close()
+
+
+def _singles(refs, lives, c, tdt, waves=None):
+    """The same batch through B separate single-reference handles: per stream (state row, path, bands)."""
+    from real_time_audio_sync_amd.otw_batch import BatchedOTW
+    out = []
+    for r, l in zip(refs, lives):
+        e = BatchedOTW(r, c, 3, batch=1, dtype=tdt, waves=waves)
+        if l.shape[1]:  # (an empty stream keeps its fresh state: nothing to run)
+            lv, ln = e.pack([l], dtype=tdt)
+            e.run(lv, ln)
+        out.append((e.states()[0], e.path(0), e.bands(0) if l.shape[1] else None))
+        e.close()
+    return out
+
+
+def _check_vs_singles(eng, want, tag):
+    states = eng.states()
+    for b, (st, path, bands) in enumerate(want):
+        assert np.array_equal(states[b], st), (tag, b)
+        assert np.array_equal(eng.path(b), path), (tag, b)
+        if bands is not None:
+            rb, cb = eng.bands(b)
+            assert np.array_equal(rb, bands[0], equal_nan=True) and np.array_equal(cb, bands[1], equal_nan=True), (tag, b)
+
+
+FLAVOURS = [("default", c) for c in (20, 100, 500, 1000, 2036)] + \
+    [("spec0", c) for c in (20, 100, 500)] + [("tp0", c) for c in (20, 100, 500)] + \
+    [("waves%d" % w, c) for w in (1, 2, 4, 8) for c in (20, 500)]
+
+
+@pytest.mark.parametrize("flavour,c", FLAVOURS)
+def test_otw_every_kernel_flavour_equals_single_handles(monkeypatch, flavour, c):
+    from real_time_audio_sync_amd.otw_batch import BatchedOTW
+    if flavour == "spec0":
+        monkeypatch.setenv("RTS_OTW_SPEC", "0")
+    if flavour == "tp0":
+        monkeypatch.setenv("RTS_OTW_TP_FROM", "0")
+    waves = int(flavour[5:]) if flavour.startswith("waves") else None
+    refs, lives = _otw_batch(seed=3)
+    for tdt in (torch.float32, torch.float64):
+        want = _singles(refs, lives, c, tdt, waves)
+        eng = BatchedOTW.with_references(refs, c, 3, dtype=tdt, waves=waves)
+        lv, ln = eng.pack(lives, dtype=tdt)
+        eng.run(lv, ln)
+        _check_vs_singles(eng, want, (flavour, c, tdt))
+        eng.close()
+
+
+def test_shared_range_equals_single_reference_handle():
+    """Every stream on the range (0, N): the per-stream tables must reproduce today's handle exactly (B = 64, c = 500)."""
+    from real_time_audio_sync_amd import synth
+    from real_time_audio_sync_amd.otw_batch import BatchedOTW
+    ref, lives = synth.synth_batch(1200, 64, seed=5)
+    lives[7] = lives[7][:, :3]
+    a = BatchedOTW(ref, 500, 3, batch=64, dtype=torch.float32)
+    m = BatchedOTW.with_references([ref] * 64, 500, 3, dtype=torch.float32)
+    assert m.ref.shape[0] == ref.shape[1] and list(m.ref_lens) == [ref.shape[1]] * 64   # uploaded once
+    lv, ln = a.pack(lives)
+    a.run(lv, ln)
+    m.run(lv, ln)
+    assert np.array_equal(a.states(), m.states())
+    for b in range(64):
+        assert np.array_equal(a.path(b), m.path(b)), b
+        ra, ca = a.bands(b)
+        rm, cm = m.bands(b)
+        assert np.array_equal(ra, rm, equal_nan=True) and np.array_equal(ca, cm, equal_nan=True), b
+    a.close()
+    m.close()
+
+
+def test_insert_and_push_equal_run_and_oracle():
+    """Frame-by-frame insert() and chunked push() through the handle-owned history (stride 2 N_max) must equal run()
+    and the oracle -- stream 1 overflows at its own 2 N_b there."""
+    import oracle
+    from real_time_audio_sync_amd import _native as nat
+    from real_time_audio_sync_amd.otw_batch import BatchedOTW
+    refs, lives = _otw_batch(seed=1)
+    c = 50
+    ref_run = BatchedOTW.with_references(refs, c, 3)
+    lv, ln = ref_run.pack(lives)
+    ref_run.run(lv, ln)
+    want_states = ref_run.states()
+    want_paths = ref_run.paths()
+    assert want_states[1][nat.ST_STATUS] == nat.LIVE_OVERFLOW
+    lens = [l.shape[1] for l in lives]
+    tmax = max(lens)
+    dev = ref_run.device
+    # insert: one frame per stream per call, streams past their end inactive
+    ins = BatchedOTW.with_references(refs, c, 3)
+    for i in range(tmax):
+        fr = lv[:, i].contiguous()
+        act = torch.tensor([1 if i < n else 0 for n in lens], dtype=torch.uint8, device=dev)
+        ins.insert(fr, act)
+    # push: uneven chunks with per-stream counts
+    pus = BatchedOTW.with_references(refs, c, 3)
+    pos, chunk = 0, 37
+    while pos < tmax:
+        n_new = torch.tensor([max(0, min(chunk, n - pos)) for n in lens], dtype=torch.int32, device=dev)
+        pus.push(lv[:, pos:pos + chunk].contiguous(), n_new)
+        pos += chunk
+    for eng, tag in ((ins, "insert"), (pus, "push")):
+        assert np.array_equal(eng.states(), want_states), tag
+        for b in range(eng.B):
+            assert np.array_equal(eng.path(b), want_paths[b]), (tag, b)
+            o, n = _oracle_run(oracle, refs[b], lives[b], c, oracle.OTW, False)
+            _check_vs_oracle(eng, b, o, n, (tag, b))
+        eng.close()
+    ref_run.close()
+
+
+def test_dense_mirror_refused():
+    from real_time_audio_sync_amd import _native as nat
+    from real_time_audio_sync_amd.otw_batch import BatchedOTW
+    refs, lives = _otw_batch()
+    eng = BatchedOTW.with_references(refs[:4], 20, 3)
+    with pytest.raises(nat.RtsyncError, match="per-stream"):
+        eng.enable_dense()
+    lv, ln = eng.pack(lives[:4])
+    eng.run(lv, ln)
+    with pytest.raises(nat.RtsyncError, match="per-stream"):
+        eng.replay_dense()
+    eng.close()
+
+
+@pytest.fixture(params=["win", "win_two_waves", "older"])
+def wtw_path(request, monkeypatch):
+    monkeypatch.setenv("RTS_WTW_WIN", "0" if request.param == "older" else "1")
+    if request.param == "win_two_waves":
+        monkeypatch.setenv("RTS_WIN_FORCE_R2", "1")
+    return request.param
+
+
+@pytest.mark.parametrize("W,hopf", [(20, 10), (100, 50), (130, 7), (700, 350)])
+def test_wtw_per_stream_references_vs_oracle(wtw_path, W, hopf):
+    """Six streams with references of different M.  Stream 0's reference is shorter than W + 1 (the boundary check stops
+    it at its first column); stream 4, a fast rendition, is stopped by ref_ptr >= M_b - 1 - W; stream 3 runs out of live
+    frames early; stream 5 shares stream 1's reference."""
+    import oracle
+    from real_time_audio_sync_amd import synth
+    from real_time_audio_sync_amd.wtw import BatchedWTW
+    dev = torch.device("cuda:0")
+    Ms = [W, 3 * W + 40, 6 * W + 10, 2 * W + 5, 4 * W + 77, 3 * W + 40]
+    refs = [synth.synth_ref(m, seed=200 + b) for b, m in enumerate(Ms)]
+    refs[5] = refs[1]                                   # a repeated reference shares its range
+    lives = [synth.synth_live(r, seed=300 + b) for b, r in enumerate(refs)]
+    lives[0] = synth.synth_live(synth.synth_ref(3 * W, seed=9), seed=9)
+    lives[3] = lives[3][:, : W + 3]                     # runs out of live frames before its reference ends
+    lives[4] = synth.synth_live(refs[4], seed=304, lo=1.3, hi=1.6)
+    lives[4] = np.concatenate([lives[4], lives[4][:, ::-1]], axis=1)
+    lives = [l * (0.5 + np.random.RandomState(b).rand(1, l.shape[1])) for b, l in enumerate(lives)]
+    eng = BatchedWTW.with_references([torch.from_numpy(np.ascontiguousarray(r.T)).to(dev) for r in refs], W, hopf)
+    assert eng.M == max(Ms) and list(eng.ref_lens) == Ms
+    tmax = max(l.shape[1] for l in lives)
+    cols = np.zeros((6, tmax, 12))
+    for b, l in enumerate(lives):
+        cols[b, : l.shape[1]] = l.T
+    n_new = torch.tensor([l.shape[1] for l in lives], dtype=torch.int32, device=dev)
+    cut = (2 * W) // 3 + 1
+    eng.push(torch.from_numpy(cols[:, :cut].copy()).to(dev), torch.clamp(n_new, max=cut), precheck=True)
+    eng.push(torch.from_numpy(cols[:, cut:].copy()).to(dev), torch.clamp(n_new - cut, min=0), precheck=True)
+    for b, l in enumerate(lives):
+        o = oracle.WtwOracle(refs[b], W, hopf)
+        for q in range(l.shape[1]):
+            if q in (0, cut) and o.insert_precheck() != oracle.RUNNING:
+                break
+            if o.push_col(l[:, q]) != oracle.RUNNING:
+                break
+        st, so = eng.state(b), o.state
+        tag = (wtw_path, W, hopf, b)
+        assert np.array_equal(eng.path(b), o.path), tag
+        assert (st["live_ptr"], st["ref_ptr"], st["status"]) == (so["live_ptr"], so["ref_ptr"], so["status"]), tag
+        assert (st["windows"], st["cells"]) == (o.counters["windows"], o.counters["cells"]), tag
+        if b == 0:
+            assert st["status"] == oracle.STOP_REF_END and st["windows"] == 0, tag
+        if b == 4:
+            assert st["status"] == oracle.STOP_REF_END and st["ref_ptr"] >= Ms[b] - 1 - W, tag
+    eng.close()
+
+
+def _chroma_of(plan, samples):
+    dev = torch.from_numpy(np.ascontiguousarray(samples)).to(plan.device)
+    return plan.frames(dev, pad_left=2048)[0].t().contiguous().cpu().numpy()   # wtw.py:37-41
+
+
+def _drive(sess, live, n):
+    """The recording to every one of n streams in 1-second buffers."""
+    for i in range(0, len(live), 22050):
+        sess.feed([live[i:i + 22050]] * n)
+    sess.sync()
+    return sess.poll()
+
+
+@pytest.mark.parametrize("kind", ["wtw", "otw"])
+def test_live_session_one_piece_per_microphone(chopin_audio, wtw_known_answer, kind):
+    """Three microphones, three references: the chopin reference (stream 0: the reference's known answer for WTW), the
+    live recording's own chroma, and the first half of the reference.  Streams 1 and 2 equal sessions of their own."""
+    from real_time_audio_sync_amd import chroma
+    from real_time_audio_sync_amd.live import LiveSession
+    plan = chroma._plan()
+    ref_chroma = _chroma_of(plan, chopin_audio["ref"])
+    live_chroma = _chroma_of(plan, chopin_audio["live"])
+    half = np.ascontiguousarray(ref_chroma[:, : ref_chroma.shape[1] // 2])
+    refs = [ref_chroma, live_chroma, half]
+    kw = dict(wtw_params=PARAMS) if kind == "wtw" else dict(c=50, max_run_count=3)
+    live = chopin_audio["live"]
+    sess = LiveSession(refs, batch=3, **kw)
+    info = _drive(sess, live, 3)
+    if kind == "wtw":
+        assert np.array_equal(sess.path(0), wtw_known_answer)
+        assert tuple(info["positions"][0]) == (380, 360)
+    for b in (0, 1, 2):
+        one = LiveSession(refs[b], batch=1, **kw)
+        want = _drive(one, live, 1)
+        assert np.array_equal(sess.path(b), one.path(0)), (kind, b)
+        assert tuple(info["positions"][b]) == tuple(want["positions"][0]), (kind, b)
+        assert info["status"][b] == want["status"][0], (kind, b)
+        one.close()
+    assert info["status"][2] == 1      # the half reference ends long before the recording does
+    sess.close()
+
+
+def test_live_create_refuses_a_tracker_of_another_batch():
+    from real_time_audio_sync_amd import _native as nat, synth
+    from real_time_audio_sync_amd.chroma import ChromaPlan
+    from real_time_audio_sync_amd.otw_batch import BatchedOTW
+    from real_time_audio_sync_amd.wtw import BatchedWTW
+    plan = ChromaPlan(4096, 2048, 22050, "cuda:0")
+    ref = synth.synth_ref(100, seed=1)
+    otw = BatchedOTW.with_references([ref, ref], 20, 3)
+    wtw = BatchedWTW(torch.from_numpy(np.ascontiguousarray(ref.T)).to("cuda:0"), 10, 5, 2)
+    h = ctypes.c_void_p()
+    for o, w in ((otw._h, None), (None, wtw._h)):
+        for B in (1, 3):
+            assert nat.lib.rts_live_create(plan._h, o, w, B, 1 << 16, ctypes.byref(h)) == -1     # RTS_ERR_INVALID
+            assert b"streams" in nat.lib.rts_last_error() and not h.value
+        assert nat.lib.rts_live_create(plan._h, o, w, 2, 1 << 16, ctypes.byref(h)) == 0
+        nat.lib.rts_live_destroy(h)
+    otw.close()
+    wtw.close()
+    plan.close()
