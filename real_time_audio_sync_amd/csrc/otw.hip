@@ -16,7 +16,8 @@
 //     last value as carry-in (DPP wave shift) until no carry changes.  Because x -> fl(x + d) and
 //     min are monotone, the fixed point is bit-identical to the sequential scan; it is reached after
 //     (longest carry run / L) + 1 rounds (1.8 extra rounds on average at c = 500, against 500
-//     dependent steps).  The same wave reduces the strip's np.argmin while the values are in registers;
+//     dependent steps).  The same wave reduces the strip's np.argmin while the values are in registers (a speculative
+//     strip only per lane: wave 0 finishes the reduction, otw_spec_argmin);
 //   * wave 0 owns the control state in registers: corner cell, best_point / direction / run-count /
 //     path logic (decide), and the plan for the next step;
 //   * plain kernel (SPEC = false): chain phase (row strip on wave 0, column strip on wave 1 in a
@@ -120,10 +121,13 @@ struct OtwLds {
 // next Row-only / Column-only step needs, minus its last cell.  When that step comes, the shadow simply becomes the
 // band.  ex[] (indexed by step parity) is what the speculating waves hand to wave 0 along with a shadow.
 struct OtwSpecOut {
-    double min;  // np.argmin of the shadow strip
+    // np.argmin of the shadow strip, per lane: the lane's first minimum and the cell that holds it (strip_chain with
+    // SPLIT).  The wave reduction over the 64 lanes is left to wave 0, which has the time for it (otw_spec_argmin).
+    double pmin[64];
+    int pidx[64];
     double d;    // cost of the strip's last cell (the one the shadow leaves out)
     double d2;   // column speculation only: cost of the corner (t+1, j+1) a Both step would add
-    int idx;
+    int k1;      // first band position of the strip
     int flag;    // column speculation: 1 if dropping the strip's first cell leaves every other cell unchanged
 };
 template <int W>
@@ -297,7 +301,7 @@ __device__ __forceinline__ void chain_store(unsigned oA, unsigned oB, const doub
 // corner slot, which the fix-up rewrites; every band position is written with its real value
 // before it is ever read (rows/columns only grow at the top index).  Valid cells are always finite:
 // each has a computed predecessor in the previous row (row strip) or column (column strip).
-template <int W, bool DENSE, bool GUARD = false, bool ALT = false>
+template <int W, bool DENSE, bool GUARD = false, bool ALT = false, bool SPLIT = false>
 __device__ __forceinline__ void strip_chain(const double *__restrict__ Dv, const double *band, double *band_out, int k1,
                                             int n, double x_in, int lane, int lo_arg, double &fmin_out, int &fidx_out,
                                             double *dense_acc, double *dense_cost, long long dense_stride,
@@ -431,6 +435,18 @@ __device__ __forceinline__ void strip_chain(const double *__restrict__ Dv, const
     double lm = v0;
 #pragma unroll
     for (int m = 1; m < L; m++) lm = vmin(lm, v[m]);
+    if constexpr (SPLIT) {
+        // per lane only: (lm, first cell equal to lm).  A lane holds a cell equal to the wave minimum g exactly when
+        // lm == g, and then its first such cell is its first cell equal to lm, so otw_spec_argmin's reduction of these
+        // pairs gives what the lines below give.
+        int mfirst = L;
+#pragma unroll
+        for (int m = L - 1; m >= 1; m--) mfirst = (v[m] == lm) ? m : mfirst;
+        mfirst = (v0 == lm) ? 0 : mfirst;
+        fmin_out = lm;
+        fidx_out = mfirst;
+        return;
+    }
     const double g = wave_min(lm);
     int ml = L;  // first cell of this lane that holds the minimum (L: none)
 #pragma unroll
@@ -1130,15 +1146,30 @@ __device__ __forceinline__ void otw_spec_strip(const double *Dv, const double *b
     const double d_last = Dv[swz<W>(pos)];
     const double d_next = Dv[swz<W>(pos + 1)];  // meaningful for the column strip: cost of (pt+1, jn+1)
     int alt_ok = 0;
-    strip_chain<W, false, true, ALT>(Dv, band, shadow, k1, pos - k1, (k1 > 0) ? sentinel : (double)INFINITY, lane, k1, fm, fi,
-                                nullptr, nullptr, 0, rounds_acc, prev0_sentinel, sentinel, &alt_ok);
+    strip_chain<W, false, true, ALT, true>(Dv, band, shadow, k1, pos - k1, (k1 > 0) ? sentinel : (double)INFINITY, lane, k1,
+                                           fm, fi, nullptr, nullptr, 0, rounds_acc, prev0_sentinel, sentinel, &alt_ok);
+    out->pmin[lane] = fm;
+    out->pidx[lane] = fi;
     if (lane == 0) {
-        out->min = fm;
-        out->idx = fi;
+        out->k1 = k1;
         out->d = d_last;
         out->d2 = d_next;
         out->flag = alt_ok;
     }
+}
+
+// np.argmin (first minimum, restricted to the strip) of a shadow strip, from the per-lane parts its chain left in `ex`
+// (lm, ml: read by the caller, in the same LDS round trip as the rest of what it needs): strip_chain's own wave reduction
+// and first-index rule, on the reading wave.  (inf, 0x7fffffff) if no cell is finite.  Uniform result.
+template <int W>
+__device__ __forceinline__ void otw_spec_argmin(double lm, int ml, int k1, double &g_out, int &idx_out) {
+    constexpr int L = W / 64;
+    const double g = wave_min(lm);
+    const unsigned long long mask = __ballot(lm == g);
+    const bool some = (g < INFINITY) && (mask != 0);
+    const int first = (int)__builtin_ctzll(mask | (1ull << 63));  // lanes hold increasing positions
+    g_out = g;
+    idx_out = some ? k1 + L * first + __builtin_amdgcn_readlane(ml, first) : 0x7fffffff;
 }
 
 // The last cell of a shadow strip, in the chain's own order: min(min(side + d, diag + 2d), previous cell + d).  `side`
@@ -1179,11 +1210,15 @@ __device__ __forceinline__ OtwSettled otw_settle_hit_both(double *R, double *C, 
     // that uses them, i.e. behind the first wait: that was a second and a third round trip per Both step)
     const int k1r_ = (j0 - c + 1 > 0) ? j0 - c + 1 : 0, k1c_ = (pt - c + 1 > 0) ? pt - c + 1 : 0;
     const double pra_raw = R[swz<W>(j0 - (j0 - k1r_ > 0 ? 1 : 0))], prb_raw = C[swz<W>(t0 - (t0 - k1c_ > 0 ? 1 : 0))];
-    const double d1_raw = exr->d, d2_raw = exc->d, d3_raw = exc->d2, rmin_raw = exr->min, cmin_raw = exc->min;
-    const int ridx_raw = exr->idx, cidx_raw = exc->idx;
+    const double d1_raw = exr->d, d2_raw = exc->d, d3_raw = exc->d2, rlm = exr->pmin[lane], clm = exc->pmin[lane];
+    const int rml = exr->pidx[lane], cml = exc->pidx[lane], rk1 = exr->k1, ck1 = exc->k1;
     const double d1 = rfl(d1_raw), d2 = rfl(d2_raw), d3 = rfl(d3_raw);
-    double rmin = rfl(rmin_raw), cmin = rfl(cmin_raw);
-    int ridx = __builtin_amdgcn_readfirstlane(ridx_raw), cidx = __builtin_amdgcn_readfirstlane(cidx_raw);
+    double rmin, cmin;
+    int ridx, cidx;
+    otw_spec_argmin<W>(rlm, rml, __builtin_amdgcn_readfirstlane(rk1), rmin, ridx);
+    otw_spec_argmin<W>(clm, cml, __builtin_amdgcn_readfirstlane(ck1), cmin, cidx);
+    rmin = rfl(rmin), cmin = rfl(cmin);
+    ridx = __builtin_amdgcn_readfirstlane(ridx), cidx = __builtin_amdgcn_readfirstlane(cidx);
     const double pra = rfl(pra_raw), prb = rfl(prb_raw);
     // the Both step's strips: row pt over [k1r, j0] -- the speculated row strip plus its last cell; column jn over
     // [k1c, pt-1] -- the speculated column strip [k1c_s, pt-2] without its first cell once the band is full
@@ -1267,13 +1302,16 @@ __device__ __forceinline__ OtwSettled otw_settle_hit(double *R, double *C, const
         if (k.pend_dir != RTS_DIR_BOTH) k.prev = k.pend_dir;
         k.pend_dir = -2;
     }
-    // four independent LDS reads (a scheduling barrier behind them, which makes it one wait instead of two, measured neutral)
+    // the LDS reads of the step, independent of each other: one round trip
     const double prev_raw = band[swz<W>(pos - (n > 0 ? 1 : 0))];
-    const double d_raw = ex->d, smin_raw = ex->min;
-    const int sidx_raw = ex->idx;
+    const double d_raw = ex->d, lm = ex->pmin[lane];
+    const int ml = ex->pidx[lane], sk1 = ex->k1;
     const double d = rfl(d_raw);
-    const double smin = rfl(smin_raw);
-    const int sidx = __builtin_amdgcn_readfirstlane(sidx_raw);
+    double smin_v;
+    int sidx_v;
+    otw_spec_argmin<W>(lm, ml, __builtin_amdgcn_readfirstlane(sk1), smin_v, sidx_v);
+    const double smin = rfl(smin_v);
+    const int sidx = __builtin_amdgcn_readfirstlane(sidx_v);
     const double prev_s = rfl(prev_raw);  // unconditional: keeps the read in the round trip above (see otw_settle_hit_both)
     const double prev = (n > 0) ? prev_s : ((k1 > 0) ? sentinel : inf);
     // row hit: cell (pt, j0), "side" = up; column hit: cell (pt, jn), "side" = left -- in the chain's order
@@ -1667,8 +1705,171 @@ otw_advance_kernel(OtwArgs a) {
 #if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 2
             l_last = (long long)__builtin_amdgcn_s_memtime();
             __builtin_amdgcn_s_waitcnt(0xC07F);
+#define RTS_W0_STEP_END(hit)                                              \
+    do {                                                                  \
+        const long long t0_ = (long long)__builtin_amdgcn_s_memtime();    \
+        __builtin_amdgcn_s_waitcnt(0xC07F);                               \
+        RTS_STEP_BARRIER();                                               \
+        const long long t1_ = (long long)__builtin_amdgcn_s_memtime();    \
+        __builtin_amdgcn_s_waitcnt(0xC07F);                               \
+        if (hit) {                                                        \
+            lw_hit += t0_ - l_last;                                       \
+            lb_hit += t1_ - t0_;                                          \
+            ln_hit += 1;                                                  \
+        } else {                                                          \
+            lw_oth += t0_ - l_last;                                       \
+            lb_oth += t1_ - t0_;                                          \
+            ln_oth += 1;                                                  \
+        }                                                                 \
+        l_last = t1_;                                                     \
+    } while (0)
+#else
+#define RTS_W0_STEP_END(hit) RTS_STEP_BARRIER()
 #endif
+            // Row-only / Column-only hit steps -- all but ~1 % of the steps at B = 64 -- in a loop of their own, compiled
+            // once per control policy (V2: LiveNoteV2's append rule; DEFER: set_live's deferred run-count update) and
+            // entered once per run of such steps: the same settle_hit / decide / plan arithmetic as the general loop
+            // below, without its other step kinds, its band reductions or its per-step policy tests.  The float64
+            // control values stay in VGPRs (every lane holds the same value); only integers that drive a branch or an
+            // address cross to SGPRs.  It returns -- before touching anything -- at the first step that is not such a
+            // hit, or whose decide() would have to reduce the band it leaves as it is (a kept minimum that slid out of its
+            // window): the general loop runs that step and comes back.  W = 512 only, and not the throughput flavour
+            // (its point is its register budget).
+            int2 *const path_row = reinterpret_cast<int2 *>(e.path) + (size_t)e.b * e.path_cap;
+            const auto hit_steps = [&](auto v2_c, auto defer_c) __attribute__((always_inline)) {
+                constexpr bool V2 = decltype(v2_c)::value, DEFER = decltype(defer_c)::value;
+                // every lane holds the same control state: said once here, the integers stay in SGPRs through the loop
+#define RTS_RFL_CTL(f) k.f = __builtin_amdgcn_readfirstlane(k.f)
+                RTS_RFL_CTL(t), RTS_RFL_CTL(j), RTS_RFL_CTL(dir), RTS_RFL_CTL(prev), RTS_RFL_CTL(run_count);
+                RTS_RFL_CTL(status), RTS_RFL_CTL(n_path), RTS_RFL_CTL(consumed), RTS_RFL_CTL(rows), RTS_RFL_CTL(cols);
+                RTS_RFL_CTL(truncated), RTS_RFL_CTL(pend_dir), RTS_RFL_CTL(pending_col), RTS_RFL_CTL(last_x);
+                RTS_RFL_CTL(last_y), RTS_RFL_CTL(spec_valid), RTS_RFL_CTL(ri), RTS_RFL_CTL(ci);
+#undef RTS_RFL_CTL
+                for (;;) {
+                    const int pt = __builtin_amdgcn_readfirstlane(pl.t), j0 = __builtin_amdgcn_readfirstlane(pl.j0);
+                    const int fl = __builtin_amdgcn_readfirstlane(pl.flags);
+                    const int kind = fl & (kPlanHit | kPlanRow | kPlanCol | kPlanStop | kPlanExit | kPlanHitIf);
+                    const bool is_row = kind == (kPlanHit | kPlanRow);
+                    if (!is_row && kind != (kPlanHit | kPlanCol)) return;
+                    const int jn = is_row ? j0 : j0 + 1;
+                    // the band this step does not recompute keeps its minimum only while that stays inside the window
+                    const int keep_lo = is_row ? pt - c + 1 : jn - c + 1;
+                    const int keep_idx = __builtin_amdgcn_readfirstlane(is_row ? k.cb_idx : k.rb_idx);
+                    if (keep_idx < ((keep_lo > 0) ? keep_lo : 0)) return;
+#if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 1
+                    stamp_base = 0;
+                    stamp_sum[6] += 1;
+#endif
+                    RTS_STAMP(0);
+                    RTS_STAMP(1);
+                    // settle: the strip's last cell (otw_settle_hit)
+                    double *R = (fl & kPlanRi) ? SP.ShR : S.R, *C = (fl & kPlanCi) ? SP.ShC : S.C;
+                    const int pos = is_row ? j0 : pt;
+                    const int k1 = (pos - c + 1 > 0) ? pos - c + 1 : 0;
+                    const int n = pos - k1;
+                    double *band = is_row ? R : C, *other = is_row ? C : R;
+                    const OtwSpecOut *ex = is_row ? &SP.row[sp] : &SP.col[sp];
+                    if constexpr (DEFER) {  // livenote_v2.py:149-155
+                        if (k.pend_dir != -2) {
+                            k.run_count = (k.pend_dir == k.prev) ? k.run_count + 1 : 1;
+                            if (k.pend_dir != RTS_DIR_BOTH) k.prev = k.pend_dir;
+                            k.pend_dir = -2;
+                        }
+                    }
+                    const double prev_raw = band[swz<W>(pos - (n > 0 ? 1 : 0))];
+                    const double d = ex->d, lm = ex->pmin[lane];
+                    const int ml = ex->pidx[lane], sk1 = ex->k1;
+                    double smin;
+                    int sidx;
+                    otw_spec_argmin<W>(lm, ml, __builtin_amdgcn_readfirstlane(sk1), smin, sidx);
+                    const double prev = (n > 0) ? prev_raw : ((k1 > 0) ? sentinel : inf);
+                    const double diag = (pos > 0) ? (is_row ? k.cL : k.cU) + 2 * d : inf;
+                    const double cl = vmin(vmin(k.cA + d, diag), prev + d);
+                    if (lane == 0) {
+                        band[swz<W>(pos)] = cl;
+                        other[swz<W>(is_row ? pt : jn)] = cl;  // column j0 gains row pt / row pt gains column jn
+                    }
+                    if (is_row) {
+                        k.rows += 1;
+                        k.consumed = pt + 1;
+                        k.cU = k.cA;
+                        k.cL = prev;
+                    } else {
+                        k.cols += 1;
+                        k.cL = k.cA;
+                        k.cU = prev;
+                    }
+                    k.cA = cl;
+                    k.cells += n + 1;
+                    RTS_STAMP(3);
+                    // decide (otw_decide): the strip's band brings the speculated argmin, the other band keeps its
+                    // minimum, and both gain `cl` at their top index (it wins only if strictly smaller)
+                    double rmin = is_row ? smin : k.rb_min, cmin = is_row ? k.cb_min : smin;
+                    int ridx = is_row ? sidx : k.rb_idx, cidx = is_row ? k.cb_idx : sidx;
+                    const bool r_new = cl < rmin, c_new = cl < cmin;
+                    rmin = r_new ? cl : rmin;
+                    ridx = r_new ? jn : ridx;
+                    cmin = c_new ? cl : cmin;
+                    cidx = c_new ? pt : cidx;
+                    k.rb_min = rmin;
+                    k.rb_idx = ridx;
+                    k.cb_min = cmin;
+                    k.cb_idx = cidx;
+                    const bool rlt = rmin < cmin;
+                    const int x = rlt ? pt : cidx, y = rlt ? ridx : jn;
+                    bool append = true;
+                    if constexpr (V2) {  // livenote_v2.py:198
+                        const int xs = __builtin_amdgcn_readfirstlane(x), ys = __builtin_amdgcn_readfirstlane(y);
+                        append = (k.n_path == 0) || (xs > k.last_x && ys >= k.last_y);
+                        if (append) {
+                            k.last_x = xs;
+                            k.last_y = ys;
+                        }
+                    }
+                    if (append) {
+                        if (k.n_path < e.path_cap) {
+                            if (lane == 0) path_row[k.n_path] = make_int2(x, y);
+                        } else {
+                            k.truncated = 1;
+                        }
+                        k.n_path += 1;
+                    }
+                    int nd = __builtin_amdgcn_readfirstlane((x < pt) ? RTS_DIR_COLUMN : (y < jn) ? RTS_DIR_ROW : RTS_DIR_BOTH);
+                    if (pt < c)
+                        nd = RTS_DIR_BOTH;
+                    else if (k.run_count >= e.max_run_count)
+                        nd = (k.prev == RTS_DIR_ROW) ? RTS_DIR_COLUMN : RTS_DIR_ROW;
+                    if constexpr (DEFER) {
+                        k.pend_dir = nd;
+                    } else {
+                        k.run_count = (nd == k.prev) ? k.run_count + 1 : 1;
+                        if (nd != RTS_DIR_BOTH) k.prev = nd;
+                    }
+                    k.dir = nd;
+                    k.pending_col = (nd == RTS_DIR_COLUMN);
+                    k.t = pt;
+                    k.j = jn;
+                    RTS_STAMP(4);
+                    k.spec_valid = 1;
+                    pl = otw_make_plan<W, RT>(S, k, e, true, sp ^ 1);
+                    RTS_STAMP(5);
+                    RTS_W0_STEP_END(true);
+                    sp ^= 1;
+                }
+            };
             for (;;) {
+                if constexpr (W == 512 && !kThroughput<RT>) {
+                    if (e.variant == RTS_VARIANT_LIVENOTE_V2) {
+                        if (e.deferred_update)
+                            hit_steps(std::true_type{}, std::true_type{});
+                        else
+                            hit_steps(std::true_type{}, std::false_type{});
+                    } else if (e.deferred_update) {
+                        hit_steps(std::false_type{}, std::true_type{});
+                    } else {
+                        hit_steps(std::false_type{}, std::false_type{});
+                    }
+                }
                 RTS_STAMP2(0);
                 // wave 0 wrote the plan itself; pinned to SGPRs so that the step's addressing and branches are scalar
                 const int pt = __builtin_amdgcn_readfirstlane(pl.t), j0 = __builtin_amdgcn_readfirstlane(pl.j0);
@@ -1733,29 +1934,10 @@ otw_advance_kernel(OtwArgs a) {
                 k.spec_valid = !o.stop;  // the shadows being computed during this step belong to (k.t, k.j)
                 pl = otw_make_plan<W, RT>(S, k, e, true, sp ^ 1);
                 RTS_STAMP2(5);
-#if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 2
-                {
-                    const long long t0_ = (long long)__builtin_amdgcn_s_memtime();
-                    __builtin_amdgcn_s_waitcnt(0xC07F);
-                    RTS_STEP_BARRIER();
-                    const long long t1_ = (long long)__builtin_amdgcn_s_memtime();
-                    __builtin_amdgcn_s_waitcnt(0xC07F);
-                    if (pflags & kPlanHit) {
-                        lw_hit += t0_ - l_last;
-                        lb_hit += t1_ - t0_;
-                        ln_hit += 1;
-                    } else {
-                        lw_oth += t0_ - l_last;
-                        lb_oth += t1_ - t0_;
-                        ln_oth += 1;
-                    }
-                    l_last = t1_;
-                }
-#else
-                RTS_STEP_BARRIER();
-#endif
+                RTS_W0_STEP_END(pflags & kPlanHit);
                 sp ^= 1;
             }
+#undef RTS_W0_STEP_END
         }
     } else if constexpr (NW >= 4) {
         // ---- role-specialised step loops.  Every wave runs only its own role's code between the two barriers of

@@ -1,0 +1,78 @@
+"""The pipelined W = 512 kernel (band widths 245..500) through every control policy: wave 0's hit-step loop is compiled
+once per policy (OTW / LiveNote / LiveNoteV2, insert loop or set_live), and the speculative strips' np.argmin is
+finished on wave 0 from per-lane parts.  Each configuration must match the dense CPU oracle bit for bit: path, end
+state and (insert mode) both accumulated-cost bands."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+
+@pytest.fixture(scope="module")
+def mods():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import oracle
+    from real_time_audio_sync_amd import otw_batch, synth
+    return oracle, otw_batch, synth
+
+
+def _check(oracle, ob, ref, lives, c, mrc, variant, mode, dtype, euclid=False):
+    vmap = {"otw": oracle.OTW, "livenote": oracle.LIVENOTE, "livenote_v2": oracle.LIVENOTE_V2}
+    eng = ob.BatchedOTW(ref, c, mrc, batch=len(lives), variant=variant, euclid=euclid, dtype=dtype)
+    lv, ln = eng.pack(lives, dtype=dtype)
+    eng.run(lv, ln, mode=mode)
+    for b, live in enumerate(lives):
+        o = oracle.OtwOracle(ref, c, mrc, vmap[variant], oracle.COST_EUCLID if euclid else oracle.COST_DOT)
+        if mode == "set_live":
+            o.set_live(live)
+        else:
+            o.run(live)
+        tag = (variant, mode, c, mrc, str(dtype), b)
+        st, so = eng.state(b), o.state
+        assert np.array_equal(eng.path(b), o.path), tag
+        for key in ("t", "j", "previous", "run_count", "status"):
+            assert st[key] == so[key], (tag, key)
+        if mode == "insert":
+            assert st["direction"] == so["direction"], tag
+            rb, cb = eng.bands(b)
+            orb, ocb = o.bands()
+            assert np.array_equal(rb, orb, equal_nan=True) and np.array_equal(cb, ocb, equal_nan=True), tag
+    eng.close()
+
+
+@pytest.mark.parametrize("variant", ["otw", "livenote", "livenote_v2"])
+@pytest.mark.parametrize("mode", ["insert", "set_live"])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_every_policy_on_the_512_cell_window(mods, variant, mode, dtype):
+    oracle, ob, synth = mods
+    c = 300 if dtype == "f32" else 480
+    ref, lives = synth.synth_batch(2 * c + 100, 3, seed=4100 + c + len(variant) + (7 if mode == "set_live" else 0))
+    lives[1] = lives[1][:, : lives[1].shape[1] // 2]
+    # the third stream runs past the reference end (stop) and, in set_live, to the end of its live frames
+    lives[2] = np.concatenate([lives[2], np.repeat(lives[2][:, -1:], 40, axis=1)], axis=1)
+    lives[2] = synth._as_f32_values(lives[2])
+    tdt = torch.float32 if dtype == "f32" else torch.float64
+    for mrc in (1, 3):
+        _check(oracle, ob, ref, lives, c, mrc, variant, mode, tdt)
+
+
+@pytest.mark.parametrize("variant", ["otw", "livenote_v2"])
+def test_exact_ties_on_the_512_cell_window(mods, variant):
+    """synth_tie makes exactly equal costs (repeated frames), hence exact ties between cells of one lane's strip slice
+    and between lanes: np.argmin's first-minimum rule decides every step."""
+    oracle, ob, synth = mods
+    ref, live = synth.synth_tie(700, seed=11)
+    lives = [live, live[:, : live.shape[1] // 2].copy()]
+    for mode in ("insert", "set_live"):
+        _check(oracle, ob, ref, lives, 400, 3, variant, mode, torch.float64)
+
+
+def test_euclidean_cost_on_the_512_cell_window(mods):
+    oracle, ob, synth = mods
+    ref, lives = synth.synth_batch(900, 2, seed=4321)
+    ref = synth._as_f32_values(np.abs(ref - 0.2))
+    lives = [synth._as_f32_values(np.abs(l - 0.2)) for l in lives]
+    _check(oracle, ob, ref, lives, 350, 2, "livenote_v2", "insert", torch.float64, euclid=True)
