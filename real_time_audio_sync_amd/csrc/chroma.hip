@@ -725,18 +725,19 @@ __global__ void __launch_bounds__(kChromaNT) chroma_project_kernel(ChromaArgs g)
     }
 }
 
-// out[m][f] = max(in[m+1][f] - in[m][f], 0), m < n_frames - 1   (np.clip(np.diff(chroma), 0, inf))
+// out[m][f] = max(in[m+1][f] - in[m][f], 0), m < n_frames - 1   (np.clip(np.diff(chroma), 0, inf): a NaN difference
+// stays NaN, as np.clip propagates it)
 __global__ void chroma_diff_kernel(const void *in, void *out, long long n_out, int f64) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_out) return;
     if (f64) {
         const double *x = reinterpret_cast<const double *>(in);
         const double d = x[i + kCh] - x[i];
-        reinterpret_cast<double *>(out)[i] = d > 0.0 ? d : 0.0;
+        reinterpret_cast<double *>(out)[i] = d < 0.0 ? 0.0 : d;
     } else {
         const float *x = reinterpret_cast<const float *>(in);
         const float d = x[i + kCh] - x[i];
-        reinterpret_cast<float *>(out)[i] = d > 0.0f ? d : 0.0f;
+        reinterpret_cast<float *>(out)[i] = d < 0.0f ? 0.0f : d;
     }
 }
 
