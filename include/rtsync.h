@@ -109,13 +109,41 @@ int rts_otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, int 
  * copied at create; ranges may overlap or repeat.  Buffers are sized by the longest reference N_max (path capacity
  * 3 N_max + 8, insert history [B][2 N_max][F]); every getter is unchanged.  RTS_ERR_INVALID for a NULL pointer, len < 1,
  * first < 0 or a range past n_ref_frames (the message names the stream); the rules of rts_otw_create apply otherwise.
- * The dense mirror (rts_otw_set_dense, rts_otw_replay_dense) returns RTS_ERR_UNSUPPORTED on such a handle. */
+ * The dense mirror (rts_otw_set_dense, rts_otw_replay_dense) returns RTS_ERR_UNSUPPORTED on such a handle.
+ * N_max is the longest range given here and never grows: to reserve room for a longer piece that rts_otw_restart
+ * may move a stream on to later, create one stream on that piece and restart it onto its own range right away. */
 int rts_otw_create_refs(const void *refs_dev, int ref_dtype, int F, long long n_ref_frames,
                         const long long *first_host, const int32_t *len_host, int B, int c, int max_run_count,
                         int variant, int cost_kind, rts_otw **out);
 int rts_otw_destroy(rts_otw *h);
 /* Back to the freshly-constructed state (all streams). */
 int rts_otw_reset(rts_otw *h, void *stream);
+
+/* Restart single streams while the others keep running: what constructing a new OnlineTimeWarping / LiveNote /
+ * LiveNoteV2 object (otw_eran.py:6-36, livenote.py:5-35, livenote_v2.py:8-40) for that one microphone is in the
+ * reference.  `mask_host`: uint8[B] in HOST memory; streams with a non-zero entry are selected.  From here on a selected
+ * stream behaves exactly like stream 0 of a handle freshly created for it alone (same c, max_run_count, variant, cost
+ * kind): state as after create, RTS_RUNNING, empty path and insert history, counters at zero, bands NaN until its first
+ * frame; with a dense mirror attached its [2N][N] slices read sentinel / -1 again (otw_eran.py:23,27).  Nothing an
+ * unselected stream owns is written.
+ *   first_host / len_host both NULL: the selected streams keep their reference.  Both given (allowed only on an
+ * rts_otw_create_refs handle): int64[B] / int32[B] host tables, read for selected streams only; stream b then follows
+ * frames [first_host[b], first_host[b] + len_host[b]) of the pool given at create, path indices relative to that range
+ * (a range that starts inside a piece is "follow from bar 50").  Checks as in rts_otw_create_refs, plus len_host[b] <=
+ * N_max of the handle, whose buffers were sized by it.
+ *   Asynchronous on `stream`, in stream order; no synchronisation and no allocation.  Mask and ranges travel as
+ * by-value kernel arguments, so the host tables may be freed as soon as the call returns and the call can be captured
+ * into a graph (a replay restarts the same streams onto the same ranges).  After an rts_otw_run a restart is allowed;
+ * frames a restarted stream then receives through rts_otw_insert / rts_otw_push put the handle in the state in which
+ * rts_otw_replay_dense answers RTS_ERR_UNSUPPORTED; until then (a restart after rts_otw_run and no frame since)
+ * rts_otw_replay_dense still replays that whole run for every stream, the restarted ones included, because the buffers
+ * it is handed are that run's.  After insert / push only, rts_otw_replay_dense shows for a
+ * restarted stream the matrices of what it consumed since its restart.
+ *   RTS_ERR_INVALID, with nothing enqueued and nothing changed: NULL handle or mask, only one of first_host /
+ * len_host, ranges on a handle without per-stream references, len < 1, first < 0, a range past the pool, len > N_max
+ * (the message names the stream), wrong current device.  An all-zero mask is RTS_OK and does nothing. */
+int rts_otw_restart(rts_otw *h, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
+                    void *stream);
 
 /* Whole live sequences, one launch.  `live_dev`: [B][T_max][F] (dtype `live_dtype`, frame-major);
  * `live_len_dev`: int32[B] valid frames per stream (<= T_max).  Resets the handle, then behaves like
@@ -145,7 +173,9 @@ int rts_otw_read_states(rts_otw *h, int32_t *states /* [B][RTS_STATE_LEN] */, vo
  * *n receives the full length (copy is truncated to cap_pairs). */
 int rts_otw_read_path(rts_otw *h, int b, int32_t *pairs, int cap_pairs, int *n, void *stream);
 /* The live part of .acc_cost: row t over columns [j-c, j] and column j over rows [t-c, t]
- * (c+1 doubles each, index i <-> offset i-c; NaN where the index is negative). */
+ * (c+1 doubles each, index i <-> offset i-c; NaN where the index is negative, and everywhere for a stream that has
+ * not consumed a frame since create / rts_otw_restart; rts_otw_reset and rts_otw_run leave the bands of such a stream as
+ * they were). */
 int rts_otw_read_bands(rts_otw *h, int b, double *row_band, double *col_band, void *stream);
 /* Device-side views for zero-copy consumers (torch): path buffer [B][path_cap][2] int32 and state
  * [B][RTS_STATE_LEN] int32. */
@@ -272,12 +302,21 @@ int rts_wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win_fr
  * rts_wtw_create handle made with chroma_ref_dev = frames [first_host[b], first_host[b] + len_host[b]) of
  * `chroma_refs_dev` ([n_ref_frames][F] float64) and M = len_host[b], so its N = 2 M_b, its boundary checks and the
  * truncation of its reference windows are its own.  Tables copied at create, ranges may overlap or repeat; the live
- * history is [B][2 M_max][F] (rts_wtw_device_views reports 2 M_max).  Errors as for rts_otw_create_refs. */
+ * history is [B][2 M_max][F] (rts_wtw_device_views reports 2 M_max).  Errors as for rts_otw_create_refs.  M_max is the
+ * longest range given here; room for a longer piece is reserved as described at rts_otw_create_refs. */
 int rts_wtw_create_refs(const double *chroma_refs_dev, int F, long long n_ref_frames,
                         const long long *first_host, const int32_t *len_host, int B, int win_frames,
                         int hop_frames, int keep_last_d, rts_wtw **out);
 int rts_wtw_destroy(rts_wtw *h);
 int rts_wtw_reset(rts_wtw *h, void *stream);
+
+/* Restart single streams (a new WTW object, wtw.py:50-68, for that one microphone) while the others keep running.
+ * Arguments, ordering, by-value transport and errors exactly as for rts_otw_restart (len_host[b] <= M_max).  A selected
+ * stream's state vector is zero again (RTS_RUNNING), its path empty, its live chroma history reads as zeros (wtw.py:55)
+ * and its appended-column count is zero, on the one-workgroup window kernels and on the strip-DP pipeline alike.  With
+ * keep_last_d the kept D of a restarted stream is unspecified until its next window, as on a fresh handle. */
+int rts_wtw_restart(rts_wtw *h, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
+                    void *stream);
 
 /* Replaces the part of WTW.insert below the per-hop chroma (wtw.py:92-128): appends n_new[b] (or
  * n_max when n_new_dev is NULL) already-normalised live chroma columns per stream -- cols_dev is
@@ -317,6 +356,15 @@ int rts_live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max
 int rts_live_destroy(rts_live *h);
 /* Drops pending samples and resets the bound tracker.  Synchronises `stream`. */
 int rts_live_reset(rts_live *h, void *stream);
+/* Restart single streams of a session: drops the selected streams' pending samples (device buffer and host mirror:
+ * rts_live_pending reads 0 for them), restarts them in the bound tracker (rts_otw_restart / rts_wtw_restart, same
+ * arguments and errors) and republishes their status / position words, so that rts_live_poll shows RTS_RUNNING and the
+ * positions of a fresh session for them; feeds_done does not go backwards.  Ordered after the feeds already submitted:
+ * samples submitted before the call belong to the stream's old run, samples submitted after it to the new one.  A
+ * staging slot handed out by rts_live_staging and not yet submitted stays valid.  Unlike rts_live_reset it does not
+ * synchronise anything. */
+int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
+                     void *stream);
 
 /* One feed, zero-copy form.  rts_live_staging hands out the next pinned host staging slot (it waits only if the feed
  * that used the slot four feeds ago has not been consumed by the device yet): the producer writes counts_host[b] = new

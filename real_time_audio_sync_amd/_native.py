@@ -61,6 +61,7 @@ _i64 = ctypes.c_longlong
 _decl("rts_otw_create_refs", _i32, [_vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)])
 _decl("rts_otw_destroy", _i32, [_vp])
 _decl("rts_otw_reset", _i32, [_vp, _vp])
+_decl("rts_otw_restart", _i32, [_vp, _vp, _vp, _vp, _vp])
 _decl("rts_otw_run", _i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp])
 _decl("rts_otw_insert", _i32, [_vp, _vp, _i32, _vp, _vp])
 _decl("rts_otw_push", _i32, [_vp, _vp, _i32, _i32, _vp, _vp])
@@ -92,6 +93,7 @@ _decl("rts_wtw_create", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.P
 _decl("rts_wtw_create_refs", _i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)])
 _decl("rts_wtw_destroy", _i32, [_vp])
 _decl("rts_wtw_reset", _i32, [_vp, _vp])
+_decl("rts_wtw_restart", _i32, [_vp, _vp, _vp, _vp, _vp])
 _decl("rts_wtw_push", _i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp])
 _decl("rts_wtw_read_states", _i32, [_vp, _vp, _vp])
 _decl("rts_wtw_read_path", _i32, [_vp, _i32, _vp, _i32, _pi32, _vp])
@@ -103,6 +105,7 @@ WTW_STATE_LEN = 8
 _decl("rts_live_create", _i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_vp)])
 _decl("rts_live_destroy", _i32, [_vp])
 _decl("rts_live_reset", _i32, [_vp, _vp])
+_decl("rts_live_restart", _i32, [_vp, _vp, _vp, _vp, _vp])
 _decl("rts_live_staging", _i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64)])
 _decl("rts_live_submit", _i32, [_vp, _i32, _vp])
 _decl("rts_live_feed", _i32, [_vp, _vp, _i32, _vp, _vp])

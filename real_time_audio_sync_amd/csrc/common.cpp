@@ -18,13 +18,51 @@ int set_error(int code, const char *fmt, ...) {
     return code;
 }
 
+int restart_check(int B, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
+                  long long n_ref_frames, int len_max, const char *len_name) {
+    if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
+    if ((first_host == nullptr) != (len_host == nullptr))
+        return set_error(RTS_ERR_INVALID, "first_host and len_host must both be given or both be NULL");
+    if (!first_host) return RTS_OK;
+    if (n_ref_frames < 0)
+        return set_error(RTS_ERR_INVALID, "new reference ranges need a handle with per-stream references (rts_*_create_refs)");
+    for (int b = 0; b < B; b++) {
+        if (!mask_host[b]) continue;
+        if (len_host[b] < 1) return set_error(RTS_ERR_INVALID, "stream %d: len must be >= 1 (got %d)", b, len_host[b]);
+        if (first_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: first must be >= 0 (got %lld)", b, first_host[b]);
+        if (first_host[b] > n_ref_frames - len_host[b])
+            return set_error(RTS_ERR_INVALID, "stream %d: frames [%lld, %lld) lie outside the %lld reference frames", b,
+                             first_host[b], first_host[b] + len_host[b], n_ref_frames);
+        if (len_host[b] > len_max)
+            return set_error(RTS_ERR_INVALID, "stream %d: len %d exceeds the handle's %s = %d (its buffers were sized by it)", b,
+                             len_host[b], len_name, len_max);
+    }
+    return RTS_OK;
+}
+
+int restart_next_chunk(int B, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host, int *pos,
+                       RestartSel *sel) {
+    int n = 0, b = *pos;
+    sel->set_ref = first_host != nullptr;
+    for (; b < B && n < kRestartChunk; b++) {
+        if (!mask_host[b]) continue;
+        sel->idx[n] = b;
+        sel->first[n] = first_host ? first_host[b] : 0;
+        sel->len[n] = len_host ? len_host[b] : 0;
+        n++;
+    }
+    *pos = b;
+    sel->n = n;
+    return n;
+}
+
 }  // namespace rts
 
 extern "C" {
 
 const char *rts_last_error(void) { return rts::last_error_buf(); }
 
-int rts_version(void) { return 100; }
+int rts_version(void) { return 101; }
 
 int rts_device_count(void) {
     int n = 0;

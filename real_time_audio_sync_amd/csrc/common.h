@@ -15,6 +15,27 @@ int set_error(int code, const char *fmt, ...);
 __attribute__((visibility("hidden"))) int otw_batch(const rts_otw *h);
 __attribute__((visibility("hidden"))) int wtw_batch(const rts_wtw *h);
 
+// rts_*_restart: how the selection reaches the device.  The selected stream indices and (optionally) their new
+// reference ranges travel as BY-VALUE kernel arguments, kRestartChunk streams per launch: the launch copies them, so
+// the caller's host tables are consumed when the call returns, nothing is allocated or pinned, no later restart can
+// overwrite what an earlier one still has to read, and a captured graph replays the values it was captured with.
+constexpr int kRestartChunk = 128;
+struct RestartSel {
+    int n;        // selected streams in this chunk
+    int set_ref;  // first[] / len[] are given: the streams move to these ranges of the reference pool
+    int32_t idx[kRestartChunk];
+    int32_t len[kRestartChunk];
+    long long first[kRestartChunk];
+};
+// The checks every rts_*_restart makes before anything is enqueued (`len_name`: "N_max" / "M_max", `len_max` its value;
+// n_ref_frames < 0: the handle has no per-stream references).  RTS_OK, or RTS_ERR_INVALID with the message set.
+__attribute__((visibility("hidden"))) int restart_check(int B, const uint8_t *mask_host, const long long *first_host,
+                                                        const int32_t *len_host, long long n_ref_frames, int len_max,
+                                                        const char *len_name);
+// Fills `sel` with the next selected streams from *pos on (at most kRestartChunk) and advances *pos; returns sel->n.
+__attribute__((visibility("hidden"))) int restart_next_chunk(int B, const uint8_t *mask_host, const long long *first_host,
+                                                             const int32_t *len_host, int *pos, RestartSel *sel);
+
 #define RTS_HIP(call)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \

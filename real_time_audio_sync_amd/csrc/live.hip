@@ -110,6 +110,22 @@ __global__ void __launch_bounds__(1024) live_compact_kernel(LiveArgs g) {
     }
 }
 
+// rts_live_restart, after the bound tracker's own restart: the selected streams' pending samples are dropped and their
+// status / position words republished from the (now fresh) tracker state.  The feed number is left alone: the words
+// still reflect every feed submitted before the restart.
+__global__ void live_restart_kernel(RestartSel sel, LiveArgs g) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= sel.n) return;
+    const int b = sel.idx[i];
+    g.pending[b] = 0;
+    const int32_t *st = g.state + (size_t)b * g.state_len;
+    volatile int32_t *p = g.pub + (size_t)b * kLiveWords;
+    p[0] = st[g.st_status];
+    p[1] = st[g.st_live];
+    p[2] = st[g.st_ref];
+    __threadfence_system();
+}
+
 }  // namespace rts
 
 struct rts_live {
@@ -257,6 +273,36 @@ int rts_live_reset(rts_live *h, void *stream) {
     h->slot = -1;
     h->feeds = 0;
     return h->otw ? rts_otw_reset(h->otw, stream) : rts_wtw_reset(h->wtw, stream);
+}
+
+int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
+                     void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
+    if (int rc = live_check_device(h); rc != RTS_OK) return rc;
+    // the tracker makes every check before it enqueues anything; behind the feeds already submitted on `stream`
+    if (int rc = h->otw ? rts_otw_restart(h->otw, mask_host, first_host, len_host, stream)
+                        : rts_wtw_restart(h->wtw, mask_host, first_host, len_host, stream);
+        rc != RTS_OK)
+        return rc;
+    LiveArgs g;
+    memset(&g, 0, sizeof(g));
+    g.pending = h->pending;
+    g.state = h->state_dev;
+    g.state_len = h->state_len;
+    g.st_status = h->st_status;
+    g.st_live = h->st_live;
+    g.st_ref = h->st_ref;
+    g.pub = h->pub_dev;
+    RestartSel sel;
+    for (int pos = 0; restart_next_chunk(h->B, mask_host, nullptr, nullptr, &pos, &sel) > 0;) {
+        hipLaunchKernelGGL(live_restart_kernel, dim3((sel.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, sel, g);
+        RTS_HIP(hipGetLastError());
+    }
+    for (int b = 0; b < h->B; b++)
+        if (mask_host[b]) h->pending_host[b] = 0;  // the mirror: samples submitted from here on belong to the new run
+    return RTS_OK;
 }
 
 int rts_live_staging(rts_live *h, int32_t **counts_host, void **samples_host, long long *capacity_samples) {

@@ -2162,10 +2162,7 @@ otw_advance_kernel(OtwArgs a) {
 }
 
 // Fresh per-stream state (otw_eran.py:29-36 / livenote_v2.py:31-37).
-__global__ void otw_reset_kernel(int32_t *state, int B, int variant) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    int32_t *st = state + (size_t)b * RTS_STATE_LEN;
+__device__ __forceinline__ void otw_fresh_state(int32_t *st, int variant) {
     for (int i = 0; i < RTS_STATE_LEN; i++) st[i] = 0;
     st[RTS_ST_DIRECTION] = RTS_DIR_BOTH;
     st[RTS_ST_PREVIOUS] = RTS_DIR_NONE;
@@ -2173,6 +2170,42 @@ __global__ void otw_reset_kernel(int32_t *state, int B, int variant) {
     st[RTS_ST_STATUS] = RTS_RUNNING;
     st[RTS_ST_FIRST_INSERT] = 1;
     st[14] = -2;
+}
+
+__global__ void otw_reset_kernel(int32_t *state, int B, int variant) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    otw_fresh_state(state + (size_t)b * RTS_STATE_LEN, variant);
+}
+
+// rts_otw_restart: the same for the selected streams only, one workgroup each, plus everything else a stream carries from
+// one launch to the next: its history length, its persisted bands (NaN = never evaluated, as after create) and, when the
+// stream moves to another piece, its row of the reference tables.  A stream whose state says first_insert takes
+// nothing else from memory (otw_advance_kernel's prologue: bands are reloaded only when !first, the band minima and the
+// pipelined kernel's shadow bands are rebuilt in every launch), so this is all "fresh" means.  Other streams' words are
+// not written.
+__global__ void __launch_bounds__(64) otw_restart_kernel(RestartSel sel, int32_t *state, int32_t *hist_len, double *bands,
+                                                         int band_len, long long *ref_first, int32_t *ref_len, int variant) {
+    if ((int)blockIdx.x >= sel.n) return;
+    const int b = sel.idx[blockIdx.x];
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    for (int i = threadIdx.x; i < band_len; i += blockDim.x) bands[(size_t)b * band_len + i] = qnan;
+    if (threadIdx.x == 0) {
+        otw_fresh_state(state + (size_t)b * RTS_STATE_LEN, variant);
+        hist_len[b] = 0;
+        if (sel.set_ref) {
+            ref_first[b] = sel.first[blockIdx.x];
+            ref_len[b] = sel.len[blockIdx.x];
+        }
+    }
+}
+
+// Dense mirror: the [per_stream] slices of the selected streams back to `v`; grid (slices, sel.n).
+__global__ void otw_fill_sel_kernel(RestartSel sel, double *p, long long per_stream, double v) {
+    if ((int)blockIdx.y >= sel.n) return;
+    double *q = p + (long long)sel.idx[blockIdx.y] * per_stream;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < per_stream; i += stride) q[i] = v;
 }
 
 __global__ void otw_fill_kernel(double *p, long long n, double v) {
@@ -2236,6 +2269,7 @@ struct rts_otw {
     double *hist;       // [B][hist_stride][F], allocated on first insert
     long long *ref_first;  // per-stream references (rts_otw_create_refs): [B] first frames, device; NULL otherwise
     int32_t *ref_len;      // [B] lengths N_b, device
+    long long n_ref_frames;  // frames in the pool `ref` points to (rts_otw_create_refs; rts_otw_restart checks new ranges against it)
     int32_t *hist_len;  // [B]
     long long *debug;   // diagnostic builds only
     double *dense_acc, *dense_cost;  // caller-owned, optional
@@ -2434,6 +2468,13 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
         rts_otw_destroy(h);
         return rc;
     }
+    // a stream that has not consumed a frame has no bands yet: they read NaN (rts_otw_restart puts a stream back there)
+    hipLaunchKernelGGL(otw_fill_kernel, dim3(64), dim3(256), 0, nullptr, h->bands, (long long)2 * (c + 1) * B,
+                       __builtin_nan(""));
+    if ((e = hipGetLastError()) != hipSuccess) {
+        rts_otw_destroy(h);
+        return set_error(RTS_ERR_HIP, "launch of the band fill failed: %s", hipGetErrorString(e));
+    }
     if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) {
         rts_otw_destroy(h);
         return set_error(RTS_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
@@ -2475,7 +2516,9 @@ int rts_otw_create_refs(const void *refs_dev, int ref_dtype, int F, long long n_
                              first_host[b], first_host[b] + len_host[b], n_ref_frames);
         if (len_host[b] > n_max) n_max = len_host[b];
     }
-    return otw_create(refs_dev, ref_dtype, F, n_max, B, c, max_run_count, variant, cost_kind, first_host, len_host, out);
+    const int rc = otw_create(refs_dev, ref_dtype, F, n_max, B, c, max_run_count, variant, cost_kind, first_host, len_host, out);
+    if (rc == RTS_OK) (*out)->n_ref_frames = n_ref_frames;
+    return rc;
 }
 
 int rts_otw_destroy(rts_otw *h) {
@@ -2508,6 +2551,33 @@ int rts_otw_reset(rts_otw *h, void *stream) {
         const double sentinel = (h->variant == RTS_VARIANT_OTW) ? 1e10 : (double)INFINITY;
         hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, h->dense_acc, n, sentinel);
         hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, h->dense_cost, n, -1.0);
+        RTS_HIP(hipGetLastError());
+    }
+    return RTS_OK;
+}
+
+int rts_otw_restart(rts_otw *h, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
+                    void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
+    if (int rc = restart_check(h->B, mask_host, first_host, len_host, h->ref_first ? h->n_ref_frames : -1, h->N, "N_max");
+        rc != RTS_OK)
+        return rc;
+    if (int rc = check_device(h); rc != RTS_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    // (src_kind stays: frames a restarted stream receives through insert / push after an rts_otw_run make the handle
+    // "mixed" there, as for any stream)
+    RestartSel sel;
+    for (int pos = 0; restart_next_chunk(h->B, mask_host, first_host, len_host, &pos, &sel) > 0;) {
+        hipLaunchKernelGGL(otw_restart_kernel, dim3(sel.n), dim3(64), 0, s, sel, h->state, h->hist_len, h->bands,
+                           2 * (h->c + 1), h->ref_first, h->ref_len, h->variant);
+        if (h->dense_acc) {  // otw_eran.py:23,27 for these streams
+            const long long per = (long long)2 * h->N * h->N;
+            const double sentinel = (h->variant == RTS_VARIANT_OTW) ? 1e10 : (double)INFINITY;
+            hipLaunchKernelGGL(otw_fill_sel_kernel, dim3(64, sel.n), dim3(256), 0, s, sel, h->dense_acc, per, sentinel);
+            hipLaunchKernelGGL(otw_fill_sel_kernel, dim3(64, sel.n), dim3(256), 0, s, sel, h->dense_cost, per, -1.0);
+        }
         RTS_HIP(hipGetLastError());
     }
     return RTS_OK;

@@ -933,6 +933,33 @@ __global__ void wtw_append_kernel(double *live, int32_t *appended, int32_t *appe
     }
 }
 
+// rts_wtw_restart: what rts_wtw_reset does, for the selected streams only; grid (slices, sel.n).  The state words, the
+// appended count (the array the next push reads; that push writes every entry of the other one), the stream's slice of
+// the live history (zeros again, wtw.py:55), its control and ticket words of the strip-DP pipeline and, when the stream
+// moves to another piece, its row of the reference tables.  Everything else a window needs (column records, boundary
+// words, step codes) is rebuilt by the hand-over of every window.  Other streams' words are not written.
+__global__ void __launch_bounds__(256) wtw_restart_kernel(RestartSel sel, int32_t *state, int32_t *appended, double *live,
+                                                          long long live_per_stream, int32_t *ctl, int32_t *ticket,
+                                                          long long *ref_first, int32_t *ref_len) {
+    if ((int)blockIdx.y >= sel.n) return;
+    const int b = sel.idx[blockIdx.y];
+    double *lv = live + (long long)b * live_per_stream;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < live_per_stream; i += stride) lv[i] = 0.0;
+    if (blockIdx.x == 0 && threadIdx.x < 8) {
+        state[(size_t)b * 8 + threadIdx.x] = 0;
+        if (ctl) ctl[(size_t)b * 8 + threadIdx.x] = 0;
+        if (threadIdx.x == 0) {
+            appended[b] = 0;
+            if (ticket) ticket[b] = 0;
+            if (sel.set_ref) {
+                ref_first[b] = sel.first[blockIdx.y];
+                ref_len[b] = sel.len[blockIdx.y];
+            }
+        }
+    }
+}
+
 }  // namespace rts
 
 struct rts_wtw {
@@ -941,6 +968,7 @@ struct rts_wtw {
     int live_stride;  // frames per stream in `live`: 2M (2 M_max with per-stream references)
     long long *ref_first;  // per-stream references (rts_wtw_create_refs): [B] first frames, device; NULL otherwise
     int32_t *ref_len;      // [B] lengths M_b, device
+    long long n_ref_frames;  // frames in the pool `ref` points to (rts_wtw_create_refs; rts_wtw_restart checks new ranges against it)
     double *live;
     int32_t *appended, *appended_next, *state, *path;
     int8_t *bwork;
@@ -1133,7 +1161,9 @@ int rts_wtw_create_refs(const double *chroma_refs_dev, int F, long long n_ref_fr
                              first_host[b], first_host[b] + len_host[b], n_ref_frames);
         if (len_host[b] > m_max) m_max = len_host[b];
     }
-    return wtw_create(chroma_refs_dev, F, m_max, B, win_frames, hop_frames, keep_last_d, first_host, len_host, out);
+    const int rc = wtw_create(chroma_refs_dev, F, m_max, B, win_frames, hop_frames, keep_last_d, first_host, len_host, out);
+    if (rc == RTS_OK) (*out)->n_ref_frames = n_ref_frames;
+    return rc;
 }
 
 int rts_wtw_destroy(rts_wtw *h) {
@@ -1176,6 +1206,25 @@ int rts_wtw_reset(rts_wtw *h, void *stream) {
     if (h->ctl) RTS_HIP(hipMemsetAsync(h->ctl, 0, sizeof(int32_t) * 8 * (size_t)h->B, s));
     if (h->err) RTS_HIP(hipMemsetAsync(h->err, 0, 16, s));
     if (h->ticket) RTS_HIP(hipMemsetAsync(h->ticket, 0, sizeof(int32_t) * (size_t)h->B, s));
+    return RTS_OK;
+}
+
+int rts_wtw_restart(rts_wtw *h, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
+                    void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
+    if (int rc = restart_check(h->B, mask_host, first_host, len_host, h->ref_first ? h->n_ref_frames : -1, h->M, "M_max");
+        rc != RTS_OK)
+        return rc;
+    if (int rc = wtw_check_device(h); rc != RTS_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    RestartSel sel;
+    for (int pos = 0; restart_next_chunk(h->B, mask_host, first_host, len_host, &pos, &sel) > 0;) {
+        hipLaunchKernelGGL(wtw_restart_kernel, dim3(16, sel.n), dim3(256), 0, s, sel, h->state, h->appended, h->live,
+                           (long long)h->live_stride * kWF, h->ctl, h->ticket, h->ref_first, h->ref_len);
+        RTS_HIP(hipGetLastError());
+    }
     return RTS_OK;
 }
 

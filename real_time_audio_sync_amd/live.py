@@ -23,28 +23,35 @@ _KINDS = {np.dtype(np.float32): nat.F32, np.dtype(np.int16): nat.I16}
 
 class LiveSession(object):
     def __init__(self, ref_chroma, batch, c=500, max_run_count=3, variant="otw", fft_len=4096, hop_size=2048,
-                 fs=22050, max_pending=1 << 16, device="cuda:0", wtw_params=None):
+                 fs=22050, max_pending=1 << 16, device="cuda:0", wtw_params=None, extra_refs=()):
         """``ref_chroma``: (12, N) reference chroma (e.g. chroma.wav_to_chroma(ref_path)), or a list of ``batch`` such
         arrays, one per stream (one piece per microphone; a list entry that repeats is uploaded once).  With
         ``wtw_params`` ({'dtw_win_size', 'dtw_hop_size'} in samples, like wtw.py:29-30) the streams are followed by
-        windowed time warping instead of ``variant`` ('otw' | 'livenote' | 'livenote_v2')."""
+        windowed time warping instead of ``variant`` ('otw' | 'livenote' | 'livenote_v2').  ``extra_refs`` (with a list
+        of references only): further pieces uploaded at create, which ``restart`` may move a microphone on to."""
         self.plan = ChromaPlan(fft_len, hop_size, fs, device)
         self.dev = self.device = self.plan.device
         self.B, self.L, self.H = int(batch), int(fft_len), int(hop_size)
         self.cap = int(max_pending)
         per_stream = isinstance(ref_chroma, (list, tuple))
+        self._conv = None   # per-stream references: id(object given) -> (object, what the tracker knows it as)
         if per_stream:
             if len(ref_chroma) != self.B:
                 raise ValueError("%d references for %d streams" % (len(ref_chroma), self.B))
-            conv = {}
-            refs = [conv.setdefault(id(r), np.asarray(r, dtype=np.float64)) for r in ref_chroma]
+            conv = self._conv = {}
+            for r in list(ref_chroma) + list(extra_refs):
+                conv.setdefault(id(r), (r, np.asarray(r, dtype=np.float64)))
+            refs = [conv[id(r)][1] for r in ref_chroma]
+            extra = [conv[id(r)][1] for r in extra_refs]
         else:
+            if len(extra_refs):
+                raise ValueError("extra_refs need per-stream references (a list as ref_chroma)")
             ref = np.asarray(ref_chroma, dtype=np.float64)
         self.otw = self.wtw = None
         if wtw_params is None:
             if per_stream:
                 self.otw = BatchedOTW.with_references(refs, c, max_run_count, variant=variant, device=device,
-                                                      dtype=torch.float64)
+                                                      dtype=torch.float64, extra_refs=extra)
             else:
                 self.otw = BatchedOTW(ref, c, max_run_count, batch=batch, variant=variant, device=device,
                                       dtype=torch.float64)
@@ -52,12 +59,11 @@ class LiveSession(object):
             from .wtw import BatchedWTW
             win, hopf = wtw_params['dtw_win_size'] // self.H, wtw_params['dtw_hop_size'] // self.H
             if per_stream:
-                devs = {}
-                for r in refs:
-                    if id(r) not in devs:
-                        devs[id(r)] = torch.from_numpy(np.ascontiguousarray(r.T)).to(self.dev)
-                self._ref_dev = [devs[id(r)] for r in refs]
-                self.wtw = BatchedWTW.with_references(self._ref_dev, win, hopf)
+                for k, (r, a) in list(conv.items()):
+                    conv[k] = (r, torch.from_numpy(np.ascontiguousarray(a.T)).to(self.dev))
+                self._ref_dev = [conv[id(r)][1] for r in ref_chroma]
+                self.wtw = BatchedWTW.with_references(self._ref_dev, win, hopf,
+                                                      extra_refs=[conv[id(r)][1] for r in extra_refs])
             else:
                 self._ref_dev = torch.from_numpy(np.ascontiguousarray(ref.T)).to(self.dev)
                 self.wtw = BatchedWTW(self._ref_dev, win, hopf, batch)
@@ -145,6 +151,25 @@ class LiveSession(object):
     @nat.on_device
     def reset(self):
         nat.check(nat.lib.rts_live_reset(self._h, self._stream()))
+
+    @nat.on_device
+    def restart(self, streams, refs=None, offsets=None):
+        """Put the listed streams back to the start while the others keep running (rts_live_restart; asynchronous,
+        ordered after the feeds already submitted): their pending samples are dropped, their tracker state is fresh,
+        ``poll()`` shows them running at the start again.  ``refs``: one entry per listed stream, each an object given
+        at create (``ref_chroma`` list / ``extra_refs``, matched by identity); ``offsets``: first frame inside the
+        piece; without ``refs``, "same piece, from this frame"."""
+        eng = self.otw or self.wtw
+        if refs is not None:
+            if self._conv is None or any(id(r) not in self._conv for r in refs):
+                raise ValueError("a reference to restart on must have been given at create (ref_chroma list / extra_refs)")
+            refs = [self._conv[id(r)][1] for r in refs]
+        mask, first, lens, pieces = eng._restart_tables(streams, refs, offsets)
+        nat.check(nat.lib.rts_live_restart(self._h, mask.ctypes.data, first.ctypes.data if first is not None else None,
+                                           lens.ctypes.data if lens is not None else None, self._stream()))
+        if self.otw:
+            self.otw._version += 1
+        eng._restarted(first, lens, pieces)
 
     def path(self, b=0):
         return (self.otw or self.wtw).path(b)

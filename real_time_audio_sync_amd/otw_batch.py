@@ -34,27 +34,87 @@ def frames_tensor(x, device, dtype=None):
 _on_device = nat.on_device
 
 
-def _concat_refs(refs, to_frames):
-    """Per-stream references -> (one device tensor [n_ref_frames][12], int64 first frames [B], int32 lengths [B]).  A
-    reference object that appears more than once is converted and uploaded once; its range is reused."""
+def _concat_refs(refs, to_frames, extra=()):
+    """Per-stream references -> (one device tensor [n_ref_frames][12], int64 first frames [B], int32 lengths [B], pool).
+    A reference object that appears more than once is converted and uploaded once; its range is reused.  ``extra``:
+    pieces uploaded behind them although no stream follows them yet.  ``pool`` maps id(object) -> (object, first frame,
+    frames) for everything uploaded (what ``restart`` looks references up in)."""
     if len(refs) < 1:
         raise ValueError("at least one reference is needed")
     parts, seen, first, lens, off = [], {}, [], [], 0
-    for r in refs:
+    for k, r in enumerate(list(refs) + list(extra)):
         if id(r) not in seen:
             t = to_frames(r)
             if parts and t.dtype != parts[0].dtype:
                 raise TypeError("all references must have the same dtype (%s, %s)" % (parts[0].dtype, t.dtype))
-            seen[id(r)] = (off, int(t.shape[0]))
+            seen[id(r)] = (r, off, int(t.shape[0]))
             parts.append(t)
             off += int(t.shape[0])
-        f, n = seen[id(r)]
-        first.append(f)
-        lens.append(n)
-    return torch.cat(parts).contiguous(), np.array(first, dtype=np.int64), np.array(lens, dtype=np.int32)
+        if k < len(refs):
+            first.append(seen[id(r)][1])
+            lens.append(seen[id(r)][2])
+    return torch.cat(parts).contiguous(), np.array(first, dtype=np.int64), np.array(lens, dtype=np.int32), seen
 
 
-class BatchedOTW:
+class _Restartable:
+    """Bookkeeping shared by BatchedOTW and BatchedWTW for ``restart``: which range of the uploaded pool every stream
+    follows.  ``_pool`` is None on a single-reference handle."""
+
+    def _init_refs(self, pool, first, lens):
+        self._pool = pool
+        self._piece = None if pool is None else [(int(f), int(n)) for f, n in zip(first, lens)]
+
+    def _grow_to_pool(self, restart_fn, first, lens):
+        """The handle's buffers are sized by the longest range given at create.  When a piece nobody follows yet is the
+        longest, stream 0 is created on it and put on its own reference by a restart right away (bit for bit a fresh
+        stream, by that call's contract)."""
+        f, n = max(((f, n) for _, f, n in self._pool.values()), key=lambda x: x[1])
+        if n <= int(lens.max()):
+            return first, lens, None
+        first0, lens0 = first.copy(), lens.copy()
+        first0[0], lens0[0] = f, n
+
+        def fix():
+            mask = np.zeros(self.B, dtype=np.uint8)
+            mask[0] = 1
+            nat.check(restart_fn(self._h, mask.ctypes.data, first.ctypes.data, lens.ctypes.data, self._stream()))
+        return first0, lens0, fix
+
+    def _restart_tables(self, streams, refs, offsets):
+        """-> (mask uint8 [B], first int64 [B] | None, lens int32 [B] | None, new (first, frames) of the pieces)."""
+        streams = [int(b) for b in streams]
+        for b in streams:
+            if not 0 <= b < self.B:
+                raise IndexError("stream %d out of range [0, %d)" % (b, self.B))
+        mask = np.zeros(self.B, dtype=np.uint8)
+        mask[streams] = 1
+        if refs is None and offsets is None:
+            return mask, None, None, {}
+        if self._pool is None:
+            raise ValueError("refs / offsets need a handle made by with_references")
+        if refs is not None and len(refs) != len(streams) or offsets is not None and len(offsets) != len(streams):
+            raise ValueError("refs / offsets need one entry per listed stream")
+        first, lens, pieces = np.zeros(self.B, dtype=np.int64), np.ones(self.B, dtype=np.int32), {}
+        for k, b in enumerate(streams):
+            if refs is None:
+                f, n = self._piece[b]
+            else:
+                if id(refs[k]) not in self._pool:
+                    raise ValueError("stream %d: this reference was not uploaded at create (refs / extra_refs)" % b)
+                _, f, n = self._pool[id(refs[k])]
+            o = int(offsets[k]) if offsets is not None else 0
+            if not 0 <= o < n:
+                raise ValueError("stream %d: offset %d outside its reference of %d frames" % (b, o, n))
+            first[b], lens[b], pieces[b] = f + o, n - o, (f, n)
+        return mask, first, lens, pieces
+
+    def _restarted(self, first, lens, pieces):
+        for b, piece in pieces.items():
+            self._piece[b] = piece
+            self.ref_lens[b] = lens[b]
+
+
+class BatchedOTW(_Restartable):
     """``ref``: (12, N) feature-major array/tensor, or a device tensor already [N][12] with
     ``frame_major=True``.  ``variant``: 'otw' | 'livenote' | 'livenote_v2'."""
 
@@ -67,6 +127,7 @@ class BatchedOTW:
             self.ref = frames_tensor(ref, self.device, dtype)
         self.N, F = self.ref.shape
         self.ref_lens = None
+        self._init_refs(None, None, None)
         self.B, self.c = int(batch), int(c)
         self.variant = variant
         h = ctypes.c_void_p()
@@ -77,24 +138,31 @@ class BatchedOTW:
 
     @classmethod
     def with_references(cls, refs, c, max_run_count, variant="otw", euclid=False, device="cuda:0", dtype=None,
-                        waves=None):
+                        waves=None, extra_refs=()):
         """One reference per stream (one piece per microphone): ``refs`` is a list of ``batch`` (12, N_b) arrays or
         tensors.  Stream b behaves exactly like stream 0 of ``BatchedOTW(refs[b], ...)``.  A reference object that
-        appears more than once is uploaded once.  ``N`` is the longest N_b, ``ref_lens`` holds them all.  The dense
-        mirror is not available on such a handle (``enable_dense`` / ``replay_dense`` raise)."""
+        appears more than once is uploaded once.  ``extra_refs``: pieces uploaded as well although no stream follows
+        them yet (the repertoire ``restart`` may move a microphone on to).  ``N`` is the longest of them all,
+        ``ref_lens`` holds what each stream follows now.  The dense mirror is not available on such a handle
+        (``enable_dense`` / ``replay_dense`` raise)."""
         self = cls.__new__(cls)
         self._set_device(device)
-        self.ref, first, lens = _concat_refs(refs, lambda r: frames_tensor(r, self.device, dtype))
+        self.ref, first, lens, pool = _concat_refs(refs, lambda r: frames_tensor(r, self.device, dtype), extra_refs)
         F = self.ref.shape[1]
-        self.N, self.ref_lens = int(lens.max()), lens
+        self.ref_lens = lens
+        self._init_refs(pool, first, lens)
         self.B, self.c = len(refs), int(c)
         self.variant = variant
+        first0, lens0, fix = self._grow_to_pool(nat.lib.rts_otw_restart, first, lens)
+        self.N = int(lens0.max())
         h = ctypes.c_void_p()
         nat.check(nat.lib.rts_otw_create_refs(self.ref.data_ptr(), _np_dtype_code(self.ref.dtype), F, self.ref.shape[0],
-                                              first.ctypes.data, lens.ctypes.data, self.B, self.c, int(max_run_count),
+                                              first0.ctypes.data, lens0.ctypes.data, self.B, self.c, int(max_run_count),
                                               _VARIANTS[variant], nat.COST_EUCLID if euclid else nat.COST_DOT,
                                               ctypes.byref(h)))
         self._finish(h, waves)
+        if fix:
+            fix()
         return self
 
     def _set_device(self, device):
@@ -169,6 +237,19 @@ class BatchedOTW:
         self._version += 1
         self._keep = None
         nat.check(nat.lib.rts_otw_reset(self._h, self._stream()))
+
+    @_on_device
+    def restart(self, streams, refs=None, offsets=None):
+        """Put the listed streams back to the start while the others keep running (rts_otw_restart; asynchronous on
+        the current stream).  ``refs``: one entry per listed stream, each an object that was uploaded at create
+        (``refs`` / ``extra_refs`` of ``with_references``, matched by identity): the stream moves on to that piece.
+        ``offsets``: first frame inside the piece, the stream then follows ``ref[:, offset:]`` and its path indices
+        count from there; without ``refs`` it means "same piece, from this frame"."""
+        mask, first, lens, pieces = self._restart_tables(streams, refs, offsets)
+        nat.check(nat.lib.rts_otw_restart(self._h, mask.ctypes.data, first.ctypes.data if first is not None else None,
+                                          lens.ctypes.data if lens is not None else None, self._stream()))
+        self._version += 1
+        self._restarted(first, lens, pieces)
 
     # ---- results ------------------------------------------------------------------------------
     @_on_device

@@ -11,9 +11,10 @@ import torch
 from . import _native as nat
 from . import filters
 from .chroma import ChromaPlan
+from .otw_batch import _Restartable, _concat_refs
 
 
-class BatchedWTW(object):
+class BatchedWTW(_Restartable):
     """B live streams against one reference chroma.  ``chroma_ref_dev``: device tensor [M][12] float64."""
 
     def __init__(self, chroma_ref_dev, win_frames, hop_frames, batch=1, keep_last_d=False):
@@ -23,6 +24,7 @@ class BatchedWTW(object):
         self.ref = chroma_ref_dev
         self.M = chroma_ref_dev.shape[0]
         self.ref_lens = None
+        self._init_refs(None, None, None)
         self.B, self.W, self.hopf = int(batch), int(win_frames), int(hop_frames)
         h = ctypes.c_void_p()
         nat.check(nat.lib.rts_wtw_create(self.ref.data_ptr(), 12, self.M, self.B, self.W, self.hopf,
@@ -31,25 +33,31 @@ class BatchedWTW(object):
         self._keep_d = keep_last_d
 
     @classmethod
-    def with_references(cls, chroma_refs, win_frames, hop_frames, keep_last_d=False):
+    def with_references(cls, chroma_refs, win_frames, hop_frames, keep_last_d=False, extra_refs=()):
         """One reference chroma per stream: ``chroma_refs`` is a list of ``batch`` device tensors [M_b][12] float64
         (one device).  Stream b behaves exactly like stream 0 of ``BatchedWTW(chroma_refs[b], ...)``; a tensor that
-        appears more than once is copied once.  ``M`` is the longest M_b, ``ref_lens`` holds them all."""
-        from .otw_batch import _concat_refs
-        for r in chroma_refs:
+        appears more than once is copied once.  ``extra_refs``: pieces uploaded as well although no stream follows them
+        yet (what ``restart`` may move a microphone on to).  ``M`` is the longest of them all, ``ref_lens`` holds what
+        each stream follows now."""
+        for r in list(chroma_refs) + list(extra_refs):
             assert r.dtype == torch.float64 and r.dim() == 2 and r.shape[1] == 12
         self = cls.__new__(cls)
         self.device = chroma_refs[0].device
         torch.cuda.set_device(self.device)
-        self.ref, first, lens = _concat_refs(chroma_refs, lambda r: r.to(self.device))
-        self.M, self.ref_lens = int(lens.max()), lens
+        self.ref, first, lens, pool = _concat_refs(chroma_refs, lambda r: r.to(self.device), extra_refs)
+        self.ref_lens = lens
+        self._init_refs(pool, first, lens)
         self.B, self.W, self.hopf = len(chroma_refs), int(win_frames), int(hop_frames)
+        first0, lens0, fix = self._grow_to_pool(nat.lib.rts_wtw_restart, first, lens)
+        self.M = int(lens0.max())
         h = ctypes.c_void_p()
-        nat.check(nat.lib.rts_wtw_create_refs(self.ref.data_ptr(), 12, self.ref.shape[0], first.ctypes.data,
-                                              lens.ctypes.data, self.B, self.W, self.hopf, int(bool(keep_last_d)),
+        nat.check(nat.lib.rts_wtw_create_refs(self.ref.data_ptr(), 12, self.ref.shape[0], first0.ctypes.data,
+                                              lens0.ctypes.data, self.B, self.W, self.hopf, int(bool(keep_last_d)),
                                               ctypes.byref(h)))
         self._h = h
         self._keep_d = keep_last_d
+        if fix:
+            fix()
         return self
 
     def close(self):
@@ -65,6 +73,16 @@ class BatchedWTW(object):
     @nat.on_device
     def reset(self):
         nat.check(nat.lib.rts_wtw_reset(self._h, self._stream()))
+
+    @nat.on_device
+    def restart(self, streams, refs=None, offsets=None):
+        """Put the listed streams back to the start while the others keep running (rts_wtw_restart; asynchronous on
+        the current stream).  ``refs`` / ``offsets`` as for ``BatchedOTW.restart``: tensors that were given to
+        ``with_references`` (``chroma_refs`` / ``extra_refs``), matched by identity, and the first frame inside them."""
+        mask, first, lens, pieces = self._restart_tables(streams, refs, offsets)
+        nat.check(nat.lib.rts_wtw_restart(self._h, mask.ctypes.data, first.ctypes.data if first is not None else None,
+                                          lens.ctypes.data if lens is not None else None, self._stream()))
+        self._restarted(first, lens, pieces)
 
     @nat.on_device
     def push(self, cols_dev, n_new_dev=None, precheck=True):
