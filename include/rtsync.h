@@ -351,6 +351,10 @@ typedef struct rts_live rts_live;
  * a tracker created for another number of streams is refused with RTS_ERR_INVALID.
  * The plan and the tracker must outlive the handle and live on the current device.  max_pending: capacity in samples of
  * each stream's pending buffer (>= fft_len + hop); a feed that would exceed it is refused with RTS_ERR_INVALID.
+ * A plan with hop > fft_len is accepted and follows the reference's slicing: a column is taken as soon as fft_len
+ * samples are pending, and `buf = buf[hop:]` on fewer than hop samples leaves none, so pending after the drop is
+ * max(0, pending - columns * hop) -- the samples between a column's end and its hop are skipped only as far as they
+ * have arrived, and the next column starts at the next sample delivered.
  * All calls of one handle must use the same `stream`. */
 int rts_live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, rts_live **out);
 int rts_live_destroy(rts_live *h);

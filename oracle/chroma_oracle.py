@@ -150,3 +150,47 @@ class WtwAudioOracle:
     @property
     def path(self):
         return self._core.path
+
+
+class LiveLoopModel:
+    """The reference's audio loops for one stream and nothing else (wtw.py:73-83, livenote_live.py:205-208): a Python
+    list and ``buf += new; while len(buf) >= L: column of buf[:L]; buf = buf[hop:]``, for any fft_len / hop.  With
+    hop > fft_len the slice ``buf[hop:]`` of a shorter list is empty, so nothing stays pending and the next column
+    starts at the next sample delivered.  Keeps the sample slice of every column, where it began among all samples fed,
+    and per feed (len(buf) before the first drop, columns taken, len(buf) afterwards)."""
+
+    def __init__(self, fft_len, hop_size):
+        self.fft_len, self.hop_size = int(fft_len), int(hop_size)
+        self.restart()
+
+    def restart(self):
+        self.buf = []
+        self.fed = 0
+        self.slices = []
+        self.starts = []
+        self.log = []
+
+    def feed(self, samples):
+        self.buf += list(samples)
+        self.fed += len(samples)
+        before, taken = len(self.buf), 0
+        while len(self.buf) >= self.fft_len:
+            self.starts.append(self.fed - len(self.buf))
+            self.slices.append(self.buf[: self.fft_len])
+            self.buf = self.buf[self.hop_size:]
+            taken += 1
+        self.log.append((before, taken, len(self.buf)))
+        return len(self.buf)
+
+    def columns(self, fs=FS):
+        """Oracle chroma of every slice, [K][12] float64, column by column like WtwAudioOracle.insert."""
+        return live_loop_columns(self.slices, self.fft_len, fs)
+
+
+def live_loop_columns(slices, fft_len, fs=FS):
+    fb, win = _fb(fs, fft_len), np.hanning(fft_len)
+    out = np.zeros((len(slices), 12))
+    for k, s in enumerate(slices):
+        spec = np.abs(np.fft.rfft(np.array(s) * win)) ** 2
+        out[k] = l2_normalize_columns(np.dot(fb, spec)[:, None])[:, 0]
+    return out

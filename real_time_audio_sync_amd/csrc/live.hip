@@ -91,7 +91,9 @@ __global__ void __launch_bounds__(1024) live_compact_kernel(LiveArgs g) {
     const int b = blockIdx.x;
     const int p = g.n_samples[b];
     const int used = g.n_frames[b] * g.hop;
-    const int rem = p - used;
+    // hop > fft_len: the last column's hop may reach past what is pending; `buf = buf[hop:]` then leaves an empty
+    // list (wtw.py:83, livenote_live.py:208), and the next column starts at the next sample delivered
+    const int rem = p > used ? p - used : 0;
     float *buf = g.buf + (size_t)b * g.cap;
     if (used > 0 && rem > 0) {
         // forward move of possibly overlapping ranges: every round reads its elements before any of them is written,
@@ -346,7 +348,8 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
         const long long q = h->pending_host[b] + counts[b];
         const int nf = q >= h->L ? (int)((q - h->L) / h->hop + 1) : 0;
         if (nf > n_max) n_max = nf;
-        h->pending_host[b] = q - (long long)nf * h->hop;
+        const long long used = (long long)nf * h->hop;
+        h->pending_host[b] = q > used ? q - used : 0;  // hop > fft_len: a slice past the end leaves nothing
     }
     h->slot = -1;
     h->next = (k + 1) % kLiveSlots;

@@ -108,7 +108,9 @@ class LiveSession(object):
         self.submit(block.dtype)
 
     def feed(self, buffers, wait=False):
-        """``buffers``: one array of new samples per stream (None / empty = nothing new).  Asynchronous: returns the
+        """``buffers``: one array of new samples per stream (None / empty = nothing new), int16 (PCM16) or float; the
+        feed goes out as int16 when every buffer is int16, else as float32 with the int16 buffers scaled by 1/32768
+        (the value the device would have made of them).  Asynchronous: returns the
         streams known to have reached the end of the reference ("stop", livenote_live.py:188-190) according to what
         the device has published so far -- the result of this very feed shows up in a later call, or at once with
         ``wait=True`` (which synchronises the stream)."""
@@ -120,6 +122,9 @@ class LiveSession(object):
             n = 0 if x is None else len(x)
             cv[b] = n
             if n:
+                if dt is np.float32 and np.asarray(x).dtype == np.int16:
+                    # mixed feed: PCM16 next to float buffers goes out as float32, scaled like the device scales (exact)
+                    x = np.asarray(x).astype(np.float32) / np.float32(32768.0)
                 sv[off:off + n] = x
                 off += n
         self.submit(dt)

@@ -31,7 +31,11 @@ def test_live_session_matches_offline(chopin_audio, otw_golden):
             n = min(sizes[b], lens[b] - pos[b])
             bufs.append(live[pos[b]:pos[b] + n] if n > 0 else None)
             pos[b] += max(n, 0)
-        stopped |= set(sess.feed(bufs))
+        stopped |= set(sess.feed(bufs))      # asynchronous: what the device had published by then
+    sess.sync()
+    final = sess.stopped()
+    assert stopped <= set(final)             # "stop" is sticky
+    want_stopped = []
     # offline: un-padded hop framing of the same samples, then one whole-sequence OTW run
     plan = chroma._plan()
     for b in range(3):
@@ -45,7 +49,11 @@ def test_live_session_matches_offline(chopin_audio, otw_golden):
         o = oracle.OtwOracle(ref_chroma, 50, 3)
         o.run(cols.t().cpu().numpy())
         assert np.array_equal(sess.path(b), o.path), b
+        if o.state["status"] == oracle.STOP_REF_END:
+            want_stopped.append(b)
+        assert sess.poll()["status"][b] == o.state["status"], b
         eng.close()
+    assert final == want_stopped
     assert sess.position(0) is not None
     sess.close()
 
