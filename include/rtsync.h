@@ -357,16 +357,38 @@ typedef struct rts_live rts_live;
  * have arrived, and the next column starts at the next sample delivered.
  * All calls of one handle must use the same `stream`. */
 int rts_live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, rts_live **out);
+
+/* What a live handle hands to its tracker. */
+#define RTS_FEATURE_CHROMA 0      /* the normalised chroma columns themselves */
+#define RTS_FEATURE_CHROMA_DIFF 1 /* max(chroma[m+1] - chroma[m], 0) per pitch class: wav_to_chroma_diff, chroma.py:77-90 */
+
+/* rts_live_create with a feature kind (rts_live_create is this with RTS_FEATURE_CHROMA).
+ * RTS_FEATURE_CHROMA_DIFF is the microphone form of the reference's headline configuration (tests.py:145-163,
+ * LiveNoteV2(..., chroma_diff=True) on wav_to_chroma_diff features): column m handed to the tracker is
+ * np.clip(np.diff(chroma), 0, inf)[:, m] of the columns the ingestion makes (un-padded hop framing), not renormalised,
+ * a NaN difference stays NaN.  The difference needs the previous chroma column of every stream, which the handle
+ * carries on the device from feed to feed: a stream's tracker receives its first frame when the stream's second chroma
+ * column is complete, and a feed in which no stream completes a difference column is an ordinary feed.
+ * The tracker's reference must itself be difference features (wav_to_chroma_diff(ref) / rts_chroma_diff of the
+ * reference's chroma).  The cost kind is the tracker's own choice at its create: tests.py:156 pairs RTS_COST_EUCLID
+ * with either feature kind, and livenote_v2.py:168 uses it for chroma_diff=True.
+ * RTS_FEATURE_CHROMA_DIFF with a `wtw` tracker returns RTS_ERR_UNSUPPORTED: the reference never runs WTW on difference
+ * features, and its cosine cost is NaN on the zero columns they contain.  Any other feature_kind: RTS_ERR_INVALID. */
+int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, int feature_kind,
+                             rts_live **out);
 int rts_live_destroy(rts_live *h);
-/* Drops pending samples and resets the bound tracker.  Synchronises `stream`. */
+/* Drops pending samples (and, with RTS_FEATURE_CHROMA_DIFF, the carried chroma column of every stream: each stream
+ * is fresh again and skips its first chroma column) and resets the bound tracker.  Synchronises `stream`. */
 int rts_live_reset(rts_live *h, void *stream);
 /* Restart single streams of a session: drops the selected streams' pending samples (device buffer and host mirror:
  * rts_live_pending reads 0 for them), restarts them in the bound tracker (rts_otw_restart / rts_wtw_restart, same
  * arguments and errors) and republishes their status / position words, so that rts_live_poll shows RTS_RUNNING and the
  * positions of a fresh session for them; feeds_done does not go backwards.  Ordered after the feeds already submitted:
  * samples submitted before the call belong to the stream's old run, samples submitted after it to the new one.  A
- * staging slot handed out by rts_live_staging and not yet submitted stays valid.  Unlike rts_live_reset it does not
- * synchronise anything. */
+ * staging slot handed out by rts_live_staging and not yet submitted stays valid.  With RTS_FEATURE_CHROMA_DIFF the
+ * carried chroma column of a selected stream is dropped with its samples: its next chroma column only becomes the new
+ * carry, so the first feed that completes columns for it hands the tracker one column fewer than it completes.
+ * Unlike rts_live_reset it does not synchronise anything. */
 int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
                      void *stream);
 
@@ -375,8 +397,10 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
  * samples of stream b and the samples of all streams packed back to back in stream order (float32 or int16) to
  * samples_host (capacity_samples = B * max_pending).  rts_live_submit then enqueues, without synchronising anything:
  * one host-to-device copy of the used part of the slot (on an internal copy stream, so that it overlaps the kernels of
- * the previous feed), append to the per-stream pending buffers, chroma of every complete hop, push into the tracker,
- * drop of the consumed samples (hop per column, livenote_live.py:208 / wtw.py:83), publication of the status words. */
+ * the previous feed), append to the per-stream pending buffers, chroma of every complete hop, with
+ * RTS_FEATURE_CHROMA_DIFF the difference against the previous column (the carried one for a feed's first), push into
+ * the tracker, drop of the consumed samples (hop per column, livenote_live.py:208 / wtw.py:83), publication of the
+ * status words.  A refused feed (RTS_ERR_INVALID) changes neither the pending counts nor the carry. */
 int rts_live_staging(rts_live *h, int32_t **counts_host, void **samples_host, long long *capacity_samples);
 int rts_live_submit(rts_live *h, int sample_kind /* RTS_F32 | RTS_I16 */, void *stream);
 /* The same from caller-owned host arrays (one memcpy into the staging slot): samples_host packed like above. */
@@ -388,6 +412,16 @@ int rts_live_feed(rts_live *h, const void *samples_host, int sample_kind, const 
  * reflect for every stream, *feeds_submitted = feeds enqueued so far.  Any pointer may be NULL. */
 int rts_live_poll(rts_live *h, int32_t *status /* [B] */, int32_t *positions /* [B][2] */, int *feeds_done,
                   int *feeds_submitted);
+/* Device views of the columns the most recently submitted feed handed to the tracker, and of their per-stream counts
+ * (zero-copy consumers, tests): *cols_dev is float64, stream b's column i at cols_dev[(b * *cols_stride + i) * 12],
+ * i < (*n_cols_dev)[b].  *cols_stride, the rows per stream, is the largest number of chroma columns any stream completed
+ * in that feed (0: the feed completed none, or nothing was fed since create / reset) -- the layout the chroma kernel
+ * and the tracker push share, so it changes from feed to feed and is returned here from the host mirror; it never
+ * exceeds *cols_cap = (max_pending - fft_len) / hop + 1, the rows per stream the buffer has room for.  Valid for both
+ * feature kinds: RTS_FEATURE_CHROMA views the chroma columns and the counts rts_chroma_frames_batch was given,
+ * RTS_FEATURE_CHROMA_DIFF the difference columns and their counts.  The pointers stay the same for the handle's
+ * life; the contents belong to the last feed in stream order, the caller synchronises.  Any pointer may be NULL. */
+int rts_live_columns_view(rts_live *h, double **cols_dev, int *cols_cap, int *cols_stride, int32_t **n_cols_dev);
 /* Samples pending per stream after everything submitted so far (the host-side mirror; exact). */
 int rts_live_pending(rts_live *h, long long *pending_host /* [B] */);
 

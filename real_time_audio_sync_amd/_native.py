@@ -16,6 +16,7 @@ SO_PATH = os.environ.get("RTSYNC_LIB") or os.path.join(_HERE, "librtsync.so")
 F32, F64, I16 = 0, 1, 2
 VARIANT_OTW, VARIANT_LIVENOTE, VARIANT_LIVENOTE_V2 = 0, 1, 2
 COST_DOT, COST_EUCLID = 0, 1
+FEATURE_CHROMA, FEATURE_CHROMA_DIFF = 0, 1
 DIR_NONE, DIR_BOTH, DIR_ROW, DIR_COLUMN = -1, 0, 1, 2
 RUNNING, STOP_REF_END, LIVE_OVERFLOW, DEVICE_FAULT = 0, 1, 2, 3
 MODE_INSERT_LOOP, MODE_SET_LIVE = 0, 1
@@ -103,6 +104,8 @@ _decl("rts_wtw_state_view", _i32, [_vp, ctypes.POINTER(_vp)])
 WTW_STATE_LEN = 8
 
 _decl("rts_live_create", _i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_vp)])
+_decl("rts_live_create_features", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_vp)])
+_decl("rts_live_columns_view", _i32, [_vp, ctypes.POINTER(_vp), _pi32, _pi32, ctypes.POINTER(_vp)])
 _decl("rts_live_destroy", _i32, [_vp])
 _decl("rts_live_reset", _i32, [_vp, _vp])
 _decl("rts_live_restart", _i32, [_vp, _vp, _vp, _vp, _vp])

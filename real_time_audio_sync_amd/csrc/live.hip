@@ -13,12 +13,16 @@
 //                         behind the pending ones in a per-stream device buffer; pending -> n_samples, complete hops ->
 //                         n_frames  ((pending - fft_len) / hop + 1 once pending >= fft_len).
 //   rts_chroma_frames_batch   un-padded framing of every stream's pending samples -> chroma columns [B][n_max][12]
+//   live_diff_kernel      RTS_FEATURE_CHROMA_DIFF only: the columns become max(chroma[m+1] - chroma[m], 0)
+//                         (np.clip(np.diff(chroma), 0, inf), chroma.py:85-90) in a second buffer; the last chroma
+//                         column of every stream is carried on the device from feed to feed
 //   rts_otw_push | rts_wtw_push   the columns into the alignment state (insert semantics, column by column)
 //   live_compact_kernel   drop hop * n_frames consumed samples per stream (data = data[2048:], livenote_live.py:208),
 //                         and publish {status, live position, ref position, feed number} of every stream into
 //                         host-mapped memory -- rts_live_poll reads those words without touching the stream.
 // The host keeps an exact mirror of the pending counts (integer arithmetic on the counts it was given), which is how it
-// knows n_max for the launch geometry without reading anything back.
+// knows n_max for the launch geometry without reading anything back; in diff mode it mirrors the carry flags the same
+// way, which is how it knows whether any stream hands a column to the tracker in a feed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -30,6 +34,7 @@ namespace rts {
 
 constexpr int kLiveSlots = 4;
 constexpr int kLiveWords = 4;  // per stream in the mapped status block: status, live position, ref position, feed number
+constexpr int kLiveF = 12;     // pitch classes of a column (96 B in float64)
 
 struct LiveArgs {
     const unsigned char *stage;  // device copy of the staging slot: int32 counts[B], int32 offs[B], then samples at samples_off
@@ -43,6 +48,12 @@ struct LiveArgs {
     int state_len, st_status, st_live, st_ref;
     int32_t *pub;                // host-mapped [B][kLiveWords]
     int feed_no;
+    // RTS_FEATURE_CHROMA_DIFF (all NULL in chroma mode)
+    const double *cols;          // [B][cols_stride][12] chroma columns of this feed
+    double *dcols;               // [B][cols_stride][12] difference columns handed to the tracker
+    double *carry;               // [B][12] last chroma column of every stream
+    int32_t *has_carry, *n_cols; // [B]
+    int cols_stride;             // rows per stream in cols / dcols: n_max of this feed
 };
 
 __device__ __forceinline__ void live_publish(const LiveArgs &g, int b) {
@@ -112,14 +123,43 @@ __global__ void __launch_bounds__(1024) live_compact_kernel(LiveArgs g) {
     }
 }
 
+// RTS_FEATURE_CHROMA_DIFF, one workgroup per stream, between the chroma kernel and the tracker push.  With n =
+// n_frames[b] new chroma columns: difference column i - skip = max(cols[i] - prev_i, 0), prev_i = cols[i - 1], or the
+// carried column for i = 0; a stream without a carry (fresh, restarted, reset) skips i = 0, so its tracker gets its
+// first frame with its second chroma column.  A NaN difference stays NaN, like chroma_diff_kernel.  Lanes run over the
+// flat (column, pitch class) index: loads and stores are contiguous 8-byte accesses.  n_frames is left as it is (the
+// compaction drops n_frames * hop samples); the tracker push takes n_cols.  Every lane reads the carry and its flag
+// before the barrier, the new carry is written behind it.
+__global__ void __launch_bounds__(256) live_diff_kernel(LiveArgs g) {
+    const int b = blockIdx.x;
+    int n = g.n_frames[b];
+    if (n > g.cols_stride) n = g.cols_stride;  // (the host mirror sizes cols_stride as the largest n_frames)
+    const int skip = g.has_carry[b] ? 0 : 1;
+    const double *in = g.cols + (size_t)b * g.cols_stride * kLiveF;
+    double *out = g.dcols + (size_t)b * g.cols_stride * kLiveF;
+    double *carry = g.carry + (size_t)b * kLiveF;
+    for (int e = skip * kLiveF + threadIdx.x; e < n * kLiveF; e += blockDim.x) {
+        const double prev = e >= kLiveF ? in[e - kLiveF] : carry[e];
+        const double d = in[e] - prev;
+        out[e - skip * kLiveF] = d < 0.0 ? 0.0 : d;
+    }
+    __syncthreads();
+    if (n > 0 && threadIdx.x < kLiveF) carry[threadIdx.x] = in[(n - 1) * kLiveF + threadIdx.x];
+    if (threadIdx.x == 0) {
+        g.n_cols[b] = n > skip ? n - skip : 0;
+        if (n > 0) g.has_carry[b] = 1;
+    }
+}
+
 // rts_live_restart, after the bound tracker's own restart: the selected streams' pending samples are dropped and their
 // status / position words republished from the (now fresh) tracker state.  The feed number is left alone: the words
-// still reflect every feed submitted before the restart.
+// still reflect every feed submitted before the restart.  In diff mode the carried chroma column goes with the samples.
 __global__ void live_restart_kernel(RestartSel sel, LiveArgs g) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= sel.n) return;
     const int b = sel.idx[i];
     g.pending[b] = 0;
+    if (g.has_carry) g.has_carry[b] = 0;
     const int32_t *st = g.state + (size_t)b * g.state_len;
     volatile int32_t *p = g.pub + (size_t)b * kLiveWords;
     p[0] = st[g.st_status];
@@ -147,6 +187,13 @@ struct rts_live {
     int32_t *pending, *n_samples, *n_frames;
     double *cols;
     long long *pending_host;
+    // RTS_FEATURE_CHROMA_DIFF (NULL in chroma mode): second column buffer, carried column and flag per stream, columns
+    // handed to the tracker per stream; host mirror of the flags and the scratch a feed computes the next ones into
+    int feature_kind;
+    double *dcols, *carry;
+    int32_t *has_carry, *n_cols;
+    uint8_t *has_carry_host, *has_carry_next;
+    int last_stride;     // rows per stream in the layout of the last submitted feed (rts_live_columns_view)
     int32_t *pub_host, *pub_dev;
     const int32_t *state_dev;
     int state_len, st_status, st_live, st_ref;
@@ -179,6 +226,12 @@ int rts_live_destroy(rts_live *h) {
     if (h->n_samples) (void)hipFree(h->n_samples);
     if (h->n_frames) (void)hipFree(h->n_frames);
     if (h->cols) (void)hipFree(h->cols);
+    if (h->dcols) (void)hipFree(h->dcols);
+    if (h->carry) (void)hipFree(h->carry);
+    if (h->has_carry) (void)hipFree(h->has_carry);
+    if (h->n_cols) (void)hipFree(h->n_cols);
+    free(h->has_carry_host);
+    free(h->has_carry_next);
     if (h->pub_host) (void)hipHostFree(h->pub_host);
     free(h->pending_host);
     free(h);
@@ -186,9 +239,19 @@ int rts_live_destroy(rts_live *h) {
 }
 
 int rts_live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, rts_live **out) {
+    return rts_live_create_features(plan, otw, wtw, B, max_pending, RTS_FEATURE_CHROMA, out);
+}
+
+int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, int feature_kind,
+                             rts_live **out) {
     using namespace rts;
     if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
     *out = nullptr;
+    if (feature_kind != RTS_FEATURE_CHROMA && feature_kind != RTS_FEATURE_CHROMA_DIFF)
+        return set_error(RTS_ERR_INVALID, "feature_kind must be RTS_FEATURE_CHROMA or RTS_FEATURE_CHROMA_DIFF, not %d", feature_kind);
+    if (feature_kind == RTS_FEATURE_CHROMA_DIFF && wtw)
+        return set_error(RTS_ERR_UNSUPPORTED, "chroma-difference features with a WTW tracker: the reference never runs WTW on "
+                                              "them, and its cosine cost is NaN on the zero columns they contain");
     if (!plan) return set_error(RTS_ERR_INVALID, "plan is NULL");
     if ((otw == nullptr) == (wtw == nullptr)) return set_error(RTS_ERR_INVALID, "exactly one of otw / wtw must be given");
     if (B < 1) return set_error(RTS_ERR_INVALID, "B must be >= 1");
@@ -210,6 +273,7 @@ int rts_live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max
     h->cap = max_pending;
     h->cols_cap = (max_pending - fft_len) / hop + 1;
     h->slot = -1;
+    h->feature_kind = feature_kind;
     h->samples_off = (2 * sizeof(int32_t) * (size_t)B + 255) & ~(size_t)255;
     h->slot_bytes = h->samples_off + sizeof(float) * (size_t)B * max_pending;
     h->pending_host = (long long *)calloc((size_t)B, sizeof(long long));
@@ -226,12 +290,25 @@ int rts_live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max
     if (e == hipSuccess) e = hipMalloc((void **)&h->n_samples, sizeof(int32_t) * (size_t)B);
     if (e == hipSuccess) e = hipMalloc((void **)&h->n_frames, sizeof(int32_t) * (size_t)B);
     if (e == hipSuccess) e = hipMalloc((void **)&h->cols, sizeof(double) * 12 * (size_t)B * h->cols_cap);
+    const bool diff = feature_kind == RTS_FEATURE_CHROMA_DIFF;
+    if (diff) {
+        h->has_carry_host = (uint8_t *)calloc((size_t)B, 1);
+        h->has_carry_next = (uint8_t *)calloc((size_t)B, 1);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->dcols, sizeof(double) * 12 * (size_t)B * h->cols_cap);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->carry, sizeof(double) * 12 * (size_t)B);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->has_carry, sizeof(int32_t) * (size_t)B);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->n_cols, sizeof(int32_t) * (size_t)B);
+        if (e == hipSuccess) e = hipMemset(h->carry, 0, sizeof(double) * 12 * (size_t)B);
+        if (e == hipSuccess) e = hipMemset(h->has_carry, 0, sizeof(int32_t) * (size_t)B);
+        if (e == hipSuccess) e = hipMemset(h->n_cols, 0, sizeof(int32_t) * (size_t)B);
+    }
+    if (e == hipSuccess) e = hipMemset(h->n_frames, 0, sizeof(int32_t) * (size_t)B);
     if (e == hipSuccess)
         e = hipHostMalloc((void **)&h->pub_host, sizeof(int32_t) * kLiveWords * (size_t)B, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&h->pub_dev, h->pub_host, 0);
     if (e == hipSuccess) e = hipMemset(h->pending, 0, sizeof(int32_t) * (size_t)B);
     if (e == hipSuccess) e = hipMemset(h->buf, 0, sizeof(float) * (size_t)B * max_pending);
-    if (e != hipSuccess || !h->pending_host) {
+    if (e != hipSuccess || !h->pending_host || (diff && (!h->has_carry_host || !h->has_carry_next))) {
         rts_live_destroy(h);
         return set_error(RTS_ERR_HIP, "rts_live_create: %s", hipGetErrorString(e));
     }
@@ -270,10 +347,15 @@ int rts_live_reset(rts_live *h, void *stream) {
     RTS_HIP(hipStreamSynchronize(h->copy_stream));
     RTS_HIP(hipMemsetAsync(h->pending, 0, sizeof(int32_t) * (size_t)h->B, (hipStream_t)stream));
     memset(h->pending_host, 0, sizeof(long long) * (size_t)h->B);
+    if (h->has_carry) {
+        RTS_HIP(hipMemsetAsync(h->has_carry, 0, sizeof(int32_t) * (size_t)h->B, (hipStream_t)stream));
+        memset(h->has_carry_host, 0, (size_t)h->B);
+    }
     memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * (size_t)h->B);
     memset(h->used, 0, sizeof(h->used));
     h->slot = -1;
     h->feeds = 0;
+    h->last_stride = 0;
     return h->otw ? rts_otw_reset(h->otw, stream) : rts_wtw_reset(h->wtw, stream);
 }
 
@@ -291,6 +373,7 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
     LiveArgs g;
     memset(&g, 0, sizeof(g));
     g.pending = h->pending;
+    g.has_carry = h->has_carry;
     g.state = h->state_dev;
     g.state_len = h->state_len;
     g.st_status = h->st_status;
@@ -303,7 +386,10 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
         RTS_HIP(hipGetLastError());
     }
     for (int b = 0; b < h->B; b++)
-        if (mask_host[b]) h->pending_host[b] = 0;  // the mirror: samples submitted from here on belong to the new run
+        if (mask_host[b]) {  // the mirrors: samples submitted from here on belong to the new run
+            h->pending_host[b] = 0;
+            if (h->has_carry_host) h->has_carry_host[b] = 0;
+        }
     return RTS_OK;
 }
 
@@ -340,7 +426,8 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
                              h->pending_host[b], counts[b], h->cap);
         total += counts[b];
     }
-    int n_max = 0;
+    const bool diff = h->feature_kind == RTS_FEATURE_CHROMA_DIFF;
+    int n_max = 0, n_max_diff = 0;  // most chroma columns of a stream; most columns a stream hands to the tracker
     total = 0;
     for (int b = 0; b < B; b++) {
         offs[b] = (int32_t)total;
@@ -348,6 +435,11 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
         const long long q = h->pending_host[b] + counts[b];
         const int nf = q >= h->L ? (int)((q - h->L) / h->hop + 1) : 0;
         if (nf > n_max) n_max = nf;
+        if (diff) {  // what live_diff_kernel will do with these counts; committed once it has been enqueued
+            const int nc = nf - (h->has_carry_host[b] ? 0 : 1);
+            if (nc > n_max_diff) n_max_diff = nc;
+            h->has_carry_next[b] = h->has_carry_host[b] || nf > 0;
+        }
         const long long used = (long long)nf * h->hop;
         h->pending_host[b] = q > used ? q - used : 0;  // hop > fft_len: a slice past the end leaves nothing
     }
@@ -380,9 +472,34 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
     g.st_ref = h->st_ref;
     g.pub = h->pub_dev;
     g.feed_no = h->feeds;
+    g.cols = h->cols;
+    g.dcols = h->dcols;
+    g.carry = h->carry;
+    g.has_carry = h->has_carry;
+    g.n_cols = h->n_cols;
+    g.cols_stride = n_max;
+    h->last_stride = n_max;
     hipLaunchKernelGGL(live_append_kernel, dim3(B, kAppendSlices), dim3(256), 0, s, g);
     RTS_HIP(hipGetLastError());
     RTS_HIP(hipEventRecord(h->done[k], s));  // the staging slot (host and device side) is free again after this point
+    if (diff) {
+        // a chain of its own: the difference kernel runs in every feed (it also writes the n_cols of a feed without a
+        // chroma column), the tracker is pushed only when some stream has a column for it, and the compaction and the
+        // publication always follow
+        if (int rc = rts_chroma_frames_batch(h->plan, h->buf, RTS_F32, h->cap, h->n_samples, 0, B, n_max, h->n_frames, 1,
+                                             h->cols, RTS_F64, stream);
+            rc != RTS_OK)
+            return rc;
+        hipLaunchKernelGGL(live_diff_kernel, dim3(B), dim3(256), 0, s, g);
+        RTS_HIP(hipGetLastError());
+        memcpy(h->has_carry_host, h->has_carry_next, (size_t)B);  // the device flags will be these from here on
+        if (n_max_diff > 0) {
+            if (int rc = rts_otw_push(h->otw, h->dcols, RTS_F64, n_max, h->n_cols, stream); rc != RTS_OK) return rc;
+        }
+        hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
+        RTS_HIP(hipGetLastError());
+        return RTS_OK;
+    }
     if (n_max == 0) {
         if (h->wtw) {  // wtw.py:76-77 runs on every insert(), new column or not
             if (int rc = rts_wtw_push(h->wtw, nullptr, RTS_F64, 0, nullptr, 1, stream); rc != RTS_OK) return rc;
@@ -439,6 +556,17 @@ int rts_live_poll(rts_live *h, int32_t *status, int32_t *positions, int *feeds_d
     }
     if (feeds_done) *feeds_done = fd;
     if (feeds_submitted) *feeds_submitted = h->feeds;
+    return RTS_OK;
+}
+
+int rts_live_columns_view(rts_live *h, double **cols_dev, int *cols_cap, int *cols_stride, int32_t **n_cols_dev) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    const bool diff = h->feature_kind == RTS_FEATURE_CHROMA_DIFF;
+    if (cols_dev) *cols_dev = diff ? h->dcols : h->cols;
+    if (cols_cap) *cols_cap = h->cols_cap;
+    if (cols_stride) *cols_stride = h->last_stride;
+    if (n_cols_dev) *n_cols_dev = diff ? h->n_cols : h->n_frames;
     return RTS_OK;
 }
 

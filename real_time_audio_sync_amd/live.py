@@ -8,7 +8,11 @@ into that stream's alignment state; ``hop_size`` samples are dropped per column 
 All of it happens behind ``rts_live_*`` (csrc/live.hip): per feed ONE host-to-device copy from a pinned staging slot
 and a fixed chain of launches, nothing read back -- the pending samples live in per-stream device buffers, and the
 device publishes status and position of every stream into host-mapped memory, which ``poll()`` reads without
-touching the stream.  The host only mirrors the pending-sample counts (integer arithmetic)."""
+touching the stream.  The host only mirrors the pending-sample counts (integer arithmetic).
+
+``features="chroma_diff"`` hands the trackers the half-wave rectified difference of consecutive chroma columns instead
+(chroma.py:77-90): with ``variant="livenote_v2", euclid=True`` and a ``wav_to_chroma_diff`` reference this is the
+reference's headline configuration (tests.py:145-163) from microphones."""
 import ctypes
 
 import numpy as np
@@ -19,16 +23,42 @@ from .chroma import ChromaPlan
 from .otw_batch import BatchedOTW
 
 _KINDS = {np.dtype(np.float32): nat.F32, np.dtype(np.int16): nat.I16}
+_FEATURES = {"chroma": nat.FEATURE_CHROMA, "chroma_diff": nat.FEATURE_CHROMA_DIFF}
+
+
+class _DeviceView(object):
+    """Library-owned device memory as something torch.as_tensor wraps without a copy."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2)
 
 
 class LiveSession(object):
     def __init__(self, ref_chroma, batch, c=500, max_run_count=3, variant="otw", fft_len=4096, hop_size=2048,
-                 fs=22050, max_pending=1 << 16, device="cuda:0", wtw_params=None, extra_refs=()):
+                 fs=22050, max_pending=1 << 16, device="cuda:0", wtw_params=None, extra_refs=(), features="chroma",
+                 euclid=False):
         """``ref_chroma``: (12, N) reference chroma (e.g. chroma.wav_to_chroma(ref_path)), or a list of ``batch`` such
         arrays, one per stream (one piece per microphone; a list entry that repeats is uploaded once).  With
         ``wtw_params`` ({'dtw_win_size', 'dtw_hop_size'} in samples, like wtw.py:29-30) the streams are followed by
         windowed time warping instead of ``variant`` ('otw' | 'livenote' | 'livenote_v2').  ``extra_refs`` (with a list
-        of references only): further pieces uploaded at create, which ``restart`` may move a microphone on to."""
+        of references only): further pieces uploaded at create, which ``restart`` may move a microphone on to.
+
+        ``features``: 'chroma' (the normalised chroma columns) or 'chroma_diff': column m handed to the tracker is
+        ``np.clip(np.diff(chroma), 0, inf)[:, m]`` of the columns the ingestion makes, so a stream's tracker gets its
+        first frame with the stream's second chroma column, and ``ref_chroma`` must itself be difference features
+        (chroma.wav_to_chroma_diff).  The previous chroma column of every stream is carried on the device; ``restart``
+        drops it for the listed streams and ``reset`` for all, like their pending samples.  Not available with
+        ``wtw_params`` (the reference never runs WTW on difference features; its cosine cost is NaN on their zero
+        columns).  ``euclid``: the OTW family's Euclidean cost (livenote_v2.py:168) instead of 1 - dot; the reference
+        pairs it with either feature kind (tests.py:156)."""
+        if features not in _FEATURES:
+            raise ValueError("features must be 'chroma' or 'chroma_diff', not %r" % (features,))
+        if features == "chroma_diff" and wtw_params is not None:
+            raise ValueError("features='chroma_diff' is not available with wtw_params (WTW's cosine cost is NaN on the "
+                             "zero columns of difference features)")
+        if euclid and wtw_params is not None:
+            raise ValueError("euclid selects the OTW family's cost; WTW has its own (wtw_params)")
+        self.features = features
         self.plan = ChromaPlan(fft_len, hop_size, fs, device)
         self.dev = self.device = self.plan.device
         self.B, self.L, self.H = int(batch), int(fft_len), int(hop_size)
@@ -50,11 +80,11 @@ class LiveSession(object):
         self.otw = self.wtw = None
         if wtw_params is None:
             if per_stream:
-                self.otw = BatchedOTW.with_references(refs, c, max_run_count, variant=variant, device=device,
-                                                      dtype=torch.float64, extra_refs=extra)
+                self.otw = BatchedOTW.with_references(refs, c, max_run_count, variant=variant, euclid=euclid,
+                                                      device=device, dtype=torch.float64, extra_refs=extra)
             else:
-                self.otw = BatchedOTW(ref, c, max_run_count, batch=batch, variant=variant, device=device,
-                                      dtype=torch.float64)
+                self.otw = BatchedOTW(ref, c, max_run_count, batch=batch, variant=variant, euclid=euclid,
+                                      device=device, dtype=torch.float64)
         else:
             from .wtw import BatchedWTW
             win, hopf = wtw_params['dtw_win_size'] // self.H, wtw_params['dtw_hop_size'] // self.H
@@ -69,8 +99,9 @@ class LiveSession(object):
                 self.wtw = BatchedWTW(self._ref_dev, win, hopf, batch)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.dev):
-            nat.check(nat.lib.rts_live_create(self.plan._h, self.otw._h if self.otw else None,
-                                              self.wtw._h if self.wtw else None, self.B, self.cap, ctypes.byref(h)))
+            nat.check(nat.lib.rts_live_create_features(self.plan._h, self.otw._h if self.otw else None,
+                                                       self.wtw._h if self.wtw else None, self.B, self.cap,
+                                                       _FEATURES[features], ctypes.byref(h)))
         self._h = h
         self._status = np.zeros(self.B, dtype=np.int32)
         self._pos = np.zeros((self.B, 2), dtype=np.int32)
@@ -150,18 +181,36 @@ class LiveSession(object):
         nat.check(nat.lib.rts_live_pending(self._h, out.ctypes.data))
         return out
 
+    def last_columns(self):
+        """(cols [B][rows][12] float64, n_cols [B] int32): device tensors that view, without a copy, the columns the most
+        recently submitted feed handed to the trackers and how many of them each stream had -- the chroma columns, or
+        with ``features='chroma_diff'`` the difference columns.  ``rows`` is that feed's largest chroma column count of
+        a stream (0 when it completed none); stream b's columns are ``cols[b, :n_cols[b]]``.  The contents belong to
+        the last feed in stream order: ``sync()`` first, or consume them on the same stream.  The memory is the
+        session's: the next feed overwrites it, and the views die with the session."""
+        cols, n_cols, cap, rows = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        nat.check(nat.lib.rts_live_columns_view(self._h, ctypes.byref(cols), ctypes.byref(cap), ctypes.byref(rows),
+                                                ctypes.byref(n_cols)))
+        n = torch.as_tensor(_DeviceView(n_cols.value, (self.B,), "<i4"), device=self.dev)
+        if rows.value == 0:
+            return torch.empty((self.B, 0, 12), dtype=torch.float64, device=self.dev), n
+        return torch.as_tensor(_DeviceView(cols.value, (self.B, rows.value, 12), "<f8"), device=self.dev), n
+
     def sync(self):
         torch.cuda.current_stream(self.dev).synchronize()
 
     @nat.on_device
     def reset(self):
+        """Every stream starts again: pending samples, the carried chroma column of ``features='chroma_diff'`` and the
+        tracker state are dropped."""
         nat.check(nat.lib.rts_live_reset(self._h, self._stream()))
 
     @nat.on_device
     def restart(self, streams, refs=None, offsets=None):
         """Put the listed streams back to the start while the others keep running (rts_live_restart; asynchronous,
         ordered after the feeds already submitted): their pending samples are dropped, their tracker state is fresh,
-        ``poll()`` shows them running at the start again.  ``refs``: one entry per listed stream, each an object given
+        ``poll()`` shows them running at the start again.  With ``features='chroma_diff'`` their carried chroma column
+        is dropped too: the first chroma column of the new run only becomes the new carry.  ``refs``: one entry per listed stream, each an object given
         at create (``ref_chroma`` list / ``extra_refs``, matched by identity); ``offsets``: first frame inside the
         piece; without ``refs``, "same piece, from this frame"."""
         eng = self.otw or self.wtw
