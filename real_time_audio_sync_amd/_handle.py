@@ -1,0 +1,121 @@
+"""Host-side plumbing the batched tracker handles share (BatchedOTW in otw_batch.py, BatchedWTW in wtw.py): the pool of
+per-stream references, the restart bookkeeping, and the calls that differ only in the ``rts_otw_`` / ``rts_wtw_``
+prefix."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _native as nat
+
+
+def _concat_refs(refs, to_frames, extra=()):
+    """Per-stream references -> (one device tensor [n_ref_frames][12], int64 first frames [B], int32 lengths [B], pool).
+    A reference object that appears more than once is converted and uploaded once; its range is reused.  ``extra``:
+    pieces uploaded behind them although no stream follows them yet.  ``pool`` maps id(object) -> (object, first frame,
+    frames) for everything uploaded (what ``restart`` looks references up in)."""
+    if len(refs) < 1:
+        raise ValueError("at least one reference is needed")
+    parts, seen, first, lens, off = [], {}, [], [], 0
+    for k, r in enumerate(list(refs) + list(extra)):
+        if id(r) not in seen:
+            t = to_frames(r)
+            if parts and t.dtype != parts[0].dtype:
+                raise TypeError("all references must have the same dtype (%s, %s)" % (parts[0].dtype, t.dtype))
+            seen[id(r)] = (r, off, int(t.shape[0]))
+            parts.append(t)
+            off += int(t.shape[0])
+        if k < len(refs):
+            first.append(seen[id(r)][1])
+            lens.append(seen[id(r)][2])
+    return torch.cat(parts).contiguous(), np.array(first, dtype=np.int64), np.array(lens, dtype=np.int32), seen
+
+
+class _BatchedHandle:
+    """What BatchedOTW and BatchedWTW share.  ``_abi`` ("otw" / "wtw") names the tracker: the handle ``_h`` is destroyed,
+    restarted and read through ``rts_<_abi>_destroy``, ``_restart`` and ``_read_path``.  The bookkeeping for ``restart``:
+    which range of the uploaded pool every stream follows; ``_pool`` is None on a single-reference handle."""
+
+    def _fn(self, name):
+        return getattr(nat.lib, "rts_%s_%s" % (self._abi, name))
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            nat.destroy_on(self.device, self._fn("destroy"), h)
+
+    __del__ = close
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    @nat.on_device
+    def path(self, b=0):
+        n = ctypes.c_int(0)
+        nat.check(self._fn("read_path")(self._h, b, None, 0, ctypes.byref(n), self._stream()))
+        out = np.empty((n.value, 2), dtype=np.int32)
+        if n.value:
+            nat.check(self._fn("read_path")(self._h, b, out.ctypes.data, n.value, ctypes.byref(n), self._stream()))
+        return out
+
+    @nat.on_device
+    def restart(self, streams, refs=None, offsets=None):
+        """Put the listed streams back to the start while the others keep running (the subclasses document ``refs`` and
+        ``offsets``)."""
+        mask, first, lens, pieces = self._restart_tables(streams, refs, offsets)
+        nat.check(self._fn("restart")(self._h, mask.ctypes.data, first.ctypes.data if first is not None else None,
+                                      lens.ctypes.data if lens is not None else None, self._stream()))
+        self._restarted(first, lens, pieces)
+
+    def _init_refs(self, pool, first, lens):
+        self._pool = pool
+        self._piece = None if pool is None else [(int(f), int(n)) for f, n in zip(first, lens)]
+
+    def _grow_to_pool(self, first, lens):
+        """The handle's buffers are sized by the longest range given at create.  When a piece nobody follows yet is the
+        longest, stream 0 is created on it and put on its own reference by a restart right away (bit for bit a fresh
+        stream, by that call's contract)."""
+        f, n = max(((f, n) for _, f, n in self._pool.values()), key=lambda x: x[1])
+        if n <= int(lens.max()):
+            return first, lens, None
+        first0, lens0 = first.copy(), lens.copy()
+        first0[0], lens0[0] = f, n
+
+        def fix():
+            mask = np.zeros(self.B, dtype=np.uint8)
+            mask[0] = 1
+            nat.check(self._fn("restart")(self._h, mask.ctypes.data, first.ctypes.data, lens.ctypes.data, self._stream()))
+        return first0, lens0, fix
+
+    def _restart_tables(self, streams, refs, offsets):
+        """-> (mask uint8 [B], first int64 [B] | None, lens int32 [B] | None, new (first, frames) of the pieces)."""
+        streams = [int(b) for b in streams]
+        for b in streams:
+            if not 0 <= b < self.B:
+                raise IndexError("stream %d out of range [0, %d)" % (b, self.B))
+        mask = np.zeros(self.B, dtype=np.uint8)
+        mask[streams] = 1
+        if refs is None and offsets is None:
+            return mask, None, None, {}
+        if self._pool is None:
+            raise ValueError("refs / offsets need a handle made by with_references")
+        if refs is not None and len(refs) != len(streams) or offsets is not None and len(offsets) != len(streams):
+            raise ValueError("refs / offsets need one entry per listed stream")
+        first, lens, pieces = np.zeros(self.B, dtype=np.int64), np.ones(self.B, dtype=np.int32), {}
+        for k, b in enumerate(streams):
+            if refs is None:
+                f, n = self._piece[b]
+            else:
+                if id(refs[k]) not in self._pool:
+                    raise ValueError("stream %d: this reference was not uploaded at create (refs / extra_refs)" % b)
+                _, f, n = self._pool[id(refs[k])]
+            o = int(offsets[k]) if offsets is not None else 0
+            if not 0 <= o < n:
+                raise ValueError("stream %d: offset %d outside its reference of %d frames" % (b, o, n))
+            first[b], lens[b], pieces[b] = f + o, n - o, (f, n)
+        return mask, first, lens, pieces
+
+    def _restarted(self, first, lens, pieces):
+        for b, piece in pieces.items():
+            self._piece[b] = piece
+            self.ref_lens[b] = lens[b]

@@ -754,15 +754,6 @@ struct rts_chroma {
     int cus;     // its compute units
 };
 
-static int chroma_check_device(const rts_chroma *h) {
-    int d = -1;
-    RTS_HIP(hipGetDevice(&d));
-    if (d != h->device)
-        return rts::set_error(RTS_ERR_INVALID, "plan was created on device %d but device %d is current "
-                                               "(one process per GPU, or hipSetDevice before the call)", h->device, d);
-    return RTS_OK;
-}
-
 static hipError_t upload_transposed(double *dst_dev, const double *fb_host, int nb) {
     double *t = (double *)malloc(sizeof(double) * rts::kCh * nb);
     if (!t) return hipErrorOutOfMemory;
@@ -892,7 +883,7 @@ int rts_chroma_frames(rts_chroma *h, const void *samples_dev, int sample_dtype, 
         return set_error(RTS_ERR_INVALID, "n_frames=%d exceeds the %lld full frames in %lld samples", n_frames,
                          rts_chroma_num_frames(n_samples, h->L, h->hop, pad_left), n_samples);
     if (n_frames == 0) return RTS_OK;
-    if (int rc = chroma_check_device(h); rc != RTS_OK) return rc;
+    if (int rc = rts::check_device(h->device, "plan"); rc != RTS_OK) return rc;
     ChromaArgs g;
     memset(&g, 0, sizeof(g));
     g.samples = samples_dev;
@@ -949,7 +940,7 @@ int rts_chroma_frames_batch(rts_chroma *h, const void *samples_dev, int sample_d
         return set_error(RTS_ERR_INVALID, "bad dtype");
     if (B < 1 || n_frames_max < 0 || pad_left < 0 || sample_stride < 0) return set_error(RTS_ERR_INVALID, "bad size");
     if (n_frames_max == 0) return RTS_OK;
-    if (int rc = chroma_check_device(h); rc != RTS_OK) return rc;
+    if (int rc = rts::check_device(h->device, "plan"); rc != RTS_OK) return rc;
     ChromaArgs g;
     memset(&g, 0, sizeof(g));
     g.samples = samples_dev;

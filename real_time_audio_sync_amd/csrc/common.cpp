@@ -1,4 +1,5 @@
-// librtsync.so: error reporting + device discovery (rts_last_error, rts_version, rts_device_count).
+// librtsync.so: error reporting, device discovery (rts_last_error, rts_version, rts_device_count) and the host-side rules
+// the tracker handles share (device check, reference ranges and tables, path read-back, restart selection).
 #include "common.h"
 
 #include <string.h>
@@ -18,6 +19,65 @@ int set_error(int code, const char *fmt, ...) {
     return code;
 }
 
+int check_device(int handle_device, const char *noun) {
+    int d = -1;
+    RTS_HIP(hipGetDevice(&d));
+    if (d != handle_device)
+        return set_error(RTS_ERR_INVALID, "%s was created on device %d but device %d is current "
+                                          "(one process per GPU, or hipSetDevice before the call)", noun, handle_device, d);
+    return RTS_OK;
+}
+
+int ref_ranges_check(int B, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
+                     long long n_ref_frames, int len_max, const char *len_name) {
+    int longest = 0;
+    for (int b = 0; b < B; b++) {
+        if (mask_host && !mask_host[b]) continue;
+        if (len_host[b] < 1) return set_error(RTS_ERR_INVALID, "stream %d: len must be >= 1 (got %d)", b, len_host[b]);
+        if (first_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: first must be >= 0 (got %lld)", b, first_host[b]);
+        if (first_host[b] > n_ref_frames - len_host[b])
+            return set_error(RTS_ERR_INVALID, "stream %d: frames [%lld, %lld) lie outside the %lld reference frames", b,
+                             first_host[b], first_host[b] + len_host[b], n_ref_frames);
+        if (len_name && len_host[b] > len_max)
+            return set_error(RTS_ERR_INVALID, "stream %d: len %d exceeds the handle's %s = %d (its buffers were sized by it)", b,
+                             len_host[b], len_name, len_max);
+        if (len_host[b] > longest) longest = len_host[b];
+    }
+    return longest;
+}
+
+hipError_t ref_table_upload(RefTable *t, const long long *first_host, const int32_t *len_host, int B) {
+    hipError_t e;
+    if ((e = hipMalloc((void **)&t->first, sizeof(long long) * (size_t)B)) != hipSuccess ||
+        (e = hipMalloc((void **)&t->len, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
+        (e = hipMemcpy(t->first, first_host, sizeof(long long) * (size_t)B, hipMemcpyHostToDevice)) != hipSuccess)
+        return e;
+    return hipMemcpy(t->len, len_host, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice);
+}
+
+void ref_table_free(RefTable *t) {
+    if (t->first) (void)hipFree(t->first);
+    if (t->len) (void)hipFree(t->len);
+    t->first = nullptr;
+    t->len = nullptr;
+}
+
+int read_path(const int32_t *state, int state_len, int n_path_slot, const int32_t *path, int path_cap, int b, int B,
+              int32_t *pairs, int cap_pairs, int *n, hipStream_t s) {
+    if (b < 0 || b >= B) return set_error(RTS_ERR_INVALID, "stream index %d out of range [0, %d)", b, B);
+    int32_t np = 0;
+    RTS_HIP(hipMemcpyAsync(&np, state + (size_t)b * state_len + n_path_slot, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    RTS_HIP(hipStreamSynchronize(s));
+    *n = np;
+    int m = np < path_cap ? np : path_cap;
+    if (m > cap_pairs) m = cap_pairs;
+    if (m > 0 && pairs) {
+        RTS_HIP(hipMemcpyAsync(pairs, path + (size_t)b * path_cap * 2, sizeof(int32_t) * 2 * (size_t)m, hipMemcpyDeviceToHost, s));
+        RTS_HIP(hipStreamSynchronize(s));
+    }
+    return RTS_OK;
+}
+
 int restart_check(int B, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
                   long long n_ref_frames, int len_max, const char *len_name) {
     if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
@@ -26,18 +86,8 @@ int restart_check(int B, const uint8_t *mask_host, const long long *first_host, 
     if (!first_host) return RTS_OK;
     if (n_ref_frames < 0)
         return set_error(RTS_ERR_INVALID, "new reference ranges need a handle with per-stream references (rts_*_create_refs)");
-    for (int b = 0; b < B; b++) {
-        if (!mask_host[b]) continue;
-        if (len_host[b] < 1) return set_error(RTS_ERR_INVALID, "stream %d: len must be >= 1 (got %d)", b, len_host[b]);
-        if (first_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: first must be >= 0 (got %lld)", b, first_host[b]);
-        if (first_host[b] > n_ref_frames - len_host[b])
-            return set_error(RTS_ERR_INVALID, "stream %d: frames [%lld, %lld) lie outside the %lld reference frames", b,
-                             first_host[b], first_host[b] + len_host[b], n_ref_frames);
-        if (len_host[b] > len_max)
-            return set_error(RTS_ERR_INVALID, "stream %d: len %d exceeds the handle's %s = %d (its buffers were sized by it)", b,
-                             len_host[b], len_name, len_max);
-    }
-    return RTS_OK;
+    const int rc = ref_ranges_check(B, mask_host, first_host, len_host, n_ref_frames, len_max, len_name);
+    return rc < 0 ? rc : RTS_OK;
 }
 
 int restart_next_chunk(int B, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host, int *pos,

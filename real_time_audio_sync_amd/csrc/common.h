@@ -15,6 +15,35 @@ int set_error(int code, const char *fmt, ...);
 __attribute__((visibility("hidden"))) int otw_batch(const rts_otw *h);
 __attribute__((visibility("hidden"))) int wtw_batch(const rts_wtw *h);
 
+// A handle (`noun`: "handle", or "plan" for rts_chroma) belongs to the device that was current when it was created;
+// driving it with another device current would launch against foreign buffers.
+__attribute__((visibility("hidden"))) int check_device(int handle_device, const char *noun);
+
+// The one rule for per-stream reference ranges (rts_*_create_refs, rts_*_restart): len >= 1, first >= 0, [first, first +
+// len) inside the pool of n_ref_frames and, where `len_name` is given, len <= len_max (the handle's buffers were sized by
+// it).  `mask_host` (may be NULL) restricts the check to the selected streams.  Returns the largest length seen, or
+// RTS_ERR_INVALID (< 0) with the message naming the stream.
+__attribute__((visibility("hidden"))) int ref_ranges_check(int B, const uint8_t *mask_host, const long long *first_host,
+                                                           const int32_t *len_host, long long n_ref_frames, int len_max,
+                                                           const char *len_name);
+
+// Per-stream references of a tracker handle: [B] first frames and [B] lengths on the device (NULL on a single-reference
+// handle) and the size of the pool they index.  The kernels receive the two pointers as they are.
+struct RefTable {
+    long long *first;
+    int32_t *len;
+    long long n_frames;
+};
+__attribute__((visibility("hidden"))) hipError_t ref_table_upload(RefTable *t, const long long *first_host,
+                                                                  const int32_t *len_host, int B);
+__attribute__((visibility("hidden"))) void ref_table_free(RefTable *t);
+
+// rts_*_read_path: the n_path word of stream b's state (`state_len` words per stream, n_path in slot `n_path_slot`) into
+// *n, then min(*n, path_cap, cap_pairs) pairs into `pairs` (may be NULL).
+__attribute__((visibility("hidden"))) int read_path(const int32_t *state, int state_len, int n_path_slot,
+                                                    const int32_t *path, int path_cap, int b, int B, int32_t *pairs,
+                                                    int cap_pairs, int *n, hipStream_t s);
+
 // rts_*_restart: how the selection reaches the device.  The selected stream indices and (optionally) their new
 // reference ranges travel as BY-VALUE kernel arguments, kRestartChunk streams per launch: the launch copies them, so
 // the caller's host tables are consumed when the call returns, nothing is allocated or pinned, no later restart can

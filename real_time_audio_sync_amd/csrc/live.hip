@@ -200,16 +200,6 @@ struct rts_live {
     int feeds;
 };
 
-namespace rts {
-static int live_check_device(const rts_live *h) {
-    int d = -1;
-    RTS_HIP(hipGetDevice(&d));
-    if (d != h->device)
-        return set_error(RTS_ERR_INVALID, "handle was created on device %d but device %d is current", h->device, d);
-    return RTS_OK;
-}
-}  // namespace rts
-
 extern "C" {
 
 int rts_live_destroy(rts_live *h) {
@@ -342,7 +332,7 @@ int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B
 int rts_live_reset(rts_live *h, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (int rc = live_check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     RTS_HIP(hipStreamSynchronize((hipStream_t)stream));
     RTS_HIP(hipStreamSynchronize(h->copy_stream));
     RTS_HIP(hipMemsetAsync(h->pending, 0, sizeof(int32_t) * (size_t)h->B, (hipStream_t)stream));
@@ -364,7 +354,7 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
-    if (int rc = live_check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     // the tracker makes every check before it enqueues anything; behind the feeds already submitted on `stream`
     if (int rc = h->otw ? rts_otw_restart(h->otw, mask_host, first_host, len_host, stream)
                         : rts_wtw_restart(h->wtw, mask_host, first_host, len_host, stream);
@@ -413,7 +403,7 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (h->slot < 0) return set_error(RTS_ERR_INVALID, "rts_live_submit without rts_live_staging");
     if (sample_kind != RTS_F32 && sample_kind != RTS_I16) return set_error(RTS_ERR_INVALID, "samples must be RTS_F32 or RTS_I16");
-    if (int rc = live_check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     const int k = h->slot, B = h->B;
     int32_t *counts = reinterpret_cast<int32_t *>(h->stage_host[k]);
     int32_t *offs = counts + B;

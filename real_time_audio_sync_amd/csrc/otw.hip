@@ -2267,9 +2267,7 @@ struct rts_otw {
     int32_t *path;      // [B][path_cap][2]
     double *bands;      // [B][2][c+1]
     double *hist;       // [B][hist_stride][F], allocated on first insert
-    long long *ref_first;  // per-stream references (rts_otw_create_refs): [B] first frames, device; NULL otherwise
-    int32_t *ref_len;      // [B] lengths N_b, device
-    long long n_ref_frames;  // frames in the pool `ref` points to (rts_otw_create_refs; rts_otw_restart checks new ranges against it)
+    rts::RefTable refs;  // per-stream references (rts_otw_create_refs): lengths N_b in the pool `ref` points to
     int32_t *hist_len;  // [B]
     long long *debug;   // diagnostic builds only
     double *dense_acc, *dense_cost;  // caller-owned, optional
@@ -2355,17 +2353,6 @@ static int launch_w(rts_otw *h, const OtwArgs &args, int B, int waves, hipStream
     return set_error(RTS_ERR_INVALID, "waves must be 1, 2, 4 or 8 (got %d)", waves);
 }
 
-// A handle belongs to the device that was current at rts_otw_create; driving it with another device current would
-// launch against foreign buffers.
-static int check_device(const rts_otw *h) {
-    int d = -1;
-    RTS_HIP(hipGetDevice(&d));
-    if (d != h->device)
-        return set_error(RTS_ERR_INVALID, "handle was created on device %d but device %d is current "
-                                          "(one process per GPU, or hipSetDevice before the call)", h->device, d);
-    return RTS_OK;
-}
-
 static int launch(rts_otw *h, const OtwArgs &args, hipStream_t s) {
     if ((uintptr_t)args.live & 15) return set_error(RTS_ERR_INVALID, "live features must be 16-byte aligned");
     switch (h->W) {
@@ -2393,14 +2380,61 @@ static OtwArgs base_args(const rts_otw *h) {
     a.cost_kind = h->cost_kind;
     a.path_cap = h->path_cap;
     a.live_cap = 2 * h->N;  // per-stream references: the kernel takes 2 N_b from ref_len instead
-    a.ref_first = h->ref_first;
-    a.ref_len = h->ref_len;
+    a.ref_first = h->refs.first;
+    a.ref_len = h->refs.len;
     a.ref_f64 = h->ref_dtype == RTS_F64;
     a.debug = h->debug;
     a.spec = h->spec;
     a.dense_acc = h->dense_acc;
     a.dense_cost = h->dense_cost;
     return a;
+}
+
+// The same with the handle-owned history as the live input (rts_otw_insert, rts_otw_push and their replay).
+static OtwArgs hist_args(const rts_otw *h) {
+    OtwArgs a = base_args(h);
+    a.live = h->hist;
+    a.live_len = h->hist_len;
+    a.live_stride = h->hist_stride;
+    a.live_f64 = 1;
+    a.mode = RTS_MODE_INSERT_LOOP;
+    return a;
+}
+
+// rts_otw_insert / rts_otw_push: the history is allocated with the first frame, and the handle has now consumed
+// frames of its own (src_kind 2, or 3 "mixed" behind an rts_otw_run).
+static int begin_append(rts_otw *h) {
+    if (!h->hist) {
+        RTS_HIP(hipMalloc((void **)&h->hist, sizeof(double) * kF * (size_t)h->hist_stride * h->B));
+    }
+    h->src_kind = (h->src_kind == 0 || h->src_kind == 2) ? 2 : 3;
+    return RTS_OK;
+}
+
+// The dense mirror's "never evaluated" values (otw_eran.py:23,27 / livenote_v2.py:21-23) into acc / cost [B][2N][N]:
+// every stream, or the streams of `sel` only.  The caller checks hipGetLastError.
+static void fill_dense(const rts_otw *h, double *acc, double *cost, const RestartSel *sel, hipStream_t s) {
+    const long long per = (long long)2 * h->N * h->N;
+    const double sentinel = (h->variant == RTS_VARIANT_OTW) ? 1e10 : (double)INFINITY;
+    if (sel) {
+        hipLaunchKernelGGL(otw_fill_sel_kernel, dim3(64, sel->n), dim3(256), 0, s, *sel, acc, per, sentinel);
+        hipLaunchKernelGGL(otw_fill_sel_kernel, dim3(64, sel->n), dim3(256), 0, s, *sel, cost, per, -1.0);
+    } else {
+        hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, acc, h->B * per, sentinel);
+        hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, cost, h->B * per, -1.0);
+    }
+}
+
+// The pipelined kernel (58 KB of LDS at c = 500 with float32 features: two workgroups per CU, like the plain kernel) is
+// the faster one at every batch size measured; RTS_OTW_SPEC=0 selects the plain kernel (A/B runs, tests).  Batches of at
+// least RTS_OTW_TP_FROM streams per CU take the residency-oriented flavour (tests: 0 selects it at any batch size).
+// Results are identical.
+struct OtwKnobs {
+    int spec, tp_from;
+};
+static OtwKnobs otw_knobs() {
+    const char *sp = getenv("RTS_OTW_SPEC"), *tp = getenv("RTS_OTW_TP_FROM");
+    return {sp ? (atoi(sp) != 0) : 1, tp ? atoi(tp) : 2};
 }
 
 // The constructor behind rts_otw_create (first_host == NULL: one reference of N frames) and rts_otw_create_refs (N =
@@ -2435,15 +2469,9 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
     h->W = 64;
     while (h->W < c + 12) h->W *= 2;
     h->waves = 8;  // wave 0: control (+ chains of steps that are not hits), waves 1/2: chains, 3..7: cost strips, ring refill
-    {
-        // The pipelined kernel (58 KB of LDS at c = 500 with float32 features: two workgroups per CU, like the plain
-        // kernel) is the faster one at every batch size measured; RTS_OTW_SPEC=0 selects the plain kernel (A/B runs,
-        // tests).  Results are identical.
-        const char *sp = getenv("RTS_OTW_SPEC");
-        h->spec = sp ? (atoi(sp) != 0) : 1;
-        const char *tp = getenv("RTS_OTW_TP_FROM");  // tests: 0 selects the residency-oriented flavour at any batch size
-        h->tp_from = tp ? atoi(tp) : 2;
-    }
+    const OtwKnobs knobs = otw_knobs();
+    h->spec = knobs.spec;
+    h->tp_from = knobs.tp_from;
     h->hist_stride = 2 * N;
     h->path_cap = 3 * N + 8;  // one point per decide(); decides <= row strips + column strips <= 2N + N
     hipError_t e;
@@ -2456,10 +2484,7 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
         (e = hipMalloc((void **)&h->path, sizeof(int32_t) * 2 * (size_t)h->path_cap * B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->bands, sizeof(double) * 2 * (size_t)(c + 1) * B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->hist_len, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
-        (first_host && (e = hipMalloc((void **)&h->ref_first, sizeof(long long) * (size_t)B)) != hipSuccess) ||
-        (first_host && (e = hipMalloc((void **)&h->ref_len, sizeof(int32_t) * (size_t)B)) != hipSuccess) ||
-        (first_host && (e = hipMemcpy(h->ref_first, first_host, sizeof(long long) * (size_t)B, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (first_host && (e = hipMemcpy(h->ref_len, len_host, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice)) != hipSuccess)) {
+        (first_host && (e = ref_table_upload(&h->refs, first_host, len_host, B)) != hipSuccess)) {
         rts_otw_destroy(h);
         return set_error(RTS_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
     }
@@ -2507,17 +2532,10 @@ int rts_otw_create_refs(const void *refs_dev, int ref_dtype, int F, long long n_
     if (!refs_dev) return set_error(RTS_ERR_INVALID, "refs_dev is NULL");
     if (!first_host || !len_host) return set_error(RTS_ERR_INVALID, "first_host / len_host is NULL");
     if (B < 1) return set_error(RTS_ERR_INVALID, "B must be >= 1 (got %d)", B);
-    int n_max = 0;
-    for (int b = 0; b < B; b++) {
-        if (len_host[b] < 1) return set_error(RTS_ERR_INVALID, "stream %d: len must be >= 1 (got %d)", b, len_host[b]);
-        if (first_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: first must be >= 0 (got %lld)", b, first_host[b]);
-        if (first_host[b] > n_ref_frames - len_host[b])
-            return set_error(RTS_ERR_INVALID, "stream %d: frames [%lld, %lld) lie outside the %lld reference frames", b,
-                             first_host[b], first_host[b] + len_host[b], n_ref_frames);
-        if (len_host[b] > n_max) n_max = len_host[b];
-    }
+    const int n_max = ref_ranges_check(B, nullptr, first_host, len_host, n_ref_frames, 0, nullptr);
+    if (n_max < 0) return n_max;
     const int rc = otw_create(refs_dev, ref_dtype, F, n_max, B, c, max_run_count, variant, cost_kind, first_host, len_host, out);
-    if (rc == RTS_OK) (*out)->n_ref_frames = n_ref_frames;
+    if (rc == RTS_OK) (*out)->refs.n_frames = n_ref_frames;
     return rc;
 }
 
@@ -2528,8 +2546,7 @@ int rts_otw_destroy(rts_otw *h) {
     if (h->bands) (void)hipFree(h->bands);
     if (h->hist) (void)hipFree(h->hist);
     if (h->hist_len) (void)hipFree(h->hist_len);
-    if (h->ref_first) (void)hipFree(h->ref_first);
-    if (h->ref_len) (void)hipFree(h->ref_len);
+    rts::ref_table_free(&h->refs);
     if (h->rp_state) (void)hipFree(h->rp_state);
     if (h->rp_path) (void)hipFree(h->rp_path);
     if (h->rp_bands) (void)hipFree(h->rp_bands);
@@ -2540,17 +2557,14 @@ int rts_otw_destroy(rts_otw *h) {
 int rts_otw_reset(rts_otw *h, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (int rc = check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     h->src_kind = 0;
     hipLaunchKernelGGL(otw_reset_kernel, dim3((h->B + 63) / 64), dim3(64), 0, s, h->state, h->B, h->variant);
     RTS_HIP(hipGetLastError());
     RTS_HIP(hipMemsetAsync(h->hist_len, 0, sizeof(int32_t) * (size_t)h->B, s));
-    if (h->dense_acc) {  // otw_eran.py:23,27 / livenote_v2.py:21-23
-        const long long n = (long long)h->B * 2 * h->N * h->N;
-        const double sentinel = (h->variant == RTS_VARIANT_OTW) ? 1e10 : (double)INFINITY;
-        hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, h->dense_acc, n, sentinel);
-        hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, h->dense_cost, n, -1.0);
+    if (h->dense_acc) {
+        fill_dense(h, h->dense_acc, h->dense_cost, nullptr, s);
         RTS_HIP(hipGetLastError());
     }
     return RTS_OK;
@@ -2561,23 +2575,18 @@ int rts_otw_restart(rts_otw *h, const uint8_t *mask_host, const long long *first
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
-    if (int rc = restart_check(h->B, mask_host, first_host, len_host, h->ref_first ? h->n_ref_frames : -1, h->N, "N_max");
+    if (int rc = restart_check(h->B, mask_host, first_host, len_host, h->refs.first ? h->refs.n_frames : -1, h->N, "N_max");
         rc != RTS_OK)
         return rc;
-    if (int rc = check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     // (src_kind stays: frames a restarted stream receives through insert / push after an rts_otw_run make the handle
     // "mixed" there, as for any stream)
     RestartSel sel;
     for (int pos = 0; restart_next_chunk(h->B, mask_host, first_host, len_host, &pos, &sel) > 0;) {
         hipLaunchKernelGGL(otw_restart_kernel, dim3(sel.n), dim3(64), 0, s, sel, h->state, h->hist_len, h->bands,
-                           2 * (h->c + 1), h->ref_first, h->ref_len, h->variant);
-        if (h->dense_acc) {  // otw_eran.py:23,27 for these streams
-            const long long per = (long long)2 * h->N * h->N;
-            const double sentinel = (h->variant == RTS_VARIANT_OTW) ? 1e10 : (double)INFINITY;
-            hipLaunchKernelGGL(otw_fill_sel_kernel, dim3(64, sel.n), dim3(256), 0, s, sel, h->dense_acc, per, sentinel);
-            hipLaunchKernelGGL(otw_fill_sel_kernel, dim3(64, sel.n), dim3(256), 0, s, sel, h->dense_cost, per, -1.0);
-        }
+                           2 * (h->c + 1), h->refs.first, h->refs.len, h->variant);
+        if (h->dense_acc) fill_dense(h, h->dense_acc, h->dense_cost, &sel, s);
         RTS_HIP(hipGetLastError());
     }
     return RTS_OK;
@@ -2586,7 +2595,7 @@ int rts_otw_restart(rts_otw *h, const uint8_t *mask_host, const long long *first
 int rts_otw_set_dense(rts_otw *h, double *acc_dev, double *cost_dev, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (h->ref_first)
+    if (h->refs.first)
         return set_error(RTS_ERR_UNSUPPORTED, "the dense mirror is not available on a handle with per-stream references");
     if ((acc_dev == nullptr) != (cost_dev == nullptr))
         return set_error(RTS_ERR_INVALID, "acc_dev and cost_dev must both be given or both be NULL");
@@ -2599,10 +2608,10 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
                          double *acc_dev, double *cost_dev, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (h->ref_first)
+    if (h->refs.first)
         return set_error(RTS_ERR_UNSUPPORTED, "the dense replay is not available on a handle with per-stream references");
     if (!acc_dev || !cost_dev) return set_error(RTS_ERR_INVALID, "acc_dev / cost_dev is NULL");
-    if (int rc = check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     if (h->src_kind == 3)
         return set_error(RTS_ERR_UNSUPPORTED, "rts_otw_insert / rts_otw_push after rts_otw_run without a reset: nothing to replay from");
     // The frames of an rts_otw_run are the caller's: the library does not keep a pointer to memory it does not own, the
@@ -2617,10 +2626,7 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
         return set_error(RTS_ERR_INVALID, "the handle's frames came through rts_otw_insert / rts_otw_push (or it is fresh): live_dev must be NULL");
     }
     hipStream_t s = (hipStream_t)stream;
-    const long long n = (long long)h->B * 2 * h->N * h->N;
-    const double sentinel = (h->variant == RTS_VARIANT_OTW) ? 1e10 : (double)INFINITY;
-    hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, acc_dev, n, sentinel);
-    hipLaunchKernelGGL(otw_fill_kernel, dim3(2048), dim3(256), 0, s, cost_dev, n, -1.0);
+    fill_dense(h, acc_dev, cost_dev, nullptr, s);
     RTS_HIP(hipGetLastError());
     if (h->src_kind == 0) return RTS_OK;  // freshly constructed: the matrices are all sentinel (otw_eran.py:23,27)
     // scratch state so that the handle itself is not disturbed; allocated on the first replay, kept with the handle
@@ -2636,7 +2642,7 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
         }
     }
     hipLaunchKernelGGL(otw_reset_kernel, dim3((h->B + 63) / 64), dim3(64), 0, s, h->rp_state, h->B, h->variant);
-    OtwArgs a = base_args(h);
+    OtwArgs a = h->src_kind == 1 ? base_args(h) : hist_args(h);
     a.state = h->rp_state;
     a.path = h->rp_path;
     a.bands = h->rp_bands;
@@ -2649,12 +2655,6 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
         a.live_f64 = live_dtype == RTS_F64;
         a.mode = h->run_mode;
         a.clamp_len = 1;
-    } else {
-        a.live = h->hist;
-        a.live_len = h->hist_len;
-        a.live_stride = h->hist_stride;
-        a.live_f64 = 1;
-        a.mode = RTS_MODE_INSERT_LOOP;
     }
     int rc = launch(h, a, s);
     if (rc != RTS_OK) return rc;
@@ -2704,21 +2704,12 @@ int rts_otw_insert(rts_otw *h, const void *frames_dev, int frames_dtype, const u
     if (!frames_dev) return set_error(RTS_ERR_INVALID, "frames_dev is NULL");
     if (frames_dtype != RTS_F32 && frames_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad frames_dtype %d", frames_dtype);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = check_device(h); rc != RTS_OK) return rc;
-    if (!h->hist) {
-        RTS_HIP(hipMalloc((void **)&h->hist, sizeof(double) * kF * (size_t)h->hist_stride * h->B));
-    }
-    h->src_kind = (h->src_kind == 0 || h->src_kind == 2) ? 2 : 3;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    if (int rc = begin_append(h); rc != RTS_OK) return rc;
     hipLaunchKernelGGL(otw_append_kernel, dim3(h->B), dim3(64), 0, s, h->hist, h->hist_len, frames_dev,
                        frames_dtype == RTS_F64, active_dev, h->B, h->hist_stride);
     RTS_HIP(hipGetLastError());
-    OtwArgs a = base_args(h);
-    a.live = h->hist;
-    a.live_len = h->hist_len;
-    a.live_stride = h->hist_stride;
-    a.live_f64 = 1;
-    a.mode = RTS_MODE_INSERT_LOOP;
-    return launch(h, a, s);
+    return launch(h, hist_args(h), s);
 }
 
 int rts_otw_push(rts_otw *h, const void *frames_dev, int frames_dtype, int n_max, const int32_t *n_new_dev,
@@ -2730,21 +2721,12 @@ int rts_otw_push(rts_otw *h, const void *frames_dev, int frames_dtype, int n_max
     if (!frames_dev) return set_error(RTS_ERR_INVALID, "frames_dev is NULL");
     if (frames_dtype != RTS_F32 && frames_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad frames_dtype %d", frames_dtype);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = check_device(h); rc != RTS_OK) return rc;
-    if (!h->hist) {
-        RTS_HIP(hipMalloc((void **)&h->hist, sizeof(double) * kF * (size_t)h->hist_stride * h->B));
-    }
-    h->src_kind = (h->src_kind == 0 || h->src_kind == 2) ? 2 : 3;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    if (int rc = begin_append(h); rc != RTS_OK) return rc;
     hipLaunchKernelGGL(otw_append_many_kernel, dim3(h->B), dim3(128), 0, s, h->hist, h->hist_len, frames_dev,
                        frames_dtype == RTS_F64, n_new_dev, n_max, n_max, h->B, h->hist_stride);
     RTS_HIP(hipGetLastError());
-    OtwArgs a = base_args(h);
-    a.live = h->hist;
-    a.live_len = h->hist_len;
-    a.live_stride = h->hist_stride;
-    a.live_f64 = 1;
-    a.mode = RTS_MODE_INSERT_LOOP;
-    return launch(h, a, s);
+    return launch(h, hist_args(h), s);
 }
 
 int rts_otw_read_states(rts_otw *h, int32_t *states, void *stream) {
@@ -2772,21 +2754,8 @@ int rts_otw_read_state(rts_otw *h, int b, int32_t *state, void *stream) {
 int rts_otw_read_path(rts_otw *h, int b, int32_t *pairs, int cap_pairs, int *n, void *stream) {
     using namespace rts;
     if (!h || !n) return set_error(RTS_ERR_INVALID, "NULL argument");
-    if (b < 0 || b >= h->B) return set_error(RTS_ERR_INVALID, "stream index %d out of range [0, %d)", b, h->B);
-    hipStream_t s = (hipStream_t)stream;
-    int32_t np = 0;
-    RTS_HIP(hipMemcpyAsync(&np, h->state + (size_t)b * RTS_STATE_LEN + RTS_ST_N_PATH, sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s));
-    RTS_HIP(hipStreamSynchronize(s));
-    *n = np;
-    int m = np < h->path_cap ? np : h->path_cap;
-    if (m > cap_pairs) m = cap_pairs;
-    if (m > 0 && pairs) {
-        RTS_HIP(hipMemcpyAsync(pairs, h->path + (size_t)b * h->path_cap * 2, sizeof(int32_t) * 2 * (size_t)m,
-                               hipMemcpyDeviceToHost, s));
-        RTS_HIP(hipStreamSynchronize(s));
-    }
-    return RTS_OK;
+    return read_path(h->state, RTS_STATE_LEN, RTS_ST_N_PATH, h->path, h->path_cap, b, h->B, pairs, cap_pairs, n,
+                     (hipStream_t)stream);
 }
 
 int rts_otw_read_bands(rts_otw *h, int b, double *row_band, double *col_band, void *stream) {

@@ -966,9 +966,7 @@ struct rts_wtw {
     const double *ref;
     int M, B, W, hopf, path_cap;
     int live_stride;  // frames per stream in `live`: 2M (2 M_max with per-stream references)
-    long long *ref_first;  // per-stream references (rts_wtw_create_refs): [B] first frames, device; NULL otherwise
-    int32_t *ref_len;      // [B] lengths M_b, device
-    long long n_ref_frames;  // frames in the pool `ref` points to (rts_wtw_create_refs; rts_wtw_restart checks new ranges against it)
+    rts::RefTable refs;  // per-stream references (rts_wtw_create_refs): lengths M_b in the pool `ref` points to
     double *live;
     int32_t *appended, *appended_next, *state, *path;
     int8_t *bwork;
@@ -984,22 +982,36 @@ struct rts_wtw {
 };
 
 namespace rts {
-// A handle belongs to the device that was current at rts_wtw_create (like rts_otw handles).
-static int wtw_check_device(const rts_wtw *h) {
-    int d = -1;
-    RTS_HIP(hipGetDevice(&d));
-    if (d != h->device)
-        return set_error(RTS_ERR_INVALID, "handle was created on device %d but device %d is current "
-                                          "(one process per GPU, or hipSetDevice before the call)", h->device, d);
-    return RTS_OK;
+
+// Which kernels serve windows of W frames.  The defaults: at most kWinAutoW (128) frames, the one-launch window kernel
+// (measured, 64 streams, hop = W / 2: 3.2x faster than the anti-diagonal sweep at W = 20, 3.8x at W = 64, on a par with
+// the strip DP's launch-per-window rounds at W = 100); above that, being more than one strip (64 rows), the strip DP:
+// on 64 streams at wtw_live.py's W = 100 / hop = 50 it is twice as fast as the single-workgroup sweep despite its five
+// launches per window.  The knobs (tuning, tests and A/B runs; results do not depend on them): RTS_WTW_WIN=0, or 1 to
+// force the window kernel up to kWinMaxW; RTS_WTW_BIG_FROM, another strip-DP threshold (at most kWtwLdsW), which also
+// turns the window kernel off; RTS_WIN_FORCE_R2, two DP waves in the window kernel at any W.
+struct WtwSelect {
+    int use_win;  // 0: off; 1 / 2: DP waves (interior rows 1 .. W-1: one wave up to 65 frames)
+    int use_big;
+    int big_from;
+};
+static WtwSelect wtw_select(int W) {
+    const char *win_e = getenv("RTS_WTW_WIN"), *big_e = getenv("RTS_WTW_BIG_FROM"), *r2_e = getenv("RTS_WIN_FORCE_R2");
+    const int big_from = big_e ? (atoi(big_e) < kWtwLdsW ? atoi(big_e) : kWtwLdsW) : kWtwStripFrom;
+    const bool win = !big_e && (win_e ? (W <= kWinMaxW && atoi(win_e) != 0) : W <= kWinAutoW);
+    return {win ? ((W <= 65 && !r2_e) ? 1 : 2) : 0, !win && W > big_from, big_from};
 }
-}  // namespace rts
 
-extern "C" {
-
-}  // extern "C"
-
-namespace rts {
+// The kernel instantiations that ask for more dynamic LDS than the default limit: 160 KB for the strip-DP and window
+// kernels, 150 KB for the two sweep kernels behind them.
+constexpr int kWtwAttrs160 = 8;
+static const void *const kWtwLdsAttrFns[10] = {
+    reinterpret_cast<const void *>(&wtw_big_dp_kernel<false, 2>), reinterpret_cast<const void *>(&wtw_big_dp_kernel<false, 3>),
+    reinterpret_cast<const void *>(&wtw_big_dp_kernel<true, 2>),  reinterpret_cast<const void *>(&wtw_big_dp_kernel<true, 3>),
+    reinterpret_cast<const void *>(&wtw_win_kernel<1, false>),    reinterpret_cast<const void *>(&wtw_win_kernel<2, false>),
+    reinterpret_cast<const void *>(&wtw_win_kernel<1, true>),     reinterpret_cast<const void *>(&wtw_win_kernel<2, true>),
+    reinterpret_cast<const void *>(&wtw_advance_kernel<true>),    reinterpret_cast<const void *>(&wtw_advance_kernel<false>),
+};
 
 // The constructor behind rts_wtw_create (first_host == NULL: one reference of M frames) and rts_wtw_create_refs (M =
 // M_max, per-stream tables of B entries, already checked).  Every argument is checked before the first HIP call.
@@ -1027,29 +1039,23 @@ static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win
     h->hopf = hop_frames;
     h->path_cap = (h->live_stride / hop_frames + 2) * (win_frames + hop_frames + 2);
     const int W = win_frames;
-    // Windows of more than one strip (64 rows) take the strip-DP path: measured on 64 streams at wtw_live.py's W = 100 /
-    // hop = 50 it is twice as fast as the single-workgroup sweep despite its five launches per window.
-    // RTS_WTW_BIG_FROM overrides the threshold (tuning and tests; results do not depend on it).
-    int big_from = kWtwStripFrom;
-    if (const char *e = getenv("RTS_WTW_BIG_FROM")) big_from = atoi(e) < kWtwLdsW ? atoi(e) : kWtwLdsW;
-    // Windows of at most 128 frames: the one-launch window kernel (RTS_WTW_WIN=0 or an explicit RTS_WTW_BIG_FROM select the
-    // older paths: tests and A/B runs; results are identical).
-    // (measured, 64 streams, hop = W / 2: 3.2x faster than the anti-diagonal sweep at W = 20, 3.8x at W = 64, on a par with
-    // the strip DP's launch-per-window rounds at W = 100, behind them from ~110 frames on: kWinAutoW)
-    bool win = W <= kWinAutoW;
-    if (const char *e = getenv("RTS_WTW_WIN")) win = W <= kWinMaxW && atoi(e) != 0;
-    if (getenv("RTS_WTW_BIG_FROM")) win = false;
-    h->use_win = win ? ((W <= 65 && !getenv("RTS_WIN_FORCE_R2")) ? 1 : 2) : 0;  // interior rows 1 .. W-1: one wave up to 65 frames (RTS_WIN_FORCE_R2: tests)
-    const bool big = !win && W > big_from;
-    h->use_big = big;
+    const WtwSelect sel = wtw_select(W);
+    const bool win = sel.use_win != 0, big = sel.use_big != 0;
+    h->use_win = sel.use_win;
+    h->use_big = sel.use_big;
+    // (before the occupancy query below: it answers for the limit in force)
+    for (int k = 0; k < 10; k++) {
+        const hipError_t ea = hipFuncSetAttribute(kWtwLdsAttrFns[k], hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  (k < kWtwAttrs160 ? 160 : 150) * 1024);
+        if (ea != hipSuccess) {
+            free(h);
+            return set_error(RTS_ERR_HIP, "WTW allocation failed: %s", hipGetErrorString(ea));
+        }
+    }
     if (big) {
         int nw, nh, grid;
         // workgroups of the one-strip / two-strip DP kernel this device holds at once (sdp::pick_config, "Residency")
         const size_t pad = sdp::lds_pad();
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_big_dp_kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_big_dp_kernel<false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_big_dp_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_big_dp_kernel<true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         const int res1 = keep_last_d ? sdp::resident_blocks(wtw_big_dp_kernel<true, 3>, 256, sdp::lds_bytes(1) + pad)
                                      : sdp::resident_blocks(wtw_big_dp_kernel<false, 3>, 256, sdp::lds_bytes(1) + pad);
         const int res2 = keep_last_d ? sdp::resident_blocks(wtw_big_dp_kernel<true, 2>, 384, sdp::lds_bytes(2) + pad)
@@ -1072,23 +1078,12 @@ static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win
     }
     hipError_t e;
     if ((e = hipMalloc((void **)&h->live, sizeof(double) * kWF * (size_t)h->live_stride * B)) != hipSuccess ||
-        (first_host && (e = hipMalloc((void **)&h->ref_first, sizeof(long long) * (size_t)B)) != hipSuccess) ||
-        (first_host && (e = hipMalloc((void **)&h->ref_len, sizeof(int32_t) * (size_t)B)) != hipSuccess) ||
-        (first_host && (e = hipMemcpy(h->ref_first, first_host, sizeof(long long) * (size_t)B, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (first_host && (e = hipMemcpy(h->ref_len, len_host, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (first_host && (e = ref_table_upload(&h->refs, first_host, len_host, B)) != hipSuccess) ||
         (e = hipMalloc((void **)&h->appended, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->appended_next, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->state, sizeof(int32_t) * 8 * (size_t)B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->path, sizeof(int32_t) * 2 * (size_t)h->path_cap * B)) != hipSuccess ||
         (!big && !win && W > kWtwLdsB && (e = hipMalloc((void **)&h->bwork, (size_t)B * W * W)) != hipSuccess) ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_win_kernel<1, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_win_kernel<2, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_win_kernel<1, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_win_kernel<2, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess ||
         (big && (e = hipMalloc((void **)&h->ws_sub, sizeof(int32_t) * 4 * (size_t)W * B)) != hipSuccess) ||
         (big && (e = hipMalloc((void **)&h->ws_scr, sizeof(int32_t) * 2 * sdp::scratch_pairs(W, W) * B)) != hipSuccess) ||
         (big && (e = hipMalloc((void **)&h->ctl, sizeof(int32_t) * 8 * (size_t)B)) != hipSuccess) ||
@@ -1100,19 +1095,7 @@ static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win
         (big && (e = hipMalloc((void **)&h->cross, sizeof(int32_t) * (size_t)sdp::n_strips(W) * B)) != hipSuccess) ||
         (big && (e = hipMalloc((void **)&h->yrec, sizeof(double) * sdp::kYRec * (size_t)W * B)) != hipSuccess) ||
         (big && (e = hipMalloc((void **)&h->lens, sizeof(int32_t) * (size_t)sdp::n_strips(W) * B)) != hipSuccess) ||
-        (keep_last_d && (e = hipMalloc((void **)&h->dlast, sizeof(double) * (size_t)B * W * W)) != hipSuccess) ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_advance_kernel<true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_advance_kernel<false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_big_dp_kernel<true, 2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_big_dp_kernel<false, 2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_big_dp_kernel<true, 3>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wtw_big_dp_kernel<false, 3>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) {
+        (keep_last_d && (e = hipMalloc((void **)&h->dlast, sizeof(double) * (size_t)B * W * W)) != hipSuccess)) {
         rts_wtw_destroy(h);
         return set_error(RTS_ERR_HIP, "WTW allocation failed: %s", hipGetErrorString(e));
     }
@@ -1152,42 +1135,20 @@ int rts_wtw_create_refs(const double *chroma_refs_dev, int F, long long n_ref_fr
     if (!chroma_refs_dev) return set_error(RTS_ERR_INVALID, "chroma_refs_dev is NULL");
     if (!first_host || !len_host) return set_error(RTS_ERR_INVALID, "first_host / len_host is NULL");
     if (B < 1) return set_error(RTS_ERR_INVALID, "B must be >= 1 (got %d)", B);
-    int m_max = 0;
-    for (int b = 0; b < B; b++) {
-        if (len_host[b] < 1) return set_error(RTS_ERR_INVALID, "stream %d: len must be >= 1 (got %d)", b, len_host[b]);
-        if (first_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: first must be >= 0 (got %lld)", b, first_host[b]);
-        if (first_host[b] > n_ref_frames - len_host[b])
-            return set_error(RTS_ERR_INVALID, "stream %d: frames [%lld, %lld) lie outside the %lld reference frames", b,
-                             first_host[b], first_host[b] + len_host[b], n_ref_frames);
-        if (len_host[b] > m_max) m_max = len_host[b];
-    }
+    const int m_max = ref_ranges_check(B, nullptr, first_host, len_host, n_ref_frames, 0, nullptr);
+    if (m_max < 0) return m_max;
     const int rc = wtw_create(chroma_refs_dev, F, m_max, B, win_frames, hop_frames, keep_last_d, first_host, len_host, out);
-    if (rc == RTS_OK) (*out)->n_ref_frames = n_ref_frames;
+    if (rc == RTS_OK) (*out)->refs.n_frames = n_ref_frames;
     return rc;
 }
 
 int rts_wtw_destroy(rts_wtw *h) {
     if (!h) return RTS_OK;
-    if (h->live) (void)hipFree(h->live);
-    if (h->ref_first) (void)hipFree(h->ref_first);
-    if (h->ref_len) (void)hipFree(h->ref_len);
-    if (h->appended) (void)hipFree(h->appended);
-    if (h->appended_next) (void)hipFree(h->appended_next);
-    if (h->state) (void)hipFree(h->state);
-    if (h->path) (void)hipFree(h->path);
-    if (h->bwork) (void)hipFree(h->bwork);
-    if (h->dlast) (void)hipFree(h->dlast);
-    if (h->ws_sub) (void)hipFree(h->ws_sub);
-    if (h->ws_scr) (void)hipFree(h->ws_scr);
-    if (h->ctl) (void)hipFree(h->ctl);
-    if (h->err) (void)hipFree(h->err);
-    if (h->ticket) (void)hipFree(h->ticket);
-    if (h->codes) (void)hipFree(h->codes);
-    if (h->bnd) (void)hipFree(h->bnd);
-    if (h->entb) (void)hipFree(h->entb);
-    if (h->cross) (void)hipFree(h->cross);
-    if (h->yrec) (void)hipFree(h->yrec);
-    if (h->lens) (void)hipFree(h->lens);
+    rts::ref_table_free(&h->refs);
+    void *const bufs[] = {h->live,   h->appended, h->appended_next, h->state, h->path, h->bwork, h->dlast, h->ws_sub, h->ws_scr,
+                          h->ctl,    h->err,      h->ticket,        h->codes, h->bnd,  h->entb,  h->cross, h->yrec,   h->lens};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
     free(h);
     return RTS_OK;
 }
@@ -1196,7 +1157,7 @@ int rts_wtw_reset(rts_wtw *h, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (h->state) {  // (rts_wtw_create resets before the handle is complete; the device is current there by construction)
-        if (int rc = wtw_check_device(h); rc != RTS_OK) return rc;
+        if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     }
     hipStream_t s = (hipStream_t)stream;
     RTS_HIP(hipMemsetAsync(h->appended, 0, sizeof(int32_t) * (size_t)h->B, s));
@@ -1214,15 +1175,15 @@ int rts_wtw_restart(rts_wtw *h, const uint8_t *mask_host, const long long *first
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
-    if (int rc = restart_check(h->B, mask_host, first_host, len_host, h->ref_first ? h->n_ref_frames : -1, h->M, "M_max");
+    if (int rc = restart_check(h->B, mask_host, first_host, len_host, h->refs.first ? h->refs.n_frames : -1, h->M, "M_max");
         rc != RTS_OK)
         return rc;
-    if (int rc = wtw_check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     RestartSel sel;
     for (int pos = 0; restart_next_chunk(h->B, mask_host, first_host, len_host, &pos, &sel) > 0;) {
         hipLaunchKernelGGL(wtw_restart_kernel, dim3(16, sel.n), dim3(256), 0, s, sel, h->state, h->appended, h->live,
-                           (long long)h->live_stride * kWF, h->ctl, h->ticket, h->ref_first, h->ref_len);
+                           (long long)h->live_stride * kWF, h->ctl, h->ticket, h->refs.first, h->refs.len);
         RTS_HIP(hipGetLastError());
     }
     return RTS_OK;
@@ -1235,10 +1196,10 @@ int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, co
     if (n_max < 0) return set_error(RTS_ERR_INVALID, "n_max < 0");
     if (n_max > 0 && !cols_dev) return set_error(RTS_ERR_INVALID, "cols_dev is NULL");
     if (cols_dtype != RTS_F32 && cols_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad cols_dtype %d", cols_dtype);
-    if (int rc = wtw_check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (precheck) {
-        hipLaunchKernelGGL(wtw_precheck_kernel, dim3((h->B + 63) / 64), dim3(64), 0, s, h->state, h->B, h->M, h->ref_len);
+        hipLaunchKernelGGL(wtw_precheck_kernel, dim3((h->B + 63) / 64), dim3(64), 0, s, h->state, h->B, h->M, h->refs.len);
         RTS_HIP(hipGetLastError());
     }
     if (n_max == 0) return RTS_OK;
@@ -1274,8 +1235,8 @@ int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, co
     g.n_strips_wg = h->big_waves;
     g.M = h->M;
     g.live_stride = h->live_stride;
-    g.ref_first = h->ref_first;
-    g.ref_len = h->ref_len;
+    g.ref_first = h->refs.first;
+    g.ref_len = h->refs.len;
     g.W = h->W;
     g.hopf = h->hopf;
     g.path_cap = h->path_cap;
@@ -1331,7 +1292,7 @@ int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, co
 int rts_wtw_read_states(rts_wtw *h, int32_t *states, void *stream) {
     using namespace rts;
     if (!h || !states) return set_error(RTS_ERR_INVALID, "NULL argument");
-    if (int rc = wtw_check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     RTS_HIP(hipMemcpyAsync(states, h->state, sizeof(int32_t) * 8 * (size_t)h->B, hipMemcpyDeviceToHost, s));
     RTS_HIP(hipStreamSynchronize(s));
@@ -1341,21 +1302,8 @@ int rts_wtw_read_states(rts_wtw *h, int32_t *states, void *stream) {
 int rts_wtw_read_path(rts_wtw *h, int b, int32_t *pairs, int cap_pairs, int *n, void *stream) {
     using namespace rts;
     if (!h || !n) return set_error(RTS_ERR_INVALID, "NULL argument");
-    if (b < 0 || b >= h->B) return set_error(RTS_ERR_INVALID, "stream index %d out of range [0, %d)", b, h->B);
-    if (int rc = wtw_check_device(h); rc != RTS_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    int32_t np = 0;
-    RTS_HIP(hipMemcpyAsync(&np, h->state + (size_t)b * 8 + 4, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    RTS_HIP(hipStreamSynchronize(s));
-    *n = np;
-    int m = np < h->path_cap ? np : h->path_cap;
-    if (m > cap_pairs) m = cap_pairs;
-    if (m > 0 && pairs) {
-        RTS_HIP(hipMemcpyAsync(pairs, h->path + (size_t)b * h->path_cap * 2, sizeof(int32_t) * 2 * (size_t)m,
-                               hipMemcpyDeviceToHost, s));
-        RTS_HIP(hipStreamSynchronize(s));
-    }
-    return RTS_OK;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    return read_path(h->state, 8, 4, h->path, h->path_cap, b, h->B, pairs, cap_pairs, n, (hipStream_t)stream);
 }
 
 int rts_wtw_read_last_d(rts_wtw *h, int b, double *d_host, void *stream) {
@@ -1363,7 +1311,7 @@ int rts_wtw_read_last_d(rts_wtw *h, int b, double *d_host, void *stream) {
     if (!h || !d_host) return set_error(RTS_ERR_INVALID, "NULL argument");
     if (b < 0 || b >= h->B) return set_error(RTS_ERR_INVALID, "stream index %d out of range [0, %d)", b, h->B);
     if (!h->dlast) return set_error(RTS_ERR_INVALID, "handle was created with keep_last_d = 0");
-    if (int rc = wtw_check_device(h); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     RTS_HIP(hipMemcpyAsync(d_host, h->dlast + (size_t)b * h->W * h->W, sizeof(double) * (size_t)h->W * h->W,
                            hipMemcpyDeviceToHost, s));

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from ._handle import _BatchedHandle, _concat_refs
 
 _VARIANTS = {"otw": nat.VARIANT_OTW, "livenote": nat.VARIANT_LIVENOTE, "livenote_v2": nat.VARIANT_LIVENOTE_V2}
 
@@ -34,89 +35,10 @@ def frames_tensor(x, device, dtype=None):
 _on_device = nat.on_device
 
 
-def _concat_refs(refs, to_frames, extra=()):
-    """Per-stream references -> (one device tensor [n_ref_frames][12], int64 first frames [B], int32 lengths [B], pool).
-    A reference object that appears more than once is converted and uploaded once; its range is reused.  ``extra``:
-    pieces uploaded behind them although no stream follows them yet.  ``pool`` maps id(object) -> (object, first frame,
-    frames) for everything uploaded (what ``restart`` looks references up in)."""
-    if len(refs) < 1:
-        raise ValueError("at least one reference is needed")
-    parts, seen, first, lens, off = [], {}, [], [], 0
-    for k, r in enumerate(list(refs) + list(extra)):
-        if id(r) not in seen:
-            t = to_frames(r)
-            if parts and t.dtype != parts[0].dtype:
-                raise TypeError("all references must have the same dtype (%s, %s)" % (parts[0].dtype, t.dtype))
-            seen[id(r)] = (r, off, int(t.shape[0]))
-            parts.append(t)
-            off += int(t.shape[0])
-        if k < len(refs):
-            first.append(seen[id(r)][1])
-            lens.append(seen[id(r)][2])
-    return torch.cat(parts).contiguous(), np.array(first, dtype=np.int64), np.array(lens, dtype=np.int32), seen
-
-
-class _Restartable:
-    """Bookkeeping shared by BatchedOTW and BatchedWTW for ``restart``: which range of the uploaded pool every stream
-    follows.  ``_pool`` is None on a single-reference handle."""
-
-    def _init_refs(self, pool, first, lens):
-        self._pool = pool
-        self._piece = None if pool is None else [(int(f), int(n)) for f, n in zip(first, lens)]
-
-    def _grow_to_pool(self, restart_fn, first, lens):
-        """The handle's buffers are sized by the longest range given at create.  When a piece nobody follows yet is the
-        longest, stream 0 is created on it and put on its own reference by a restart right away (bit for bit a fresh
-        stream, by that call's contract)."""
-        f, n = max(((f, n) for _, f, n in self._pool.values()), key=lambda x: x[1])
-        if n <= int(lens.max()):
-            return first, lens, None
-        first0, lens0 = first.copy(), lens.copy()
-        first0[0], lens0[0] = f, n
-
-        def fix():
-            mask = np.zeros(self.B, dtype=np.uint8)
-            mask[0] = 1
-            nat.check(restart_fn(self._h, mask.ctypes.data, first.ctypes.data, lens.ctypes.data, self._stream()))
-        return first0, lens0, fix
-
-    def _restart_tables(self, streams, refs, offsets):
-        """-> (mask uint8 [B], first int64 [B] | None, lens int32 [B] | None, new (first, frames) of the pieces)."""
-        streams = [int(b) for b in streams]
-        for b in streams:
-            if not 0 <= b < self.B:
-                raise IndexError("stream %d out of range [0, %d)" % (b, self.B))
-        mask = np.zeros(self.B, dtype=np.uint8)
-        mask[streams] = 1
-        if refs is None and offsets is None:
-            return mask, None, None, {}
-        if self._pool is None:
-            raise ValueError("refs / offsets need a handle made by with_references")
-        if refs is not None and len(refs) != len(streams) or offsets is not None and len(offsets) != len(streams):
-            raise ValueError("refs / offsets need one entry per listed stream")
-        first, lens, pieces = np.zeros(self.B, dtype=np.int64), np.ones(self.B, dtype=np.int32), {}
-        for k, b in enumerate(streams):
-            if refs is None:
-                f, n = self._piece[b]
-            else:
-                if id(refs[k]) not in self._pool:
-                    raise ValueError("stream %d: this reference was not uploaded at create (refs / extra_refs)" % b)
-                _, f, n = self._pool[id(refs[k])]
-            o = int(offsets[k]) if offsets is not None else 0
-            if not 0 <= o < n:
-                raise ValueError("stream %d: offset %d outside its reference of %d frames" % (b, o, n))
-            first[b], lens[b], pieces[b] = f + o, n - o, (f, n)
-        return mask, first, lens, pieces
-
-    def _restarted(self, first, lens, pieces):
-        for b, piece in pieces.items():
-            self._piece[b] = piece
-            self.ref_lens[b] = lens[b]
-
-
-class BatchedOTW(_Restartable):
+class BatchedOTW(_BatchedHandle):
     """``ref``: (12, N) feature-major array/tensor, or a device tensor already [N][12] with
     ``frame_major=True``.  ``variant``: 'otw' | 'livenote' | 'livenote_v2'."""
+    _abi = "otw"
 
     def __init__(self, ref, c, max_run_count, batch=1, variant="otw", euclid=False, device="cuda:0",
                  dtype=None, frame_major=False, waves=None):
@@ -153,7 +75,7 @@ class BatchedOTW(_Restartable):
         self._init_refs(pool, first, lens)
         self.B, self.c = len(refs), int(c)
         self.variant = variant
-        first0, lens0, fix = self._grow_to_pool(nat.lib.rts_otw_restart, first, lens)
+        first0, lens0, fix = self._grow_to_pool(first, lens)
         self.N = int(lens0.max())
         h = ctypes.c_void_p()
         nat.check(nat.lib.rts_otw_create_refs(self.ref.data_ptr(), _np_dtype_code(self.ref.dtype), F, self.ref.shape[0],
@@ -179,16 +101,6 @@ class BatchedOTW(_Restartable):
             nat.check(nat.lib.rts_otw_set_waves(self._h, int(waves)))
         self._keep = None
         self._version = 0  # bumped by everything that changes what the handle has consumed
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            nat.destroy_on(self.device, nat.lib.rts_otw_destroy, h)
-
-    __del__ = close
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- whole sequences -------------------------------------------------------------------
     def pack(self, lives, dtype=None):
@@ -238,18 +150,14 @@ class BatchedOTW(_Restartable):
         self._keep = None
         nat.check(nat.lib.rts_otw_reset(self._h, self._stream()))
 
-    @_on_device
     def restart(self, streams, refs=None, offsets=None):
         """Put the listed streams back to the start while the others keep running (rts_otw_restart; asynchronous on
         the current stream).  ``refs``: one entry per listed stream, each an object that was uploaded at create
         (``refs`` / ``extra_refs`` of ``with_references``, matched by identity): the stream moves on to that piece.
         ``offsets``: first frame inside the piece, the stream then follows ``ref[:, offset:]`` and its path indices
         count from there; without ``refs`` it means "same piece, from this frame"."""
-        mask, first, lens, pieces = self._restart_tables(streams, refs, offsets)
-        nat.check(nat.lib.rts_otw_restart(self._h, mask.ctypes.data, first.ctypes.data if first is not None else None,
-                                          lens.ctypes.data if lens is not None else None, self._stream()))
+        super().restart(streams, refs, offsets)
         self._version += 1
-        self._restarted(first, lens, pieces)
 
     # ---- results ------------------------------------------------------------------------------
     @_on_device
@@ -267,16 +175,6 @@ class BatchedOTW(_Restartable):
                     n_path=int(s[nat.ST_N_PATH]), consumed=int(s[nat.ST_CONSUMED]),
                     row_strips=int(s[nat.ST_ROW_STRIPS]), col_strips=int(s[nat.ST_COL_STRIPS]), cells=cells,
                     path_truncated=int(s[nat.ST_PATH_TRUNCATED]), band_recomputes=int(s[nat.ST_BAND_RECOMPUTES]))
-
-    @_on_device
-    def path(self, b=0):
-        n = ctypes.c_int(0)
-        nat.check(nat.lib.rts_otw_read_path(self._h, b, None, 0, ctypes.byref(n), self._stream()))
-        out = np.empty((n.value, 2), dtype=np.int32)
-        if n.value:
-            nat.check(nat.lib.rts_otw_read_path(self._h, b, out.ctypes.data, n.value, ctypes.byref(n),
-                                                self._stream()))
-        return out
 
     def paths(self):
         return [self.path(b) for b in range(self.B)]

@@ -11,11 +11,12 @@ import torch
 from . import _native as nat
 from . import filters
 from .chroma import ChromaPlan
-from .otw_batch import _Restartable, _concat_refs
+from ._handle import _BatchedHandle, _concat_refs
 
 
-class BatchedWTW(_Restartable):
+class BatchedWTW(_BatchedHandle):
     """B live streams against one reference chroma.  ``chroma_ref_dev``: device tensor [M][12] float64."""
+    _abi = "wtw"
 
     def __init__(self, chroma_ref_dev, win_frames, hop_frames, batch=1, keep_last_d=False):
         assert chroma_ref_dev.dtype == torch.float64 and chroma_ref_dev.is_contiguous()
@@ -48,7 +49,7 @@ class BatchedWTW(_Restartable):
         self.ref_lens = lens
         self._init_refs(pool, first, lens)
         self.B, self.W, self.hopf = len(chroma_refs), int(win_frames), int(hop_frames)
-        first0, lens0, fix = self._grow_to_pool(nat.lib.rts_wtw_restart, first, lens)
+        first0, lens0, fix = self._grow_to_pool(first, lens)
         self.M = int(lens0.max())
         h = ctypes.c_void_p()
         nat.check(nat.lib.rts_wtw_create_refs(self.ref.data_ptr(), 12, self.ref.shape[0], first0.ctypes.data,
@@ -60,29 +61,15 @@ class BatchedWTW(_Restartable):
             fix()
         return self
 
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            nat.destroy_on(self.device, nat.lib.rts_wtw_destroy, h)
-
-    __del__ = close
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     @nat.on_device
     def reset(self):
         nat.check(nat.lib.rts_wtw_reset(self._h, self._stream()))
 
-    @nat.on_device
     def restart(self, streams, refs=None, offsets=None):
         """Put the listed streams back to the start while the others keep running (rts_wtw_restart; asynchronous on
         the current stream).  ``refs`` / ``offsets`` as for ``BatchedOTW.restart``: tensors that were given to
         ``with_references`` (``chroma_refs`` / ``extra_refs``), matched by identity, and the first frame inside them."""
-        mask, first, lens, pieces = self._restart_tables(streams, refs, offsets)
-        nat.check(nat.lib.rts_wtw_restart(self._h, mask.ctypes.data, first.ctypes.data if first is not None else None,
-                                          lens.ctypes.data if lens is not None else None, self._stream()))
-        self._restarted(first, lens, pieces)
+        super().restart(streams, refs, offsets)
 
     @nat.on_device
     def push(self, cols_dev, n_new_dev=None, precheck=True):
@@ -107,15 +94,6 @@ class BatchedWTW(_Restartable):
         s = self.states()[b]
         return dict(chroma_ptr=int(s[0]), live_ptr=int(s[1]), ref_ptr=int(s[2]), status=int(s[3]), n_path=int(s[4]),
                     windows=int(s[5]), cells=(int(np.uint32(s[7])) << 32) | int(np.uint32(s[6])))
-
-    @nat.on_device
-    def path(self, b=0):
-        n = ctypes.c_int(0)
-        nat.check(nat.lib.rts_wtw_read_path(self._h, b, None, 0, ctypes.byref(n), self._stream()))
-        out = np.empty((n.value, 2), dtype=np.int32)
-        if n.value:
-            nat.check(nat.lib.rts_wtw_read_path(self._h, b, out.ctypes.data, n.value, ctypes.byref(n), self._stream()))
-        return out
 
     @nat.on_device
     def last_d(self, b=0):

@@ -84,3 +84,35 @@ def test_create_refs_valid_arguments_pass_the_checks(nat):
 
 def test_create_refs_exports(nat):
     assert "rts_otw_create_refs" in nat.EXPORTS and "rts_wtw_create_refs" in nat.EXPORTS
+
+
+BAD_TABLES = [dict(lens=(40, 0, 10)),                                  # len 0
+              dict(first=(0, 40, -1)),                                 # first -1
+              dict(first=(0, 41, 40)),                                 # 41 + 60 > 100
+              dict(n_ref=49, first=(0, 0, 40), lens=(40, 40, 10))]     # the last stream past a 49-frame pool
+
+
+@pytest.mark.parametrize("bad", BAD_TABLES)
+def test_create_refs_one_rule_one_text(nat, bad):
+    """Both trackers check the ranges with one routine: a bad table draws the same message from either."""
+    rc_o, msg_o = _otw(nat, **bad)
+    rc_w, msg_w = _wtw(nat, **bad)
+    assert rc_o == rc_w == -1
+    assert msg_o == msg_w and msg_o.startswith("stream ")
+
+
+@pytest.mark.parametrize("kind", ["otw", "wtw"])
+def test_create_refs_range_ending_at_the_pool_end_is_valid(nat, kind):
+    """first == n_ref_frames - len (the last stream's range ends with the pool) passes the range check.  As in
+    test_create_refs_valid_arguments_pass_the_checks a handle may come into being where a GPU is present."""
+    f, l = _tables((0, 40, 90), (40, 60, 10))
+    h = ctypes.c_void_p()
+    if kind == "otw":
+        rc = nat.lib.rts_otw_create_refs(FAKE, nat.F32, 12, 100, f.ctypes.data, l.ctypes.data, 3, 50, 3,
+                                         nat.VARIANT_OTW, nat.COST_DOT, ctypes.byref(h))
+    else:
+        rc = nat.lib.rts_wtw_create_refs(FAKE, 12, 100, f.ctypes.data, l.ctypes.data, 3, 20, 10, 0, ctypes.byref(h))
+    assert rc in (0, -3, -4), nat.lib.rts_last_error()
+    assert (rc == 0) == bool(h.value)
+    if h.value:
+        (nat.lib.rts_otw_destroy if kind == "otw" else nat.lib.rts_wtw_destroy)(h)

@@ -256,6 +256,61 @@ def test_wtw_per_stream_references_vs_oracle(wtw_path, W, hopf):
     eng.close()
 
 
+def _path_capped(eng, kind, b, cap):
+    """rts_<kind>_read_path with room for `cap` pairs -> (the n it reports, the buffer; four rows of -7 lie behind it)."""
+    from real_time_audio_sync_amd import _native as nat
+    n = ctypes.c_int(-1)
+    buf = np.full((cap + 4, 2), -7, dtype=np.int32)
+    nat.check(getattr(nat.lib, "rts_%s_read_path" % kind)(eng._h, b, buf.ctypes.data, cap, ctypes.byref(n), eng._stream()))
+    return n.value, buf
+
+
+@pytest.mark.parametrize("kind", ["otw", "wtw"])
+def test_path_read_back_equals_single_reference_handles(kind):
+    """path(b) of a with_references handle (both trackers read it through one library routine) equals the path of a
+    single-reference handle on the same reference.  Stream 2 receives no frame: its path is empty (n == 0, nothing
+    written).  A read with room for fewer pairs than the path has reports the full count and writes only that many."""
+    from real_time_audio_sync_amd import synth
+    from real_time_audio_sync_amd.otw_batch import BatchedOTW
+    from real_time_audio_sync_amd.wtw import BatchedWTW
+    dev = torch.device("cuda:0")
+    if kind == "otw":
+        refs = [synth.synth_ref(n, seed=400 + b) for b, n in enumerate((40, 60, 10))]
+        lives = [synth.synth_live(r, seed=410 + b) for b, r in enumerate(refs)]
+        lives[2] = lives[2][:, :0]
+        want = [path for _, path, _ in _singles(refs, lives, 12, torch.float64)]
+        eng = BatchedOTW.with_references(refs, 12, 3, dtype=torch.float64)
+        lv, ln = eng.pack(lives, dtype=torch.float64)
+        eng.run(lv, ln)
+    else:
+        W, hopf = 20, 10
+        refs = [synth.synth_ref(m, seed=420 + b) for b, m in enumerate((120, 90, 30))]
+        lives = [synth.synth_live(r, seed=430 + b) for b, r in enumerate(refs)]
+        lives[2] = lives[2][:, :0]
+        refs_dev = [torch.from_numpy(np.ascontiguousarray(r.T)).to(dev) for r in refs]
+        cols = np.zeros((3, max(l.shape[1] for l in lives), 12))
+        for b, l in enumerate(lives):
+            cols[b, : l.shape[1]] = l.T
+        want = []
+        for b, l in enumerate(lives):
+            one = BatchedWTW(refs_dev[b], W, hopf, 1)
+            if l.shape[1]:
+                one.push(torch.from_numpy(cols[b:b + 1, : l.shape[1]].copy()).to(dev))
+            want.append(one.path(0))
+            one.close()
+        eng = BatchedWTW.with_references(refs_dev, W, hopf)
+        eng.push(torch.from_numpy(cols).to(dev), torch.tensor([l.shape[1] for l in lives], dtype=torch.int32, device=dev))
+    assert len(want[0]) >= 2 and len(want[1]) >= 2 and want[2].shape == (0, 2)
+    for b in range(3):
+        got = eng.path(b)
+        assert got.shape == want[b].shape and np.array_equal(got, want[b]), (kind, b)
+        cap = len(want[b]) // 2
+        n, buf = _path_capped(eng, kind, b, cap)
+        assert n == len(want[b]), (kind, b)
+        assert np.array_equal(buf[:cap], want[b][:cap]) and (buf[cap:] == -7).all(), (kind, b)
+    eng.close()
+
+
 def _chroma_of(plan, samples):
     dev = torch.from_numpy(np.ascontiguousarray(samples)).to(plan.device)
     return plan.frames(dev, pad_left=2048)[0].t().contiguous().cpu().numpy()   # wtw.py:37-41
