@@ -228,6 +228,45 @@ int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_de
             void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Locate: subsequence DTW of B live excerpts against P pieces of a reference pool.
+ * ------------------------------------------------------------------------------------------ */
+
+/* Where in the repertoire is this microphone?  The reference has no such function; the recurrence is dtw.DTW's
+ * (dtw.py:32-40: same cell cost, same step weights, same first-minimum rule) with the first row freed, so that a match
+ * may begin and end anywhere on the piece.  For one query x ([M][F], rows) and one piece y ([N][F], columns), c(i, j)
+ * the cell cost:
+ *   D[0][j] = c(0, j),               S[0][j] = j
+ *   D[i][0] = D[i-1][0] + c(i, 0),   S[i][0] = S[i-1][0]
+ *   D[i][j] = first minimum of (D[i][j-1] + c, D[i-1][j] + c, D[i-1][j-1] + 2c), S[i][j] = S of the chosen predecessor
+ *   end = first j minimising D[M-1][j], cost = D[M-1][end], start = S[M-1][end]   (frame indices inside the piece)
+ * All arithmetic is float64, float32 inputs widened.  cost equals acc_cost[-1][-1] of rts_dtw of the query against frames
+ * [start, end] of the piece, bit for bit.  cost_kind: RTS_COST_DOT is 1 - <x_i, y_j> as one fma chain (the cost of
+ * rts_dtw), RTS_COST_EUCLID is ||x_i - y_j||_2 in the order of the Euclidean tracker.  Features must be finite; a NaN
+ * frame makes the results of the (stream, piece) pairs it takes part in unspecified, nothing else.
+ *   queries_dev: [B][M_max][F] (q_dtype); q_len_dev: int32[B] DEVICE array of valid frames per stream, NULL = M_max for
+ *          all, values above M_max are clamped to it.
+ *   pool_dev: [n_pool_frames][F] (pool_dtype), e.g. the pool given to rts_otw_create_refs; piece p is frames
+ *          [piece_first_dev[p], piece_first_dev[p] + piece_len_dev[p]).  The two tables are DEVICE arrays (int64[P],
+ *          int32[P]) and only checked for NULL on the host.  Pieces may overlap or repeat.
+ *   cost_dev double[B][P], end_dev / start_dev int32[B][P].  A piece with len < 1 or a range outside the pool gives
+ *          cost = +inf, end = start = -1 for every stream (nothing is read out of bounds); so does a stream with
+ *          q_len <= 0 for every piece.
+ *   row_dev / rowstart_dev: optional (either may be NULL) double / int32 [B][n_pool_frames]: D[M-1][:] / S[M-1][:] of
+ *          every valid piece at its pool position.  Cells that belong to no piece are left untouched; where pieces
+ *          overlap, a cell holds the value of one of them.
+ * One workgroup works on one (piece, stream) pair from end to end -- the recurrence is a chain along the piece and a
+ * split would not be exact -- so the call is built for many pairs: a caller with one very long piece gets one
+ * workgroup per stream.
+ * Limits: F == 12 and M_max <= 256 (RTS_ERR_UNSUPPORTED otherwise), 1 <= B, P <= 65535.  RTS_ERR_INVALID, naming the
+ * argument: a NULL pointer other than q_len_dev / row_dev / rowstart_dev, M_max < 1, B or P out of range,
+ * n_pool_frames < 1, a bad q_dtype, pool_dtype or cost_kind.
+ * Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable). */
+int rts_locate(const void *queries_dev, int q_dtype, int M_max, const int32_t *q_len_dev, int B, const void *pool_dev,
+               int pool_dtype, int F, long long n_pool_frames, const long long *piece_first_dev,
+               const int32_t *piece_len_dev, int P, int cost_kind, double *cost_dev, int32_t *end_dev,
+               int32_t *start_dev, double *row_dev, int32_t *rowstart_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Chroma front end: frame -> window -> rFFT -> power -> 12-bin filterbank -> L2 normalise.
  * ------------------------------------------------------------------------------------------ */
 typedef struct rts_chroma rts_chroma;

@@ -6,3 +6,15 @@ hand-written gfx950 HIP kernels behind a C-ABI shared library (include/rtsync.h)
 There is no CPU fallback: importing the native layer fails loudly if librtsync.so is missing.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # locate_batch / BatchedOTW / BatchedWTW load the native library: resolved on first use, so that importing the
+    # package alone (the build does) needs no librtsync.so
+    if name == "locate_batch":
+        from .locate import locate_batch
+        return locate_batch
+    if name == "locate":
+        import importlib
+        return importlib.import_module(".locate", __name__)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -67,6 +67,50 @@ class _BatchedHandle:
                                       lens.ctypes.data if lens is not None else None, self._stream()))
         self._restarted(first, lens, pieces)
 
+    @nat.on_device
+    def locate(self, queries, q_len=None, euclid=None):
+        """Where in the repertoire is each microphone?  ``queries``: the last frames every stream heard -- a device
+        tensor [B][M_max][12] (frame-major like ``push`` takes them), or a list of B arrays (12, M_b) in the
+        reference's layout; at most 256 frames.  ``q_len``: valid frames per stream for the tensor form (list of ints
+        or int32 device tensor; a stream with 0 gets an empty answer).  ``euclid``: cost kind, None = the tracker's
+        own.  Needs a handle made by ``with_references``.
+
+        Returns, per stream, a list of ``(ref_object, start, end, cost)`` for every distinct piece uploaded at create
+        (``refs`` + ``extra_refs``), cheapest first, ties in upload order: the excerpt matches frames start..end of
+        that piece.  ``restart([b], refs=[ref_object], offsets=[start])`` puts the stream there.  Features must be
+        finite (``locate.locate_batch``).  Synchronises."""
+        from .locate import locate_batch
+        if self._pool is None:
+            raise ValueError("locate needs a handle made by with_references")
+        if not torch.is_tensor(queries):
+            lens = [int(q.shape[1]) for q in queries]
+            buf = torch.zeros((len(queries), max(max(lens), 1), 12), dtype=self.ref.dtype)
+            for b, q in enumerate(queries):
+                q = torch.from_numpy(np.ascontiguousarray(q)) if isinstance(q, np.ndarray) else q
+                buf[b, :lens[b]] = q.t().to(self.ref.dtype)
+            queries, q_len = buf, lens
+        queries = queries.to(self.device)
+        if queries.dim() != 3 or queries.shape[0] != self.B or queries.shape[2] != 12:
+            raise ValueError("queries must be [B][M_max][12] with B = %d" % self.B)
+        if q_len is not None and not torch.is_tensor(q_len):
+            q_len = torch.tensor([int(n) for n in q_len], dtype=torch.int32)
+        if q_len is not None:
+            q_len = q_len.to(self.device)
+        pieces = list(self._pool.values())
+        if getattr(self, "_piece_tables", None) is None:
+            self._piece_tables = (torch.tensor([f for _, f, _ in pieces], dtype=torch.int64, device=self.device),
+                                  torch.tensor([n for _, _, n in pieces], dtype=torch.int32, device=self.device))
+        if euclid is None:
+            euclid = bool(getattr(self, "euclid", False))
+        cost, end, start = (t.cpu().numpy() for t in
+                            locate_batch(queries, q_len, self.ref, *self._piece_tables, euclid=euclid))
+        out = []
+        for b in range(self.B):
+            order = sorted((p for p in range(len(pieces)) if np.isfinite(cost[b, p]) and end[b, p] >= 0),
+                           key=lambda p: (cost[b, p], p))
+            out.append([(pieces[p][0], int(start[b, p]), int(end[b, p]), float(cost[b, p])) for p in order])
+        return out
+
     def _init_refs(self, pool, first, lens):
         self._pool = pool
         self._piece = None if pool is None else [(int(f), int(n)) for f, n in zip(first, lens)]

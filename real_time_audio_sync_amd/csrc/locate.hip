@@ -1,0 +1,321 @@
+// Locate: subsequence DTW of B live excerpts (M <= 256 frames each) against P pieces of a reference pool, for gfx950.
+//
+// The recurrence is dtw.py:32-40 (cost c, options left + c, up + c, diag + 2c in this order, first minimum) with the
+// first row freed: D[0][j] = c(0, j), and every cell carries along the column S at which its best path left row 0.  The
+// answer per (stream, piece) is the first minimum of the last row, its column (end) and its S (start): no dense matrix,
+// no back-pointers, no backtrack pass.
+//
+// Mapping (sdp.h in small).  One workgroup per (piece, stream), one wave per STRIP of 64 query rows, lane = row, lanes
+// skewed in time: at strip step s lane l evaluates column j = s - l, so (i, j-1) is the lane's own previous value and
+// (i-1, j), (i-1, j-1) arrive by wave_shr:1 DPP (value and start index).  Strip w + 1 runs kLag chunks of 16 steps behind
+// strip w in the same workgroup and takes strip w's bottom row from a 64-column LDS ring; all waves advance in lockstep,
+// one LDS-only barrier per chunk.  Nothing is handed through HBM and nothing spins.
+//
+// Costs.  Every lane keeps its query row in registers (float64).  Wave 0 stages the piece's frames through LDS, one chunk
+// of 16 columns ahead, in the pool's own element type: a ring of 5 S + 1 chunks covers the columns all S strips are
+// working on.  The 16 costs of a chunk do not depend on the recurrence; a lane computes them from its 16 skewed column
+// records before it enters the dependent chain.  Reading the records skewed (every lane another column) instead of
+// sweeping whole columns into a cost ring costs LDS bandwidth (48 or 96 bytes per cell) but needs 9 / 4.6 KB of LDS per
+// strip instead of sdp.h's 48 KB ring, so a CU holds sixteen 64-row problems at once: this kernel is fed B x P
+// independent problems and is built for residency, not for the latency of one.
+//
+// The lane that owns row M - 1 keeps the running first minimum.  The optional last row (D and S) leaves through a
+// 16-entry LDS tile per chunk, so that HBM sees one 128-byte / 64-byte segment per chunk instead of a store per step.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <type_traits>
+
+#include "common.h"
+#include "cost.h"
+#include "sdp.h"
+
+namespace rts {
+
+constexpr int kLocF = 12;
+constexpr int kLocMaxM = 256;
+constexpr int kLocChunk = 16;  // steps between two workgroup barriers
+constexpr int kLocLag = 5;     // chunks strip w + 1 runs behind strip w: lane 63 finishes column 16m + 15 at step 16m + 78
+
+struct LocArgs {
+    const void *q;           // [B][M_max][12]
+    const int32_t *q_len;    // [B] or NULL
+    const void *pool;        // [n_pool][12]
+    const long long *first;  // [P]
+    const int32_t *len;      // [P]
+    double *cost;            // [B][P]
+    int32_t *end, *start;    // [B][P]
+    double *row;             // optional [B][n_pool]
+    int32_t *rowstart;       // optional [B][n_pool]
+    long long n_pool;
+    int M_max, P, q_f64;
+};
+
+__host__ __device__ inline int loc_ring_chunks(int S) { return kLocLag * S + 1; }
+// frame ring, bottom rows of strips 0 .. S-2 (value, start), the last-row tile of the current chunk (value, start)
+__host__ __device__ inline size_t loc_lds_bytes(int S, bool y64) {
+    return (size_t)loc_ring_chunks(S) * kLocChunk * kLocF * (y64 ? 8 : 4) + (size_t)(S - 1) * 64 * 12 + kLocChunk * 12;
+}
+
+template <bool Y64, bool EUCLID>
+__global__ void __launch_bounds__(kLocMaxM) locate_kernel(LocArgs g) {
+    using yel = typename std::conditional<Y64, double, float>::type;
+    extern __shared__ __align__(16) unsigned char loc_smem[];
+    const int p = blockIdx.x, b = blockIdx.y;
+    const int S = (int)(blockDim.x >> 6);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const size_t out = (size_t)b * g.P + p;
+
+    int M = g.q_len ? g.q_len[b] : g.M_max;
+    M = M < g.M_max ? M : g.M_max;
+    const long long first = g.first[p];
+    const int N = g.len[p];
+    if (M < 1 || N < 1 || first < 0 || first > g.n_pool - N) {  // nothing to match: the whole workgroup leaves
+        if (threadIdx.x == 0) {
+            g.cost[out] = INFINITY;
+            g.end[out] = -1;
+            g.start[out] = -1;
+        }
+        return;
+    }
+
+    const int RC = loc_ring_chunks(S), R = RC * kLocChunk;  // ring size in chunks / columns
+    yel *ring = reinterpret_cast<yel *>(loc_smem);           // [R][12]
+    double *brD = reinterpret_cast<double *>(loc_smem + (size_t)R * kLocF * sizeof(yel));  // [S-1][64]
+    double *obD = brD + (size_t)(S - 1) * 64;                                                // [16]
+    int32_t *brS = reinterpret_cast<int32_t *>(obD + kLocChunk);                             // [S-1][64]
+    int32_t *obS = brS + (size_t)(S - 1) * 64;                                               // [16]
+
+    const int nact = sdp::n_strips(M);  // strips that hold rows of this stream's query (waves beyond only keep the barriers)
+    const int nch = (N + 63 + kLocChunk - 1) / kLocChunk;
+    const int K = nch + kLocLag * (nact - 1);
+    const int i = wave * 64 + lane;
+    const int own_wave = (M - 1) >> 6, own_lane = (M - 1) & 63;
+    const bool own = (wave == own_wave) && (lane == own_lane);
+    const bool want_rows = (g.row != nullptr) || (g.rowstart != nullptr);
+
+    double x[kLocF];
+    {
+        const long long fr = (long long)b * g.M_max + (i < M ? i : M - 1);
+        sdp::load_frame(g.q, g.q_f64, fr, x);
+    }
+
+    // wave 0: the 192 elements of column chunk cc, three per lane (columns past the piece repeat its last one: their
+    // costs feed cells outside the matrix only)
+    const yel *ypool = reinterpret_cast<const yel *>(g.pool);
+    yel pf[3];
+    auto fetch = [&](int cc) {
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+            const int v = lane + 64 * e;
+            int col = kLocChunk * cc + v / kLocF;
+            col = col < N ? col : N - 1;
+            pf[e] = ypool[(first + col) * kLocF + v % kLocF];
+        }
+    };
+    auto commit = [&](int cc) {
+        yel *dst = ring + (size_t)(cc % RC) * kLocChunk * kLocF;
+#pragma unroll
+        for (int e = 0; e < 3; e++) dst[lane + 64 * e] = pf[e];
+    };
+    if (wave == 0) {
+        fetch(0);
+        commit(0);
+    }
+    lds_barrier();
+
+    double prev = 0.0, upprev = 0.0, minv = INFINITY;
+    int sprev = 0, supprev = 0, mine = -1, mins = -1;
+    int ridx = lane == 0 ? 0 : R - lane;  // ring slot of my current column (-lane at step 0)
+
+    for (int k = 0; k < K; k++) {
+        // Slot (k + 1) % RC holds chunk k - 5 S, which no strip reads any more: strip S - 1 is at columns >= 16 (k - 5 S + 1) + 1.
+        const bool pre = (wave == 0) && (k + 1 < nch);
+        if (pre) fetch(k + 1);
+        const int m = k - kLocLag * wave;  // my strip's chunk
+        if (wave < nact && m >= 0 && m < nch) {
+            // ---- the row above, columns [16m, 16m + 16): lane q holds column 16m + q
+            double upD = 0.0;
+            int upS = 0;
+            if (wave > 0 && lane < kLocChunk) {
+                const int c = (kLocChunk * m + lane) & 63;
+                upD = brD[(wave - 1) * 64 + c];
+                upS = brS[(wave - 1) * 64 + c];
+            }
+            const int jneg = lane - kLocChunk * m;  // column of step q is q - jneg
+            // ---- the chunk's 16 costs, ahead of the dependent chain
+            double cst[kLocChunk];
+#pragma unroll
+            for (int q = 0; q < kLocChunk; q++) {
+                double y[kLocF];
+                if constexpr (Y64) {
+                    const double2 *rec = reinterpret_cast<const double2 *>(ring + (size_t)ridx * kLocF);
+#pragma unroll
+                    for (int f = 0; f < kLocF / 2; f++) {
+                        const double2 t = rec[f];
+                        y[2 * f] = t.x;
+                        y[2 * f + 1] = t.y;
+                    }
+                } else {
+                    const float4 *rec = reinterpret_cast<const float4 *>(ring + (size_t)ridx * kLocF);
+#pragma unroll
+                    for (int f = 0; f < kLocF / 4; f++) {
+                        const float4 t = rec[f];
+                        y[4 * f] = (double)t.x;
+                        y[4 * f + 1] = (double)t.y;
+                        y[4 * f + 2] = (double)t.z;
+                        y[4 * f + 3] = (double)t.w;
+                    }
+                }
+                if constexpr (EUCLID) {
+                    cst[q] = euclid12(x, y);
+                } else {  // sdp::DtwPolicy::cost: one fma chain in k order
+                    double s = 0.0;
+#pragma unroll
+                    for (int f = 0; f < kLocF; f++) s = fma(x[f], y[f], s);
+                    cst[q] = 1.0 - s;
+                }
+                ridx = (ridx + 1 == R) ? 0 : ridx + 1;
+            }
+            // ---- 16 steps of the recurrence.  FIRST: this strip holds query row 0 (lane 0); COL0: some lane is at column 0.
+            auto steps = [&](auto first_c, auto col0_c) {
+                constexpr bool FIRST = decltype(first_c)::value;
+                constexpr bool COL0 = decltype(col0_c)::value;
+                const bool first_row = FIRST && lane == 0;
+                sdp::static_for<0, kLocChunk>([&](auto qc) {
+                    constexpr int q = decltype(qc)::value;
+                    const double c = cst[q];
+                    const int j = q - jneg;
+                    const double up = sdp::shr1(prev, sdp::readlane_d(upD, q));
+                    const int sup = sdp::shr1_i(sprev, __builtin_amdgcn_readlane(upS, q));
+                    // the value by two v_min_f64, the start index of the first minimum by compares off that chain
+                    const double o0 = prev + c, o1 = up + c, o2 = upprev + 2 * c;
+                    const double m01 = sdp::vmin(o0, o1);
+                    double best = sdp::vmin(m01, o2);
+                    int ss = (o1 < o0) ? sup : sprev;
+                    ss = (o2 < m01) ? supprev : ss;
+                    if (COL0 && q == jneg) {  // column 0: only (i-1, 0)
+                        best = o1;
+                        ss = sup;
+                    }
+                    if (first_row) {  // free start: D[0][j] = c, S[0][j] = j
+                        best = c;
+                        ss = j;
+                    }
+                    upprev = up;
+                    supprev = sup;
+                    prev = best;
+                    sprev = ss;
+                    if (wave + 1 < nact && lane == 63) {  // bottom row, for the strip below
+                        brD[wave * 64 + (j & 63)] = best;
+                        brS[wave * 64 + (j & 63)] = ss;
+                    }
+                    const bool upd = own && j >= 0 && j < N && best < minv;  // strict: the first minimum stays
+                    minv = upd ? best : minv;
+                    mine = upd ? j : mine;
+                    mins = upd ? ss : mins;
+                    if (want_rows && own) {
+                        obD[q] = best;
+                        obS[q] = ss;
+                    }
+                });
+            };
+            const bool col0 = (kLocChunk * m < 64);
+            if (wave == 0) {
+                if (col0)
+                    steps(sdp::BoolC<true>(), sdp::BoolC<true>());
+                else
+                    steps(sdp::BoolC<true>(), sdp::BoolC<false>());
+            } else {
+                if (col0)
+                    steps(sdp::BoolC<false>(), sdp::BoolC<true>());
+                else
+                    steps(sdp::BoolC<false>(), sdp::BoolC<false>());
+            }
+            // ---- the last row's 16 cells of this chunk: columns 16m - own_lane + [0, 16), lane q stores step q's
+            if (want_rows && wave == own_wave) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const int col = kLocChunk * m - own_lane + lane;
+                if (lane < kLocChunk && col >= 0 && col < N) {
+                    const size_t at = (size_t)b * (size_t)g.n_pool + (size_t)(first + col);
+                    if (g.row) g.row[at] = obD[lane];
+                    if (g.rowstart) g.rowstart[at] = obS[lane];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+        }
+        if (pre) commit(k + 1);
+        lds_barrier();
+    }
+    if (own) {
+        g.cost[out] = minv;
+        g.end[out] = mine;
+        g.start[out] = mins;
+    }
+}
+
+}  // namespace rts
+
+extern "C" {
+
+int rts_locate(const void *queries_dev, int q_dtype, int M_max, const int32_t *q_len_dev, int B, const void *pool_dev,
+               int pool_dtype, int F, long long n_pool_frames, const long long *piece_first_dev,
+               const int32_t *piece_len_dev, int P, int cost_kind, double *cost_dev, int32_t *end_dev,
+               int32_t *start_dev, double *row_dev, int32_t *rowstart_dev, void *stream) {
+    using namespace rts;
+    if (!queries_dev) return set_error(RTS_ERR_INVALID, "queries_dev is NULL");
+    if (!pool_dev) return set_error(RTS_ERR_INVALID, "pool_dev is NULL");
+    if (!piece_first_dev) return set_error(RTS_ERR_INVALID, "piece_first_dev is NULL");
+    if (!piece_len_dev) return set_error(RTS_ERR_INVALID, "piece_len_dev is NULL");
+    if (!cost_dev) return set_error(RTS_ERR_INVALID, "cost_dev is NULL");
+    if (!end_dev) return set_error(RTS_ERR_INVALID, "end_dev is NULL");
+    if (!start_dev) return set_error(RTS_ERR_INVALID, "start_dev is NULL");
+    if (F != kLocF) return set_error(RTS_ERR_UNSUPPORTED, "F must be 12 chroma bins (got %d)", F);
+    if (M_max < 1) return set_error(RTS_ERR_INVALID, "M_max must be >= 1 (got %d)", M_max);
+    if (M_max > kLocMaxM)
+        return set_error(RTS_ERR_UNSUPPORTED, "M_max must be <= %d query frames (got %d)", kLocMaxM, M_max);
+    if (B < 1 || B > 65535) return set_error(RTS_ERR_INVALID, "B must be in [1, 65535] (got %d)", B);
+    if (P < 1 || P > 65535) return set_error(RTS_ERR_INVALID, "P must be in [1, 65535] (got %d)", P);
+    if (n_pool_frames < 1) return set_error(RTS_ERR_INVALID, "n_pool_frames must be >= 1 (got %lld)", n_pool_frames);
+    if (q_dtype != RTS_F32 && q_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad q_dtype %d", q_dtype);
+    if (pool_dtype != RTS_F32 && pool_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad pool_dtype %d", pool_dtype);
+    if (cost_kind != RTS_COST_DOT && cost_kind != RTS_COST_EUCLID)
+        return set_error(RTS_ERR_INVALID, "bad cost_kind %d", cost_kind);
+    LocArgs g;
+    g.q = queries_dev;
+    g.q_len = q_len_dev;
+    g.pool = pool_dev;
+    g.first = piece_first_dev;
+    g.len = piece_len_dev;
+    g.cost = cost_dev;
+    g.end = end_dev;
+    g.start = start_dev;
+    g.row = row_dev;
+    g.rowstart = rowstart_dev;
+    g.n_pool = n_pool_frames;
+    g.M_max = M_max;
+    g.P = P;
+    g.q_f64 = q_dtype == RTS_F64;
+    const int S = sdp::n_strips(M_max);
+    const bool y64 = pool_dtype == RTS_F64, euclid = cost_kind == RTS_COST_EUCLID;
+    const dim3 grid(P, B), block(64 * S);
+    const size_t smem = loc_lds_bytes(S, y64);
+    hipStream_t s = (hipStream_t)stream;
+    if (y64 && euclid)
+        hipLaunchKernelGGL((locate_kernel<true, true>), grid, block, smem, s, g);
+    else if (y64)
+        hipLaunchKernelGGL((locate_kernel<true, false>), grid, block, smem, s, g);
+    else if (euclid)
+        hipLaunchKernelGGL((locate_kernel<false, true>), grid, block, smem, s, g);
+    else
+        hipLaunchKernelGGL((locate_kernel<false, false>), grid, block, smem, s, g);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+
+}  // extern "C"

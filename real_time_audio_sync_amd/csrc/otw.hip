@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "cost.h"
 
 namespace rts {
 
@@ -163,22 +164,6 @@ __device__ __forceinline__ double dot_strided12(const double (&x)[kF], const dou
         t2 = t2 + b;
     }
     return t1 + t2;
-}
-
-// np.sqrt(np.sum((a-b)**2)) with numpy's pairwise order for 12 terms (oracle: orc_euclid).
-__device__ __forceinline__ double euclid12(const double (&a)[kF], const double (&b)[kF]) {
-    double sq[kF];
-#pragma unroll
-    for (int i = 0; i < kF; i++) {
-        const double d = a[i] - b[i];
-        sq[i] = d * d;
-    }
-    double res = ((sq[0] + sq[1]) + (sq[2] + sq[3])) + ((sq[4] + sq[5]) + (sq[6] + sq[7]));
-    res = res + sq[8];
-    res = res + sq[9];
-    res = res + sq[10];
-    res = res + sq[11];
-    return sqrt(res);
 }
 
 __device__ __forceinline__ double cell_cost(const double (&lf)[kF], const double (&rf)[kF], int euclid) {

@@ -225,6 +225,16 @@ class LiveSession(object):
             self.otw._version += 1
         eng._restarted(first, lens, pieces)
 
+    def locate(self, queries, q_len=None, euclid=None):
+        """Where in the repertoire is each microphone?  ``BatchedOTW.locate`` / ``BatchedWTW.locate`` of the bound
+        tracker (needs per-stream references: a list as ``ref_chroma``), with the pieces named by the objects given at
+        create, so that every entry ``(ref, start, end, cost)`` goes straight into ``restart([b], refs=[ref],
+        offsets=[start])``.  The session keeps no history of columns: ``queries`` are what the caller collected from
+        ``last_columns()``."""
+        found = (self.otw or self.wtw).locate(queries, q_len, euclid)
+        given = {id(conv): obj for obj, conv in self._conv.values()}
+        return [[(given[id(r)], s, e, c) for r, s, e, c in entries] for entries in found]
+
     def path(self, b=0):
         return (self.otw or self.wtw).path(b)
 

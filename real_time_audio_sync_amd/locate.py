@@ -1,0 +1,57 @@
+"""Locate: where in the repertoire is this microphone?  Subsequence DTW of short live excerpts against every piece of
+a reference pool (csrc/locate.hip, ``rts_locate`` in include/rtsync.h).  The reference has no such function; the
+recurrence is dtw.py's with the first row freed, so a match may begin and end anywhere on a piece."""
+import ctypes
+
+import torch
+
+from . import _native as nat
+
+
+def _dtype_code(dt):
+    if dt == torch.float32:
+        return nat.F32
+    if dt == torch.float64:
+        return nat.F64
+    raise TypeError("feature tensors must be float32 or float64, got %s" % dt)
+
+
+def locate_batch(queries_dev, q_len_dev, pool_dev, first_dev, len_dev, euclid=False, want_rows=False):
+    """queries_dev: [B][M_max][12] (or [M_max][12] for one stream), M_max <= 256; q_len_dev: int32 [B] valid frames per
+    stream or None; pool_dev: [n_pool][12]; first_dev int64 [P] / len_dev int32 [P]: piece p is frames
+    [first[p], first[p] + len[p]) of the pool.  All device tensors, features float32 or float64.
+
+    Returns device tensors ``(cost [B][P] float64, end [B][P] int32, start [B][P] int32)``: the cheapest warping of
+    stream b's excerpt onto piece p covers frames start..end of the piece (both inclusive, relative to the piece) at
+    accumulated cost ``cost``.  ``+inf, -1, -1`` where there is nothing to match: a piece with len < 1 or outside the
+    pool, a stream with q_len 0.  With ``want_rows`` also ``row [B][n_pool] float64`` and ``rowstart [B][n_pool]
+    int32``: the last row of the accumulated-cost matrix of every piece at its pool position and the start each of
+    its cells carries (+inf / -1 where no piece lies; where pieces overlap, one of them).
+
+    Features must be finite: a NaN frame (a silent microphone normalises to one) makes the results of the (stream,
+    piece) pairs it takes part in unspecified.  Asynchronous on the current stream."""
+    dev = pool_dev.device
+    if queries_dev.dim() == 2:
+        queries_dev = queries_dev.unsqueeze(0)
+    queries_dev, pool_dev = queries_dev.contiguous(), pool_dev.contiguous()
+    B, M_max, F = queries_dev.shape
+    P = int(first_dev.shape[0])
+    if first_dev.dtype != torch.int64 or len_dev.dtype != torch.int32 or len_dev.shape[0] != P:
+        raise TypeError("first_dev must be int64 [P] and len_dev int32 [P]")
+    if q_len_dev is not None and (q_len_dev.dtype != torch.int32 or q_len_dev.shape[0] != B):
+        raise TypeError("q_len_dev must be int32 [B]")
+    n_pool = int(pool_dev.shape[0])
+    cost = torch.empty((B, P), dtype=torch.float64, device=dev)
+    end = torch.empty((B, P), dtype=torch.int32, device=dev)
+    start = torch.empty((B, P), dtype=torch.int32, device=dev)
+    row = torch.full((B, n_pool), float("inf"), dtype=torch.float64, device=dev) if want_rows else None
+    rowstart = torch.full((B, n_pool), -1, dtype=torch.int32, device=dev) if want_rows else None
+    nat.check(nat.lib.rts_locate(queries_dev.data_ptr(), _dtype_code(queries_dev.dtype), M_max,
+                                 q_len_dev.data_ptr() if q_len_dev is not None else None, B,
+                                 pool_dev.data_ptr(), _dtype_code(pool_dev.dtype), F, n_pool,
+                                 first_dev.data_ptr(), len_dev.data_ptr(), P,
+                                 nat.COST_EUCLID if euclid else nat.COST_DOT,
+                                 cost.data_ptr(), end.data_ptr(), start.data_ptr(),
+                                 row.data_ptr() if want_rows else None, rowstart.data_ptr() if want_rows else None,
+                                 ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return (cost, end, start, row, rowstart) if want_rows else (cost, end, start)

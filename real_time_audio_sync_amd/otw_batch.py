@@ -52,6 +52,7 @@ class BatchedOTW(_BatchedHandle):
         self._init_refs(None, None, None)
         self.B, self.c = int(batch), int(c)
         self.variant = variant
+        self.euclid = bool(euclid)
         h = ctypes.c_void_p()
         nat.check(nat.lib.rts_otw_create(self.ref.data_ptr(), _np_dtype_code(self.ref.dtype), F, self.N, self.B,
                                          self.c, int(max_run_count), _VARIANTS[variant],
@@ -75,6 +76,7 @@ class BatchedOTW(_BatchedHandle):
         self._init_refs(pool, first, lens)
         self.B, self.c = len(refs), int(c)
         self.variant = variant
+        self.euclid = bool(euclid)
         first0, lens0, fix = self._grow_to_pool(first, lens)
         self.N = int(lens0.max())
         h = ctypes.c_void_p()
