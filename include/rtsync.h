@@ -166,6 +166,39 @@ int rts_otw_insert(rts_otw *h, const void *frames_dev, int frames_dtype, const u
 int rts_otw_push(rts_otw *h, const void *frames_dev, int frames_dtype, int n_max, const int32_t *n_new_dev,
                  void *stream);
 
+/* The tail of the tracker's own history: what a stream last heard, as the (queries_dev, q_len_dev) pair rts_locate takes.
+ * The reference has nothing comparable (its self.live, otw_eran.py:14,20, is never read back as an excerpt).  Stream b has
+ * consumed n frames through rts_otw_insert / rts_otw_push since create, reset or its last restart, n capped at the
+ * history capacity of its own range, 2 N_b (the count runs past it on RTS_LIVE_OVERFLOW).  len_dev[b] = min(M_max, n);
+ * out_dev[b][0 .. len) are frames n - len .. n - 1 in order, as float64 whatever dtype they were pushed in; rows
+ * [len, M_max) are written as zeros.  `mask_dev`: optional uint8[B] DEVICE array, a stream with a zero entry gets len 0 and
+ * all-zero rows (rts_locate then spends nothing on it: its kernel leaves on M < 1); NULL = all streams.
+ *   out_dev double [B][M_max][12], len_dev int32 [B].  A fresh handle, whose history is not allocated yet, gives len 0
+ * everywhere.  The handle is only read.  Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable).
+ *   RTS_ERR_INVALID, naming the argument: NULL handle, out_dev or len_dev, M_max < 1.  RTS_ERR_UNSUPPORTED: M_max > 256 (the
+ * bound of rts_locate), and a handle that has consumed an rts_otw_run since its last reset -- those frames are the
+ * caller's memory, not the handle's. */
+int rts_otw_recent(rts_otw *h, int M_max, double *out_dev /* [B][M_max][12] */, int32_t *len_dev /* [B] */,
+                   const uint8_t *mask_dev /* optional uint8[B], DEVICE */, void *stream);
+
+/* Tracking confidence: the handle's own cell cost along the path it recorded.  The reference has nothing comparable (it
+ * plots acc_cost after the fact, livenote_v2.ipynb).  Stream b has stored path points (t_i, j_i) -- min(n_path, path
+ * capacity) of them once RTS_ST_PATH_TRUNCATED is set; n = min(K, stored) and the last n points count, in recording order.
+ * costs_dev[b][k] is the cost between history frame t and frame j of the stream's current reference range (pool frame
+ * first_b + j on an rts_otw_create_refs handle, also after a restart onto an offset range), bit for bit what the tracker
+ * computes: RTS_COST_DOT 1 - <live, ref> in the strided-dot order of otw_eran.py:220, RTS_COST_EUCLID the norm of
+ * livenote_v2.py:168, a float32 reference widened as the tracker widens it.  costs_dev[b][n .. K) are NaN.
+ * mean_dev[b] is the sequential float64 sum of the n costs, oldest first, divided by (double)n -- NaN for n = 0 -- and
+ * n_dev[b] = n.  A NaN cost (a silent column normalises to NaN) stays NaN and makes that stream's mean NaN, nothing else.
+ * The mean is in the unit of rts_locate's cost / (M + end - start + 1).
+ *   mean_dev double [B], n_dev int32 [B], costs_dev optional double [B][K].  1 <= K <= 256.  The handle is only read.
+ * Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable).
+ *   RTS_ERR_INVALID, naming the argument: NULL handle, mean_dev or n_dev, K outside [1, 256].  RTS_ERR_UNSUPPORTED after an
+ * rts_otw_run, as for rts_otw_recent.
+ *   There is no WTW counterpart: its cosine cost is NaN on silent frames, and its windows re-decide the path. */
+int rts_otw_path_cost(rts_otw *h, int K, double *mean_dev /* [B] */, int32_t *n_dev /* [B] */,
+                      double *costs_dev /* optional [B][K] */, void *stream);
+
 /* Getters (synchronise `stream`). */
 int rts_otw_read_state(rts_otw *h, int b, int32_t *state /* RTS_STATE_LEN */, void *stream);
 int rts_otw_read_states(rts_otw *h, int32_t *states /* [B][RTS_STATE_LEN] */, void *stream);
@@ -366,6 +399,11 @@ int rts_wtw_restart(rts_wtw *h, const uint8_t *mask_host, const long long *first
 int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, const int32_t *n_new_dev,
                  int precheck, void *stream);
 
+/* rts_otw_recent for the live chroma history (wtw.py:52,:55) of a WTW handle: same contract, n being the columns appended
+ * since create, reset or the stream's last restart, capped at 2 M_b.  rts_wtw_push alternates between two count arrays, and
+ * a captured call reads the one that was current at capture: capture it behind the pushes it follows, in one graph. */
+int rts_wtw_recent(rts_wtw *h, int M_max, double *out_dev, int32_t *len_dev, const uint8_t *mask_dev, void *stream);
+
 int rts_wtw_read_states(rts_wtw *h, int32_t *states /* [B][RTS_WTW_STATE_LEN] */, void *stream);
 int rts_wtw_read_path(rts_wtw *h, int b, int32_t *pairs, int cap_pairs, int *n, void *stream);
 /* The last window's accumulated-cost matrix D, [W][W] doubles (needs keep_last_d). */
@@ -451,6 +489,19 @@ int rts_live_feed(rts_live *h, const void *samples_host, int sample_kind, const 
  * reflect for every stream, *feeds_submitted = feeds enqueued so far.  Any pointer may be NULL. */
 int rts_live_poll(rts_live *h, int32_t *status /* [B] */, int32_t *positions /* [B][2] */, int *feeds_done,
                   int *feeds_submitted);
+/* The confidence of rts_otw_path_cost without a read-back.  rts_live_watch(K): 0 = off (the default), 1..256 = on.
+ * With watch on, every rts_live_submit enqueues one more launch, between the tracker push and the publication of the
+ * status words (in a feed without columns too): rts_otw_path_cost over the last K path points, its mean / n written to a
+ * second host-mapped block, which the first rts_live_watch(K > 0) allocates.  With watch off a feed enqueues exactly what
+ * it enqueues without this function.  rts_live_confidence is the non-blocking look at those words: mean_cost[b], n_points[b]
+ * and *feeds_done, computed as by rts_live_poll, with the same guarantee: when *feeds_done >= k, every word read reflects a
+ * feed >= k in which watch was on.  rts_live_watch(0) leaves the words as they are.  rts_live_restart republishes n = 0,
+ * mean = NaN for the selected streams, rts_live_reset for all.  Any output pointer may be NULL.
+ *   RTS_ERR_INVALID: NULL handle, K outside [0, 256], rts_live_confidence before any rts_live_watch(K > 0).
+ * RTS_ERR_UNSUPPORTED: rts_live_watch on a handle bound to a WTW tracker (there is no WTW path cost). */
+int rts_live_watch(rts_live *h, int K);
+int rts_live_confidence(rts_live *h, double *mean_cost /* [B] */, int32_t *n_points /* [B] */, int *feeds_done);
+
 /* Device views of the columns the most recently submitted feed handed to the tracker, and of their per-stream counts
  * (zero-copy consumers, tests): *cols_dev is float64, stream b's column i at cols_dev[(b * *cols_stride + i) * 12],
  * i < (*n_cols_dev)[b].  *cols_stride, the rows per stream, is the largest number of chroma columns any stream completed

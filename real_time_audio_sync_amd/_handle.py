@@ -111,6 +111,52 @@ class _BatchedHandle:
             out.append([(pieces[p][0], int(start[b, p]), int(end[b, p]), float(cost[b, p])) for p in order])
         return out
 
+    @nat.on_device
+    def recent(self, M=128, streams=None):
+        """The last frames every stream heard, from the tracker's own history (rts_otw_recent / rts_wtw_recent): device
+        tensors ``(frames [B][M][12] float64, lens int32 [B])``, ``frames[b, :lens[b]]`` being the last ``lens[b] =
+        min(M, consumed)`` frames of stream b in order and zeros behind them -- what ``locate`` takes as ``queries`` /
+        ``q_len``.  ``streams``: only these (the others get lens 0 and zeros).  Frames consumed since create, ``reset`` or
+        the stream's last ``restart``; at most 256.  Asynchronous, nothing is read back."""
+        M = int(M)
+        frames = torch.empty((self.B, max(M, 0), 12), dtype=torch.float64, device=self.device)
+        lens = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        mask = None
+        if streams is not None:
+            mask = self._restart_tables(streams, None, None)[0]
+            mask = torch.from_numpy(mask).to(self.device)
+        nat.check(self._fn("recent")(self._h, M, frames.data_ptr(), lens.data_ptr(),
+                                     mask.data_ptr() if mask is not None else None, self._stream()))
+        return frames, lens
+
+    def locate_recent(self, M=128, streams=None, euclid=None):
+        """``locate`` on what the streams heard last: ``recent(M, streams)`` handed to ``locate``.  Same return value;
+        streams not listed get ``[]``."""
+        frames, lens = self.recent(M, streams)
+        return self.locate(frames, lens, euclid)
+
+    def reacquire(self, streams, M=128):
+        """This microphone is lost: put it where it really is.  For the listed streams: take the last ``M`` frames each
+        heard (``recent``, before anything is cleared), ``locate`` them in the repertoire, ``restart`` every stream
+        that got an answer onto the cheapest ``(piece, start)``, and ``push`` its excerpt into the restarted tracker, so
+        that it re-follows those frames from ``start`` and stands at "now" instead of M frames behind.  One restart
+        and one push in all; the other streams receive no frame and no restart.  Returns ``{b: (piece, start, end,
+        cost) | None}`` (None: nothing heard yet, nothing changed).  Whether a stream is lost is the caller's decision:
+        compare ``path_cost`` with ``cost / (M + end - start + 1)`` of a ``locate_recent``.  Synchronises (locate)."""
+        return self._reacquire(streams, M, self.restart)
+
+    def _reacquire(self, streams, M, restart):
+        streams = list(dict.fromkeys(int(b) for b in streams))
+        frames, lens = self.recent(M, streams)
+        found = self.locate(frames, lens)
+        out = {b: (found[b][0] if found[b] else None) for b in streams}
+        moved = [b for b in streams if out[b] is not None]
+        if moved:
+            restart(moved, refs=[out[b][0] for b in moved], offsets=[out[b][1] for b in moved])
+            keep = torch.from_numpy(self._restart_tables(moved, None, None)[0]).to(self.device)
+            self.push(frames, lens * keep.to(torch.int32))
+        return out
+
     def _init_refs(self, pool, first, lens):
         self._pool = pool
         self._piece = None if pool is None else [(int(f), int(n)) for f, n in zip(first, lens)]

@@ -66,6 +66,8 @@ _decl("rts_otw_restart", _i32, [_vp, _vp, _vp, _vp, _vp])
 _decl("rts_otw_run", _i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp])
 _decl("rts_otw_insert", _i32, [_vp, _vp, _i32, _vp, _vp])
 _decl("rts_otw_push", _i32, [_vp, _vp, _i32, _i32, _vp, _vp])
+_decl("rts_otw_recent", _i32, [_vp, _i32, _vp, _vp, _vp, _vp])
+_decl("rts_otw_path_cost", _i32, [_vp, _i32, _vp, _vp, _vp, _vp])
 _decl("rts_otw_read_state", _i32, [_vp, _i32, _vp, _vp])
 _decl("rts_otw_read_states", _i32, [_vp, _vp, _vp])
 _decl("rts_otw_read_path", _i32, [_vp, _i32, _vp, _i32, _pi32, _vp])
@@ -98,6 +100,7 @@ _decl("rts_wtw_destroy", _i32, [_vp])
 _decl("rts_wtw_reset", _i32, [_vp, _vp])
 _decl("rts_wtw_restart", _i32, [_vp, _vp, _vp, _vp, _vp])
 _decl("rts_wtw_push", _i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp])
+_decl("rts_wtw_recent", _i32, [_vp, _i32, _vp, _vp, _vp, _vp])
 _decl("rts_wtw_read_states", _i32, [_vp, _vp, _vp])
 _decl("rts_wtw_read_path", _i32, [_vp, _i32, _vp, _i32, _pi32, _vp])
 _decl("rts_wtw_read_last_d", _i32, [_vp, _i32, _vp, _vp])
@@ -116,6 +119,8 @@ _decl("rts_live_submit", _i32, [_vp, _i32, _vp])
 _decl("rts_live_feed", _i32, [_vp, _vp, _i32, _vp, _vp])
 _decl("rts_live_poll", _i32, [_vp, _vp, _vp, _pi32, _pi32])
 _decl("rts_live_pending", _i32, [_vp, _vp])
+_decl("rts_live_watch", _i32, [_vp, _i32])
+_decl("rts_live_confidence", _i32, [_vp, _vp, _vp, _pi32])
 
 
 def check(rc):

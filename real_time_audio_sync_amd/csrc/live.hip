@@ -17,6 +17,8 @@
 //                         (np.clip(np.diff(chroma), 0, inf), chroma.py:85-90) in a second buffer; the last chroma
 //                         column of every stream is carried on the device from feed to feed
 //   rts_otw_push | rts_wtw_push   the columns into the alignment state (insert semantics, column by column)
+//   rts_otw_path_cost     only after rts_live_watch(K > 0): the tracker's mean cell cost over its last K path points into a
+//                         second host-mapped block -- rts_live_confidence reads it like rts_live_poll reads the status words
 //   live_compact_kernel   drop hop * n_frames consumed samples per stream (data = data[2048:], livenote_live.py:208),
 //                         and publish {status, live position, ref position, feed number} of every stream into
 //                         host-mapped memory -- rts_live_poll reads those words without touching the stream.
@@ -54,6 +56,9 @@ struct LiveArgs {
     double *carry;               // [B][12] last chroma column of every stream
     int32_t *has_carry, *n_cols; // [B]
     int cols_stride;             // rows per stream in cols / dcols: n_max of this feed
+    // rts_live_watch (NULL until its first call): host-mapped confidence words, republished by live_restart_kernel
+    double *conf_mean;           // [B]
+    int32_t *conf_n;             // [B]
 };
 
 __device__ __forceinline__ void live_publish(const LiveArgs &g, int b) {
@@ -165,6 +170,10 @@ __global__ void live_restart_kernel(RestartSel sel, LiveArgs g) {
     p[0] = st[g.st_status];
     p[1] = st[g.st_live];
     p[2] = st[g.st_ref];
+    if (g.conf_n) {  // a fresh stream has no path point yet
+        g.conf_n[b] = 0;
+        g.conf_mean[b] = __longlong_as_double(0x7ff8000000000000LL);
+    }
     __threadfence_system();
 }
 
@@ -198,7 +207,34 @@ struct rts_live {
     const int32_t *state_dev;
     int state_len, st_status, st_live, st_ref;
     int feeds;
+    // rts_live_watch: K path points per stream (0 = off) and the second host-mapped block, double mean[B] then int32 n[B],
+    // allocated by the first rts_live_watch(K > 0)
+    int watch_k;
+    unsigned char *conf_host;
+    double *conf_mean_dev;
+    int32_t *conf_n_dev;
 };
+
+namespace rts {
+
+static void live_conf_clear(rts_live *h) {
+    double *mean = reinterpret_cast<double *>(h->conf_host);
+    int32_t *n = reinterpret_cast<int32_t *>(h->conf_host + sizeof(double) * (size_t)h->B);
+    for (int b = 0; b < h->B; b++) {
+        mean[b] = __builtin_nan("");
+        n[b] = 0;
+    }
+}
+
+// With watch on, one more launch per feed between the tracker push and live_compact_kernel: the path-cost kernel of
+// rts_otw_path_cost with its mean / n outputs in the mapped confidence block.  It precedes the compaction, which
+// writes the feed number last, so a reader that sees feed k sees confidence words of a feed >= k.
+static int live_watch_launch(rts_live *h, void *stream) {
+    if (h->watch_k < 1) return RTS_OK;
+    return rts_otw_path_cost(h->otw, h->watch_k, h->conf_mean_dev, h->conf_n_dev, nullptr, stream);
+}
+
+}  // namespace rts
 
 extern "C" {
 
@@ -223,6 +259,7 @@ int rts_live_destroy(rts_live *h) {
     free(h->has_carry_host);
     free(h->has_carry_next);
     if (h->pub_host) (void)hipHostFree(h->pub_host);
+    if (h->conf_host) (void)hipHostFree(h->conf_host);
     free(h->pending_host);
     free(h);
     return RTS_OK;
@@ -342,6 +379,7 @@ int rts_live_reset(rts_live *h, void *stream) {
         memset(h->has_carry_host, 0, (size_t)h->B);
     }
     memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * (size_t)h->B);
+    if (h->conf_host) live_conf_clear(h);
     memset(h->used, 0, sizeof(h->used));
     h->slot = -1;
     h->feeds = 0;
@@ -370,6 +408,8 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
     g.st_live = h->st_live;
     g.st_ref = h->st_ref;
     g.pub = h->pub_dev;
+    g.conf_mean = h->conf_mean_dev;
+    g.conf_n = h->conf_n_dev;
     RestartSel sel;
     for (int pos = 0; restart_next_chunk(h->B, mask_host, nullptr, nullptr, &pos, &sel) > 0;) {
         hipLaunchKernelGGL(live_restart_kernel, dim3((sel.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, sel, g);
@@ -486,6 +526,7 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
         if (n_max_diff > 0) {
             if (int rc = rts_otw_push(h->otw, h->dcols, RTS_F64, n_max, h->n_cols, stream); rc != RTS_OK) return rc;
         }
+        if (int rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
         hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
         RTS_HIP(hipGetLastError());
         return RTS_OK;
@@ -494,6 +535,7 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
         if (h->wtw) {  // wtw.py:76-77 runs on every insert(), new column or not
             if (int rc = rts_wtw_push(h->wtw, nullptr, RTS_F64, 0, nullptr, 1, stream); rc != RTS_OK) return rc;
         }
+        if (int rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
         hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);  // nothing to drop: pending, publication
         RTS_HIP(hipGetLastError());
         return RTS_OK;
@@ -504,6 +546,7 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
     rc = h->otw ? rts_otw_push(h->otw, h->cols, RTS_F64, n_max, h->n_frames, stream)
                 : rts_wtw_push(h->wtw, h->cols, RTS_F64, n_max, h->n_frames, 1, stream);
     if (rc != RTS_OK) return rc;
+    if (rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
     hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -546,6 +589,50 @@ int rts_live_poll(rts_live *h, int32_t *status, int32_t *positions, int *feeds_d
     }
     if (feeds_done) *feeds_done = fd;
     if (feeds_submitted) *feeds_submitted = h->feeds;
+    return RTS_OK;
+}
+
+int rts_live_watch(rts_live *h, int K) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (K < 0 || K > 256) return set_error(RTS_ERR_INVALID, "K must be in [0, 256] (got %d)", K);
+    if (!h->otw)
+        return set_error(RTS_ERR_UNSUPPORTED, "rts_live_watch on a WTW tracker: there is no WTW path cost (its cosine cost is NaN "
+                                              "on silent frames and its windows re-decide the path)");
+    if (K > 0 && !h->conf_host) {
+        if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+        const size_t bytes = (sizeof(double) + sizeof(int32_t)) * (size_t)h->B;
+        RTS_HIP(hipHostMalloc((void **)&h->conf_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        void *dev = nullptr;
+        if (hipError_t e = hipHostGetDevicePointer(&dev, h->conf_host, 0); e != hipSuccess) {
+            (void)hipHostFree(h->conf_host);
+            h->conf_host = nullptr;
+            return set_error(RTS_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
+        }
+        h->conf_mean_dev = reinterpret_cast<double *>(dev);
+        h->conf_n_dev = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(dev) + sizeof(double) * (size_t)h->B);
+        live_conf_clear(h);
+    }
+    h->watch_k = K;
+    return RTS_OK;
+}
+
+int rts_live_confidence(rts_live *h, double *mean_cost, int32_t *n_points, int *feeds_done) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!h->conf_host) return set_error(RTS_ERR_INVALID, "rts_live_confidence before any rts_live_watch(K > 0)");
+    const volatile int32_t *p = h->pub_host;
+    const volatile double *mean = reinterpret_cast<const volatile double *>(h->conf_host);
+    const volatile int32_t *n = reinterpret_cast<const volatile int32_t *>(h->conf_host + sizeof(double) * (size_t)h->B);
+    int fd = h->feeds;
+    for (int b = 0; b < h->B; b++) {
+        const int seq = p[(size_t)b * kLiveWords + 3];
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        if (mean_cost) mean_cost[b] = mean[b];
+        if (n_points) n_points[b] = n[b];
+        if (seq < fd) fd = seq;
+    }
+    if (feeds_done) *feeds_done = fd;
     return RTS_OK;
 }
 

@@ -2238,6 +2238,86 @@ __global__ void otw_append_many_kernel(double *hist, int32_t *hist_len, const vo
     if (threadIdx.x == 0) hist_len[b] = base + (nn > 0 ? nn : 0);
 }
 
+// rts_otw_recent: the last min(M_max, n) frames of stream b's history into out[b], zeros behind them; one workgroup per
+// stream.  n is what the stream has consumed, capped at its own capacity 2 N_b (hist_len runs past it on
+// RTS_LIVE_OVERFLOW) and at the history stride.  `hist` is NULL until the first insert / push: every stream then reads
+// as empty.  Nothing the tracker owns is written.
+__global__ void __launch_bounds__(256) otw_recent_kernel(const double *hist, const int32_t *hist_len, int hist_stride, int N,
+                                                         const int32_t *ref_len, int M_max, double *out, int32_t *len_out,
+                                                         const uint8_t *mask) {
+    const int b = blockIdx.x;
+    const int cap = 2 * (ref_len ? ref_len[b] : N);
+    int n = hist ? hist_len[b] : 0;
+    n = n < 0 ? 0 : n;
+    n = n > cap ? cap : n;
+    n = n > hist_stride ? hist_stride : n;
+    const int len = (mask && !mask[b]) ? 0 : (n < M_max ? n : M_max);
+    const long long src0 = ((long long)b * hist_stride + (n - len)) * kF;
+    double *dst = out + (size_t)b * M_max * kF;
+    for (int idx = threadIdx.x; idx < M_max * kF; idx += blockDim.x) dst[idx] = idx < len * kF ? hist[src0 + idx] : 0.0;
+    if (threadIdx.x == 0) len_out[b] = len;
+}
+
+// rts_otw_path_cost: the tracker's own cell cost at the last n = min(K, stored points) path points of every stream.
+// One workgroup of 64 * ceil(K / 64) threads per stream; lane k owns point (stored - n + k): one int2 pair, the history
+// frame t and the frame j of the stream's current reference range through the tracker's own loaders (otw_live_frame /
+// otw_ref_frame: the reference widened as the tracker widens it), one cell_cost.  The mean is the sequential float64 sum,
+// oldest point first, so thread 0 walks the LDS array in order behind one barrier -- a tree would round differently.
+// A point whose indices lie outside the history or the range (never recorded by the tracker) costs NaN instead of being
+// read.  Reads the handle's state only; the stores end with a system-scope fence because rts_live_watch points mean / n_out
+// at host-mapped memory.
+struct PathCostArgs {
+    const int32_t *state, *path, *hist_len;
+    const double *hist;
+    const void *ref;
+    const long long *ref_first;
+    const int32_t *ref_len;
+    int N, path_cap, hist_stride, ref_f64, euclid, K;
+    double *mean, *costs;
+    int32_t *n_out;
+};
+__global__ void __launch_bounds__(256) otw_path_cost_kernel(PathCostArgs a) {
+    __shared__ double cost_s[256];
+    const int b = blockIdx.x, k = threadIdx.x;
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const int Nb = a.ref_len ? a.ref_len[b] : a.N;
+    int points = a.state[(size_t)b * RTS_STATE_LEN + RTS_ST_N_PATH];  // counts past path_cap once RTS_ST_PATH_TRUNCATED
+    points = points > a.path_cap ? a.path_cap : (points < 0 ? 0 : points);
+    if (!a.hist) points = 0;  // no frame has come through insert / push yet
+    const int n = points < a.K ? points : a.K;
+    int frames = a.hist ? a.hist_len[b] : 0;
+    frames = frames > a.hist_stride ? a.hist_stride : frames;
+    if (k < a.K) {
+        double cost = qnan;
+        if (k < n) {
+            const int2 p = reinterpret_cast<const int2 *>(a.path)[(size_t)b * a.path_cap + (points - n + k)];
+            if (p.x >= 0 && p.x < frames && p.y >= 0 && p.y < Nb) {
+                OtwEnv e;
+                e.live = a.hist;
+                e.live_f64 = 1;
+                e.live_base = (long long)b * a.hist_stride * kF;
+                e.ref_f64 = a.ref_f64;
+                e.ref = a.ref_first ? static_cast<const char *>(a.ref) + a.ref_first[b] * (long long)kF * (a.ref_f64 ? 8 : 4)
+                                    : a.ref;
+                double lf[kF], rf[kF];
+                otw_live_frame(e, p.x, lf);
+                otw_ref_frame(e, p.y, rf);
+                cost = cell_cost(lf, rf, a.euclid);
+            }
+        }
+        cost_s[k] = cost;
+        if (a.costs) a.costs[(size_t)b * a.K + k] = cost;
+    }
+    __syncthreads();
+    if (k == 0) {
+        double sum = 0.0;
+        for (int i = 0; i < n; i++) sum = sum + cost_s[i];
+        a.mean[b] = n > 0 ? sum / (double)n : qnan;
+        a.n_out[b] = n;
+        __threadfence_system();
+    }
+}
+
 }  // namespace rts
 
 // ------------------------------------------------------------------------------------------------
@@ -2712,6 +2792,59 @@ int rts_otw_push(rts_otw *h, const void *frames_dev, int frames_dtype, int n_max
                        frames_dtype == RTS_F64, n_new_dev, n_max, n_max, h->B, h->hist_stride);
     RTS_HIP(hipGetLastError());
     return launch(h, hist_args(h), s);
+}
+
+// rts_otw_recent / rts_otw_path_cost read the handle-owned history: frames of an rts_otw_run are the caller's memory.
+static int refuse_run_frames(const rts_otw *h, const char *what) {
+    if (h->src_kind == 1 || h->src_kind == 3)
+        return rts::set_error(RTS_ERR_UNSUPPORTED, "%s: the handle has consumed an rts_otw_run since its last reset, whose frames "
+                                                   "are the caller's memory and not in the handle's history", what);
+    return RTS_OK;
+}
+
+int rts_otw_recent(rts_otw *h, int M_max, double *out_dev, int32_t *len_dev, const uint8_t *mask_dev, void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!out_dev) return set_error(RTS_ERR_INVALID, "out_dev is NULL");
+    if (!len_dev) return set_error(RTS_ERR_INVALID, "len_dev is NULL");
+    if (M_max < 1) return set_error(RTS_ERR_INVALID, "M_max must be >= 1 (got %d)", M_max);
+    if (M_max > 256) return set_error(RTS_ERR_UNSUPPORTED, "M_max = %d exceeds the 256 frames rts_locate takes", M_max);
+    if (int rc = refuse_run_frames(h, "rts_otw_recent"); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    hipLaunchKernelGGL(otw_recent_kernel, dim3(h->B), dim3(256), 0, (hipStream_t)stream, h->hist, h->hist_len, h->hist_stride,
+                       h->N, h->refs.len, M_max, out_dev, len_dev, mask_dev);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+
+int rts_otw_path_cost(rts_otw *h, int K, double *mean_dev, int32_t *n_dev, double *costs_dev, void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!mean_dev) return set_error(RTS_ERR_INVALID, "mean_dev is NULL");
+    if (!n_dev) return set_error(RTS_ERR_INVALID, "n_dev is NULL");
+    if (K < 1 || K > 256) return set_error(RTS_ERR_INVALID, "K must be in [1, 256] (got %d)", K);
+    if (int rc = refuse_run_frames(h, "rts_otw_path_cost"); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    PathCostArgs a;
+    a.state = h->state;
+    a.path = h->path;
+    a.hist_len = h->hist_len;
+    a.hist = h->hist;
+    a.ref = h->ref;
+    a.ref_first = h->refs.first;
+    a.ref_len = h->refs.len;
+    a.N = h->N;
+    a.path_cap = h->path_cap;
+    a.hist_stride = h->hist_stride;
+    a.ref_f64 = h->ref_dtype == RTS_F64;
+    a.euclid = h->cost_kind == RTS_COST_EUCLID;
+    a.K = K;
+    a.mean = mean_dev;
+    a.costs = costs_dev;
+    a.n_out = n_dev;
+    hipLaunchKernelGGL(otw_path_cost_kernel, dim3(h->B), dim3(64 * ((K + 63) / 64)), 0, (hipStream_t)stream, a);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
 }
 
 int rts_otw_read_states(rts_otw *h, int32_t *states, void *stream) {

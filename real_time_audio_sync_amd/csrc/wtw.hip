@@ -960,6 +960,25 @@ __global__ void __launch_bounds__(256) wtw_restart_kernel(RestartSel sel, int32_
     }
 }
 
+// rts_wtw_recent: the last min(M_max, n) columns of stream b's live chroma history into out[b], zeros behind them; one
+// workgroup per stream.  n is the appended count capped at the stream's own capacity 2 M_b (the count reads past the
+// history stride when a column was dropped).  Nothing the tracker owns is written.
+__global__ void __launch_bounds__(256) wtw_recent_kernel(const double *live, const int32_t *appended, int live_stride, int M,
+                                                         const int32_t *ref_len, int M_max, double *out, int32_t *len_out,
+                                                         const uint8_t *mask) {
+    const int b = blockIdx.x;
+    const int cap = 2 * (ref_len ? ref_len[b] : M);
+    int n = appended[b];
+    n = n < 0 ? 0 : n;
+    n = n > cap ? cap : n;
+    n = n > live_stride ? live_stride : n;
+    const int len = (mask && !mask[b]) ? 0 : (n < M_max ? n : M_max);
+    const long long src0 = ((long long)b * live_stride + (n - len)) * kWF;
+    double *dst = out + (size_t)b * M_max * kWF;
+    for (int idx = threadIdx.x; idx < M_max * kWF; idx += blockDim.x) dst[idx] = idx < len * kWF ? live[src0 + idx] : 0.0;
+    if (threadIdx.x == 0) len_out[b] = len;
+}
+
 }  // namespace rts
 
 struct rts_wtw {
@@ -1186,6 +1205,20 @@ int rts_wtw_restart(rts_wtw *h, const uint8_t *mask_host, const long long *first
                            (long long)h->live_stride * kWF, h->ctl, h->ticket, h->refs.first, h->refs.len);
         RTS_HIP(hipGetLastError());
     }
+    return RTS_OK;
+}
+
+int rts_wtw_recent(rts_wtw *h, int M_max, double *out_dev, int32_t *len_dev, const uint8_t *mask_dev, void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!out_dev) return set_error(RTS_ERR_INVALID, "out_dev is NULL");
+    if (!len_dev) return set_error(RTS_ERR_INVALID, "len_dev is NULL");
+    if (M_max < 1) return set_error(RTS_ERR_INVALID, "M_max must be >= 1 (got %d)", M_max);
+    if (M_max > 256) return set_error(RTS_ERR_UNSUPPORTED, "M_max = %d exceeds the 256 frames rts_locate takes", M_max);
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    hipLaunchKernelGGL(wtw_recent_kernel, dim3(h->B), dim3(256), 0, (hipStream_t)stream, h->live, h->appended, h->live_stride,
+                       h->M, h->refs.len, M_max, out_dev, len_dev, mask_dev);
+    RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
 

@@ -213,11 +213,16 @@ class LiveSession(object):
         is dropped too: the first chroma column of the new run only becomes the new carry.  ``refs``: one entry per listed stream, each an object given
         at create (``ref_chroma`` list / ``extra_refs``, matched by identity); ``offsets``: first frame inside the
         piece; without ``refs``, "same piece, from this frame"."""
-        eng = self.otw or self.wtw
         if refs is not None:
             if self._conv is None or any(id(r) not in self._conv for r in refs):
                 raise ValueError("a reference to restart on must have been given at create (ref_chroma list / extra_refs)")
             refs = [self._conv[id(r)][1] for r in refs]
+        self._restart_known(streams, refs, offsets)
+
+    @nat.on_device
+    def _restart_known(self, streams, refs=None, offsets=None):
+        """``restart`` with the references named as the bound tracker knows them."""
+        eng = self.otw or self.wtw
         mask, first, lens, pieces = eng._restart_tables(streams, refs, offsets)
         nat.check(nat.lib.rts_live_restart(self._h, mask.ctypes.data, first.ctypes.data if first is not None else None,
                                            lens.ctypes.data if lens is not None else None, self._stream()))
@@ -234,6 +239,54 @@ class LiveSession(object):
         found = (self.otw or self.wtw).locate(queries, q_len, euclid)
         given = {id(conv): obj for obj, conv in self._conv.values()}
         return [[(given[id(r)], s, e, c) for r, s, e, c in entries] for entries in found]
+
+    def _given(self, entry):
+        """A ``(ref, start, end, cost)`` of the bound tracker with the piece named by the object given at create."""
+        given = {id(conv): obj for obj, conv in self._conv.values()}
+        return (given[id(entry[0])],) + tuple(entry[1:])
+
+    def locate_recent(self, M=128, streams=None, euclid=None):
+        """``locate`` on the last ``M`` columns every stream (or the listed ones) handed to its tracker, taken from the
+        tracker's own history on the device (``recent`` of the bound tracker): no column is collected on the host.  Same
+        return value as ``locate``; streams not listed get ``[]``."""
+        if self._conv is None:
+            raise ValueError("locate needs per-stream references (a list as ref_chroma)")
+        found = (self.otw or self.wtw).locate_recent(M, streams, euclid)
+        return [[self._given(e) for e in entries] for entries in found]
+
+    def reacquire(self, streams, M=128):
+        """This microphone is lost: put it where it really is (``BatchedOTW.reacquire`` / ``BatchedWTW.reacquire`` of the
+        bound tracker, the pieces named by the objects given at create).  The restart goes through ``restart``: the
+        listed streams' pending samples -- and with ``features='chroma_diff'`` their carried chroma column -- are
+        dropped as documented there; the excerpt is then pushed into the bound tracker directly, so the position words
+        ``poll()`` shows for these streams are those of a fresh stream until the next feed publishes the caught-up
+        ones, and ``confidence()`` reads n = 0 until then.  Returns ``{b: (ref, start, end, cost) | None}``."""
+        if self._conv is None:
+            raise ValueError("reacquire needs per-stream references (a list as ref_chroma)")
+        eng = self.otw or self.wtw
+        out = eng._reacquire(streams, M, self._restart_known)
+        return {b: (self._given(e) if e is not None else None) for b, e in out.items()}
+
+    @nat.on_device
+    def watch(self, K):
+        """Tracking confidence with every feed (rts_live_watch): K = 1..256 path points per stream, 0 = off (the
+        default).  With watch on, each feed enqueues one more small launch, ``BatchedOTW.path_cost(K)`` of the bound
+        tracker published into host-mapped memory; ``confidence()`` reads it.  OTW family only."""
+        nat.check(nat.lib.rts_live_watch(self._h, int(K)))
+        if getattr(self, "_conf_mean", None) is None:
+            self._conf_mean = np.zeros(self.B, dtype=np.float64)
+            self._conf_n = np.zeros(self.B, dtype=np.int32)
+
+    def confidence(self):
+        """Non-blocking: {'mean' float64 [B], 'n' int32 [B], 'feeds_done'} as last published by the device: the mean
+        cell cost over the last ``n`` path points of every stream (NaN with n = 0: no path point yet, or just
+        restarted) -- ``BatchedOTW.path_cost`` as of feed ``feeds_done`` or later.  Needs ``watch(K)`` first.  No
+        threshold is applied: compare with ``cost / (M + end - start + 1)`` of a ``locate_recent`` entry."""
+        done = ctypes.c_int()
+        mean = getattr(self, "_conf_mean", None)
+        nat.check(nat.lib.rts_live_confidence(self._h, mean.ctypes.data if mean is not None else None,
+                                              self._conf_n.ctypes.data if mean is not None else None, ctypes.byref(done)))
+        return dict(mean=self._conf_mean.copy(), n=self._conf_n.copy(), feeds_done=done.value)
 
     def path(self, b=0):
         return (self.otw or self.wtw).path(b)

@@ -163,6 +163,22 @@ class BatchedOTW(_BatchedHandle):
 
     # ---- results ------------------------------------------------------------------------------
     @_on_device
+    def path_cost(self, K=64, want_costs=False):
+        """Tracking confidence (rts_otw_path_cost): the tracker's own cell cost at the last ``n = min(K, path points)``
+        points of every stream's path.  Device tensors ``(mean float64 [B], n int32 [B])``, with ``want_costs`` also
+        ``costs float64 [B][K]`` (NaN behind the n-th).  ``mean`` is NaN for a stream without a path point, and for one
+        that heard a silent (NaN) column among those points.  It is in the unit of ``locate``'s normalised cost,
+        ``cost / (M + end - start + 1)``; what value means "lost" depends on the features and the room.  At most 256
+        points; not after ``run`` (those frames are the caller's).  Asynchronous, nothing is read back."""
+        K = int(K)
+        mean = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        n = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        costs = torch.empty((self.B, max(K, 0)), dtype=torch.float64, device=self.device) if want_costs else None
+        nat.check(nat.lib.rts_otw_path_cost(self._h, K, mean.data_ptr(), n.data_ptr(),
+                                            costs.data_ptr() if want_costs else None, self._stream()))
+        return (mean, n, costs) if want_costs else (mean, n)
+
+    @_on_device
     def states(self):
         out = np.zeros((self.B, nat.STATE_LEN), dtype=np.int32)
         nat.check(nat.lib.rts_otw_read_states(self._h, out.ctypes.data, self._stream()))
