@@ -260,6 +260,36 @@ int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_de
             int8_t *back_dev, int32_t *path_dev, int32_t *path_len_dev, void *ws_dev, size_t ws_bytes,
             void *stream);
 
+/* Bytes of the device workspace rts_dtw_paths needs for B pairs of at most M_max x N_max: per-pair slices sized by the
+ * maxima (2-bit step codes, boundary rows, entry columns, column records: about 0.45 bytes per cell), no [M][N] array
+ * of 8-byte elements. */
+int rts_dtw_paths_workspace_bytes(int M_max, int N_max, int B, size_t *bytes);
+
+/* dtw.DTW (dtw.py:5-53) for callers who want the alignment path and its total cost and never read the matrices, over
+ * pairs of different lengths in one call: what the reference's corpus harness does one pair at a time (tests.py:199-262,
+ * test_all(..., DTW) -> test_dtw(wav_ref, wav_live), every recording of a piece against every other).  Neither cost nor
+ * acc_cost is written anywhere, so a 30-minute pair (19 380 x 19 380) needs about 165 MB instead of 6 GB.
+ *   a_dev: [B][M_max][F] padded frames of the seq_a's, `a_stride` = frames between consecutive pairs (0 = every pair
+ *          shares one a; otherwise >= M_max); a_len_dev: int32[B] DEVICE array, pair k uses frames [0, a_len_dev[k]);
+ *          NULL = M_max for every pair, values above M_max are clamped to it (the convention of rts_locate's
+ *          q_len_dev).  b_dev / b_stride / b_len_dev likewise with N_max.  Frames beyond a pair's length are not read.
+ *   Pair k, with M_k x N_k its own lengths, gets exactly what rts_dtw gives for (M_k, N_k) -- same recurrence, same
+ *          first-minimum rule, same backtrack (dtw.py:32-52):
+ *   path_dev: int32 [B][M_max + N_max][2]; the first path_len_dev[k] rows of pair k are the pairs (i, j) from (0, 0) to
+ *          (M_k - 1, N_k - 1); the rows behind them are left untouched.
+ *   path_len_dev: int32 [B]; total_dev: double [B], acc_cost[M_k - 1][N_k - 1] bit for bit.
+ *   A pair with M_k < 1 or N_k < 1 gets path_len = 0 and total = +inf; nothing of it is read.
+ *   If the device pipeline reports a fault (as in rts_dtw), path_len = -1 and total = NaN for the call's pairs.
+ *   ws_dev / ws_bytes: caller-owned, 16-byte aligned scratch of at least rts_dtw_paths_workspace_bytes(M_max, N_max, B).
+ * Limits and errors as rts_dtw: F == 12 (RTS_ERR_UNSUPPORTED otherwise), M_max, N_max, B >= 1, B <= 65535, the same
+ * bound on M_max * N_max; RTS_ERR_INVALID names the argument (a NULL a_dev, b_dev, path_dev, path_len_dev, total_dev or
+ * ws_dev, a stride between 1 and the maximum, a short or misaligned workspace).
+ * Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable). */
+int rts_dtw_paths(const void *a_dev, int a_dtype, long long a_stride, const int32_t *a_len_dev, const void *b_dev,
+                  int b_dtype, long long b_stride, const int32_t *b_len_dev, int F, int M_max, int N_max, int B,
+                  int32_t *path_dev, int32_t *path_len_dev, double *total_dev, void *ws_dev, size_t ws_bytes,
+                  void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Locate: subsequence DTW of B live excerpts against P pieces of a reference pool.
  * ------------------------------------------------------------------------------------------ */

@@ -11,6 +11,10 @@
 //   dtw_hops_kernel /     dtw.py:43-52 over the packed step codes: the columns at which the path crosses the strip
 //   dtw_segment_kernel    boundaries (one dependent load per strip), then every strip's segment walked by its own wave.
 //   dtw_back_decode_kernel optional: the reference's `back` matrix as int8 [M][N].
+//
+// rts_dtw_paths is the same pipeline without the dense outputs: no dtw_cost_kernel, the strip DP without staging
+// (nothing but step codes, boundary rows and entry columns leaves the chip), and every pair with lengths of its own
+// (pair_dims) inside a workspace slice sized by the call's maxima.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -41,7 +45,31 @@ struct DtwArgs {
     int32_t *err;
     int32_t *ticket;           // [B] next row group of each pair (sdp::for_each_rowgroup)
     int n_rg, n_strips_wg;
+    // rts_dtw_paths only (NULL in rts_dtw): M and N above are then the maxima that size every pair's slices
+    const int32_t *a_len, *b_len;  // [B] the pairs' own lengths (NULL = the maximum)
+    double *total;                 // [B] acc_cost[M_k-1][N_k-1]
 };
+
+// The pair's own M and N: the maximum without a length table, and never more than it.  Everything a pair keeps in the
+// workspace is indexed with its own N inside its slice (the DP and the backtrack both get it from here).
+__device__ __forceinline__ void pair_dims(const DtwArgs &g, int pair, int &M, int &N) {
+    M = g.M;
+    N = g.N;
+    if (g.a_len) M = min(g.a_len[pair], g.M);
+    if (g.b_len) N = min(g.b_len[pair], g.N);
+}
+
+// What path_len / total say beyond the path itself: the fault contract, and a pair without cells.  One thread, after
+// the pair's backtrack.
+__device__ __forceinline__ void dtw_report(const DtwArgs &g, int pair, bool has_cells) {
+    if (*g.err != 0) {
+        g.path_len[pair] = -1;
+        if (g.total) g.total[pair] = __longlong_as_double(0x7ff8000000000000LL);  // NaN
+    } else if (!has_cells) {
+        g.path_len[pair] = 0;
+        if (g.total) g.total[pair] = __longlong_as_double(0x7ff0000000000000LL);  // +inf
+    }
+}
 
 // One thread per column j and kCostRows consecutive rows: b_j stays in registers, the a rows are wave-uniform
 // (broadcast) loads, every store instruction writes 512 contiguous bytes of one row.
@@ -71,40 +99,56 @@ __global__ void __launch_bounds__(256) dtw_cost_kernel(DtwArgs g) {
 __global__ void __launch_bounds__(256) dtw_prep_kernel(DtwArgs g) {
     const int pair = blockIdx.y;
     const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= g.N) return;
+    int M, N;
+    pair_dims(g, pair, M, N);
+    if (j >= N || M < 1) return;
     const void *b = g.b_f64 ? (const void *)(reinterpret_cast<const double *>(g.b) + (long long)pair * g.b_stride * kDtwF)
                             : (const void *)(reinterpret_cast<const float *>(g.b) + (long long)pair * g.b_stride * kDtwF);
     sdp::prep_column<sdp::DtwPolicy>(b, g.b_f64, j, g.yrec + (size_t)pair * g.N * sdp::kYRec);
 }
 
 // H helper waves per strip.  <2>: two strips per workgroup (6 waves); <3>: one strip per workgroup (4 waves, the DP wave
-// has a SIMD to itself) -- see sdp::pick_config.
-template <int H>
+// has a SIMD to itself) -- see sdp::pick_config.  STAGE: acc_cost goes to HBM (rts_dtw); without it (rts_dtw_paths) the
+// pair has its own lengths and row-group count, and its final cost goes to total[pair].
+template <int H, bool STAGE>
 __global__ void __launch_bounds__(H == 2 ? 384 : 256) dtw_sdp_kernel(DtwArgs g) {
     extern __shared__ __align__(16) unsigned char dtw_smem[];
     const int pair = blockIdx.y;
+    // rts_dtw: every pair is M x N.  rts_dtw_paths: the pair's own lengths and, from them, its own row-group count
+    // -- the grid is sized for the longest pair, and the workgroups beyond a shorter one's row groups leave at their
+    // first ticket.
+    int M = g.M, N = g.N, n_rg = g.n_rg;
+    if constexpr (!STAGE) {
+        pair_dims(g, pair, M, N);
+        if (M < 1 || N < 1) return;  // the whole workgroup: nothing of such a pair is read
+        n_rg = (sdp::n_strips(M) + g.n_strips_wg - 1) / g.n_strips_wg;
+    }
     sdp::Problem pb;
     pb.x = g.a_f64 ? (const void *)(reinterpret_cast<const double *>(g.a) + (long long)pair * g.a_stride * kDtwF)
                    : (const void *)(reinterpret_cast<const float *>(g.a) + (long long)pair * g.a_stride * kDtwF);
     pb.x_f64 = g.a_f64;
     pb.yrec = g.yrec + (size_t)pair * g.N * sdp::kYRec;
-    pb.M = g.M;
-    pb.N = g.N;
-    pb.D = g.acc + (size_t)pair * g.M * g.N;
+    pb.M = M;
+    pb.N = N;
+    pb.D = STAGE ? g.acc + (size_t)pair * g.M * g.N : nullptr;
     pb.ldD = g.N;
     pb.codes = g.codes + (size_t)pair * sdp::codes_words(g.M, g.N);
     pb.bnd = g.bnd + (size_t)pair * sdp::n_strips(g.M) * g.N;
     pb.entb = g.entb + (size_t)pair * sdp::n_strips(g.M) * g.N;
     pb.err = g.err;
-    sdp::for_each_rowgroup(g.ticket + pair, g.n_rg, g.n_strips_wg, dtw_smem, [&](int rg) {
-        sdp::run_rowgroup<sdp::DtwPolicy, true, H>(pb, rg, g.n_rg, g.n_strips_wg, dtw_smem);
+    pb.last = STAGE ? nullptr : g.total + pair;
+    sdp::for_each_rowgroup(g.ticket + pair, n_rg, g.n_strips_wg, dtw_smem, [&](int rg) {
+        sdp::run_rowgroup<sdp::DtwPolicy, STAGE, H>(pb, rg, n_rg, g.n_strips_wg, dtw_smem);
     });
 }
 
 __global__ void __launch_bounds__(64) dtw_hops_kernel(DtwArgs g) {
     __shared__ uint32_t win[2 * sdp::kBtChunks * 64];
     const int pair = blockIdx.x, S = sdp::n_strips(g.M);
-    sdp::path_hops(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), g.entb + (size_t)pair * S * g.N, g.M, g.N,
+    int M, N;
+    pair_dims(g, pair, M, N);
+    if (M < 1 || N < 1) return;
+    sdp::path_hops(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), g.entb + (size_t)pair * S * g.N, M, N,
                    g.cross + (size_t)pair * S, win);
 }
 
@@ -113,22 +157,33 @@ __global__ void __launch_bounds__(64) dtw_segment_kernel(DtwArgs g) {
     __shared__ uint32_t win[2 * sdp::kBtChunks * 64];
     const int pair = blockIdx.y, s = blockIdx.x, S = sdp::n_strips(g.M);
     int32_t *path = g.path + (size_t)pair * (g.M + g.N) * 2;
-    sdp::path_segment(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), g.M, g.N, s, g.cross + (size_t)pair * S,
-                      g.lens + (size_t)pair * S, PASS, path, g.path_len + pair, win,
-                      g.pscr + (size_t)pair * 2 * sdp::scratch_pairs(g.M, g.N));
-    if (PASS == 1 && s == 0 && threadIdx.x == 0 && *g.err != 0) g.path_len[pair] = -1;
+    int M, N;
+    pair_dims(g, pair, M, N);
+    const bool has_cells = (M >= 1 && N >= 1);
+    // the grid has a workgroup per strip of the longest pair: the ones beyond this pair's strips touch nothing
+    if (has_cells && s < sdp::n_strips(M))
+        sdp::path_segment(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), M, N, s, g.cross + (size_t)pair * S,
+                          g.lens + (size_t)pair * S, PASS, path, g.path_len + pair, win,
+                          g.pscr + (size_t)pair * 2 * sdp::scratch_pairs(g.M, g.N));
+    if (PASS == 1 && s == 0 && threadIdx.x == 0) dtw_report(g, pair, has_cells);
 }
 
 // hops + both segment passes of a short pair in one launch (at most sdp::kTailStrips strips: one wave each)
 __global__ void __launch_bounds__(64 * sdp::kTailStrips) dtw_tail_kernel(DtwArgs g) {
     extern __shared__ __align__(16) unsigned char dtw_smem[];
     const int pair = blockIdx.x, S = sdp::n_strips(g.M);
-    sdp::path_tail(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), g.entb + (size_t)pair * S * g.N, g.M, g.N,
-                   g.cross + (size_t)pair * S, g.lens + (size_t)pair * S, g.path + (size_t)pair * (g.M + g.N) * 2,
-                   g.path_len + pair, reinterpret_cast<uint32_t *>(dtw_smem),
-                   g.pscr + (size_t)pair * 2 * sdp::scratch_pairs(g.M, g.N));
+    int M, N;
+    pair_dims(g, pair, M, N);
+    const bool has_cells = (M >= 1 && N >= 1);  // uniform over the workgroup
+    // one wave per strip of the longest pair: the waves beyond this pair's strips go through path_tail's barriers and
+    // write nothing
+    if (has_cells)
+        sdp::path_tail(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), g.entb + (size_t)pair * S * g.N, M, N,
+                       g.cross + (size_t)pair * S, g.lens + (size_t)pair * S, g.path + (size_t)pair * (g.M + g.N) * 2,
+                       g.path_len + pair, reinterpret_cast<uint32_t *>(dtw_smem),
+                       g.pscr + (size_t)pair * 2 * sdp::scratch_pairs(g.M, g.N));
     __syncthreads();
-    if (threadIdx.x == 0 && *g.err != 0) g.path_len[pair] = -1;
+    if (threadIdx.x == 0) dtw_report(g, pair, has_cells);
 }
 
 __global__ void __launch_bounds__(256) dtw_back_decode_kernel(DtwArgs g) {
@@ -143,8 +198,9 @@ __global__ void __launch_bounds__(256) dtw_back_decode_kernel(DtwArgs g) {
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// Workgroups of dtw_sdp_kernel<3> (one strip each) / <2> (two strips each) the current device holds at once;
-// queried once per device and LDS padding (sdp::pick_config, "Residency").
+// Workgroups of dtw_sdp_kernel<3, STAGE> (one strip each) / <2, STAGE> (two strips each) the current device holds at
+// once; queried once per device and LDS padding (sdp::pick_config, "Residency").
+template <bool STAGE>
 static int dtw_residency(int &r1, int &r2) {
     static int cache[16][3];  // [device]: pad + 1, r1, r2
     int dev = 0;
@@ -156,10 +212,10 @@ static int dtw_residency(int &r1, int &r2) {
         r2 = c[2];
         return RTS_OK;
     }
-    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dtw_sdp_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dtw_sdp_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    r1 = sdp::resident_blocks(dtw_sdp_kernel<3>, 256, sdp::lds_bytes(1) + pad);
-    r2 = sdp::resident_blocks(dtw_sdp_kernel<2>, 384, sdp::lds_bytes(2) + pad);
+    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dtw_sdp_kernel<2, STAGE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dtw_sdp_kernel<3, STAGE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    r1 = sdp::resident_blocks(dtw_sdp_kernel<3, STAGE>, 256, sdp::lds_bytes(1) + pad);
+    r2 = sdp::resident_blocks(dtw_sdp_kernel<2, STAGE>, 384, sdp::lds_bytes(2) + pad);
     if (c) {
         c[1] = r1;
         c[2] = r2;
@@ -168,14 +224,10 @@ static int dtw_residency(int &r1, int &r2) {
     return RTS_OK;
 }
 
-}  // namespace rts
-
-extern "C" {
-
-int rts_dtw_workspace_bytes(int M, int N, int B, size_t *bytes) {
-    using namespace rts;
+// The one workspace formula behind rts_dtw_workspace_bytes and rts_dtw_paths_workspace_bytes (dtw_enqueue carves it).
+static int dtw_workspace(int M, int N, int B, size_t *bytes, const char *m_name, const char *n_name) {
     if (!bytes) return set_error(RTS_ERR_INVALID, "bytes is NULL");
-    if (M < 1 || N < 1 || B < 1) return set_error(RTS_ERR_INVALID, "M, N, B must be >= 1");
+    if (M < 1 || N < 1 || B < 1) return set_error(RTS_ERR_INVALID, "%s, %s, B must be >= 1", m_name, n_name);
     const size_t strips = (size_t)B * sdp::n_strips(M);
     *bytes = 256 + align256(sizeof(unsigned long long) * strips * N) + align256(sizeof(int32_t) * strips * N) +
              2 * align256(sizeof(int32_t) * strips) + align256(sizeof(double) * (size_t)B * N * sdp::kYRec) +
@@ -184,47 +236,38 @@ int rts_dtw_workspace_bytes(int M, int N, int B, size_t *bytes) {
     return RTS_OK;
 }
 
-int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_dev, int b_dtype,
-            long long b_stride, int F, int M, int N, int B, double *cost_dev, double *acc_dev,
-            int8_t *back_dev, int32_t *path_dev, int32_t *path_len_dev, void *ws_dev, size_t ws_bytes,
-            void *stream) {
-    using namespace rts;
-    if (!a_dev || !b_dev || !cost_dev || !acc_dev || !path_dev || !path_len_dev || !ws_dev)
-        return set_error(RTS_ERR_INVALID, "NULL device buffer");
+// The argument checks rts_dtw and rts_dtw_paths share (M, N: the call's maxima), workspace included: `ws_size` is the
+// caller's own rts_*_workspace_bytes, `ws_fn` its name for the message.
+static int dtw_check(int a_dtype, int b_dtype, int F, int M, int N, int B, const void *ws_dev, size_t ws_bytes,
+                     const char *m_name, const char *n_name, int (*ws_size)(int, int, int, size_t *), const char *ws_fn) {
     if (F != kDtwF) return set_error(RTS_ERR_UNSUPPORTED, "F must be 12 chroma bins (got %d)", F);
-    if (M < 1 || N < 1 || B < 1) return set_error(RTS_ERR_INVALID, "M, N, B must be >= 1 (got %d %d %d)", M, N, B);
+    if (M < 1 || N < 1 || B < 1)
+        return set_error(RTS_ERR_INVALID, "%s, %s, B must be >= 1 (got %d %d %d)", m_name, n_name, M, N, B);
     if ((a_dtype != RTS_F32 && a_dtype != RTS_F64) || (b_dtype != RTS_F32 && b_dtype != RTS_F64))
         return set_error(RTS_ERR_INVALID, "bad dtype");
-    if ((long long)M * N > 0x7fffffffLL * 4) return set_error(RTS_ERR_INVALID, "M*N too large");
+    if ((long long)M * N > 0x7fffffffLL * 4) return set_error(RTS_ERR_INVALID, "%s*%s too large", m_name, n_name);
     if (B > 65535) return set_error(RTS_ERR_INVALID, "at most 65535 pairs per call");
     size_t need = 0;
-    rts_dtw_workspace_bytes(M, N, B, &need);
+    ws_size(M, N, B, &need);
     if (ws_bytes < need)
-        return set_error(RTS_ERR_INVALID, "workspace of %zu bytes is smaller than rts_dtw_workspace_bytes = %zu", ws_bytes, need);
+        return set_error(RTS_ERR_INVALID, "workspace of %zu bytes is smaller than %s = %zu", ws_bytes, ws_fn, need);
     if (((uintptr_t)ws_dev & 15) != 0) return set_error(RTS_ERR_INVALID, "workspace must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
+    return RTS_OK;
+}
+
+// Carves the workspace and enqueues the pipeline; `g` arrives with the caller's buffers, sizes and dtypes filled in.
+// DENSE: rts_dtw (cost and acc_cost are written); otherwise rts_dtw_paths.
+template <bool DENSE>
+static int dtw_enqueue(DtwArgs g, int B, void *ws_dev, hipStream_t s) {
+    const int M = g.M, N = g.N;
     const int strips = sdp::n_strips(M);
     int NS, H, G, res1 = 0, res2 = 0;
-    if (int rc = dtw_residency(res1, res2); rc != RTS_OK) return rc;
+    if (int rc = dtw_residency<DENSE>(res1, res2); rc != RTS_OK) return rc;
     if (res1 < 1 && res2 < 1)
         return set_error(RTS_ERR_HIP, "the occupancy query reports no resident workgroup for the strip-DP kernel on this device");
     sdp::pick_config(strips, B, res1, res2, NS, H, G);
     const int n_rg = (strips + NS - 1) / NS;
     unsigned char *ws = reinterpret_cast<unsigned char *>(ws_dev);
-    DtwArgs g;
-    g.a = a_dev;
-    g.b = b_dev;
-    g.cost = cost_dev;
-    g.acc = acc_dev;
-    g.back = back_dev;
-    g.path = path_dev;
-    g.path_len = path_len_dev;
-    g.a_stride = a_stride;
-    g.b_stride = b_stride;
-    g.M = M;
-    g.N = N;
-    g.a_f64 = a_dtype == RTS_F64;
-    g.b_f64 = b_dtype == RTS_F64;
     g.err = reinterpret_cast<int32_t *>(ws);
     {
         unsigned char *p = ws + 256;
@@ -248,8 +291,9 @@ int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_de
     g.n_strips_wg = NS;
     RTS_HIP(hipMemsetAsync(g.err, 0, 16, s));
     RTS_HIP(hipMemsetAsync(g.ticket, 0, sizeof(int32_t) * (size_t)B, s));
+    // (n_rg is the longest pair's: with per-pair lengths, whenever any pair can have more than one row group)
     if (n_rg > 1) RTS_HIP(hipMemsetD32Async((hipDeviceptr_t)g.bnd, (int)sdp::kSentinel32, (size_t)2 * B * strips * N, s));
-    {
+    if (DENSE) {
         const dim3 grid((N + 255) / 256, (M + kCostRows - 1) / kCostRows, B);
         if (g.a_f64 && g.b_f64)
             hipLaunchKernelGGL((dtw_cost_kernel<true, true>), grid, dim3(256), 0, s, g);
@@ -259,14 +303,14 @@ int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_de
             hipLaunchKernelGGL((dtw_cost_kernel<false, true>), grid, dim3(256), 0, s, g);
         else
             hipLaunchKernelGGL((dtw_cost_kernel<false, false>), grid, dim3(256), 0, s, g);
+        RTS_HIP(hipGetLastError());
     }
-    RTS_HIP(hipGetLastError());
     hipLaunchKernelGGL(dtw_prep_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, g);
     const size_t smem = sdp::lds_bytes(NS) + sdp::lds_pad();
     if (H == 2)
-        hipLaunchKernelGGL((dtw_sdp_kernel<2>), dim3(G, B), dim3(64 * NS * 3), smem, s, g);
+        hipLaunchKernelGGL((dtw_sdp_kernel<2, DENSE>), dim3(G, B), dim3(64 * NS * 3), smem, s, g);
     else
-        hipLaunchKernelGGL((dtw_sdp_kernel<3>), dim3(G, B), dim3(64 * NS * 4), smem, s, g);
+        hipLaunchKernelGGL((dtw_sdp_kernel<3, DENSE>), dim3(G, B), dim3(64 * NS * 4), smem, s, g);
     RTS_HIP(hipGetLastError());
     if (strips <= sdp::kTailStrips) {
         hipLaunchKernelGGL(dtw_tail_kernel, dim3(B), dim3(64 * strips), sdp::tail_lds_bytes(strips), s, g);
@@ -276,11 +320,94 @@ int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_de
         hipLaunchKernelGGL((dtw_segment_kernel<1>), dim3(strips, B), dim3(64), 0, s, g);
     }
     RTS_HIP(hipGetLastError());
-    if (back_dev) {
+    if (g.back) {
         hipLaunchKernelGGL(dtw_back_decode_kernel, dim3((N + 255) / 256, M, B), dim3(256), 0, s, g);
         RTS_HIP(hipGetLastError());
     }
     return RTS_OK;
+}
+
+}  // namespace rts
+
+extern "C" {
+
+int rts_dtw_workspace_bytes(int M, int N, int B, size_t *bytes) {
+    return rts::dtw_workspace(M, N, B, bytes, "M", "N");
+}
+
+int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_dev, int b_dtype,
+            long long b_stride, int F, int M, int N, int B, double *cost_dev, double *acc_dev,
+            int8_t *back_dev, int32_t *path_dev, int32_t *path_len_dev, void *ws_dev, size_t ws_bytes,
+            void *stream) {
+    using namespace rts;
+    if (!a_dev || !b_dev || !cost_dev || !acc_dev || !path_dev || !path_len_dev || !ws_dev)
+        return set_error(RTS_ERR_INVALID, "NULL device buffer");
+    if (int rc = dtw_check(a_dtype, b_dtype, F, M, N, B, ws_dev, ws_bytes, "M", "N", rts_dtw_workspace_bytes,
+                           "rts_dtw_workspace_bytes");
+        rc != RTS_OK)
+        return rc;
+    DtwArgs g;
+    g.a = a_dev;
+    g.b = b_dev;
+    g.cost = cost_dev;
+    g.acc = acc_dev;
+    g.back = back_dev;
+    g.path = path_dev;
+    g.path_len = path_len_dev;
+    g.a_stride = a_stride;
+    g.b_stride = b_stride;
+    g.M = M;
+    g.N = N;
+    g.a_f64 = a_dtype == RTS_F64;
+    g.b_f64 = b_dtype == RTS_F64;
+    g.a_len = nullptr;
+    g.b_len = nullptr;
+    g.total = nullptr;
+    return dtw_enqueue<true>(g, B, ws_dev, (hipStream_t)stream);
+}
+
+// The layout is rts_dtw's, sized by the maxima: a pair's slices hold its own, smaller arrays from their start.
+int rts_dtw_paths_workspace_bytes(int M_max, int N_max, int B, size_t *bytes) {
+    return rts::dtw_workspace(M_max, N_max, B, bytes, "M_max", "N_max");
+}
+
+int rts_dtw_paths(const void *a_dev, int a_dtype, long long a_stride, const int32_t *a_len_dev, const void *b_dev,
+                  int b_dtype, long long b_stride, const int32_t *b_len_dev, int F, int M_max, int N_max, int B,
+                  int32_t *path_dev, int32_t *path_len_dev, double *total_dev, void *ws_dev, size_t ws_bytes,
+                  void *stream) {
+    using namespace rts;
+    if (!a_dev) return set_error(RTS_ERR_INVALID, "a_dev is NULL");
+    if (!b_dev) return set_error(RTS_ERR_INVALID, "b_dev is NULL");
+    if (!path_dev) return set_error(RTS_ERR_INVALID, "path_dev is NULL");
+    if (!path_len_dev) return set_error(RTS_ERR_INVALID, "path_len_dev is NULL");
+    if (!total_dev) return set_error(RTS_ERR_INVALID, "total_dev is NULL");
+    if (!ws_dev) return set_error(RTS_ERR_INVALID, "ws_dev is NULL");
+    if (int rc = dtw_check(a_dtype, b_dtype, F, M_max, N_max, B, ws_dev, ws_bytes, "M_max", "N_max",
+                           rts_dtw_paths_workspace_bytes, "rts_dtw_paths_workspace_bytes");
+        rc != RTS_OK)
+        return rc;
+    if (a_stride != 0 && a_stride < M_max)
+        return set_error(RTS_ERR_INVALID, "a_stride must be 0 (shared) or >= M_max (got %lld)", a_stride);
+    if (b_stride != 0 && b_stride < N_max)
+        return set_error(RTS_ERR_INVALID, "b_stride must be 0 (shared) or >= N_max (got %lld)", b_stride);
+    DtwArgs g;
+    g.a = a_dev;
+    g.b = b_dev;
+    g.cost = nullptr;
+    g.acc = nullptr;
+    g.back = nullptr;
+    g.path = path_dev;
+    g.path_len = path_len_dev;
+    g.a_stride = a_stride;
+    g.b_stride = b_stride;
+    g.M = M_max;
+    g.N = N_max;
+    g.a_f64 = a_dtype == RTS_F64;
+    g.b_f64 = b_dtype == RTS_F64;
+    g.a_len = a_len_dev;
+    g.b_len = b_len_dev;
+    g.total = total_dev;
+    return dtw_enqueue<false>(g, B, ws_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -127,6 +127,8 @@ struct Problem {
     int32_t *entb;         // [n_strips][N]: for every cell of a strip's bottom row, the column at which its best path
                            // entered the strip from the row above (what lets the backtrack hop strip to strip)
     int32_t *err;          // set to 1 if a poll ran into its bound (never expected)
+    double *last = nullptr;  // optional: receives the accumulated cost of cell (M-1, N-1) (with D == NULL nothing else
+                             // the host can see holds it: the last row group publishes no boundary row)
 };
 
 __device__ __forceinline__ void load_frame(const void *p, int f64, long long frame, double (&v)[kF]) {
@@ -699,6 +701,10 @@ __device__ __forceinline__ void run_rowgroup(const Problem &pb, int rg, int n_rg
 #endif
             pb.codes[((size_t)strip * nch + m) * 64 + lane] = codes;
             codes_l[(m & 1) * 64 + lane] = codes;
+            if (pb.last) {  // uniform.  Cell (M-1, N-1): lane (M-1) & 63 of the last strip, at strip-step N-1 + lane
+                const int ll = (M - 1) & 63, sl = N - 1 + ll;
+                if (strip == n_strips(M) - 1 && (sl >> 4) == m && lane == ll) *pb.last = tile_w[(sl & 15) * kStageLd];
+            }
             if (to_hbm) {  // bottom-row columns finished in this chunk: [16m - 63, 16m - 48] (my lane 63, steps 0..15)
                 const int col = kChunk * m - 63 + lane;
                 if (lane < kChunk && col >= 0 && col < N) {

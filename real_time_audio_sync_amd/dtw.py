@@ -1,5 +1,6 @@
 """Drop-in for the reference's dtw.py: ``DTW(seq_a, seq_b) -> (cost, acc_cost, path)``, plus a
-batched form over many pairs.  Computation: csrc/dtw.hip (reference: dtw.py:5-53)."""
+batched form over many pairs and a path-only form over pairs of different lengths (``dtw_paths``, ``align_pairs``).
+Computation: csrc/dtw.hip (reference: dtw.py:5-53)."""
 import ctypes
 
 import numpy as np
@@ -56,3 +57,117 @@ def DTW(seq_a, seq_b, device="cuda:0"):
     if n < 1:
         raise nat.RtsyncError("rts_dtw: the device pipeline reported a fault")
     return cost[0].cpu().numpy(), acc[0].cpu().numpy(), path[0, :n].cpu().numpy().astype(np.int64)
+
+
+def _lengths(v, B, dev, name):
+    """A per-pair length table as the C-ABI wants it: None, or a device int32 [B] tensor."""
+    if v is None:
+        return None
+    t = torch.as_tensor(v).to(device=dev, dtype=torch.int32).contiguous()
+    if t.dim() != 1 or t.shape[0] != B:
+        raise ValueError("%s must hold one length per pair (%d), got shape %s" % (name, B, tuple(t.shape)))
+    return t
+
+
+def _paths_call(a_dev, b_dev, a_len, b_len, B, path, plen, total):
+    dev = a_dev.device
+    M, N = a_dev.shape[-2], b_dev.shape[-2]
+    nbytes = ctypes.c_size_t(0)
+    nat.check(nat.lib.rts_dtw_paths_workspace_bytes(M, N, B, ctypes.byref(nbytes)))
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+    nat.check(nat.lib.rts_dtw_paths(a_dev.data_ptr(), _np_dtype_code(a_dev.dtype), 0 if a_dev.dim() == 2 else M,
+                                    a_len.data_ptr() if a_len is not None else None,
+                                    b_dev.data_ptr(), _np_dtype_code(b_dev.dtype), 0 if b_dev.dim() == 2 else N,
+                                    b_len.data_ptr() if b_len is not None else None,
+                                    12, M, N, B, path.data_ptr(), plen.data_ptr(), total.data_ptr(),
+                                    ws.data_ptr(), nbytes.value,
+                                    ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+
+def dtw_paths(a_dev, b_dev, a_len=None, b_len=None, check=False):
+    """Alignment paths and total costs only, for pairs of different lengths in one call: no cost or acc_cost matrix is
+    written or allocated (about 0.45 bytes of workspace per cell instead of 16).
+
+    a_dev: [B][M_max][12] or [M_max][12] (shared), b_dev: [B][N_max][12] or [N_max][12] (shared); device tensors,
+    float32/float64, padded.  a_len / b_len: the pairs' own lengths -- device int32 tensors or anything torch.as_tensor
+    takes; None = the maximum for every pair, larger values are clamped to it.  With both sequences shared, B is the
+    number of lengths given (1 without any).  Pair k is ``dtw_batch`` of a[k, :a_len[k]] against b[k, :b_len[k]].
+
+    Returns device tensors (path [B][M_max+N_max][2] int32, path_len [B] int32, total [B] float64): the first
+    path_len[k] rows of path[k] run from (0, 0) to (a_len[k]-1, b_len[k]-1), the rows behind them are not written;
+    total[k] is acc_cost[-1, -1].  A pair with a length < 1 has path_len 0 and total +inf.  Asynchronous.
+
+    Fault contract as ``dtw_batch``: path_len[k] == -1 (and total NaN); ``check=True`` synchronises and raises.
+
+    Errors: ValueError when a length table does not hold one length per pair (with both sequences shared that includes
+    a_len and b_len of different sizes: B is the size of a_len if given, else of b_len) or when a_dev and b_dev hold
+    different numbers of pairs.  Both sequences shared and no lengths is one pair, not an error."""
+    dev = a_dev.device
+    sa = a_dev.dim() == 2
+    sb = b_dev.dim() == 2
+    if not sa:
+        B = a_dev.shape[0]
+    elif not sb:
+        B = b_dev.shape[0]
+    else:
+        given = a_len if a_len is not None else b_len
+        B = 1 if given is None else int(torch.as_tensor(given).numel())
+    if not sa and not sb and a_dev.shape[0] != b_dev.shape[0]:
+        raise ValueError("a_dev holds %d pairs, b_dev %d" % (a_dev.shape[0], b_dev.shape[0]))
+    M, N = a_dev.shape[-2], b_dev.shape[-2]
+    a_dev, b_dev = a_dev.contiguous(), b_dev.contiguous()
+    a_len, b_len = _lengths(a_len, B, dev, "a_len"), _lengths(b_len, B, dev, "b_len")
+    path = torch.empty((B, M + N, 2), dtype=torch.int32, device=dev)
+    plen = torch.zeros((B,), dtype=torch.int32, device=dev)
+    total = torch.empty((B,), dtype=torch.float64, device=dev)
+    _paths_call(a_dev, b_dev, a_len, b_len, B, path, plen, total)
+    if check and int(plen.min().item()) < 0:
+        raise nat.RtsyncError("rts_dtw_paths: the device pipeline reported a fault (path_len = -1)")
+    return path, plen, total
+
+
+def _pad_frames(seqs, B, dtype):
+    """(12, n_k) feature-major arrays -> (host [B][n_max][12] or, for a single shared array, [n][12]; lengths or None)."""
+    if isinstance(seqs, (np.ndarray, torch.Tensor)):
+        x = torch.as_tensor(np.asarray(seqs)).to(dtype)
+        return x.t().contiguous(), None
+    if len(seqs) != B:
+        raise ValueError("align_pairs: %d sequences on one side, %d on the other" % (len(seqs), B))
+    lens = [int(np.shape(x)[1]) for x in seqs]
+    out = torch.zeros((B, max(max(lens), 1), 12), dtype=dtype)
+    for k, x in enumerate(seqs):
+        out[k, :lens[k]] = torch.as_tensor(np.asarray(x)).to(dtype).t()
+    return out, lens
+
+
+def align_pairs(seqs_a, seqs_b, device="cuda:0", dtype=torch.float64):
+    """Offline DTW of many pairs of different lengths at once, for a corpus harness (the reference's tests.py:199-262
+    aligns every recording of a piece against every other, one DTW call per pair).
+
+    seqs_a, seqs_b: lists of feature-major (12, M_k) / (12, N_k) arrays like ``DTW()`` takes; a single array on either
+    side is shared by all pairs.  Pads, uploads once, makes one ``rts_dtw_paths`` call and one read-back.
+    Returns [(path (P_k, 2) int64 ndarray, total float), ...], each path what ``DTW(seqs_a[k], seqs_b[k])[2]`` is and
+    ready for ``evaluate.AlignmentError(ref_csv, live_csv, path)``; total is acc_cost[-1, -1]."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("align_pairs needs a ROCm GPU (no CPU fallback)")
+    dev = torch.device(device)
+    a_one, b_one = isinstance(seqs_a, (np.ndarray, torch.Tensor)), isinstance(seqs_b, (np.ndarray, torch.Tensor))
+    B = 1 if (a_one and b_one) else (len(seqs_b) if a_one else len(seqs_a))
+    if B < 1:
+        return []
+    a, a_len = _pad_frames(seqs_a, B, dtype)
+    b, b_len = _pad_frames(seqs_b, B, dtype)
+    a, b = a.to(dev), b.to(dev)
+    M, N = a.shape[-2], b.shape[-2]
+    # one int32 buffer for all three outputs, so that one copy brings them back: total (as float64), path_len (padded
+    # to an even count: the path is written in 8-byte pairs), path
+    Bp = B + (B & 1)
+    out = torch.zeros((2 * B + Bp + B * (M + N) * 2,), dtype=torch.int32, device=dev)
+    total, plen, path = out[:2 * B].view(torch.float64), out[2 * B:2 * B + B], out[2 * B + Bp:].view(B, M + N, 2)
+    _paths_call(a, b, _lengths(a_len, B, dev, "a_len"), _lengths(b_len, B, dev, "b_len"), B, path, plen, total)
+    host = out.cpu().numpy()
+    total_h, plen_h = host[:2 * B].view(np.float64), host[2 * B:2 * B + B]
+    path_h = host[2 * B + Bp:].reshape(B, M + N, 2)
+    if int(plen_h.min()) < 0:
+        raise nat.RtsyncError("rts_dtw_paths: the device pipeline reported a fault")
+    return [(path_h[k, :int(plen_h[k])].astype(np.int64), float(total_h[k])) for k in range(B)]
