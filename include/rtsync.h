@@ -375,6 +375,44 @@ int rts_chroma_project(rts_chroma *h, const double *spec_dev, int n_frames, int 
 int rts_chroma_diff(const void *chroma_dev, int dtype, int n_frames, void *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Resampler: audio at any rate to the plan's rate, by a rational ratio L / M = fs_out / fs_in (reduced).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct rts_resample rts_resample;
+
+/* Replaces the resampling librosa.load does silently when a file is not at 22 050 Hz (chroma.py:27, wtw.py:23).  It is
+ * not that resampler (a third-party dependency the reference does not pin) but one this project defines to the bit.
+ * With taps h[-half .. half] (host doubles, e.g. filters.resample_taps) and input samples x[n] (float32, or PCM16 scaled
+ * by 1/32768 exactly as rts_live_* scales it; x[n] = 0 for n < 0 and past the end), output sample k is
+ *   c    = k * M + half                                                              (64-bit)
+ *   y[k] = (float) sum over n = ceil((c - 2 half) / L) .. floor(c / L) of h[c - n L - half] * (double)x[n]
+ * with n ascending, every term one float64 multiply followed by one float64 add (no fused multiply-add), and the sum
+ * rounded once to float32: the result does not depend on how the input was cut into feeds. */
+
+/* Output samples of a one-shot run over n_in input samples, ceil(n_in L / M) (chroma.py:27: len(librosa.load(path)[0])).
+ * Pure host arithmetic; 0 for n_in <= 0. */
+long long rts_resample_out_len(long long n_in, int L, int M);
+/* Output samples that exist once in_total input samples have arrived: max(0, ceil((in_total L - half) / M)), i.e. every
+ * k whose last input floor((k M + half) / L) has been seen.  They are the first samples of the one-shot result on the
+ * same input, bit for bit; the latency is half / L input samples.  Pure host arithmetic (the microphone loops of
+ * livenote_live.py:161-209 have no counterpart: PyAudio is opened at the rate they need). */
+long long rts_resample_avail(long long in_total, int L, int M, int half);
+/* The plan: the table on the current device, phase-major (librosa.load's resampling filter, chroma.py:27 / wtw.py:23; the
+ * library is filter-agnostic like rts_chroma_create).  taps_host: 2 half + 1 doubles, h[-half] first.
+ * RTS_ERR_INVALID, naming the argument, before any GPU call: NULL out or taps_host, L < 1, M < 1, gcd(L, M) != 1,
+ * half < 1.  RTS_ERR_UNSUPPORTED: 2 half + 1 > 4 194 304 taps, ceil(2 half / L) > 4096 input samples under one output,
+ * or floor((12 288 - floor(2 half / L) - 1) * L / M) < 64, the outputs whose inputs fit a workgroup's 12 288-sample
+ * window (with filters.resample_taps' 16 zero crossings both mean fs_in above about 128 fs_out). */
+int rts_resample_create(int L, int M, const double *taps_host, int half, rts_resample **out);
+int rts_resample_destroy(rts_resample *p);
+/* One-shot, ragged over B streams (librosa.load's resampling of whole files, chroma.py:27 / wtw.py:23): samples_dev is
+ * [B][sample_stride] of sample_dtype (RTS_F32 | RTS_I16), stream b holds n_in_dev[b] (int32, DEVICE) samples and gets
+ * n_out_dev[b] = min(rts_resample_out_len(n_in_dev[b]), n_out_max) samples written to out_dev[b][0 .. n_out_dev[b]);
+ * samples behind them are left untouched.  out_dev float32 [B][n_out_max], n_out_dev int32 [B].  1 <= B <= 65535.
+ * Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable). */
+int rts_resample_run(rts_resample *p, const void *samples_dev, int sample_dtype, long long sample_stride,
+                     const int32_t *n_in_dev, int B, int n_out_max, float *out_dev, int32_t *n_out_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Windowed time warping, batched over B live streams against one reference chroma (or one each).
  * ------------------------------------------------------------------------------------------ */
 typedef struct rts_wtw rts_wtw;
@@ -483,6 +521,26 @@ int rts_live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max
  * features, and its cosine cost is NaN on the zero columns they contain.  Any other feature_kind: RTS_ERR_INVALID. */
 int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, int feature_kind,
                              rts_live **out);
+/* rts_live_create_features for microphones at another rate than the plan's: what librosa.load's resampling (chroma.py:27 /
+ * wtw.py:23) is for files, for the live loops, whose reference form opens PyAudio at the rate it needs.  The handle takes
+ * INPUT-rate samples in rts_live_staging / rts_live_submit / rts_live_feed.  Per feed one more launch sits between the copy
+ * and the append: it resamples (the stream's carried tail + the staged samples) with `resample_plan` -- held by
+ * reference, it must outlive the handle -- into a second device buffer laid out like a staging slot, from which the
+ * unchanged chain goes on.  Per stream the device carries the last ceil(2 half / L) input samples (float32, after
+ * scaling) and two int64 totals; the host mirrors the totals with rts_resample_avail, which is how it knows every
+ * stream's new sample count without a read-back: a stream that has been fed in_total samples has handed
+ * rts_resample_avail(in_total) plan-rate samples on, the first that many of a one-shot run, bit for bit, however the
+ * input was cut into feeds.  max_pending stays a capacity in plan-rate samples; a feed whose OUTPUT would exceed it is
+ * refused with RTS_ERR_INVALID and changes nothing (totals, tail, pending).  rts_live_staging reports the input-rate
+ * capacity, B * in_cap with in_cap = ceil((max_pending + 1) M / L) + ceil(2 half / L) + 2 samples per stream: no feed
+ * whose output fits max_pending is longer than in_cap, whatever table the plan holds; a stream's count above in_cap is
+ * refused with RTS_ERR_INVALID naming the staging capacity, like a feed that exceeds the slot as a whole.  rts_live_reset zeroes tail and totals of all
+ * streams and rts_live_restart those of the selected ones (device and mirror): the new run starts on silence.
+ * resample_plan NULL: RTS_ERR_INVALID (equal rates never build a resampler: use rts_live_create_features); a
+ * resample_plan created on another device than the current one: RTS_ERR_INVALID; B * in_cap >= 2^31: RTS_ERR_INVALID
+ * naming max_pending; everything else as rts_live_create_features. */
+int rts_live_create_resampled(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, int feature_kind,
+                              rts_resample *resample_plan, rts_live **out);
 int rts_live_destroy(rts_live *h);
 /* Drops pending samples (and, with RTS_FEATURE_CHROMA_DIFF, the carried chroma column of every stream: each stream
  * is fresh again and skips its first chroma column) and resets the bound tracker.  Synchronises `stream`. */

@@ -97,6 +97,13 @@ _decl("rts_chroma_project", _i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp])
 _decl("rts_chroma_diff", _i32, [_vp, _i32, _i32, _vp, _vp])
 
 
+_decl("rts_resample_out_len", _i64, [_i64, _i32, _i32])
+_decl("rts_resample_avail", _i64, [_i64, _i32, _i32, _i32])
+_decl("rts_resample_create", _i32, [_i32, _i32, _vp, _i32, ctypes.POINTER(_vp)])
+_decl("rts_resample_destroy", _i32, [_vp])
+_decl("rts_resample_run", _i32, [_vp, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _vp])
+
+
 _decl("rts_wtw_create", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)])
 _decl("rts_wtw_create_refs", _i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)])
 _decl("rts_wtw_destroy", _i32, [_vp])
@@ -113,6 +120,7 @@ WTW_STATE_LEN = 8
 
 _decl("rts_live_create", _i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_vp)])
 _decl("rts_live_create_features", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_vp)])
+_decl("rts_live_create_resampled", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, ctypes.POINTER(_vp)])
 _decl("rts_live_columns_view", _i32, [_vp, ctypes.POINTER(_vp), _pi32, _pi32, ctypes.POINTER(_vp)])
 _decl("rts_live_destroy", _i32, [_vp])
 _decl("rts_live_reset", _i32, [_vp, _vp])

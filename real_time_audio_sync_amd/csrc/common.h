@@ -65,6 +65,25 @@ __attribute__((visibility("hidden"))) int restart_check(int B, const uint8_t *ma
 __attribute__((visibility("hidden"))) int restart_next_chunk(int B, const uint8_t *mask_host, const long long *first_host,
                                                              const int32_t *len_host, int *pos, RestartSel *sel);
 
+// A resampling plan as the live handle uses it (csrc/resample.hip).  resample_info: the ratio, the table's half length,
+// T = ceil(2 half / L), the input samples a stream carries from feed to feed, and the device the plan lives on.
+// resample_live_enqueue: one launch that resamples every stream's (tail [B][T], staged feed) into `out_stage`, a buffer
+// laid out like a staging slot (int32 counts[B], int32 offs[B] = b * cap, float32 samples at samples_off), reading tail
+// and totals ([B][2]: input samples taken, output samples made) of this feed and writing those of the next into
+// `tail_next` / `tot_next`: the caller keeps two copies and alternates.  n_out_max: the most new output samples of a
+// stream (from the host mirror), which sizes the grid.  resample_live_restart_enqueue zeroes both copies ([2][B][T],
+// [2][B][2]) for the selected streams.
+__attribute__((visibility("hidden"))) int resample_info(const rts_resample *p, int *L, int *M, int *half, int *T,
+                                                        int *device);
+__attribute__((visibility("hidden"))) int resample_live_enqueue(const rts_resample *p, const unsigned char *stage,
+                                                                size_t samples_off, int sample_kind, int B, int cap,
+                                                                unsigned char *out_stage, const float *tail,
+                                                                const long long *tot, float *tail_next,
+                                                                long long *tot_next, int n_out_max, hipStream_t s);
+__attribute__((visibility("hidden"))) int resample_live_restart_enqueue(const rts_resample *p, const RestartSel &sel,
+                                                                        int B, float *tail, long long *tot,
+                                                                        hipStream_t s);
+
 #define RTS_HIP(call)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \

@@ -9,6 +9,9 @@
 //          (rts_live_staging hands the slot out, so a producer can write there directly) and copied by one
 //          hipMemcpyAsync on the handle's copy stream; the compute stream waits for that copy by event, so the copy of
 //          feed k+1 overlaps the kernels of feed k (a ring of kSlots pinned + device slots).
+//   resample_live_kernel  rts_live_create_resampled only (csrc/resample.hip): the staged samples are at the microphones' own
+//                         rate; (carried tail + staged samples) of every stream are resampled into a second device
+//                         buffer laid out like a staging slot, which the append below reads instead of the slot
 //   live_append_kernel    per stream (16 slices each): append the new samples (float32, or PCM16 scaled by 1/32768 like librosa.load)
 //                         behind the pending ones in a per-stream device buffer; pending -> n_samples, complete hops ->
 //                         n_frames  ((pending - fft_len) / hop + 1 once pending >= fft_len).
@@ -24,7 +27,8 @@
 //                         host-mapped memory -- rts_live_poll reads those words without touching the stream.
 // The host keeps an exact mirror of the pending counts (integer arithmetic on the counts it was given), which is how it
 // knows n_max for the launch geometry without reading anything back; in diff mode it mirrors the carry flags the same
-// way, which is how it knows whether any stream hands a column to the tracker in a feed.
+// way, which is how it knows whether any stream hands a column to the tracker in a feed.  A resampling handle mirrors the
+// input / output totals of every stream (rts_resample_avail), which is how it knows the streams' new sample counts.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -213,6 +217,18 @@ struct rts_live {
     unsigned char *conf_host;
     double *conf_mean_dev;
     int32_t *conf_n_dev;
+    // rts_live_create_resampled (rs NULL otherwise): the plan and its geometry, input-rate samples a staging slot holds
+    // per stream, the second staging-layout device buffer the resampling launch writes and the append reads, tail
+    // [B][rs_T] and totals [B][2] (input samples taken, output samples made) on the device, the host mirror of the
+    // totals, and the scratch a feed computes the next totals and the new output counts into
+    rts_resample *rs;
+    int rs_L, rs_M, rs_half, rs_T;
+    long long in_cap;
+    unsigned char *rs_stage;
+    float *rs_tail;  // [2][B][rs_T]: the copy feed k reads and the one it writes, alternating (rs_cur)
+    int rs_cur;
+    long long *rs_tot, *rs_tot_host, *rs_tot_next;
+    int32_t *rs_nout;
 };
 
 namespace rts {
@@ -260,6 +276,12 @@ int rts_live_destroy(rts_live *h) {
     free(h->has_carry_next);
     if (h->pub_host) (void)hipHostFree(h->pub_host);
     if (h->conf_host) (void)hipHostFree(h->conf_host);
+    if (h->rs_stage) (void)hipFree(h->rs_stage);
+    if (h->rs_tail) (void)hipFree(h->rs_tail);
+    if (h->rs_tot) (void)hipFree(h->rs_tot);
+    free(h->rs_tot_host);
+    free(h->rs_tot_next);
+    free(h->rs_nout);
     free(h->pending_host);
     free(h);
     return RTS_OK;
@@ -269,11 +291,10 @@ int rts_live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max
     return rts_live_create_features(plan, otw, wtw, B, max_pending, RTS_FEATURE_CHROMA, out);
 }
 
-int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, int feature_kind,
-                             rts_live **out) {
+// rts_live_create_features (rs NULL) and rts_live_create_resampled
+static int live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, int feature_kind,
+                       rts_resample *rs, rts_live **out) {
     using namespace rts;
-    if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
-    *out = nullptr;
     if (feature_kind != RTS_FEATURE_CHROMA && feature_kind != RTS_FEATURE_CHROMA_DIFF)
         return set_error(RTS_ERR_INVALID, "feature_kind must be RTS_FEATURE_CHROMA or RTS_FEATURE_CHROMA_DIFF, not %d", feature_kind);
     if (feature_kind == RTS_FEATURE_CHROMA_DIFF && wtw)
@@ -289,6 +310,17 @@ int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B
     if (int rc = rts_chroma_plan_info(plan, &fft_len, &hop); rc != RTS_OK) return rc;
     if (max_pending < fft_len + hop || (long long)max_pending * B > 0x7fffffffLL)
         return set_error(RTS_ERR_INVALID, "max_pending must be at least fft_len + hop samples (and B * max_pending < 2^31)");
+    int rs_L = 0, rs_M = 0, rs_half = 0, rs_T = 0, rs_device = -1;
+    long long in_cap = 0;
+    if (rs) {
+        (void)resample_info(rs, &rs_L, &rs_M, &rs_half, &rs_T, &rs_device);
+        if (int rc = check_device(rs_device, "resample_plan"); rc != RTS_OK) return rc;
+        // the most input samples whose output fits max_pending: n_out >= n L / M - 1 once a stream's first output exists,
+        // n_out >= (n L - half) / M before
+        in_cap = ((long long)(max_pending + 1) * rs_M + rs_L - 1) / rs_L + rs_T + 2;
+        if (in_cap * B > 0x7fffffffLL)
+            return set_error(RTS_ERR_INVALID, "max_pending: B * %lld input-rate samples per staging slot must stay below 2^31", in_cap);
+    }
     rts_live *h = (rts_live *)calloc(1, sizeof(rts_live));
     if (!h) return set_error(RTS_ERR_INVALID, "out of host memory");
     h->plan = plan;
@@ -304,6 +336,18 @@ int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B
     h->samples_off = (2 * sizeof(int32_t) * (size_t)B + 255) & ~(size_t)255;
     h->slot_bytes = h->samples_off + sizeof(float) * (size_t)B * max_pending;
     h->pending_host = (long long *)calloc((size_t)B, sizeof(long long));
+    if (rs) {
+        h->rs = rs;
+        h->rs_L = rs_L;
+        h->rs_M = rs_M;
+        h->rs_half = rs_half;
+        h->rs_T = rs_T;
+        h->in_cap = in_cap;
+        h->slot_bytes = h->samples_off + sizeof(float) * (size_t)B * (size_t)h->in_cap;
+        h->rs_tot_host = (long long *)calloc(2 * (size_t)B, sizeof(long long));
+        h->rs_tot_next = (long long *)calloc(2 * (size_t)B, sizeof(long long));
+        h->rs_nout = (int32_t *)calloc((size_t)B, sizeof(int32_t));
+    }
     hipError_t e = hipGetDevice(&h->device);
     for (int k = 0; k < kLiveSlots && e == hipSuccess; k++) {
         if ((e = hipHostMalloc((void **)&h->stage_host[k], h->slot_bytes, hipHostMallocDefault)) != hipSuccess) break;
@@ -329,13 +373,23 @@ int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B
         if (e == hipSuccess) e = hipMemset(h->has_carry, 0, sizeof(int32_t) * (size_t)B);
         if (e == hipSuccess) e = hipMemset(h->n_cols, 0, sizeof(int32_t) * (size_t)B);
     }
+    if (rs) {
+        const size_t out_bytes = h->samples_off + sizeof(float) * (size_t)B * max_pending;
+        if (e == hipSuccess) e = hipMalloc((void **)&h->rs_stage, out_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->rs_tail, sizeof(float) * 2 * (size_t)B * h->rs_T);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->rs_tot, sizeof(long long) * 4 * (size_t)B);
+        if (e == hipSuccess) e = hipMemset(h->rs_stage, 0, out_bytes);
+        if (e == hipSuccess) e = hipMemset(h->rs_tail, 0, sizeof(float) * 2 * (size_t)B * h->rs_T);
+        if (e == hipSuccess) e = hipMemset(h->rs_tot, 0, sizeof(long long) * 4 * (size_t)B);
+    }
     if (e == hipSuccess) e = hipMemset(h->n_frames, 0, sizeof(int32_t) * (size_t)B);
     if (e == hipSuccess)
         e = hipHostMalloc((void **)&h->pub_host, sizeof(int32_t) * kLiveWords * (size_t)B, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&h->pub_dev, h->pub_host, 0);
     if (e == hipSuccess) e = hipMemset(h->pending, 0, sizeof(int32_t) * (size_t)B);
     if (e == hipSuccess) e = hipMemset(h->buf, 0, sizeof(float) * (size_t)B * max_pending);
-    if (e != hipSuccess || !h->pending_host || (diff && (!h->has_carry_host || !h->has_carry_next))) {
+    if (e != hipSuccess || !h->pending_host || (diff && (!h->has_carry_host || !h->has_carry_next)) ||
+        (rs && (!h->rs_tot_host || !h->rs_tot_next || !h->rs_nout))) {
         rts_live_destroy(h);
         return set_error(RTS_ERR_HIP, "rts_live_create: %s", hipGetErrorString(e));
     }
@@ -366,6 +420,24 @@ int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B
     return RTS_OK;
 }
 
+int rts_live_create_features(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, int feature_kind,
+                             rts_live **out) {
+    using namespace rts;
+    if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    return live_create(plan, otw, wtw, B, max_pending, feature_kind, nullptr, out);
+}
+
+int rts_live_create_resampled(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int max_pending, int feature_kind,
+                              rts_resample *resample_plan, rts_live **out) {
+    using namespace rts;
+    if (!out) return set_error(RTS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!resample_plan)
+        return set_error(RTS_ERR_INVALID, "resample_plan is NULL (equal rates build no resampler: rts_live_create_features)");
+    return live_create(plan, otw, wtw, B, max_pending, feature_kind, resample_plan, out);
+}
+
 int rts_live_reset(rts_live *h, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
@@ -377,6 +449,11 @@ int rts_live_reset(rts_live *h, void *stream) {
     if (h->has_carry) {
         RTS_HIP(hipMemsetAsync(h->has_carry, 0, sizeof(int32_t) * (size_t)h->B, (hipStream_t)stream));
         memset(h->has_carry_host, 0, (size_t)h->B);
+    }
+    if (h->rs) {
+        RTS_HIP(hipMemsetAsync(h->rs_tail, 0, sizeof(float) * 2 * (size_t)h->B * h->rs_T, (hipStream_t)stream));
+        RTS_HIP(hipMemsetAsync(h->rs_tot, 0, sizeof(long long) * 4 * (size_t)h->B, (hipStream_t)stream));
+        memset(h->rs_tot_host, 0, sizeof(long long) * 2 * (size_t)h->B);
     }
     memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * (size_t)h->B);
     if (h->conf_host) live_conf_clear(h);
@@ -414,11 +491,16 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
     for (int pos = 0; restart_next_chunk(h->B, mask_host, nullptr, nullptr, &pos, &sel) > 0;) {
         hipLaunchKernelGGL(live_restart_kernel, dim3((sel.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, sel, g);
         RTS_HIP(hipGetLastError());
+        if (h->rs) {
+            if (int rc = resample_live_restart_enqueue(h->rs, sel, h->B, h->rs_tail, h->rs_tot, (hipStream_t)stream); rc != RTS_OK)
+                return rc;
+        }
     }
     for (int b = 0; b < h->B; b++)
         if (mask_host[b]) {  // the mirrors: samples submitted from here on belong to the new run
             h->pending_host[b] = 0;
             if (h->has_carry_host) h->has_carry_host[b] = 0;
+            if (h->rs) h->rs_tot_host[2 * b] = h->rs_tot_host[2 * b + 1] = 0;
         }
     return RTS_OK;
 }
@@ -434,7 +516,7 @@ int rts_live_staging(rts_live *h, int32_t **counts_host, void **samples_host, lo
     }
     if (counts_host) *counts_host = reinterpret_cast<int32_t *>(h->stage_host[h->slot]);
     if (samples_host) *samples_host = h->stage_host[h->slot] + h->samples_off;
-    if (capacity_samples) *capacity_samples = (long long)h->B * h->cap;
+    if (capacity_samples) *capacity_samples = (long long)h->B * (h->rs ? h->in_cap : h->cap);
     return RTS_OK;
 }
 
@@ -451,7 +533,22 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
     long long total = 0;
     for (int b = 0; b < B; b++) {
         if (counts[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: negative sample count", b);
-        if (h->pending_host[b] + counts[b] > h->cap)
+        if (h->rs) {
+            // what the resampling launch will make of these counts: the next totals go to scratch and are committed once
+            // that launch has been enqueued; the tracker side sees the output samples
+            const long long in_next = h->rs_tot_host[2 * b] + counts[b];
+            const long long out_next = rts_resample_avail(in_next, h->rs_L, h->rs_M, h->rs_half);
+            const long long n_out = out_next - h->rs_tot_host[2 * b + 1];
+            if (counts[b] > h->in_cap)  // (more than any feed whose output fits max_pending)
+                return set_error(RTS_ERR_INVALID, "stream %d: %d new input samples exceed the staging capacity of %lld per stream",
+                                 b, counts[b], h->in_cap);
+            if (h->pending_host[b] + n_out > h->cap)
+                return set_error(RTS_ERR_INVALID, "stream %d: %lld pending + %lld resampled samples (of %d new input samples) "
+                                 "exceed max_pending = %d", b, h->pending_host[b], n_out, counts[b], h->cap);
+            h->rs_tot_next[2 * b] = in_next;
+            h->rs_tot_next[2 * b + 1] = out_next;
+            h->rs_nout[b] = (int32_t)n_out;
+        } else if (h->pending_host[b] + counts[b] > h->cap)
             return set_error(RTS_ERR_INVALID, "stream %d: %lld pending + %d new samples exceed max_pending = %d", b,
                              h->pending_host[b], counts[b], h->cap);
         total += counts[b];
@@ -462,7 +559,7 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
     for (int b = 0; b < B; b++) {
         offs[b] = (int32_t)total;
         total += counts[b];
-        const long long q = h->pending_host[b] + counts[b];
+        const long long q = h->pending_host[b] + (h->rs ? h->rs_nout[b] : counts[b]);
         const int nf = q >= h->L ? (int)((q - h->L) / h->hop + 1) : 0;
         if (nf > n_max) n_max = nf;
         if (diff) {  // what live_diff_kernel will do with these counts; committed once it has been enqueued
@@ -509,6 +606,22 @@ int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
     g.n_cols = h->n_cols;
     g.cols_stride = n_max;
     h->last_stride = n_max;
+    if (h->rs) {  // input-rate samples: resampled into the second staging-layout buffer, which the chain goes on from
+        const int cur = h->rs_cur, nxt = cur ^ 1;
+        const size_t tail_n = (size_t)B * h->rs_T, tot_n = 2 * (size_t)B;
+        int n_out_max = 0;
+        for (int b = 0; b < B; b++)
+            if (h->rs_nout[b] > n_out_max) n_out_max = h->rs_nout[b];
+        if (int rc = resample_live_enqueue(h->rs, h->stage_dev[k], h->samples_off, sample_kind, B, h->cap, h->rs_stage,
+                                           h->rs_tail + cur * tail_n, h->rs_tot + cur * tot_n, h->rs_tail + nxt * tail_n,
+                                           h->rs_tot + nxt * tot_n, n_out_max, s);
+            rc != RTS_OK)
+            return rc;
+        memcpy(h->rs_tot_host, h->rs_tot_next, sizeof(long long) * 2 * (size_t)B);  // the device totals will be these
+        h->rs_cur = nxt;
+        g.stage = h->rs_stage;
+        g.sample_kind = RTS_F32;
+    }
     hipLaunchKernelGGL(live_append_kernel, dim3(B, kAppendSlices), dim3(256), 0, s, g);
     RTS_HIP(hipGetLastError());
     RTS_HIP(hipEventRecord(h->done[k], s));  // the staging slot (host and device side) is free again after this point
@@ -565,7 +678,9 @@ int rts_live_feed(rts_live *h, const void *samples_host, int sample_kind, const 
         if (counts_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: negative sample count", b);
         total += counts_host[b];
     }
-    if (total > capacity) return set_error(RTS_ERR_INVALID, "%lld samples in one feed exceed B * max_pending = %lld", total, capacity);
+    if (total > capacity)
+        return set_error(RTS_ERR_INVALID, h->rs ? "%lld samples in one feed exceed the staging capacity of %lld input-rate samples"
+                                                : "%lld samples in one feed exceed B * max_pending = %lld", total, capacity);
     if (total > 0 && !samples_host) return set_error(RTS_ERR_INVALID, "samples_host is NULL");
     memcpy(counts, counts_host, sizeof(int32_t) * (size_t)h->B);
     if (total > 0) memcpy(samples, samples_host, (size_t)total * (sample_kind == RTS_F32 ? sizeof(float) : sizeof(int16_t)));

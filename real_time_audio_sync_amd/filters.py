@@ -5,6 +5,7 @@ reference calls it at chroma.py:69 and wtw.py:39; librosa itself is not a depend
 package and is absent from the build image): a Gaussian bump per pitch class around each FFT bin's
 fractional chroma position, columns L2-normalised, a Gaussian octave weighting centred on
 ``ctroct`` octaves above A0/16, rows rolled so that row 0 is C."""
+import math
 import wave
 
 import numpy as np
@@ -30,6 +31,45 @@ def chroma_filterbank(sr=22050, n_fft=4096, n_chroma=12, a440=440.0, ctroct=5.0,
 def hann_window(n):
     """The symmetric window the reference multiplies every frame by (np.hanning, chroma.py:39,:62)."""
     return np.hanning(n).astype(np.float64)
+
+
+def resample_ratio(fs_in, fs_out=22050):
+    """(L, M) with L / M = fs_out / fs_in, reduced by the gcd: 44 100 -> 22 050 is (1, 2), 48 000 -> 22 050 (147, 320)."""
+    fs_in, fs_out = int(fs_in), int(fs_out)
+    if fs_in < 1 or fs_out < 1:
+        raise ValueError("sample rates must be positive integers")
+    g = math.gcd(fs_in, fs_out)
+    return fs_out // g, fs_in // g
+
+
+def resample_taps(fs_in, fs_out=22050, zeros=16, atten_db=80.0, rolloff=0.945):
+    """The resampler's filter table h[-half .. half] as 2 * half + 1 float64 taps (index 0 is h[-half]): a Kaiser-windowed
+    sinc at the rate fs_in * L with ``zeros`` zero crossings on either side, cut off at ``rolloff`` of the lower Nyquist
+    frequency, gain L.  half = zeros * max(L, M), fc = rolloff / max(L, M),
+    h[n] = L * fc * sinc(fc * n) * kaiser(2 * half + 1, 0.1102 * (atten_db - 8.7))[n + half].
+    This table stands where librosa.load's resampling filter stands in the reference (chroma.py:27, wtw.py:23); like the
+    chroma filterbank it is handed to the library as host doubles (rts_resample_create)."""
+    L, M = resample_ratio(fs_in, fs_out)
+    half = int(zeros) * max(L, M)
+    fc = float(rolloff) / max(L, M)
+    n = np.arange(-half, half + 1, dtype=np.float64)
+    h = L * fc * np.sinc(fc * n) * np.kaiser(2 * half + 1, 0.1102 * (float(atten_db) - 8.7))
+    return np.ascontiguousarray(h, dtype=np.float64)
+
+
+def load_wav_native(path):
+    """``load_wav`` without the refusal: (float32 samples scaled by 1/32768 with the channels averaged, the file's own
+    rate).  What ``librosa.load(path, sr=None)`` returns; bringing it to 22 050 Hz is the device resampler's job
+    (chroma.resample, the ``resample=True`` keyword of the file entry points)."""
+    with wave.open(path, "rb") as w:
+        if w.getsampwidth() != 2:
+            raise ValueError("only 16-bit PCM WAV files are supported")
+        fs = w.getframerate()
+        nch = w.getnchannels()
+        raw = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
+    x = raw.reshape(-1, nch).astype(np.float32) / np.float32(32768.0)
+    y = x.mean(axis=1, dtype=np.float32) if nch > 1 else x[:, 0]
+    return np.ascontiguousarray(y, dtype=np.float32), fs
 
 
 def load_wav(path):

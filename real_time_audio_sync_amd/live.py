@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .chroma import ChromaPlan
+from .chroma import ChromaPlan, ResamplePlan
 from .otw_batch import BatchedOTW
 
 _KINDS = {np.dtype(np.float32): nat.F32, np.dtype(np.int16): nat.I16}
@@ -36,7 +36,7 @@ class _DeviceView(object):
 class LiveSession(object):
     def __init__(self, ref_chroma, batch, c=500, max_run_count=3, variant="otw", fft_len=4096, hop_size=2048,
                  fs=22050, max_pending=1 << 16, device="cuda:0", wtw_params=None, extra_refs=(), features="chroma",
-                 euclid=False):
+                 euclid=False, fs_in=None):
         """``ref_chroma``: (12, N) reference chroma (e.g. chroma.wav_to_chroma(ref_path)), or a list of ``batch`` such
         arrays, one per stream (one piece per microphone; a list entry that repeats is uploaded once).  With
         ``wtw_params`` ({'dtw_win_size', 'dtw_hop_size'} in samples, like wtw.py:29-30) the streams are followed by
@@ -50,7 +50,12 @@ class LiveSession(object):
         drops it for the listed streams and ``reset`` for all, like their pending samples.  Not available with
         ``wtw_params`` (the reference never runs WTW on difference features; its cosine cost is NaN on their zero
         columns).  ``euclid``: the OTW family's Euclidean cost (livenote_v2.py:168) instead of 1 - dot; the reference
-        pairs it with either feature kind (tests.py:156)."""
+        pairs it with either feature kind (tests.py:156).
+
+        ``fs_in``: the microphones' own sample rate.  None or ``fs`` gives the ordinary session.  Anything else puts the
+        device resampler (chroma.ResamplePlan) in front of the chain: ``feed``, ``feed_block`` and ``staging`` then take
+        samples at ``fs_in``, ``max_pending`` and ``pending()`` stay in samples at ``fs``, and a stream that has been
+        fed n samples has handed ``resampler.avail(n)`` samples on, the same ones however the input was cut."""
         if features not in _FEATURES:
             raise ValueError("features must be 'chroma' or 'chroma_diff', not %r" % (features,))
         if features == "chroma_diff" and wtw_params is not None:
@@ -97,11 +102,18 @@ class LiveSession(object):
             else:
                 self._ref_dev = torch.from_numpy(np.ascontiguousarray(ref.T)).to(self.dev)
                 self.wtw = BatchedWTW(self._ref_dev, win, hopf, batch)
+        self.resampler = None
+        if fs_in is not None and int(fs_in) != int(fs):
+            self.resampler = ResamplePlan(fs_in, fs, self.dev)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.dev):
-            nat.check(nat.lib.rts_live_create_features(self.plan._h, self.otw._h if self.otw else None,
-                                                       self.wtw._h if self.wtw else None, self.B, self.cap,
-                                                       _FEATURES[features], ctypes.byref(h)))
+            otw_h, wtw_h = self.otw._h if self.otw else None, self.wtw._h if self.wtw else None
+            if self.resampler is None:
+                nat.check(nat.lib.rts_live_create_features(self.plan._h, otw_h, wtw_h, self.B, self.cap,
+                                                           _FEATURES[features], ctypes.byref(h)))
+            else:
+                nat.check(nat.lib.rts_live_create_resampled(self.plan._h, otw_h, wtw_h, self.B, self.cap,
+                                                            _FEATURES[features], self.resampler._h, ctypes.byref(h)))
         self._h = h
         self._status = np.zeros(self.B, dtype=np.int32)
         self._pos = np.zeros((self.B, 2), dtype=np.int32)
@@ -111,7 +123,8 @@ class LiveSession(object):
         return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
 
     def staging(self, dtype=np.float32):
-        """The next pinned staging slot as numpy views: (counts int32 [B], samples `dtype` [B * max_pending]).  Write
+        """The next pinned staging slot as numpy views: (counts int32 [B], samples `dtype` [B * max_pending], or with
+        ``fs_in`` the input-rate capacity rts_live_staging reports).  Write
         the new sample count of every stream and the samples of all streams packed back to back in stream order, then
         call ``submit(dtype)``.  A producer that writes here directly (an audio callback, a socket reader) saves the
         copy ``feed`` makes."""
@@ -304,7 +317,8 @@ class LiveSession(object):
             except Exception:
                 pass
             nat.destroy_on(self.dev, nat.lib.rts_live_destroy, h)
-        for o in (getattr(self, "otw", None), getattr(self, "wtw", None), getattr(self, "plan", None)):
+        for o in (getattr(self, "otw", None), getattr(self, "wtw", None), getattr(self, "plan", None),
+                  getattr(self, "resampler", None)):
             if o is not None:
                 o.close()
 

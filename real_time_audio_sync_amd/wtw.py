@@ -107,9 +107,16 @@ class WTW():
     """``WTW(ref_recording, {'fft_len','hop_size','dtw_win_size','dtw_hop_size'}, debug_params)``;
     ``insert(list_of_float_samples)`` returns None or "stop"; ``.path`` is a list of (live, ref)."""
 
-    def __init__(self, ref_recording, params, debug_params, device="cuda:0"):
-        # reference audio, fs = 22050 (wtw.py:23-24)
-        self.ref, self.fs = filters.load_wav(ref_recording)
+    def __init__(self, ref_recording, params, debug_params, device="cuda:0", resample=False):
+        # reference audio, fs = 22050 (wtw.py:23-24); resample=True: a file at another rate is resampled on the device,
+        # where librosa.load resamples silently (wtw.py:23)
+        if resample:
+            self.ref, self.fs = filters.load_wav_native(ref_recording)
+            if self.fs != 22050:
+                from .chroma import resample as resample_on_device
+                self.ref, self.fs = resample_on_device(self.ref, self.fs, 22050, device), 22050
+        else:
+            self.ref, self.fs = filters.load_wav(ref_recording)
         assert (self.fs == 22050)
         self._init_from_samples(self.ref, params, debug_params, device)
 
