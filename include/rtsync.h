@@ -565,7 +565,11 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
  * the previous feed), append to the per-stream pending buffers, chroma of every complete hop, with
  * RTS_FEATURE_CHROMA_DIFF the difference against the previous column (the carried one for a feed's first), push into
  * the tracker, drop of the consumed samples (hop per column, livenote_live.py:208 / wtw.py:83), publication of the
- * status words.  A refused feed (RTS_ERR_INVALID) changes neither the pending counts nor the carry. */
+ * status words.  A refused feed (RTS_ERR_INVALID) changes neither the pending counts nor the carry.
+ * If one of those enqueues itself fails (RTS_ERR_HIP, or the tracker's error), the device may have run a part of the
+ * feed, and the handle no longer knows what its buffers hold: from then on rts_live_staging, rts_live_submit,
+ * rts_live_feed and rts_live_restart return RTS_ERR_INVALID (the message says that an earlier feed failed while it was
+ * being enqueued) until rts_live_reset, which starts every stream afresh, has succeeded. */
 int rts_live_staging(rts_live *h, int32_t **counts_host, void **samples_host, long long *capacity_samples);
 int rts_live_submit(rts_live *h, int sample_kind /* RTS_F32 | RTS_I16 */, void *stream);
 /* The same from caller-owned host arrays (one memcpy into the staging slot): samples_host packed like above. */

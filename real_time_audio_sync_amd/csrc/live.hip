@@ -2,13 +2,18 @@
 //   livenote_live.py:161-209  receive_audio -> _process_input: while len(data) >= 4096: wav_to_chroma_col(data[:4096]);
 //                              OnlineTimeWarping.insert(col); data = data[2048:]
 //   wtw.py:71-93              WTW.insert: self.buf += list; while len(buf) >= fft_len: column of buf[:fft_len]; buf = buf[hop:]
-// for B independent streams per call ("feed").
+// for B independent streams per call ("feed").  The host side of a feed (rts_live_submit) is plan, chain, commit.
 //
-// One feed = ONE host-to-device copy and a fixed chain of launches on the caller's stream, no synchronisation:
-//   host   counts[B], offsets[B] and the packed new samples of all streams are written into one pinned staging slot
-//          (rts_live_staging hands the slot out, so a producer can write there directly) and copied by one
-//          hipMemcpyAsync on the handle's copy stream; the compute stream waits for that copy by event, so the copy of
-//          feed k+1 overlaps the kernels of feed k (a ring of kSlots pinned + device slots).
+// Plan (csrc/live_plan.h, no HIP in it).  The producer has written counts[B] and the packed new samples of all streams
+// into a pinned staging slot (rts_live_staging hands the slot out, so it can write there directly).  Nothing is ever read
+// back: the host mirrors the pending counts, the carry flags of diff mode and a resampling handle's input / output totals,
+// and live_plan_feed derives from mirror and counts whether the feed is refused, the launch geometry (n_max and its
+// kin) and the mirror after the feed, which it leaves in scratch.
+//
+// Chain (live_enqueue: ONE host-to-device copy and a fixed sequence of launches on the caller's stream, no synchronisation)
+//   copy                  of the used part of the slot by one hipMemcpyAsync on the handle's copy stream; the compute
+//                         stream waits for it by event, so the copy of feed k+1 overlaps the kernels of feed k (a ring
+//                         of kSlots pinned + device slots)
 //   resample_live_kernel  rts_live_create_resampled only (csrc/resample.hip): the staged samples are at the microphones' own
 //                         rate; (carried tail + staged samples) of every stream are resampled into a second device
 //                         buffer laid out like a staging slot, which the append below reads instead of the slot
@@ -25,16 +30,17 @@
 //   live_compact_kernel   drop hop * n_frames consumed samples per stream (data = data[2048:], livenote_live.py:208),
 //                         and publish {status, live position, ref position, feed number} of every stream into
 //                         host-mapped memory -- rts_live_poll reads those words without touching the stream.
-// The host keeps an exact mirror of the pending counts (integer arithmetic on the counts it was given), which is how it
-// knows n_max for the launch geometry without reading anything back; in diff mode it mirrors the carry flags the same
-// way, which is how it knows whether any stream hands a column to the tracker in a feed.  A resampling handle mirrors the
-// input / output totals of every stream (rts_resample_avail), which is how it knows the streams' new sample counts.
+//
+// Commit (live_commit).  Once the last step has been enqueued the planned values become the mirror, and the slot ring
+// and the feed counter move on.  A chain that fails part-way commits nothing and marks the handle failed -- the device
+// may have run a part of it -- and every feed and restart is refused until rts_live_reset has zeroed both sides.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "common.h"
+#include "live_plan.h"
 
 namespace rts {
 
@@ -55,7 +61,7 @@ struct LiveArgs {
     int32_t *pub;                // host-mapped [B][kLiveWords]
     int feed_no;
     // RTS_FEATURE_CHROMA_DIFF (all NULL in chroma mode)
-    const double *cols;          // [B][cols_stride][12] chroma columns of this feed
+    double *cols;                // [B][cols_stride][12] chroma columns of this feed
     double *dcols;               // [B][cols_stride][12] difference columns handed to the tracker
     double *carry;               // [B][12] last chroma column of every stream
     int32_t *has_carry, *n_cols; // [B]
@@ -187,8 +193,11 @@ struct rts_live {
     rts_chroma *plan;
     rts_otw *otw;
     rts_wtw *wtw;
-    int B, L, hop, cap, cols_cap, device;
-    size_t samples_off, slot_bytes;
+    rts::LiveGeom geo;   // B, fft_len, hop, max_pending, diff mode, the resampler's ratio and in_cap
+    // what every launch takes, from create and rts_live_watch; a feed adds stage, sample_kind, feed_no, cols_stride to a copy.
+    // Every kernel gets every field: none may take a NULL field for the mode (live_restart_kernel's two tests are of buffers)
+    rts::LiveArgs args;
+    int cols_cap, device;
     unsigned char *stage_host[rts::kLiveSlots];  // pinned
     unsigned char *stage_dev[rts::kLiveSlots];
     hipEvent_t copied[rts::kLiveSlots], done[rts::kLiveSlots];
@@ -196,47 +205,44 @@ struct rts_live {
     int slot;            // the slot rts_live_staging handed out last (-1: none outstanding)
     int next;
     hipStream_t copy_stream;
-    float *buf;
-    int32_t *pending, *n_samples, *n_frames;
-    double *cols;
-    long long *pending_host;
-    // RTS_FEATURE_CHROMA_DIFF (NULL in chroma mode): second column buffer, carried column and flag per stream, columns
-    // handed to the tracker per stream; host mirror of the flags and the scratch a feed computes the next ones into
-    int feature_kind;
-    double *dcols, *carry;
-    int32_t *has_carry, *n_cols;
-    uint8_t *has_carry_host, *has_carry_next;
+    // the host mirror, and the plan of the feed being submitted with its scratch (the next mirror, rs_nout, offs): the arrays
+    // follow the handle in its own allocation (kMirrorBytes per stream), whatever the mode
+    rts::LiveMirror cur;
+    rts::FeedPlan fp;
     int last_stride;     // rows per stream in the layout of the last submitted feed (rts_live_columns_view)
-    int32_t *pub_host, *pub_dev;
-    const int32_t *state_dev;
-    int state_len, st_status, st_live, st_ref;
+    int32_t *pub_host;
     int feeds;
+    int failed;          // a feed's chain was enqueued in part: the mirror no longer describes the device (rts_live_reset)
     // rts_live_watch: K path points per stream (0 = off) and the second host-mapped block, double mean[B] then int32 n[B],
     // allocated by the first rts_live_watch(K > 0)
     int watch_k;
     unsigned char *conf_host;
-    double *conf_mean_dev;
-    int32_t *conf_n_dev;
-    // rts_live_create_resampled (rs NULL otherwise): the plan and its geometry, input-rate samples a staging slot holds
-    // per stream, the second staging-layout device buffer the resampling launch writes and the append reads, tail
-    // [B][rs_T] and totals [B][2] (input samples taken, output samples made) on the device, the host mirror of the
-    // totals, and the scratch a feed computes the next totals and the new output counts into
+    // rts_live_create_resampled (rs NULL otherwise): the plan, the input samples a stream carries (rs_T), the second
+    // staging-layout device buffer the resampling launch writes and the append reads, tail [B][rs_T] and totals [B][2]
+    // (input samples taken, output samples made) on the device
     rts_resample *rs;
-    int rs_L, rs_M, rs_half, rs_T;
-    long long in_cap;
+    int rs_T;
     unsigned char *rs_stage;
     float *rs_tail;  // [2][B][rs_T]: the copy feed k reads and the one it writes, alternating (rs_cur)
     int rs_cur;
-    long long *rs_tot, *rs_tot_host, *rs_tot_next;
-    int32_t *rs_nout;
+    long long *rs_tot;
 };
 
 namespace rts {
 
+constexpr size_t kMirrorBytes = 6 * sizeof(long long) + 2 * sizeof(int32_t) + 2;  // per stream: two mirrors, rs_nout, offs
+
+static int live_usable(const rts_live *h) {
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (h->failed)
+        return set_error(RTS_ERR_INVALID, "an earlier feed failed while it was being enqueued: the handle needs rts_live_reset");
+    return RTS_OK;
+}
+
 static void live_conf_clear(rts_live *h) {
     double *mean = reinterpret_cast<double *>(h->conf_host);
-    int32_t *n = reinterpret_cast<int32_t *>(h->conf_host + sizeof(double) * (size_t)h->B);
-    for (int b = 0; b < h->B; b++) {
+    int32_t *n = reinterpret_cast<int32_t *>(h->conf_host + sizeof(double) * (size_t)h->geo.B);
+    for (int b = 0; b < h->geo.B; b++) {
         mean[b] = __builtin_nan("");
         n[b] = 0;
     }
@@ -247,7 +253,106 @@ static void live_conf_clear(rts_live *h) {
 // writes the feed number last, so a reader that sees feed k sees confidence words of a feed >= k.
 static int live_watch_launch(rts_live *h, void *stream) {
     if (h->watch_k < 1) return RTS_OK;
-    return rts_otw_path_cost(h->otw, h->watch_k, h->conf_mean_dev, h->conf_n_dev, nullptr, stream);
+    return rts_otw_path_cost(h->otw, h->watch_k, h->args.conf_mean, h->args.conf_n, nullptr, stream);
+}
+
+static int live_refuse(const rts_live *h, LiveRefusal why, const FeedPlan &p, const int32_t *counts) {
+    const int b = p.stream;
+    if (why == kLiveNegativeCount) return set_error(RTS_ERR_INVALID, "stream %d: negative sample count", b);
+    if (why == kLiveOverStaging)
+        return set_error(RTS_ERR_INVALID, "stream %d: %d new input samples exceed the staging capacity of %lld per stream", b,
+                         counts[b], h->geo.in_cap);
+    if (h->rs)
+        return set_error(RTS_ERR_INVALID, "stream %d: %lld pending + %lld resampled samples (of %d new input samples) "
+                         "exceed max_pending = %d", b, h->cur.pending[b], p.n_new, counts[b], h->geo.cap);
+    return set_error(RTS_ERR_INVALID, "stream %d: %lld pending + %d new samples exceed max_pending = %d", b,
+                     h->cur.pending[b], counts[b], h->geo.cap);
+}
+
+// The chain of feed h->feeds + 1 from staging slot k, as `p` plans it.  Every feed enqueues every step, except: the
+// resampling launch exists on a resampling handle only, live_diff_kernel in diff mode only (there in a feed without a
+// chroma column too: it writes the feed's n_cols); rts_chroma_frames_batch and rts_otw_push return at once when their
+// n_max is 0, rts_wtw_push after its entry check, which wtw.py:76-77 runs on every insert(), new column or not; in diff
+// mode the tracker is pushed only when some stream hands it a column (n_max_diff > 0; the rows still lie n_max apart);
+// the watch launch follows rts_live_watch.  The compaction and the publication end every feed.
+static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, void *stream) {
+    const int B = h->geo.B;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = h->args.samples_off + (size_t)p.total * (sample_kind == RTS_F32 ? sizeof(float) : sizeof(int16_t));
+    RTS_HIP(hipMemcpyAsync(h->stage_dev[k], h->stage_host[k], bytes, hipMemcpyHostToDevice, h->copy_stream));
+    RTS_HIP(hipEventRecord(h->copied[k], h->copy_stream));
+    RTS_HIP(hipStreamWaitEvent(s, h->copied[k], 0));
+    LiveArgs g = h->args;
+    g.stage = h->stage_dev[k];
+    g.sample_kind = sample_kind;
+    g.feed_no = h->feeds + 1;
+    g.cols_stride = p.n_max;
+    if (h->rs) {  // input-rate samples: resampled into the second staging-layout buffer, which the chain goes on from
+        const int cur = h->rs_cur, nxt = cur ^ 1;
+        const size_t tail_n = (size_t)B * h->rs_T, tot_n = 2 * (size_t)B;
+        if (int rc = resample_live_enqueue(h->rs, h->stage_dev[k], h->args.samples_off, sample_kind, B, h->geo.cap, h->rs_stage,
+                                           h->rs_tail + cur * tail_n, h->rs_tot + cur * tot_n, h->rs_tail + nxt * tail_n,
+                                           h->rs_tot + nxt * tot_n, p.n_out_max, s);
+            rc != RTS_OK)
+            return rc;
+        g.stage = h->rs_stage;
+        g.sample_kind = RTS_F32;
+    }
+    hipLaunchKernelGGL(live_append_kernel, dim3(B, kAppendSlices), dim3(256), 0, s, g);
+    RTS_HIP(hipGetLastError());
+    RTS_HIP(hipEventRecord(h->done[k], s));  // the staging slot (host and device side) is free again after this point
+    if (int rc = rts_chroma_frames_batch(h->plan, h->args.buf, RTS_F32, h->geo.cap, h->args.n_samples, 0, B, p.n_max, h->args.n_frames, 1,
+                                         h->args.cols, RTS_F64, stream);
+        rc != RTS_OK)
+        return rc;
+    if (h->geo.diff) {
+        hipLaunchKernelGGL(live_diff_kernel, dim3(B), dim3(256), 0, s, g);
+        RTS_HIP(hipGetLastError());
+    }
+    const double *cols = h->geo.diff ? h->args.dcols : h->args.cols;
+    const int32_t *n_new = h->geo.diff ? h->args.n_cols : h->args.n_frames;
+    const int n_push = h->geo.diff && p.n_max_diff == 0 ? 0 : p.n_max;
+    if (int rc = h->otw ? rts_otw_push(h->otw, cols, RTS_F64, n_push, n_new, stream)
+                        : rts_wtw_push(h->wtw, cols, RTS_F64, n_push, n_new, 1, stream);
+        rc != RTS_OK)
+        return rc;
+    if (int rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
+    hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+
+static void live_commit(rts_live *h, const FeedPlan &p, int k) {
+    live_mirror_commit(h->geo, h->cur, p.next);
+    if (h->rs) h->rs_cur ^= 1;
+    h->feeds += 1;
+    h->slot = -1;
+    h->next = (k + 1) % kLiveSlots;
+    h->used[k] = 1;
+    h->last_stride = p.n_max;
+}
+
+// rts_live_poll / rts_live_confidence: `read(b)` under stream b's sequence word.  Returns the feeds whose results the
+// words read reflect for every stream.
+template <class Read>
+static int live_read_published(const rts_live *h, Read read) {
+    const volatile int32_t *p = h->pub_host;
+    int fd = h->feeds;
+    for (int b = 0; b < h->geo.B; b++) {
+        const int seq = p[(size_t)b * kLiveWords + 3];
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        read(b);
+        if (seq < fd) fd = seq;
+    }
+    return fd;
+}
+
+// hipMalloc of n zeroed elements, once everything before it has succeeded.
+template <class T>
+static hipError_t live_dev_zeroed(hipError_t e, T **p, size_t n) {
+    if (e == hipSuccess) e = hipMalloc((void **)p, sizeof(T) * n);
+    if (e == hipSuccess) e = hipMemset(*p, 0, sizeof(T) * n);
+    return e;
 }
 
 }  // namespace rts
@@ -263,27 +368,13 @@ int rts_live_destroy(rts_live *h) {
         if (h->done[k]) (void)hipEventDestroy(h->done[k]);
     }
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->buf) (void)hipFree(h->buf);
-    if (h->pending) (void)hipFree(h->pending);
-    if (h->n_samples) (void)hipFree(h->n_samples);
-    if (h->n_frames) (void)hipFree(h->n_frames);
-    if (h->cols) (void)hipFree(h->cols);
-    if (h->dcols) (void)hipFree(h->dcols);
-    if (h->carry) (void)hipFree(h->carry);
-    if (h->has_carry) (void)hipFree(h->has_carry);
-    if (h->n_cols) (void)hipFree(h->n_cols);
-    free(h->has_carry_host);
-    free(h->has_carry_next);
+    void *dev[] = {h->args.buf,   h->args.pending,   h->args.n_samples, h->args.n_frames, h->args.cols,    h->args.dcols,
+                   h->args.carry, h->args.has_carry, h->args.n_cols,    h->rs_stage, h->rs_tail, h->rs_tot};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
     if (h->pub_host) (void)hipHostFree(h->pub_host);
     if (h->conf_host) (void)hipHostFree(h->conf_host);
-    if (h->rs_stage) (void)hipFree(h->rs_stage);
-    if (h->rs_tail) (void)hipFree(h->rs_tail);
-    if (h->rs_tot) (void)hipFree(h->rs_tot);
-    free(h->rs_tot_host);
-    free(h->rs_tot_next);
-    free(h->rs_nout);
-    free(h->pending_host);
-    free(h);
+    free(h);  // the mirrors with it
     return RTS_OK;
 }
 
@@ -306,112 +397,85 @@ static int live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int 
     if ((otw ? otw_batch(otw) : wtw_batch(wtw)) != B)
         return set_error(RTS_ERR_INVALID, "the tracker was created for %d streams, not B = %d",
                          otw ? otw_batch(otw) : wtw_batch(wtw), B);
-    int fft_len = 0, hop = 0;
-    if (int rc = rts_chroma_plan_info(plan, &fft_len, &hop); rc != RTS_OK) return rc;
-    if (max_pending < fft_len + hop || (long long)max_pending * B > 0x7fffffffLL)
+    LiveGeom geo = {B, 0, 0, max_pending, feature_kind == RTS_FEATURE_CHROMA_DIFF};  // no resampler so far
+    if (int rc = rts_chroma_plan_info(plan, &geo.L, &geo.hop); rc != RTS_OK) return rc;
+    if (max_pending < geo.L + geo.hop || (long long)max_pending * B > 0x7fffffffLL)
         return set_error(RTS_ERR_INVALID, "max_pending must be at least fft_len + hop samples (and B * max_pending < 2^31)");
-    int rs_L = 0, rs_M = 0, rs_half = 0, rs_T = 0, rs_device = -1;
-    long long in_cap = 0;
+    int rs_T = 0, rs_device = -1;
     if (rs) {
-        (void)resample_info(rs, &rs_L, &rs_M, &rs_half, &rs_T, &rs_device);
+        (void)resample_info(rs, &geo.rs_L, &geo.rs_M, &geo.rs_half, &rs_T, &rs_device);
         if (int rc = check_device(rs_device, "resample_plan"); rc != RTS_OK) return rc;
         // the most input samples whose output fits max_pending: n_out >= n L / M - 1 once a stream's first output exists,
         // n_out >= (n L - half) / M before
-        in_cap = ((long long)(max_pending + 1) * rs_M + rs_L - 1) / rs_L + rs_T + 2;
-        if (in_cap * B > 0x7fffffffLL)
-            return set_error(RTS_ERR_INVALID, "max_pending: B * %lld input-rate samples per staging slot must stay below 2^31", in_cap);
+        geo.in_cap = ((long long)(max_pending + 1) * geo.rs_M + geo.rs_L - 1) / geo.rs_L + rs_T + 2;
+        if (geo.in_cap * B > 0x7fffffffLL)
+            return set_error(RTS_ERR_INVALID, "max_pending: B * %lld input-rate samples per staging slot must stay below 2^31", geo.in_cap);
     }
-    rts_live *h = (rts_live *)calloc(1, sizeof(rts_live));
+    const size_t nB = (size_t)B;
+    rts_live *h = (rts_live *)calloc(1, sizeof(rts_live) + kMirrorBytes * nB);
     if (!h) return set_error(RTS_ERR_INVALID, "out of host memory");
     h->plan = plan;
     h->otw = otw;
     h->wtw = wtw;
-    h->B = B;
-    h->L = fft_len;
-    h->hop = hop;
-    h->cap = max_pending;
-    h->cols_cap = (max_pending - fft_len) / hop + 1;
+    h->geo = geo;
+    h->args.B = B;
+    h->args.cap = max_pending;
+    h->args.L = geo.L;
+    h->args.hop = geo.hop;
+    h->cols_cap = (max_pending - geo.L) / geo.hop + 1;
     h->slot = -1;
-    h->feature_kind = feature_kind;
-    h->samples_off = (2 * sizeof(int32_t) * (size_t)B + 255) & ~(size_t)255;
-    h->slot_bytes = h->samples_off + sizeof(float) * (size_t)B * max_pending;
-    h->pending_host = (long long *)calloc((size_t)B, sizeof(long long));
-    if (rs) {
-        h->rs = rs;
-        h->rs_L = rs_L;
-        h->rs_M = rs_M;
-        h->rs_half = rs_half;
-        h->rs_T = rs_T;
-        h->in_cap = in_cap;
-        h->slot_bytes = h->samples_off + sizeof(float) * (size_t)B * (size_t)h->in_cap;
-        h->rs_tot_host = (long long *)calloc(2 * (size_t)B, sizeof(long long));
-        h->rs_tot_next = (long long *)calloc(2 * (size_t)B, sizeof(long long));
-        h->rs_nout = (int32_t *)calloc((size_t)B, sizeof(int32_t));
-    }
+    h->args.samples_off = (2 * sizeof(int32_t) * nB + 255) & ~(size_t)255;
+    const size_t slot_bytes = h->args.samples_off + sizeof(float) * nB * (size_t)(rs ? geo.in_cap : max_pending);
+    h->rs = rs;
+    h->rs_T = rs_T;
+    long long *ll = reinterpret_cast<long long *>(h + 1);  // 8-byte values first
+    h->cur.pending = ll;
+    h->cur.rs_tot = ll + nB;
+    h->fp.next.pending = ll + 3 * nB;
+    h->fp.next.rs_tot = ll + 4 * nB;
+    h->fp.rs_nout = reinterpret_cast<int32_t *>(ll + 6 * nB);
+    h->fp.offs = h->fp.rs_nout + nB;
+    h->cur.has_carry = reinterpret_cast<uint8_t *>(h->fp.offs + nB);
+    h->fp.next.has_carry = h->cur.has_carry + nB;
     hipError_t e = hipGetDevice(&h->device);
     for (int k = 0; k < kLiveSlots && e == hipSuccess; k++) {
-        if ((e = hipHostMalloc((void **)&h->stage_host[k], h->slot_bytes, hipHostMallocDefault)) != hipSuccess) break;
-        if ((e = hipMalloc((void **)&h->stage_dev[k], h->slot_bytes)) != hipSuccess) break;
+        if ((e = hipHostMalloc((void **)&h->stage_host[k], slot_bytes, hipHostMallocDefault)) != hipSuccess) break;
+        if ((e = hipMalloc((void **)&h->stage_dev[k], slot_bytes)) != hipSuccess) break;
         if ((e = hipEventCreateWithFlags(&h->copied[k], hipEventDisableTiming)) != hipSuccess) break;
         if ((e = hipEventCreateWithFlags(&h->done[k], hipEventDisableTiming)) != hipSuccess) break;
     }
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->buf, sizeof(float) * (size_t)B * max_pending);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->pending, sizeof(int32_t) * (size_t)B);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->n_samples, sizeof(int32_t) * (size_t)B);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->n_frames, sizeof(int32_t) * (size_t)B);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->cols, sizeof(double) * 12 * (size_t)B * h->cols_cap);
-    const bool diff = feature_kind == RTS_FEATURE_CHROMA_DIFF;
-    if (diff) {
-        h->has_carry_host = (uint8_t *)calloc((size_t)B, 1);
-        h->has_carry_next = (uint8_t *)calloc((size_t)B, 1);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->dcols, sizeof(double) * 12 * (size_t)B * h->cols_cap);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->carry, sizeof(double) * 12 * (size_t)B);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->has_carry, sizeof(int32_t) * (size_t)B);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->n_cols, sizeof(int32_t) * (size_t)B);
-        if (e == hipSuccess) e = hipMemset(h->carry, 0, sizeof(double) * 12 * (size_t)B);
-        if (e == hipSuccess) e = hipMemset(h->has_carry, 0, sizeof(int32_t) * (size_t)B);
-        if (e == hipSuccess) e = hipMemset(h->n_cols, 0, sizeof(int32_t) * (size_t)B);
+    e = live_dev_zeroed(e, &h->args.buf, nB * max_pending);
+    e = live_dev_zeroed(e, &h->args.pending, nB);
+    e = live_dev_zeroed(e, &h->args.n_frames, nB);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->args.n_samples, sizeof(int32_t) * nB);  // written by every feed before it is read
+    if (e == hipSuccess) e = hipMalloc((void **)&h->args.cols, sizeof(double) * 12 * nB * h->cols_cap);
+    if (geo.diff) {
+        if (e == hipSuccess) e = hipMalloc((void **)&h->args.dcols, sizeof(double) * 12 * nB * h->cols_cap);
+        e = live_dev_zeroed(e, &h->args.carry, 12 * nB);
+        e = live_dev_zeroed(e, &h->args.has_carry, nB);
+        e = live_dev_zeroed(e, &h->args.n_cols, nB);
     }
     if (rs) {
-        const size_t out_bytes = h->samples_off + sizeof(float) * (size_t)B * max_pending;
-        if (e == hipSuccess) e = hipMalloc((void **)&h->rs_stage, out_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->rs_tail, sizeof(float) * 2 * (size_t)B * h->rs_T);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->rs_tot, sizeof(long long) * 4 * (size_t)B);
-        if (e == hipSuccess) e = hipMemset(h->rs_stage, 0, out_bytes);
-        if (e == hipSuccess) e = hipMemset(h->rs_tail, 0, sizeof(float) * 2 * (size_t)B * h->rs_T);
-        if (e == hipSuccess) e = hipMemset(h->rs_tot, 0, sizeof(long long) * 4 * (size_t)B);
+        e = live_dev_zeroed(e, &h->rs_stage, h->args.samples_off + sizeof(float) * nB * max_pending);
+        e = live_dev_zeroed(e, &h->rs_tail, 2 * nB * rs_T);
+        e = live_dev_zeroed(e, &h->rs_tot, 4 * nB);
     }
-    if (e == hipSuccess) e = hipMemset(h->n_frames, 0, sizeof(int32_t) * (size_t)B);
     if (e == hipSuccess)
-        e = hipHostMalloc((void **)&h->pub_host, sizeof(int32_t) * kLiveWords * (size_t)B, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&h->pub_dev, h->pub_host, 0);
-    if (e == hipSuccess) e = hipMemset(h->pending, 0, sizeof(int32_t) * (size_t)B);
-    if (e == hipSuccess) e = hipMemset(h->buf, 0, sizeof(float) * (size_t)B * max_pending);
-    if (e != hipSuccess || !h->pending_host || (diff && (!h->has_carry_host || !h->has_carry_next)) ||
-        (rs && (!h->rs_tot_host || !h->rs_tot_next || !h->rs_nout))) {
+        e = hipHostMalloc((void **)&h->pub_host, sizeof(int32_t) * kLiveWords * nB, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&h->args.pub, h->pub_host, 0);
+    if (e != hipSuccess) {
         rts_live_destroy(h);
         return set_error(RTS_ERR_HIP, "rts_live_create: %s", hipGetErrorString(e));
     }
-    memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * (size_t)B);
-    int rc;
-    if (otw) {
-        int32_t *st = nullptr;
-        rc = rts_otw_device_views(otw, nullptr, nullptr, &st);
-        h->state_dev = st;
-        h->state_len = RTS_STATE_LEN;
-        h->st_status = RTS_ST_STATUS;
-        h->st_live = RTS_ST_T;
-        h->st_ref = RTS_ST_J;
-    } else {
-        int32_t *st = nullptr;
-        rc = rts_wtw_state_view(wtw, &st);
-        h->state_dev = st;
-        h->state_len = RTS_WTW_STATE_LEN;
-        h->st_status = RTS_WTW_ST_STATUS;
-        h->st_live = RTS_WTW_ST_LIVE_PTR;
-        h->st_ref = RTS_WTW_ST_REF_PTR;
-    }
+    memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * nB);
+    int32_t *st = nullptr;
+    const int rc = otw ? rts_otw_device_views(otw, nullptr, nullptr, &st) : rts_wtw_state_view(wtw, &st);
+    h->args.state = st;
+    h->args.state_len = otw ? RTS_STATE_LEN : RTS_WTW_STATE_LEN;
+    h->args.st_status = otw ? RTS_ST_STATUS : RTS_WTW_ST_STATUS;
+    h->args.st_live = otw ? RTS_ST_T : RTS_WTW_ST_LIVE_PTR;
+    h->args.st_ref = otw ? RTS_ST_J : RTS_WTW_ST_REF_PTR;
     if (rc != RTS_OK) {
         rts_live_destroy(h);
         return rc;
@@ -442,32 +506,31 @@ int rts_live_reset(rts_live *h, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    const size_t nB = (size_t)h->geo.B;
     RTS_HIP(hipStreamSynchronize((hipStream_t)stream));
     RTS_HIP(hipStreamSynchronize(h->copy_stream));
-    RTS_HIP(hipMemsetAsync(h->pending, 0, sizeof(int32_t) * (size_t)h->B, (hipStream_t)stream));
-    memset(h->pending_host, 0, sizeof(long long) * (size_t)h->B);
-    if (h->has_carry) {
-        RTS_HIP(hipMemsetAsync(h->has_carry, 0, sizeof(int32_t) * (size_t)h->B, (hipStream_t)stream));
-        memset(h->has_carry_host, 0, (size_t)h->B);
-    }
+    RTS_HIP(hipMemsetAsync(h->args.pending, 0, sizeof(int32_t) * nB, (hipStream_t)stream));
+    if (h->args.has_carry) RTS_HIP(hipMemsetAsync(h->args.has_carry, 0, sizeof(int32_t) * nB, (hipStream_t)stream));
     if (h->rs) {
-        RTS_HIP(hipMemsetAsync(h->rs_tail, 0, sizeof(float) * 2 * (size_t)h->B * h->rs_T, (hipStream_t)stream));
-        RTS_HIP(hipMemsetAsync(h->rs_tot, 0, sizeof(long long) * 4 * (size_t)h->B, (hipStream_t)stream));
-        memset(h->rs_tot_host, 0, sizeof(long long) * 2 * (size_t)h->B);
+        RTS_HIP(hipMemsetAsync(h->rs_tail, 0, sizeof(float) * 2 * nB * h->rs_T, (hipStream_t)stream));
+        RTS_HIP(hipMemsetAsync(h->rs_tot, 0, sizeof(long long) * 4 * nB, (hipStream_t)stream));
     }
-    memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * (size_t)h->B);
+    memset(h + 1, 0, kMirrorBytes * nB);
+    memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * nB);
     if (h->conf_host) live_conf_clear(h);
     memset(h->used, 0, sizeof(h->used));
     h->slot = -1;
     h->feeds = 0;
     h->last_stride = 0;
-    return h->otw ? rts_otw_reset(h->otw, stream) : rts_wtw_reset(h->wtw, stream);
+    const int rc = h->otw ? rts_otw_reset(h->otw, stream) : rts_wtw_reset(h->wtw, stream);
+    if (rc == RTS_OK) h->failed = 0;  // everything a half-enqueued chain may have touched is as at create again
+    return rc;
 }
 
 int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,
                      void *stream) {
     using namespace rts;
-    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (int rc = live_usable(h); rc != RTS_OK) return rc;
     if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     // the tracker makes every check before it enqueues anything; behind the feeds already submitted on `stream`
@@ -475,39 +538,27 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
                         : rts_wtw_restart(h->wtw, mask_host, first_host, len_host, stream);
         rc != RTS_OK)
         return rc;
-    LiveArgs g;
-    memset(&g, 0, sizeof(g));
-    g.pending = h->pending;
-    g.has_carry = h->has_carry;
-    g.state = h->state_dev;
-    g.state_len = h->state_len;
-    g.st_status = h->st_status;
-    g.st_live = h->st_live;
-    g.st_ref = h->st_ref;
-    g.pub = h->pub_dev;
-    g.conf_mean = h->conf_mean_dev;
-    g.conf_n = h->conf_n_dev;
     RestartSel sel;
-    for (int pos = 0; restart_next_chunk(h->B, mask_host, nullptr, nullptr, &pos, &sel) > 0;) {
-        hipLaunchKernelGGL(live_restart_kernel, dim3((sel.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, sel, g);
+    for (int pos = 0; restart_next_chunk(h->geo.B, mask_host, nullptr, nullptr, &pos, &sel) > 0;) {
+        hipLaunchKernelGGL(live_restart_kernel, dim3((sel.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, sel, h->args);
         RTS_HIP(hipGetLastError());
         if (h->rs) {
-            if (int rc = resample_live_restart_enqueue(h->rs, sel, h->B, h->rs_tail, h->rs_tot, (hipStream_t)stream); rc != RTS_OK)
+            if (int rc = resample_live_restart_enqueue(h->rs, sel, h->geo.B, h->rs_tail, h->rs_tot, (hipStream_t)stream); rc != RTS_OK)
                 return rc;
         }
     }
-    for (int b = 0; b < h->B; b++)
-        if (mask_host[b]) {  // the mirrors: samples submitted from here on belong to the new run
-            h->pending_host[b] = 0;
-            if (h->has_carry_host) h->has_carry_host[b] = 0;
-            if (h->rs) h->rs_tot_host[2 * b] = h->rs_tot_host[2 * b + 1] = 0;
+    for (int b = 0; b < h->geo.B; b++)
+        if (mask_host[b]) {  // the mirror: samples submitted from here on belong to the new run
+            h->cur.pending[b] = 0;
+            h->cur.has_carry[b] = 0;
+            h->cur.rs_tot[2 * b] = h->cur.rs_tot[2 * b + 1] = 0;
         }
     return RTS_OK;
 }
 
 int rts_live_staging(rts_live *h, int32_t **counts_host, void **samples_host, long long *capacity_samples) {
     using namespace rts;
-    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (int rc = live_usable(h); rc != RTS_OK) return rc;
     if (h->slot < 0) {
         const int k = h->next;
         if (h->used[k]) RTS_HIP(hipEventSynchronize(h->done[k]));  // the feed that used this slot kSlots feeds ago
@@ -515,153 +566,28 @@ int rts_live_staging(rts_live *h, int32_t **counts_host, void **samples_host, lo
         h->slot = k;
     }
     if (counts_host) *counts_host = reinterpret_cast<int32_t *>(h->stage_host[h->slot]);
-    if (samples_host) *samples_host = h->stage_host[h->slot] + h->samples_off;
-    if (capacity_samples) *capacity_samples = (long long)h->B * (h->rs ? h->in_cap : h->cap);
+    if (samples_host) *samples_host = h->stage_host[h->slot] + h->args.samples_off;
+    if (capacity_samples) *capacity_samples = (long long)h->geo.B * (h->rs ? h->geo.in_cap : h->geo.cap);
     return RTS_OK;
 }
 
 int rts_live_submit(rts_live *h, int sample_kind, void *stream) {
     using namespace rts;
-    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (int rc = live_usable(h); rc != RTS_OK) return rc;
     if (h->slot < 0) return set_error(RTS_ERR_INVALID, "rts_live_submit without rts_live_staging");
     if (sample_kind != RTS_F32 && sample_kind != RTS_I16) return set_error(RTS_ERR_INVALID, "samples must be RTS_F32 or RTS_I16");
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
-    const int k = h->slot, B = h->B;
+    const int k = h->slot;
     int32_t *counts = reinterpret_cast<int32_t *>(h->stage_host[k]);
-    int32_t *offs = counts + B;
-    // validate, prefix offsets, and the mirror of what the device will do with these counts
-    long long total = 0;
-    for (int b = 0; b < B; b++) {
-        if (counts[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: negative sample count", b);
-        if (h->rs) {
-            // what the resampling launch will make of these counts: the next totals go to scratch and are committed once
-            // that launch has been enqueued; the tracker side sees the output samples
-            const long long in_next = h->rs_tot_host[2 * b] + counts[b];
-            const long long out_next = rts_resample_avail(in_next, h->rs_L, h->rs_M, h->rs_half);
-            const long long n_out = out_next - h->rs_tot_host[2 * b + 1];
-            if (counts[b] > h->in_cap)  // (more than any feed whose output fits max_pending)
-                return set_error(RTS_ERR_INVALID, "stream %d: %d new input samples exceed the staging capacity of %lld per stream",
-                                 b, counts[b], h->in_cap);
-            if (h->pending_host[b] + n_out > h->cap)
-                return set_error(RTS_ERR_INVALID, "stream %d: %lld pending + %lld resampled samples (of %d new input samples) "
-                                 "exceed max_pending = %d", b, h->pending_host[b], n_out, counts[b], h->cap);
-            h->rs_tot_next[2 * b] = in_next;
-            h->rs_tot_next[2 * b + 1] = out_next;
-            h->rs_nout[b] = (int32_t)n_out;
-        } else if (h->pending_host[b] + counts[b] > h->cap)
-            return set_error(RTS_ERR_INVALID, "stream %d: %lld pending + %d new samples exceed max_pending = %d", b,
-                             h->pending_host[b], counts[b], h->cap);
-        total += counts[b];
+    const FeedPlan &p = h->fp;
+    if (const LiveRefusal why = live_plan_feed(h->geo, h->cur, counts, &h->fp); why != kLiveFeedOk)
+        return live_refuse(h, why, p, counts);
+    memcpy(counts + h->geo.B, p.offs, sizeof(int32_t) * (size_t)h->geo.B);  // the second table of the slot
+    if (int rc = live_enqueue(h, p, k, sample_kind, stream); rc != RTS_OK) {
+        h->failed = 1;
+        return rc;
     }
-    const bool diff = h->feature_kind == RTS_FEATURE_CHROMA_DIFF;
-    int n_max = 0, n_max_diff = 0;  // most chroma columns of a stream; most columns a stream hands to the tracker
-    total = 0;
-    for (int b = 0; b < B; b++) {
-        offs[b] = (int32_t)total;
-        total += counts[b];
-        const long long q = h->pending_host[b] + (h->rs ? h->rs_nout[b] : counts[b]);
-        const int nf = q >= h->L ? (int)((q - h->L) / h->hop + 1) : 0;
-        if (nf > n_max) n_max = nf;
-        if (diff) {  // what live_diff_kernel will do with these counts; committed once it has been enqueued
-            const int nc = nf - (h->has_carry_host[b] ? 0 : 1);
-            if (nc > n_max_diff) n_max_diff = nc;
-            h->has_carry_next[b] = h->has_carry_host[b] || nf > 0;
-        }
-        const long long used = (long long)nf * h->hop;
-        h->pending_host[b] = q > used ? q - used : 0;  // hop > fft_len: a slice past the end leaves nothing
-    }
-    h->slot = -1;
-    h->next = (k + 1) % kLiveSlots;
-    h->used[k] = 1;
-    h->feeds += 1;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = h->samples_off + (size_t)total * (sample_kind == RTS_F32 ? sizeof(float) : sizeof(int16_t));
-    RTS_HIP(hipMemcpyAsync(h->stage_dev[k], h->stage_host[k], bytes, hipMemcpyHostToDevice, h->copy_stream));
-    RTS_HIP(hipEventRecord(h->copied[k], h->copy_stream));
-    RTS_HIP(hipStreamWaitEvent(s, h->copied[k], 0));
-    LiveArgs g;
-    memset(&g, 0, sizeof(g));
-    g.stage = h->stage_dev[k];
-    g.samples_off = h->samples_off;
-    g.sample_kind = sample_kind;
-    g.buf = h->buf;
-    g.pending = h->pending;
-    g.n_samples = h->n_samples;
-    g.n_frames = h->n_frames;
-    g.B = B;
-    g.cap = h->cap;
-    g.L = h->L;
-    g.hop = h->hop;
-    g.state = h->state_dev;
-    g.state_len = h->state_len;
-    g.st_status = h->st_status;
-    g.st_live = h->st_live;
-    g.st_ref = h->st_ref;
-    g.pub = h->pub_dev;
-    g.feed_no = h->feeds;
-    g.cols = h->cols;
-    g.dcols = h->dcols;
-    g.carry = h->carry;
-    g.has_carry = h->has_carry;
-    g.n_cols = h->n_cols;
-    g.cols_stride = n_max;
-    h->last_stride = n_max;
-    if (h->rs) {  // input-rate samples: resampled into the second staging-layout buffer, which the chain goes on from
-        const int cur = h->rs_cur, nxt = cur ^ 1;
-        const size_t tail_n = (size_t)B * h->rs_T, tot_n = 2 * (size_t)B;
-        int n_out_max = 0;
-        for (int b = 0; b < B; b++)
-            if (h->rs_nout[b] > n_out_max) n_out_max = h->rs_nout[b];
-        if (int rc = resample_live_enqueue(h->rs, h->stage_dev[k], h->samples_off, sample_kind, B, h->cap, h->rs_stage,
-                                           h->rs_tail + cur * tail_n, h->rs_tot + cur * tot_n, h->rs_tail + nxt * tail_n,
-                                           h->rs_tot + nxt * tot_n, n_out_max, s);
-            rc != RTS_OK)
-            return rc;
-        memcpy(h->rs_tot_host, h->rs_tot_next, sizeof(long long) * 2 * (size_t)B);  // the device totals will be these
-        h->rs_cur = nxt;
-        g.stage = h->rs_stage;
-        g.sample_kind = RTS_F32;
-    }
-    hipLaunchKernelGGL(live_append_kernel, dim3(B, kAppendSlices), dim3(256), 0, s, g);
-    RTS_HIP(hipGetLastError());
-    RTS_HIP(hipEventRecord(h->done[k], s));  // the staging slot (host and device side) is free again after this point
-    if (diff) {
-        // a chain of its own: the difference kernel runs in every feed (it also writes the n_cols of a feed without a
-        // chroma column), the tracker is pushed only when some stream has a column for it, and the compaction and the
-        // publication always follow
-        if (int rc = rts_chroma_frames_batch(h->plan, h->buf, RTS_F32, h->cap, h->n_samples, 0, B, n_max, h->n_frames, 1,
-                                             h->cols, RTS_F64, stream);
-            rc != RTS_OK)
-            return rc;
-        hipLaunchKernelGGL(live_diff_kernel, dim3(B), dim3(256), 0, s, g);
-        RTS_HIP(hipGetLastError());
-        memcpy(h->has_carry_host, h->has_carry_next, (size_t)B);  // the device flags will be these from here on
-        if (n_max_diff > 0) {
-            if (int rc = rts_otw_push(h->otw, h->dcols, RTS_F64, n_max, h->n_cols, stream); rc != RTS_OK) return rc;
-        }
-        if (int rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
-        hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
-        RTS_HIP(hipGetLastError());
-        return RTS_OK;
-    }
-    if (n_max == 0) {
-        if (h->wtw) {  // wtw.py:76-77 runs on every insert(), new column or not
-            if (int rc = rts_wtw_push(h->wtw, nullptr, RTS_F64, 0, nullptr, 1, stream); rc != RTS_OK) return rc;
-        }
-        if (int rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
-        hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);  // nothing to drop: pending, publication
-        RTS_HIP(hipGetLastError());
-        return RTS_OK;
-    }
-    int rc = rts_chroma_frames_batch(h->plan, h->buf, RTS_F32, h->cap, h->n_samples, 0, B, n_max, h->n_frames, 1, h->cols,
-                                     RTS_F64, stream);
-    if (rc != RTS_OK) return rc;
-    rc = h->otw ? rts_otw_push(h->otw, h->cols, RTS_F64, n_max, h->n_frames, stream)
-                : rts_wtw_push(h->wtw, h->cols, RTS_F64, n_max, h->n_frames, 1, stream);
-    if (rc != RTS_OK) return rc;
-    if (rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
-    hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
-    RTS_HIP(hipGetLastError());
+    live_commit(h, p, k);
     return RTS_OK;
 }
 
@@ -674,7 +600,7 @@ int rts_live_feed(rts_live *h, const void *samples_host, int sample_kind, const 
     long long capacity = 0;
     if (int rc = rts_live_staging(h, &counts, &samples, &capacity); rc != RTS_OK) return rc;
     long long total = 0;
-    for (int b = 0; b < h->B; b++) {
+    for (int b = 0; b < h->geo.B; b++) {
         if (counts_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: negative sample count", b);
         total += counts_host[b];
     }
@@ -682,7 +608,7 @@ int rts_live_feed(rts_live *h, const void *samples_host, int sample_kind, const 
         return set_error(RTS_ERR_INVALID, h->rs ? "%lld samples in one feed exceed the staging capacity of %lld input-rate samples"
                                                 : "%lld samples in one feed exceed B * max_pending = %lld", total, capacity);
     if (total > 0 && !samples_host) return set_error(RTS_ERR_INVALID, "samples_host is NULL");
-    memcpy(counts, counts_host, sizeof(int32_t) * (size_t)h->B);
+    memcpy(counts, counts_host, sizeof(int32_t) * (size_t)h->geo.B);
     if (total > 0) memcpy(samples, samples_host, (size_t)total * (sample_kind == RTS_F32 ? sizeof(float) : sizeof(int16_t)));
     return rts_live_submit(h, sample_kind, stream);
 }
@@ -691,17 +617,13 @@ int rts_live_poll(rts_live *h, int32_t *status, int32_t *positions, int *feeds_d
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     const volatile int32_t *p = h->pub_host;
-    int fd = h->feeds;
-    for (int b = 0; b < h->B; b++) {
-        const int seq = p[(size_t)b * kLiveWords + 3];
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const int fd = live_read_published(h, [=](int b) {
         if (status) status[b] = p[(size_t)b * kLiveWords + 0];
         if (positions) {
             positions[2 * b] = p[(size_t)b * kLiveWords + 1];
             positions[2 * b + 1] = p[(size_t)b * kLiveWords + 2];
         }
-        if (seq < fd) fd = seq;
-    }
+    });
     if (feeds_done) *feeds_done = fd;
     if (feeds_submitted) *feeds_submitted = h->feeds;
     return RTS_OK;
@@ -716,7 +638,7 @@ int rts_live_watch(rts_live *h, int K) {
                                               "on silent frames and its windows re-decide the path)");
     if (K > 0 && !h->conf_host) {
         if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
-        const size_t bytes = (sizeof(double) + sizeof(int32_t)) * (size_t)h->B;
+        const size_t bytes = (sizeof(double) + sizeof(int32_t)) * (size_t)h->geo.B;
         RTS_HIP(hipHostMalloc((void **)&h->conf_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
         void *dev = nullptr;
         if (hipError_t e = hipHostGetDevicePointer(&dev, h->conf_host, 0); e != hipSuccess) {
@@ -724,8 +646,8 @@ int rts_live_watch(rts_live *h, int K) {
             h->conf_host = nullptr;
             return set_error(RTS_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
         }
-        h->conf_mean_dev = reinterpret_cast<double *>(dev);
-        h->conf_n_dev = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(dev) + sizeof(double) * (size_t)h->B);
+        h->args.conf_mean = reinterpret_cast<double *>(dev);
+        h->args.conf_n = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(dev) + sizeof(double) * (size_t)h->geo.B);
         live_conf_clear(h);
     }
     h->watch_k = K;
@@ -736,17 +658,12 @@ int rts_live_confidence(rts_live *h, double *mean_cost, int32_t *n_points, int *
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (!h->conf_host) return set_error(RTS_ERR_INVALID, "rts_live_confidence before any rts_live_watch(K > 0)");
-    const volatile int32_t *p = h->pub_host;
     const volatile double *mean = reinterpret_cast<const volatile double *>(h->conf_host);
-    const volatile int32_t *n = reinterpret_cast<const volatile int32_t *>(h->conf_host + sizeof(double) * (size_t)h->B);
-    int fd = h->feeds;
-    for (int b = 0; b < h->B; b++) {
-        const int seq = p[(size_t)b * kLiveWords + 3];
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const volatile int32_t *n = reinterpret_cast<const volatile int32_t *>(h->conf_host + sizeof(double) * (size_t)h->geo.B);
+    const int fd = live_read_published(h, [=](int b) {
         if (mean_cost) mean_cost[b] = mean[b];
         if (n_points) n_points[b] = n[b];
-        if (seq < fd) fd = seq;
-    }
+    });
     if (feeds_done) *feeds_done = fd;
     return RTS_OK;
 }
@@ -754,18 +671,17 @@ int rts_live_confidence(rts_live *h, double *mean_cost, int32_t *n_points, int *
 int rts_live_columns_view(rts_live *h, double **cols_dev, int *cols_cap, int *cols_stride, int32_t **n_cols_dev) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    const bool diff = h->feature_kind == RTS_FEATURE_CHROMA_DIFF;
-    if (cols_dev) *cols_dev = diff ? h->dcols : h->cols;
+    if (cols_dev) *cols_dev = h->geo.diff ? h->args.dcols : h->args.cols;
     if (cols_cap) *cols_cap = h->cols_cap;
     if (cols_stride) *cols_stride = h->last_stride;
-    if (n_cols_dev) *n_cols_dev = diff ? h->n_cols : h->n_frames;
+    if (n_cols_dev) *n_cols_dev = h->geo.diff ? h->args.n_cols : h->args.n_frames;
     return RTS_OK;
 }
 
 int rts_live_pending(rts_live *h, long long *pending_host /* [B] */) {
     using namespace rts;
     if (!h || !pending_host) return set_error(RTS_ERR_INVALID, "NULL argument");
-    memcpy(pending_host, h->pending_host, sizeof(long long) * (size_t)h->B);
+    memcpy(pending_host, h->cur.pending, sizeof(long long) * (size_t)h->geo.B);
     return RTS_OK;
 }
 

@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "live_plan.h"
 
 // The bit contract forbids contracting the multiply and the add of a term into a fused multiply-add.  This pragma
 // switches contraction off for everything below under the build's -ffp-contract=off and under hipcc's own default
@@ -229,11 +230,7 @@ long long rts_resample_out_len(long long n_in, int L, int M) {
     return (n_in * L + M - 1) / M;
 }
 
-long long rts_resample_avail(long long in_total, int L, int M, int half) {
-    if (in_total <= 0 || L < 1 || M < 1) return 0;
-    const long long a = in_total * L - half;
-    return a > 0 ? (a + M - 1) / M : 0;
-}
+long long rts_resample_avail(long long in_total, int L, int M, int half) { return rts::resample_avail(in_total, L, M, half); }
 
 int rts_resample_destroy(rts_resample *p) {
     if (!p) return RTS_OK;
