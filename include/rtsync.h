@@ -290,6 +290,48 @@ int rts_dtw_paths(const void *a_dev, int a_dtype, long long a_stride, const int3
                   int32_t *path_dev, int32_t *path_len_dev, double *total_dev, void *ws_dev, size_t ws_bytes,
                   void *stream);
 
+/* Bytes of the device workspace rts_dtw_subseq_paths needs for B pairs of at most M_max x N_max: the layout and the size
+ * of rts_dtw_paths_workspace_bytes (the last row lives in a boundary row that call leaves unused). */
+int rts_dtw_subseq_paths_workspace_bytes(int M_max, int N_max, int B, size_t *bytes);
+
+/* Subsequence DTW with the path: rts_dtw_paths with both ends of b free, for aligning an excerpt (a restarted or
+ * re-acquired stream's history, a rehearsal take, a cut of a recording) against a whole piece offline.  The reference
+ * has no such function; the recurrence is dtw.DTW's (dtw.py:32-52: same cell cost, same step weights, same
+ * first-minimum rule) with the first row freed, and it serves the same corpus harness (tests.py:199-262) once the
+ * recordings on one side are excerpts.  For one pair, a ([M][F], rows, matched entirely) and b ([N][F], columns),
+ * c(i, j) = 1 - <a_i, b_j> as one fma chain (the cost of rts_dtw), float64, float32 inputs widened:
+ *   D[0][j] = c(0, j)
+ *   D[i][0] = D[i-1][0] + c(i, 0)
+ *   D[i][j] = first minimum of (D[i][j-1] + c, D[i-1][j] + c, D[i-1][j-1] + 2c)
+ *   end = first j minimising D[M-1][j], total = D[M-1][end]
+ *   path = from (M-1, end) the chosen predecessor of every cell until a cell of row 0 is reached, in forward order;
+ *          start = the column of that row-0 cell
+ * This is rts_locate's recurrence with RTS_COST_DOT -- (total, end, start) are its (cost, end, start) bit for bit --
+ * without its bound on M and with the path; total equals rts_dtw_paths' total of a against b[start .. end].  Features
+ * must be finite: a NaN frame makes that pair's results unspecified, nothing else (nothing is read or written out of
+ * bounds, path_len stays within [0, M_max + N_max]).
+ *   a_dev / a_dtype / a_stride / a_len_dev, b_dev / b_dtype / b_stride / b_len_dev, F, M_max, N_max, B: as rts_dtw_paths
+ *          (padding, 0 = shared -- typically many excerpts against one b --, device length tables or NULL, clamping).
+ *   path_dev: int32 [B][M_max + N_max][2]; the first path_len_dev[k] rows of pair k are the pairs (i, j) from
+ *          (0, start) to (M_k - 1, end); the rows behind them are left untouched.
+ *   path_len_dev: int32 [B]; total_dev: double [B]; start_dev, end_dev: int32 [B].
+ *   row_dev: optional (may be NULL) double [B][N_max]: row_dev[k][0 .. N_k) = D[M_k - 1][:], the rest is left untouched.
+ *   A pair with M_k < 1 or N_k < 1 gets path_len = 0, total = +inf and start = end = -1; nothing of it is read.
+ *   If the device pipeline reports a fault (as in rts_dtw), path_len = -1, total = NaN and start = end = -1.
+ *   ws_dev / ws_bytes: caller-owned, 16-byte aligned scratch of at least
+ *          rts_dtw_subseq_paths_workspace_bytes(M_max, N_max, B).
+ * Limits and errors as rts_dtw_paths: F == 12 (RTS_ERR_UNSUPPORTED otherwise), M_max, N_max, B >= 1, B <= 65535;
+ * RTS_ERR_INVALID names the argument (a NULL a_dev, b_dev, path_dev, path_len_dev, total_dev, start_dev, end_dev or
+ * ws_dev, a stride between 1 and the maximum, a short or misaligned workspace); all of them are reported before any
+ * HIP call.
+ * Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable). */
+int rts_dtw_subseq_paths(const void *a_dev, int a_dtype, long long a_stride, const int32_t *a_len_dev,
+                         const void *b_dev, int b_dtype, long long b_stride, const int32_t *b_len_dev,
+                         int F, int M_max, int N_max, int B,
+                         int32_t *path_dev, int32_t *path_len_dev, double *total_dev,
+                         int32_t *start_dev, int32_t *end_dev, double *row_dev /* optional [B][N_max] */,
+                         void *ws_dev, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Locate: subsequence DTW of B live excerpts against P pieces of a reference pool.
  * ------------------------------------------------------------------------------------------ */

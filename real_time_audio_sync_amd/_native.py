@@ -83,6 +83,9 @@ _decl("rts_dtw", _i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _i32
 _decl("rts_dtw_paths_workspace_bytes", _i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_size_t)])
 _decl("rts_dtw_paths", _i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                               ctypes.c_size_t, _vp])
+_decl("rts_dtw_subseq_paths_workspace_bytes", _i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_size_t)])
+_decl("rts_dtw_subseq_paths", _i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, ctypes.c_size_t, _vp])
 _decl("rts_locate", _i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                            _vp, _vp])
 

@@ -15,6 +15,10 @@
 // rts_dtw_paths is the same pipeline without the dense outputs: no dtw_cost_kernel, the strip DP without staging
 // (nothing but step codes, boundary rows and entry columns leaves the chip), and every pair with lengths of its own
 // (pair_dims) inside a workspace slice sized by the call's maxima.
+//
+// rts_dtw_subseq_paths is rts_dtw_paths with both ends of b free (sdp::DtwSubseqPolicy): dtw_subseq_sdp_kernel frees the
+// first row and parks the last one in the workspace, the backtrack (the FREE instantiations of dtw_hops_kernel / dtw_segment_kernel, or of
+// dtw_tail_kernel) starts at that row's first minimum and stops on row 0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -48,6 +52,9 @@ struct DtwArgs {
     // rts_dtw_paths only (NULL in rts_dtw): M and N above are then the maxima that size every pair's slices
     const int32_t *a_len, *b_len;  // [B] the pairs' own lengths (NULL = the maximum)
     double *total;                 // [B] acc_cost[M_k-1][N_k-1]
+    // rts_dtw_subseq_paths only: total is D[M_k-1][end]
+    int32_t *start, *end;          // [B] columns of the path's first and last point
+    double *row;                   // [B][N] D[M_k-1][:] or NULL
 };
 
 // The pair's own M and N: the maximum without a length table, and never more than it.  Everything a pair keeps in the
@@ -69,6 +76,27 @@ __device__ __forceinline__ void dtw_report(const DtwArgs &g, int pair, bool has_
         g.path_len[pair] = 0;
         if (g.total) g.total[pair] = __longlong_as_double(0x7ff0000000000000LL);  // +inf
     }
+}
+
+// The same for rts_dtw_subseq_paths, which also reports start and end.
+__device__ __forceinline__ void dtw_subseq_report(const DtwArgs &g, int pair, bool has_cells) {
+    dtw_report(g, pair, has_cells);
+    if (*g.err != 0 || !has_cells) {
+        g.start[pair] = -1;
+        g.end[pair] = -1;
+    }
+}
+
+// Where pair `pair` (M x N, its own lengths) keeps its last row and where its free-ended backtrack reports.
+__device__ __forceinline__ sdp::FreeEnds dtw_free_ends(const DtwArgs &g, int pair, int M, int N) {
+    const int last_rg = (sdp::n_strips(M) + g.n_strips_wg - 1) / g.n_strips_wg - 1;
+    sdp::FreeEnds fe;
+    fe.row = g.bnd + (size_t)pair * sdp::n_strips(g.M) * g.N + (size_t)last_rg * N;
+    fe.total = g.total + pair;
+    fe.start = g.start + pair;
+    fe.end = g.end + pair;
+    fe.row_out = g.row ? g.row + (size_t)pair * g.N : nullptr;
+    return fe;
 }
 
 // One thread per column j and kCostRows consecutive rows: b_j stays in registers, the a rows are wave-uniform
@@ -142,17 +170,52 @@ __global__ void __launch_bounds__(H == 2 ? 384 : 256) dtw_sdp_kernel(DtwArgs g) 
     });
 }
 
+// The strip DP of rts_dtw_subseq_paths: dtw_sdp_kernel<H, false> with the first row freed and the last row kept
+// (sdp::DtwSubseqPolicy) instead of the last cell.  A kernel of its own, so that the instantiations above stay the code
+// they were.
+template <int H>
+__global__ void __launch_bounds__(H == 2 ? 384 : 256) dtw_subseq_sdp_kernel(DtwArgs g) {
+    extern __shared__ __align__(16) unsigned char dtw_smem[];
+    const int pair = blockIdx.y;
+    int M, N;
+    pair_dims(g, pair, M, N);
+    if (M < 1 || N < 1) return;  // the whole workgroup: nothing of such a pair is read
+    const int n_rg = (sdp::n_strips(M) + g.n_strips_wg - 1) / g.n_strips_wg;
+    sdp::Problem pb;
+    pb.x = g.a_f64 ? (const void *)(reinterpret_cast<const double *>(g.a) + (long long)pair * g.a_stride * kDtwF)
+                   : (const void *)(reinterpret_cast<const float *>(g.a) + (long long)pair * g.a_stride * kDtwF);
+    pb.x_f64 = g.a_f64;
+    pb.yrec = g.yrec + (size_t)pair * g.N * sdp::kYRec;
+    pb.M = M;
+    pb.N = N;
+    pb.D = nullptr;
+    pb.ldD = g.N;
+    pb.codes = g.codes + (size_t)pair * sdp::codes_words(g.M, g.N);
+    pb.bnd = g.bnd + (size_t)pair * sdp::n_strips(g.M) * g.N;  // slot n_rg - 1 receives the last row (dtw_free_ends)
+    pb.entb = g.entb + (size_t)pair * sdp::n_strips(g.M) * g.N;
+    pb.err = g.err;
+    pb.last = nullptr;
+    sdp::for_each_rowgroup(g.ticket + pair, n_rg, g.n_strips_wg, dtw_smem, [&](int rg) {
+        sdp::run_rowgroup<sdp::DtwSubseqPolicy, false, H>(pb, rg, n_rg, g.n_strips_wg, dtw_smem);
+    });
+}
+
+// The backtrack kernels.  FREE: the ends of b are free (rts_dtw_subseq_paths, sdp::FreeEnds): the hops begin at the
+// first minimum of the last row, strip 0's walk stops on row 0, and start / end are reported too.
+template <bool FREE>
 __global__ void __launch_bounds__(64) dtw_hops_kernel(DtwArgs g) {
     __shared__ uint32_t win[2 * sdp::kBtChunks * 64];
     const int pair = blockIdx.x, S = sdp::n_strips(g.M);
     int M, N;
     pair_dims(g, pair, M, N);
     if (M < 1 || N < 1) return;
-    sdp::path_hops(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), g.entb + (size_t)pair * S * g.N, M, N,
-                   g.cross + (size_t)pair * S, win);
+    sdp::FreeEnds fe;
+    if constexpr (FREE) fe = dtw_free_ends(g, pair, M, N);
+    sdp::path_hops<FREE>(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), g.entb + (size_t)pair * S * g.N, M, N,
+                         g.cross + (size_t)pair * S, win, FREE ? &fe : nullptr);
 }
 
-template <int PASS>
+template <int PASS, bool FREE>
 __global__ void __launch_bounds__(64) dtw_segment_kernel(DtwArgs g) {
     __shared__ uint32_t win[2 * sdp::kBtChunks * 64];
     const int pair = blockIdx.y, s = blockIdx.x, S = sdp::n_strips(g.M);
@@ -161,14 +224,23 @@ __global__ void __launch_bounds__(64) dtw_segment_kernel(DtwArgs g) {
     pair_dims(g, pair, M, N);
     const bool has_cells = (M >= 1 && N >= 1);
     // the grid has a workgroup per strip of the longest pair: the ones beyond this pair's strips touch nothing
-    if (has_cells && s < sdp::n_strips(M))
-        sdp::path_segment(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), M, N, s, g.cross + (size_t)pair * S,
-                          g.lens + (size_t)pair * S, PASS, path, g.path_len + pair, win,
-                          g.pscr + (size_t)pair * 2 * sdp::scratch_pairs(g.M, g.N));
-    if (PASS == 1 && s == 0 && threadIdx.x == 0) dtw_report(g, pair, has_cells);
+    if (has_cells && s < sdp::n_strips(M)) {
+        sdp::FreeEnds fe;
+        if constexpr (FREE) fe = dtw_free_ends(g, pair, M, N);
+        sdp::path_segment<FREE>(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), M, N, s, g.cross + (size_t)pair * S,
+                                g.lens + (size_t)pair * S, PASS, path, g.path_len + pair, win,
+                                g.pscr + (size_t)pair * 2 * sdp::scratch_pairs(g.M, g.N), FREE ? &fe : nullptr);
+    }
+    if (PASS == 1 && s == 0 && threadIdx.x == 0) {
+        if constexpr (FREE)
+            dtw_subseq_report(g, pair, has_cells);
+        else
+            dtw_report(g, pair, has_cells);
+    }
 }
 
 // hops + both segment passes of a short pair in one launch (at most sdp::kTailStrips strips: one wave each)
+template <bool FREE>
 __global__ void __launch_bounds__(64 * sdp::kTailStrips) dtw_tail_kernel(DtwArgs g) {
     extern __shared__ __align__(16) unsigned char dtw_smem[];
     const int pair = blockIdx.x, S = sdp::n_strips(g.M);
@@ -177,13 +249,22 @@ __global__ void __launch_bounds__(64 * sdp::kTailStrips) dtw_tail_kernel(DtwArgs
     const bool has_cells = (M >= 1 && N >= 1);  // uniform over the workgroup
     // one wave per strip of the longest pair: the waves beyond this pair's strips go through path_tail's barriers and
     // write nothing
-    if (has_cells)
-        sdp::path_tail(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), g.entb + (size_t)pair * S * g.N, M, N,
-                       g.cross + (size_t)pair * S, g.lens + (size_t)pair * S, g.path + (size_t)pair * (g.M + g.N) * 2,
-                       g.path_len + pair, reinterpret_cast<uint32_t *>(dtw_smem),
-                       g.pscr + (size_t)pair * 2 * sdp::scratch_pairs(g.M, g.N));
+    if (has_cells) {
+        sdp::FreeEnds fe;
+        if constexpr (FREE) fe = dtw_free_ends(g, pair, M, N);
+        sdp::path_tail<FREE>(g.codes + (size_t)pair * sdp::codes_words(g.M, g.N), g.entb + (size_t)pair * S * g.N, M, N,
+                             g.cross + (size_t)pair * S, g.lens + (size_t)pair * S,
+                             g.path + (size_t)pair * (g.M + g.N) * 2, g.path_len + pair,
+                             reinterpret_cast<uint32_t *>(dtw_smem),
+                             g.pscr + (size_t)pair * 2 * sdp::scratch_pairs(g.M, g.N), FREE ? &fe : nullptr);
+    }
     __syncthreads();
-    if (threadIdx.x == 0) dtw_report(g, pair, has_cells);
+    if (threadIdx.x == 0) {
+        if constexpr (FREE)
+            dtw_subseq_report(g, pair, has_cells);
+        else
+            dtw_report(g, pair, has_cells);
+    }
 }
 
 __global__ void __launch_bounds__(256) dtw_back_decode_kernel(DtwArgs g) {
@@ -198,9 +279,9 @@ __global__ void __launch_bounds__(256) dtw_back_decode_kernel(DtwArgs g) {
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// Workgroups of dtw_sdp_kernel<3, STAGE> (one strip each) / <2, STAGE> (two strips each) the current device holds at
-// once; queried once per device and LDS padding (sdp::pick_config, "Residency").
-template <bool STAGE>
+// Workgroups of the strip-DP kernel K3 (one strip each) / K2 (two strips each) the current device holds at once; queried
+// once per kernel pair, device and LDS padding (sdp::pick_config, "Residency").
+template <void (*K3)(DtwArgs), void (*K2)(DtwArgs)>
 static int dtw_residency(int &r1, int &r2) {
     static int cache[16][3];  // [device]: pad + 1, r1, r2
     int dev = 0;
@@ -212,10 +293,10 @@ static int dtw_residency(int &r1, int &r2) {
         r2 = c[2];
         return RTS_OK;
     }
-    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dtw_sdp_kernel<2, STAGE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dtw_sdp_kernel<3, STAGE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    r1 = sdp::resident_blocks(dtw_sdp_kernel<3, STAGE>, 256, sdp::lds_bytes(1) + pad);
-    r2 = sdp::resident_blocks(dtw_sdp_kernel<2, STAGE>, 384, sdp::lds_bytes(2) + pad);
+    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K2), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K3), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    r1 = sdp::resident_blocks(K3, 256, sdp::lds_bytes(1) + pad);
+    r2 = sdp::resident_blocks(K2, 384, sdp::lds_bytes(2) + pad);
     if (c) {
         c[1] = r1;
         c[2] = r2;
@@ -256,13 +337,16 @@ static int dtw_check(int a_dtype, int b_dtype, int F, int M, int N, int B, const
 }
 
 // Carves the workspace and enqueues the pipeline; `g` arrives with the caller's buffers, sizes and dtypes filled in.
-// DENSE: rts_dtw (cost and acc_cost are written); otherwise rts_dtw_paths.
-template <bool DENSE>
+// DENSE: rts_dtw (cost and acc_cost are written); otherwise rts_dtw_paths or, with SUBSEQ, rts_dtw_subseq_paths.
+template <bool DENSE, bool SUBSEQ = false>
 static int dtw_enqueue(DtwArgs g, int B, void *ws_dev, hipStream_t s) {
+    static_assert(!(DENSE && SUBSEQ), "the subsequence form has no dense outputs");
+    constexpr auto k_sdp3 = SUBSEQ ? &dtw_subseq_sdp_kernel<3> : &dtw_sdp_kernel<3, DENSE>;
+    constexpr auto k_sdp2 = SUBSEQ ? &dtw_subseq_sdp_kernel<2> : &dtw_sdp_kernel<2, DENSE>;
     const int M = g.M, N = g.N;
     const int strips = sdp::n_strips(M);
     int NS, H, G, res1 = 0, res2 = 0;
-    if (int rc = dtw_residency<DENSE>(res1, res2); rc != RTS_OK) return rc;
+    if (int rc = dtw_residency<k_sdp3, k_sdp2>(res1, res2); rc != RTS_OK) return rc;
     if (res1 < 1 && res2 < 1)
         return set_error(RTS_ERR_HIP, "the occupancy query reports no resident workgroup for the strip-DP kernel on this device");
     sdp::pick_config(strips, B, res1, res2, NS, H, G);
@@ -308,16 +392,16 @@ static int dtw_enqueue(DtwArgs g, int B, void *ws_dev, hipStream_t s) {
     hipLaunchKernelGGL(dtw_prep_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, g);
     const size_t smem = sdp::lds_bytes(NS) + sdp::lds_pad();
     if (H == 2)
-        hipLaunchKernelGGL((dtw_sdp_kernel<2, DENSE>), dim3(G, B), dim3(64 * NS * 3), smem, s, g);
+        hipLaunchKernelGGL(k_sdp2, dim3(G, B), dim3(64 * NS * 3), smem, s, g);
     else
-        hipLaunchKernelGGL((dtw_sdp_kernel<3, DENSE>), dim3(G, B), dim3(64 * NS * 4), smem, s, g);
+        hipLaunchKernelGGL(k_sdp3, dim3(G, B), dim3(64 * NS * 4), smem, s, g);
     RTS_HIP(hipGetLastError());
     if (strips <= sdp::kTailStrips) {
-        hipLaunchKernelGGL(dtw_tail_kernel, dim3(B), dim3(64 * strips), sdp::tail_lds_bytes(strips), s, g);
+        hipLaunchKernelGGL(dtw_tail_kernel<SUBSEQ>, dim3(B), dim3(64 * strips), sdp::tail_lds_bytes(strips), s, g);
     } else {
-        hipLaunchKernelGGL(dtw_hops_kernel, dim3(B), dim3(64), 0, s, g);
-        hipLaunchKernelGGL((dtw_segment_kernel<0>), dim3(strips, B), dim3(64), 0, s, g);
-        hipLaunchKernelGGL((dtw_segment_kernel<1>), dim3(strips, B), dim3(64), 0, s, g);
+        hipLaunchKernelGGL(dtw_hops_kernel<SUBSEQ>, dim3(B), dim3(64), 0, s, g);
+        hipLaunchKernelGGL((dtw_segment_kernel<0, SUBSEQ>), dim3(strips, B), dim3(64), 0, s, g);
+        hipLaunchKernelGGL((dtw_segment_kernel<1, SUBSEQ>), dim3(strips, B), dim3(64), 0, s, g);
     }
     RTS_HIP(hipGetLastError());
     if (g.back) {
@@ -363,6 +447,8 @@ int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_de
     g.a_len = nullptr;
     g.b_len = nullptr;
     g.total = nullptr;
+    g.start = g.end = nullptr;
+    g.row = nullptr;
     return dtw_enqueue<true>(g, B, ws_dev, (hipStream_t)stream);
 }
 
@@ -407,7 +493,59 @@ int rts_dtw_paths(const void *a_dev, int a_dtype, long long a_stride, const int3
     g.a_len = a_len_dev;
     g.b_len = b_len_dev;
     g.total = total_dev;
+    g.start = g.end = nullptr;
+    g.row = nullptr;
     return dtw_enqueue<false>(g, B, ws_dev, (hipStream_t)stream);
+}
+
+// The workspace is rts_dtw_paths': the last row lives in the boundary slot of a pair's last row group, which that call
+// leaves unused.
+int rts_dtw_subseq_paths_workspace_bytes(int M_max, int N_max, int B, size_t *bytes) {
+    return rts::dtw_workspace(M_max, N_max, B, bytes, "M_max", "N_max");
+}
+
+int rts_dtw_subseq_paths(const void *a_dev, int a_dtype, long long a_stride, const int32_t *a_len_dev, const void *b_dev,
+                         int b_dtype, long long b_stride, const int32_t *b_len_dev, int F, int M_max, int N_max, int B,
+                         int32_t *path_dev, int32_t *path_len_dev, double *total_dev, int32_t *start_dev,
+                         int32_t *end_dev, double *row_dev, void *ws_dev, size_t ws_bytes, void *stream) {
+    using namespace rts;
+    if (!a_dev) return set_error(RTS_ERR_INVALID, "a_dev is NULL");
+    if (!b_dev) return set_error(RTS_ERR_INVALID, "b_dev is NULL");
+    if (!path_dev) return set_error(RTS_ERR_INVALID, "path_dev is NULL");
+    if (!path_len_dev) return set_error(RTS_ERR_INVALID, "path_len_dev is NULL");
+    if (!total_dev) return set_error(RTS_ERR_INVALID, "total_dev is NULL");
+    if (!start_dev) return set_error(RTS_ERR_INVALID, "start_dev is NULL");
+    if (!end_dev) return set_error(RTS_ERR_INVALID, "end_dev is NULL");
+    if (!ws_dev) return set_error(RTS_ERR_INVALID, "ws_dev is NULL");
+    if (int rc = dtw_check(a_dtype, b_dtype, F, M_max, N_max, B, ws_dev, ws_bytes, "M_max", "N_max",
+                           rts_dtw_subseq_paths_workspace_bytes, "rts_dtw_subseq_paths_workspace_bytes");
+        rc != RTS_OK)
+        return rc;
+    if (a_stride != 0 && a_stride < M_max)
+        return set_error(RTS_ERR_INVALID, "a_stride must be 0 (shared) or >= M_max (got %lld)", a_stride);
+    if (b_stride != 0 && b_stride < N_max)
+        return set_error(RTS_ERR_INVALID, "b_stride must be 0 (shared) or >= N_max (got %lld)", b_stride);
+    DtwArgs g;
+    g.a = a_dev;
+    g.b = b_dev;
+    g.cost = nullptr;
+    g.acc = nullptr;
+    g.back = nullptr;
+    g.path = path_dev;
+    g.path_len = path_len_dev;
+    g.a_stride = a_stride;
+    g.b_stride = b_stride;
+    g.M = M_max;
+    g.N = N_max;
+    g.a_f64 = a_dtype == RTS_F64;
+    g.b_f64 = b_dtype == RTS_F64;
+    g.a_len = a_len_dev;
+    g.b_len = b_len_dev;
+    g.total = total_dev;
+    g.start = start_dev;
+    g.end = end_dev;
+    g.row = row_dev;
+    return dtw_enqueue<false, true>(g, B, ws_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -123,7 +123,8 @@ struct Problem {
     double *D;             // optional row-major output, leading dimension ldD
     long long ldD;
     uint32_t *codes;       // [n_strips][n_chunks][64] packed step codes
-    unsigned long long *bnd;  // [n_rowgroups][N] bottom rows handed between row groups (sentinel-filled)
+    unsigned long long *bnd;  // [n_rowgroups][N] bottom rows handed between row groups (sentinel-filled); the last row
+                              // group hands nothing on: with P::kSubseq its slot receives the matrix's last row
     int32_t *entb;         // [n_strips][N]: for every cell of a strip's bottom row, the column at which its best path
                            // entered the strip from the row above (what lets the backtrack hop strip to strip)
     int32_t *err;          // set to 1 if a poll ran into its bound (never expected)
@@ -192,6 +193,7 @@ __device__ __forceinline__ double vmin(double a, double b) {
 // np.argmin = first minimum.
 struct DtwPolicy {
     static constexpr bool kNorm = false;
+    static constexpr bool kSubseq = false;  // see DtwSubseqPolicy
     static constexpr int kHelper0Cols = 0;  // cost columns per chunk on the helper that also runs the entry-column pass
     static __device__ __forceinline__ double norm(const double (&)[kF]) { return 0.0; }
     static __device__ __forceinline__ double cost(const double (&x)[kF], double, const double (&y)[kF], double) {
@@ -239,10 +241,38 @@ struct DtwPolicy {
     }
 };
 
+// Subsequence DTW (rts_dtw_subseq_paths): DtwPolicy's costs and options with the first row freed -- D[0][j] = c(0, j),
+// so that a match may begin at any column -- and, because it may also end at any column, the whole last row kept
+// (kSubseq: run_rowgroup parks it in the boundary slot the last row group does not use).  Below row 0 the cell is
+// DtwPolicy's: the same DPP -> min -> min -> add chain, the same first-column rule.  Row 0's step codes are never read
+// (the backtrack stops when it reaches row 0).
+struct DtwSubseqPolicy : DtwPolicy {
+    static constexpr bool kSubseq = true;
+    static __device__ __forceinline__ void cell(bool first_row, bool first_col, double up, double left, double diag,
+                                                double c, double &dv, int &code) {
+        const double o0 = left + c, o1 = up + c, o2 = diag + 2 * c;
+        const double m01 = vmin(o0, o1);
+        double best = vmin(m01, o2);
+        int s = (o1 < o0) ? kUp : kLeft;
+        s = (o2 < m01) ? kDiag : s;
+        if (first_col) {
+            best = o1;
+            s = kUp;
+        }
+        if (first_row) {  // whatever the column
+            best = c;
+            s = kLeft;
+        }
+        dv = best;
+        code = s;
+    }
+};
+
 // wtw.py:169 cost = 1 - x.y / (|x| |y|) (np.dot on strided columns: OpenBLAS ddot order, two accumulators; norms
 // are fma chains), wtw.py:201-215 candidates (i-1,j), (i,j-1), (i-1,j-1) with strict '<' in that order.
 struct WtwPolicy {
     static constexpr bool kNorm = true;
+    static constexpr bool kSubseq = false;
     static constexpr int kHelper0Cols = 2;  // a normalised-cosine cost is ~3x the work of a plain dot product
     static __device__ __forceinline__ double norm(const double (&v)[kF]) {
         double s = 0.0;
@@ -701,6 +731,17 @@ __device__ __forceinline__ void run_rowgroup(const Problem &pb, int rg, int n_rg
 #endif
             pb.codes[((size_t)strip * nch + m) * 64 + lane] = codes;
             codes_l[(m & 1) * 64 + lane] = codes;
+            if constexpr (P::kSubseq) {
+                // The matrix's last row, lane (M-1) & 63 of the last strip: the columns finished in this chunk go to
+                // the boundary slot of the last row group, which hands nothing on (to_hbm is false there).  Plain
+                // fire-and-forget stores like the step codes; the backtrack's first kernel reads them (last_row_min).
+                const int ll = (M - 1) & 63, col = kChunk * m - ll + lane;
+                if (strip == n_strips(M) - 1 && lane < kChunk && col >= 0 && col < N) {
+                    __builtin_amdgcn_wave_barrier();
+                    bnd_out[col] = (unsigned long long)__double_as_longlong(
+                        tile_mine[(size_t)(m % kTiles) * kChunk * kStageLd + lane * kStageLd + ll]);
+                }
+            }
             if (pb.last) {  // uniform.  Cell (M-1, N-1): lane (M-1) & 63 of the last strip, at strip-step N-1 + lane
                 const int ll = (M - 1) & 63, sl = N - 1 + ll;
                 if (strip == n_strips(M) - 1 && (sl >> 4) == m && lane == ll) *pb.last = tile_w[(sl & 15) * kStageLd];
@@ -750,6 +791,9 @@ constexpr int kBtChunks = 8;
 // (the start included, the first point outside the strip excluded) is written to out[2 * (out_base + k)] when `out` is
 // not null -- in walk order, i.e. the path backwards.  Returns the number of visited points; (i, j) is left at the first
 // position outside the strip (or at (0, 0), which counts as visited).
+// ROW0: the walk also ends at the first cell of row 0 it reaches, whatever its column (subsequence DTW: the path may
+// begin anywhere on row 0); that cell counts as visited, (i, j) is left on it and its step code is not read.
+template <bool ROW0 = false>
 __device__ __forceinline__ int walk_strip(const uint32_t *codes, int N, int &i, int &j, int32_t *out, int out_base,
                                           uint32_t *win) {
     const int lane = threadIdx.x & 63;
@@ -792,7 +836,7 @@ __device__ __forceinline__ int walk_strip(const uint32_t *codes, int N, int &i, 
             // the current position is inside the strip: visit it
             if (out && lane == 0) *reinterpret_cast<int2 *>(out + 2 * (size_t)(out_base + n)) = make_int2(i, j);
             n++;
-            if (i == 0 && j == 0) {
+            if (i == 0 && (ROW0 || j == 0)) {
                 inside = false;
                 break;
             }
@@ -825,15 +869,61 @@ __device__ __forceinline__ int walk_strip(const uint32_t *codes, int N, int &i, 
     return n;
 }
 
-// One wave: cross[s] = column at which the path crosses the bottom row of strip s (s < S - 1), cross[S-1] = N - 1.
+// Free ends (subsequence DTW, DtwSubseqPolicy): the path ends at the first minimum of the last row and begins wherever it
+// reaches row 0.  What the backtrack needs for that, and where the answers go.
+struct FreeEnds {
+    const unsigned long long *row;  // D[M-1][0..N) as the DP wave parked it (the last row group's boundary slot)
+    double *total;                  // D[M-1][end]
+    int32_t *start, *end;           // columns of the path's first and last point
+    double *row_out;                // optional copy of D[M-1][0..N)
+};
+
+// One wave: the first minimum of the last row (strict <, columns ascending; wave-uniform return, always inside [0, N)
+// whatever the values), stored with its column; the row is copied out on the way when wanted.  Coalesced loads, each
+// lane keeps the first minimum of its columns, then a butterfly over (value, column) pairs -- a total order for
+// non-NaN values, so every lane ends with the same pair.
+__device__ __forceinline__ int last_row_min(const FreeEnds &fe, int N) {
+    const int lane = threadIdx.x & 63;
+    double v = __longlong_as_double(0x7ff0000000000000LL);  // +inf: a lane without columns never wins
+    int c = 0x7fffffff;
+    for (int j = lane; j < N; j += 64) {
+        const double d = __longlong_as_double((long long)fe.row[j]);
+        if (fe.row_out) fe.row_out[j] = d;
+        if (j == lane || d < v) {
+            v = d;
+            c = j;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double ov = __shfl_xor(v, d);
+        const int oc = __shfl_xor(c, d);
+        if (ov < v || (ov == v && oc < c)) {
+            v = ov;
+            c = oc;
+        }
+    }
+    v = readlane_d(v, 0);  // lane 0 always holds a column of its own, NaN or not
+    c = __builtin_amdgcn_readlane(c, 0);
+    c = c < 0 ? 0 : (c >= N ? N - 1 : c);
+    if (lane == 0) {
+        *fe.total = v;
+        *fe.end = c;
+    }
+    return c;
+}
+
+// One wave: cross[s] = column at which the path crosses the bottom row of strip s (s < S - 1), cross[S-1] = the column
+// the path ends at: N - 1, or with FREE ends the column of the last row's first minimum.
 // entb[s][j] is the column at which the best path of (exit row of strip s, column j) came in from the row above the
 // strip (the exit row is the bottom row, or the matrix's last row in the last strip), so the crossings follow from one
 // dependent load per strip and no strip has to be walked.
+template <bool FREE = false>
 __device__ __forceinline__ void path_hops(const uint32_t *codes, const int32_t *entb, int M, int N, int32_t *cross,
-                                          uint32_t *win) {
+                                          uint32_t *win, const FreeEnds *fe = nullptr) {
     const int lane = threadIdx.x & 63;
     const int S = n_strips(M);
     int j = N - 1;
+    if constexpr (FREE) j = last_row_min(*fe, N);
     if (lane == 0) cross[S - 1] = j;
     for (int s = S - 1; s >= 1; s--) {
         j = entb[(size_t)s * N + j];  // uniform load; one dependent round trip per strip
@@ -847,17 +937,23 @@ __device__ __forceinline__ void path_hops(const uint32_t *codes, const int32_t *
 // different strips cannot overlap (a segment has at most 64 + cross[s] - cross[s-1] points), and 64 n_strips + N pairs
 // hold them all.  pass 1: with the lens of all strips known, a coalesced copy to the segment's place in path[] in
 // forward order; *total (if not null, strip 0 only) receives the path length.
+// FREE ends: strip 0's walk stops at the first cell of row 0 it reaches and reports that cell's column as the path's
+// start (a segment of strip 0 then has at most 64 + cross[0] - start points: the parking places hold as before).
 __host__ __device__ inline size_t scratch_pairs(int M, int N) { return (size_t)64 * n_strips(M) + N; }
+template <bool FREE = false>
 __device__ __forceinline__ void path_segment(const uint32_t *codes, int M, int N, int s, const int32_t *cross,
                                              int32_t *lens, int pass, int32_t *path, int32_t *total, uint32_t *win,
-                                             int32_t *scratch) {
+                                             int32_t *scratch, const FreeEnds *fe = nullptr) {
     const int lane = threadIdx.x & 63;
     const int S = n_strips(M);
     const int park = 64 * s + (s > 0 ? cross[s - 1] : 0);
     if (pass == 0) {
         int i = (s == S - 1) ? M - 1 : 64 * s + 63, j = cross[s];
-        const int n = walk_strip(codes, N, i, j, scratch, park, win);
+        const int n = walk_strip<FREE>(codes, N, i, j, scratch, park, win);
         if (lane == 0) lens[s] = n;
+        if constexpr (FREE) {
+            if (s == 0 && lane == 0) *fe->start = j;
+        }
         return;
     }
     int off = 0, all = 0;  // points in the strips above mine come first
@@ -883,16 +979,18 @@ __device__ __forceinline__ void path_segment(const uint32_t *codes, int M, int N
 // dynamic LDS, 2 * kBtChunks * 64 dwords per wave.
 constexpr int kTailStrips = 12;  // 48 KB of dynamic LDS: below the 64 KB a launch gets without an attribute, static LDS included
 __host__ __device__ inline size_t tail_lds_bytes(int S) { return sizeof(uint32_t) * 2 * kBtChunks * 64 * (size_t)S; }
+template <bool FREE = false>
 __device__ __forceinline__ void path_tail(const uint32_t *codes, const int32_t *entb, int M, int N, int32_t *cross,
-                                          int32_t *lens, int32_t *path, int32_t *total, uint32_t *win, int32_t *scratch) {
+                                          int32_t *lens, int32_t *path, int32_t *total, uint32_t *win, int32_t *scratch,
+                                          const FreeEnds *fe = nullptr) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int S = n_strips(M);
     uint32_t *mywin = win + (size_t)wave * 2 * kBtChunks * 64;
-    if (wave == 0) path_hops(codes, entb, M, N, cross, mywin);
+    if (wave == 0) path_hops<FREE>(codes, entb, M, N, cross, mywin, fe);
     __syncthreads();
-    if (wave < S) path_segment(codes, M, N, wave, cross, lens, 0, path, total, mywin, scratch);
+    if (wave < S) path_segment<FREE>(codes, M, N, wave, cross, lens, 0, path, total, mywin, scratch, fe);
     __syncthreads();
-    if (wave < S) path_segment(codes, M, N, wave, cross, lens, 1, path, total, mywin, scratch);
+    if (wave < S) path_segment<FREE>(codes, M, N, wave, cross, lens, 1, path, total, mywin, scratch, fe);
 }
 
 }  // namespace sdp

@@ -1,5 +1,6 @@
 """Drop-in for the reference's dtw.py: ``DTW(seq_a, seq_b) -> (cost, acc_cost, path)``, plus a
-batched form over many pairs and a path-only form over pairs of different lengths (``dtw_paths``, ``align_pairs``).
+batched form over many pairs, a path-only form over pairs of different lengths (``dtw_paths``, ``align_pairs``) and its
+subsequence form for excerpts against whole pieces (``dtw_subseq_paths``, ``align_excerpts``).
 Computation: csrc/dtw.hip (reference: dtw.py:5-53)."""
 import ctypes
 
@@ -69,6 +70,20 @@ def _lengths(v, B, dev, name):
     return t
 
 
+def _infer_pairs(a_dev, b_dev, a_len, b_len):
+    """The number of pairs of a path-only call: that of whichever side is batched; with both sides shared, the number of
+    lengths given (a_len if given, else b_len), 1 without any.  ValueError when the two sides hold different numbers."""
+    sa, sb = a_dev.dim() == 2, b_dev.dim() == 2
+    if not sa and not sb and a_dev.shape[0] != b_dev.shape[0]:
+        raise ValueError("a_dev holds %d pairs, b_dev %d" % (a_dev.shape[0], b_dev.shape[0]))
+    if not sa:
+        return a_dev.shape[0]
+    if not sb:
+        return b_dev.shape[0]
+    given = a_len if a_len is not None else b_len
+    return 1 if given is None else int(torch.as_tensor(given).numel())
+
+
 def _paths_call(a_dev, b_dev, a_len, b_len, B, path, plen, total):
     dev = a_dev.device
     M, N = a_dev.shape[-2], b_dev.shape[-2]
@@ -103,17 +118,7 @@ def dtw_paths(a_dev, b_dev, a_len=None, b_len=None, check=False):
     a_len and b_len of different sizes: B is the size of a_len if given, else of b_len) or when a_dev and b_dev hold
     different numbers of pairs.  Both sequences shared and no lengths is one pair, not an error."""
     dev = a_dev.device
-    sa = a_dev.dim() == 2
-    sb = b_dev.dim() == 2
-    if not sa:
-        B = a_dev.shape[0]
-    elif not sb:
-        B = b_dev.shape[0]
-    else:
-        given = a_len if a_len is not None else b_len
-        B = 1 if given is None else int(torch.as_tensor(given).numel())
-    if not sa and not sb and a_dev.shape[0] != b_dev.shape[0]:
-        raise ValueError("a_dev holds %d pairs, b_dev %d" % (a_dev.shape[0], b_dev.shape[0]))
+    B = _infer_pairs(a_dev, b_dev, a_len, b_len)
     M, N = a_dev.shape[-2], b_dev.shape[-2]
     a_dev, b_dev = a_dev.contiguous(), b_dev.contiguous()
     a_len, b_len = _lengths(a_len, B, dev, "a_len"), _lengths(b_len, B, dev, "b_len")
@@ -126,13 +131,13 @@ def dtw_paths(a_dev, b_dev, a_len=None, b_len=None, check=False):
     return path, plen, total
 
 
-def _pad_frames(seqs, B, dtype):
+def _pad_frames(seqs, B, dtype, who="align_pairs"):
     """(12, n_k) feature-major arrays -> (host [B][n_max][12] or, for a single shared array, [n][12]; lengths or None)."""
     if isinstance(seqs, (np.ndarray, torch.Tensor)):
         x = torch.as_tensor(np.asarray(seqs)).to(dtype)
         return x.t().contiguous(), None
     if len(seqs) != B:
-        raise ValueError("align_pairs: %d sequences on one side, %d on the other" % (len(seqs), B))
+        raise ValueError("%s: %d sequences on one side, %d on the other" % (who, len(seqs), B))
     lens = [int(np.shape(x)[1]) for x in seqs]
     out = torch.zeros((B, max(max(lens), 1), 12), dtype=dtype)
     for k, x in enumerate(seqs):
@@ -171,3 +176,93 @@ def align_pairs(seqs_a, seqs_b, device="cuda:0", dtype=torch.float64):
     if int(plen_h.min()) < 0:
         raise nat.RtsyncError("rts_dtw_paths: the device pipeline reported a fault")
     return [(path_h[k, :int(plen_h[k])].astype(np.int64), float(total_h[k])) for k in range(B)]
+
+
+def _subseq_call(a_dev, b_dev, a_len, b_len, B, path, plen, total, start, end, row):
+    dev = a_dev.device
+    M, N = a_dev.shape[-2], b_dev.shape[-2]
+    nbytes = ctypes.c_size_t(0)
+    nat.check(nat.lib.rts_dtw_subseq_paths_workspace_bytes(M, N, B, ctypes.byref(nbytes)))
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+    nat.check(nat.lib.rts_dtw_subseq_paths(
+        a_dev.data_ptr(), _np_dtype_code(a_dev.dtype), 0 if a_dev.dim() == 2 else M,
+        a_len.data_ptr() if a_len is not None else None,
+        b_dev.data_ptr(), _np_dtype_code(b_dev.dtype), 0 if b_dev.dim() == 2 else N,
+        b_len.data_ptr() if b_len is not None else None,
+        12, M, N, B, path.data_ptr(), plen.data_ptr(), total.data_ptr(), start.data_ptr(), end.data_ptr(),
+        row.data_ptr() if row is not None else None, ws.data_ptr(), nbytes.value,
+        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+
+def dtw_subseq_paths(a_dev, b_dev, a_len=None, b_len=None, want_row=False, check=False):
+    """Subsequence DTW with paths: every a (an excerpt, matched entirely) against the stretch of its b (a whole piece,
+    free at both ends) it fits best.  ``dtw_paths`` with the first row freed and the end taken at the first minimum of the
+    last row; any excerpt length, same workspace (about 0.45 bytes per cell), no matrix written.
+
+    a_dev, b_dev, a_len, b_len: as ``dtw_paths`` (B inferred the same way; a shared b_dev [N_max][12] is the common case:
+    many excerpts against one piece).
+
+    Returns device tensors (path [B][M_max+N_max][2] int32, path_len [B] int32, total [B] float64, start [B] int32,
+    end [B] int32) and, with ``want_row``, row [B][N_max] float64: the first path_len[k] rows of path[k] run from
+    (0, start[k]) to (a_len[k]-1, end[k]), the rows behind them are not written; total[k] is the accumulated cost of
+    that path, equal to ``dtw_paths``' total of a[k] against b[k, start[k]:end[k]+1]; row[k, :b_len[k]] is the last row
+    of the accumulated-cost matrix (its cells behind b_len[k] are not written).  A pair with a length < 1 has path_len 0,
+    total +inf and start = end = -1.  Asynchronous.
+
+    Fault contract as ``dtw_paths``: path_len[k] == -1 (total NaN, start = end = -1); ``check=True`` synchronises and
+    raises.  Errors as ``dtw_paths``."""
+    dev = a_dev.device
+    B = _infer_pairs(a_dev, b_dev, a_len, b_len)
+    M, N = a_dev.shape[-2], b_dev.shape[-2]
+    a_dev, b_dev = a_dev.contiguous(), b_dev.contiguous()
+    a_len, b_len = _lengths(a_len, B, dev, "a_len"), _lengths(b_len, B, dev, "b_len")
+    path = torch.empty((B, M + N, 2), dtype=torch.int32, device=dev)
+    plen = torch.zeros((B,), dtype=torch.int32, device=dev)
+    total = torch.empty((B,), dtype=torch.float64, device=dev)
+    start = torch.empty((B,), dtype=torch.int32, device=dev)
+    end = torch.empty((B,), dtype=torch.int32, device=dev)
+    row = torch.empty((B, N), dtype=torch.float64, device=dev) if want_row else None
+    _subseq_call(a_dev, b_dev, a_len, b_len, B, path, plen, total, start, end, row)
+    if check and int(plen.min().item()) < 0:
+        raise nat.RtsyncError("rts_dtw_subseq_paths: the device pipeline reported a fault (path_len = -1)")
+    return (path, plen, total, start, end, row) if want_row else (path, plen, total, start, end)
+
+
+def align_excerpts(excerpts, pieces, device="cuda:0", dtype=torch.float64):
+    """``align_pairs`` for excerpts: each excerpt is aligned against the stretch of its piece it fits best (a stream
+    restarted inside a piece, a re-acquired stream's history, a rehearsal take, a cut of a recording).
+
+    excerpts, pieces: lists of feature-major (12, M_k) / (12, N_k) arrays; a single array on either side is shared by
+    all pairs (typically one piece).  Pads, uploads once, makes one ``rts_dtw_subseq_paths`` call and one read-back.
+    Returns [(path (P_k, 2) int64 ndarray, total float, start int, end int), ...]: path[:, 0] indexes the excerpt's
+    frames, path[:, 1] the piece's, from (0, start) to (M_k-1, end) -- ready for
+    ``evaluate.AlignmentError(excerpt_csv, piece_csv, path)``.  A pair without frames on either side gives an empty
+    path, total inf and start = end = -1."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("align_excerpts needs a ROCm GPU (no CPU fallback)")
+    dev = torch.device(device)
+    a_one, b_one = isinstance(excerpts, (np.ndarray, torch.Tensor)), isinstance(pieces, (np.ndarray, torch.Tensor))
+    B = 1 if (a_one and b_one) else (len(pieces) if a_one else len(excerpts))
+    if B < 1:
+        return []
+    a, a_len = _pad_frames(excerpts, B, dtype, "align_excerpts")
+    b, b_len = _pad_frames(pieces, B, dtype, "align_excerpts")
+    a, b = a.to(dev), b.to(dev)
+    M, N = a.shape[-2], b.shape[-2]
+    # one int32 buffer for all outputs, so that one copy brings them back: total (as float64), then path_len, start and
+    # end (padded together to an even count: the path is written in 8-byte pairs), path
+    Bp = 3 * B + (B & 1)
+    out = torch.zeros((2 * B + Bp + B * (M + N) * 2,), dtype=torch.int32, device=dev)
+    total = out[:2 * B].view(torch.float64)
+    plen, start, end = out[2 * B:3 * B], out[3 * B:4 * B], out[4 * B:5 * B]
+    path = out[2 * B + Bp:].view(B, M + N, 2)
+    _subseq_call(a, b, _lengths(a_len, B, dev, "a_len"), _lengths(b_len, B, dev, "b_len"), B, path, plen, total, start,
+                 end, None)
+    host = out.cpu().numpy()
+    total_h = host[:2 * B].view(np.float64)
+    plen_h, start_h, end_h = host[2 * B:3 * B], host[3 * B:4 * B], host[4 * B:5 * B]
+    path_h = host[2 * B + Bp:].reshape(B, M + N, 2)
+    if int(plen_h.min()) < 0:
+        raise nat.RtsyncError("rts_dtw_subseq_paths: the device pipeline reported a fault")
+    return [(path_h[k, :int(plen_h[k])].astype(np.int64), float(total_h[k]), int(start_h[k]), int(end_h[k]))
+            for k in range(B)]
