@@ -57,7 +57,7 @@ struct OtwArgs {
     int path_cap, live_cap;   // live_cap = 2N (otw_eran.py:14); the history stride is live_stride
     int ref_f64, live_f64;
     int clamp_len;            // run mode: never read past live_stride frames
-    long long *debug;         // diagnostic builds only (-DRTS_OTW_STAMPS): [B][16] cycle sums
+    long long *debug;         // diagnostic builds only (-DRTS_OTW_STAMPS): [B][16] cycle sums (level 2: [B][64])
     int spec;                 // 1: the pipelined kernel was selected (host-side choice; the kernel does not read it)
     double *dense_acc;        // optional [B][2N][N]: the reference's dense acc_cost (otw_eran.py:27), NULL = off
     double *dense_cost;       // optional [B][2N][N]: the reference's dense cost (otw_eran.py:23)
@@ -216,6 +216,31 @@ __device__ __forceinline__ double wave_min(double x) {
     RTS_DPP_MIN_STEP(0x142, 0xa);  // row_bcast:15
     RTS_DPP_MIN_STEP(0x143, 0xc);  // row_bcast:31
     return wave_bcast(x, 63);
+}
+
+// Two such minima at once, their DPP steps interleaved: a wave issues a dependent VALU instruction every 8.25 cycles, the
+// instructions of two independent chains every 6.2 (profiles/experiments/r03_chain_latency.jsonl).
+__device__ __forceinline__ void wave_min2(double &x0, double &x1) {
+#define RTS_DPP_MIN_STEP2(CTRL, ROWMASK) \
+    do {                                 \
+        {                                \
+            double &x = x0;              \
+            RTS_DPP_MIN_STEP(CTRL, ROWMASK); \
+        }                                \
+        {                                \
+            double &x = x1;              \
+            RTS_DPP_MIN_STEP(CTRL, ROWMASK); \
+        }                                \
+    } while (0)
+    RTS_DPP_MIN_STEP2(0x111, 0xf);  // row_shr:1
+    RTS_DPP_MIN_STEP2(0x112, 0xf);  // row_shr:2
+    RTS_DPP_MIN_STEP2(0x114, 0xf);  // row_shr:4
+    RTS_DPP_MIN_STEP2(0x118, 0xf);  // row_shr:8
+    RTS_DPP_MIN_STEP2(0x142, 0xa);  // row_bcast:15
+    RTS_DPP_MIN_STEP2(0x143, 0xc);  // row_bcast:31
+#undef RTS_DPP_MIN_STEP2
+    x0 = wave_bcast(x0, 63);
+    x1 = wave_bcast(x1, 63);
 }
 
 // LDS access with the row offset as an instruction immediate (the pipelined kernel's strips; see strip_chain).  The
@@ -1157,6 +1182,22 @@ __device__ __forceinline__ void otw_spec_argmin(double lm, int ml, int k1, doubl
     idx_out = some ? k1 + L * first + __builtin_amdgcn_readlane(ml, first) : 0x7fffffff;
 }
 
+// otw_spec_argmin of the row and of the column shadow strip at once (a Both step as a hit): the same reductions, run side by side.
+template <int W>
+__device__ __forceinline__ void otw_spec_argmin2(double rlm, int rml, int rk1, double clm, int cml, int ck1, double &rg_out,
+                                                 int &ridx_out, double &cg_out, int &cidx_out) {
+    constexpr int L = W / 64;
+    double rg = rlm, cg = clm;
+    wave_min2(rg, cg);
+    const unsigned long long rmask = __ballot(rlm == rg), cmask = __ballot(clm == cg);
+    const bool rsome = (rg < INFINITY) && (rmask != 0), csome = (cg < INFINITY) && (cmask != 0);
+    const int rfirst = (int)__builtin_ctzll(rmask | (1ull << 63)), cfirst = (int)__builtin_ctzll(cmask | (1ull << 63));
+    rg_out = rg;
+    cg_out = cg;
+    ridx_out = rsome ? rk1 + L * rfirst + __builtin_amdgcn_readlane(rml, rfirst) : 0x7fffffff;
+    cidx_out = csome ? ck1 + L * cfirst + __builtin_amdgcn_readlane(cml, cfirst) : 0x7fffffff;
+}
+
 // The last cell of a shadow strip, in the chain's own order: min(min(side + d, diag + 2d), previous cell + d).  `side`
 // is the old band's slot at `pos` (up for a row strip, left for a column strip), `diag` its slot at pos-1.
 // (`prev_raw`: the band's slot at pos - 1, or at pos when the strip has only this cell -- read by the caller, so that wave 0
@@ -1360,16 +1401,32 @@ otw_advance_kernel(OtwArgs a) {
     __builtin_amdgcn_s_waitcnt(0xC07F);
 #endif
 #if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 2
-    long long lw_hit = 0, lb_hit = 0, lw_oth = 0, lb_oth = 0, ln_hit = 0, ln_oth = 0, l_last = 0;
-    long long lo_work = 0, lo_t0 = 0;  // waves 1..7: own work in hit steps
-    long long lo_rounds = 0;           // waves 1, 2: extra carry rounds of their speculative chains
+    // by step kind: 0 Row-only / Column-only hit, 1 Both hit while the band fills (planned as a hit), 2 Both hit with a full
+    // band (planned "hit if", resolved to a hit), 3 every other step.  Separate scalars: an indexed array would go to scratch.
+    long long lw_k0 = 0, lw_k1 = 0, lw_k2 = 0, lw_k3 = 0;  // wave 0: work
+    long long lb_k0 = 0, lb_k1 = 0, lb_k2 = 0, lb_k3 = 0;  // wave 0: end-of-step barrier wait
+    long long ln_k0 = 0, ln_k1 = 0, ln_k2 = 0, ln_k3 = 0;  // wave 0: steps
+    long long l_last = 0;
+    long long lo_k0 = 0, lo_k1 = 0, lo_k2 = 0, lo_t0 = 0;  // waves 1..7: own work in hit steps
+    long long lo_rounds = 0;                               // waves 1, 2: extra carry rounds of their speculative chains
 #define RTS_ROUNDS_ACC (&lo_rounds)
+#define RTS_STEP_KIND(raw, res)                                                                          \
+    (!((res) & kPlanHit) ? 3 : (((res) & (kPlanRow | kPlanCol)) != (kPlanRow | kPlanCol)) ? 0 : ((raw) & kPlanHitIf) ? 2 : 1)
 #define RTS_LW_BEGIN() do { lo_t0 = (long long)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); } while (0)
-#define RTS_LW_END(hit) do { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); if (hit) lo_work += t_ - lo_t0; } while (0)
+#define RTS_LW_END(kind)                                                  \
+    do {                                                                  \
+        const long long t_ = (long long)__builtin_amdgcn_s_memtime();     \
+        __builtin_amdgcn_s_waitcnt(0xC07F);                               \
+        const int kd_ = (kind);                                           \
+        if (kd_ == 0) lo_k0 += t_ - lo_t0;                                \
+        if (kd_ == 1) lo_k1 += t_ - lo_t0;                                \
+        if (kd_ == 2) lo_k2 += t_ - lo_t0;                                \
+    } while (0)
 #else
 #define RTS_ROUNDS_ACC nullptr
+#define RTS_STEP_KIND(raw, res) 0
 #define RTS_LW_BEGIN() do { } while (0)
-#define RTS_LW_END(hit) do { } while (0)
+#define RTS_LW_END(kind) do { } while (0)
 #endif
     extern __shared__ __align__(16) unsigned char smem_raw[];
     OtwLds<W, RT> &S = *reinterpret_cast<OtwLds<W, RT> *>(smem_raw);
@@ -1599,7 +1656,8 @@ otw_advance_kernel(OtwArgs a) {
         if (wave >= HW0) {
             for (;;) {
                 const int pt = __builtin_amdgcn_readfirstlane(S.plan_t[sp]), j0 = __builtin_amdgcn_readfirstlane(S.plan_j0[sp]);
-                const int pflags = otw_resolve_plan(__builtin_amdgcn_readfirstlane(S.plan_flags[sp]), pt, c, &SP.col[sp]);
+                const int praw = __builtin_amdgcn_readfirstlane(S.plan_flags[sp]);
+                const int pflags = otw_resolve_plan(praw, pt, c, &SP.col[sp]);
                 if (pflags & kPlanExit) break;
                 const bool do_row = (pflags & kPlanRow) != 0, do_col = (pflags & kPlanCol) != 0;
                 RTS_LW_BEGIN();
@@ -1610,14 +1668,15 @@ otw_advance_kernel(OtwArgs a) {
                 if (!(pflags & kPlanHit)) RTS_STEP_BARRIER();  // this step's chains have read their cost buffers
                 if (!(pflags & kPlanStop))
                     otw_costs_advance<W, RT>(S, e, pt, j0 + (do_col ? 1 : 0), do_row, do_col, tid - 64 * HW0, NHELP);
-                RTS_LW_END(pflags & kPlanHit);
+                RTS_LW_END(RTS_STEP_KIND(praw, pflags));
                 RTS_STEP_BARRIER();
                 sp ^= 1;
             }
         } else if (wave == 1) {
             for (;;) {
                 const int pt = __builtin_amdgcn_readfirstlane(S.plan_t[sp]), j0 = __builtin_amdgcn_readfirstlane(S.plan_j0[sp]);
-                const int pflags = otw_resolve_plan(__builtin_amdgcn_readfirstlane(S.plan_flags[sp]), pt, c, &SP.col[sp]);
+                const int praw = __builtin_amdgcn_readfirstlane(S.plan_flags[sp]);
+                const int pflags = otw_resolve_plan(praw, pt, c, &SP.col[sp]);
                 if (pflags & kPlanExit) break;
                 const int jn = j0 + ((pflags & kPlanCol) ? 1 : 0);
                 double *R = (pflags & kPlanRi) ? SP.ShR : S.R, *Rsh = (pflags & kPlanRi) ? S.R : SP.ShR;
@@ -1637,14 +1696,15 @@ otw_advance_kernel(OtwArgs a) {
                 }
                 if (!(pflags & kPlanStop) && pt + 1 < live_len && pt + 1 < e.live_cap)  // row pt+1 over [.., jn-1]
                     otw_spec_strip<W, false>(S.Dr[(pt + 1) & 1], R, Rsh, jn, c, lane, sentinel, &SP.row[sp ^ 1], RTS_ROUNDS_ACC);
-                RTS_LW_END(pflags & kPlanHit);
+                RTS_LW_END(RTS_STEP_KIND(praw, pflags));
                 RTS_STEP_BARRIER();
                 sp ^= 1;
             }
         } else if (wave == 2) {
             for (;;) {
                 const int pt = __builtin_amdgcn_readfirstlane(S.plan_t[sp]), j0 = __builtin_amdgcn_readfirstlane(S.plan_j0[sp]);
-                const int pflags = otw_resolve_plan(__builtin_amdgcn_readfirstlane(S.plan_flags[sp]), pt, c, &SP.col[sp]);
+                const int praw = __builtin_amdgcn_readfirstlane(S.plan_flags[sp]);
+                const int pflags = otw_resolve_plan(praw, pt, c, &SP.col[sp]);
                 if (pflags & kPlanExit) break;
                 const int jn = j0 + ((pflags & kPlanCol) ? 1 : 0);
                 double *C = (pflags & kPlanCi) ? SP.ShC : S.C, *Csh = (pflags & kPlanCi) ? S.C : SP.ShC;
@@ -1680,7 +1740,7 @@ otw_advance_kernel(OtwArgs a) {
                 }
                 if (!(pflags & kPlanStop) && jn + 1 < N)  // column jn+1 over rows [.., pt-1]
                     otw_spec_strip<W, true>(S.Dc[(jn + 1) & 1], C, Csh, pt, c, lane, sentinel, &SP.col[sp ^ 1], RTS_ROUNDS_ACC, drop);
-                RTS_LW_END(pflags & kPlanHit);
+                RTS_LW_END(RTS_STEP_KIND(praw, pflags));
                 RTS_STEP_BARRIER();
                 sp ^= 1;
             }
@@ -1690,39 +1750,41 @@ otw_advance_kernel(OtwArgs a) {
 #if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 2
             l_last = (long long)__builtin_amdgcn_s_memtime();
             __builtin_amdgcn_s_waitcnt(0xC07F);
-#define RTS_W0_STEP_END(hit)                                              \
+#define RTS_W0_STEP_END(kind)                                             \
     do {                                                                  \
         const long long t0_ = (long long)__builtin_amdgcn_s_memtime();    \
         __builtin_amdgcn_s_waitcnt(0xC07F);                               \
         RTS_STEP_BARRIER();                                               \
         const long long t1_ = (long long)__builtin_amdgcn_s_memtime();    \
         __builtin_amdgcn_s_waitcnt(0xC07F);                               \
-        if (hit) {                                                        \
-            lw_hit += t0_ - l_last;                                       \
-            lb_hit += t1_ - t0_;                                          \
-            ln_hit += 1;                                                  \
-        } else {                                                          \
-            lw_oth += t0_ - l_last;                                       \
-            lb_oth += t1_ - t0_;                                          \
-            ln_oth += 1;                                                  \
-        }                                                                 \
+        const int kd_ = (kind);                                           \
+        if (kd_ == 0) lw_k0 += t0_ - l_last, lb_k0 += t1_ - t0_, ln_k0 += 1; \
+        if (kd_ == 1) lw_k1 += t0_ - l_last, lb_k1 += t1_ - t0_, ln_k1 += 1; \
+        if (kd_ == 2) lw_k2 += t0_ - l_last, lb_k2 += t1_ - t0_, ln_k2 += 1; \
+        if (kd_ == 3) lw_k3 += t0_ - l_last, lb_k3 += t1_ - t0_, ln_k3 += 1; \
         l_last = t1_;                                                     \
     } while (0)
 #else
-#define RTS_W0_STEP_END(hit) RTS_STEP_BARRIER()
+#define RTS_W0_STEP_END(kind) RTS_STEP_BARRIER()
 #endif
-            // Row-only / Column-only hit steps -- all but ~1 % of the steps at B = 64 -- in a loop of their own, compiled
+            // Hit steps -- Row-only, Column-only and Both; all but ~1 % of the steps at B = 64 -- in a loop of their own, compiled
             // once per control policy (V2: LiveNoteV2's append rule; DEFER: set_live's deferred run-count update) and
-            // entered once per run of such steps: the same settle_hit / decide / plan arithmetic as the general loop
-            // below, without its other step kinds, its band reductions or its per-step policy tests.  The float64
+            // entered once per run of such steps: the same settle_hit / settle_hit_both / decide / plan arithmetic as the
+            // general loop below, without its other step kinds, its band reductions or its per-step policy tests.  The float64
             // control values stay in VGPRs (every lane holds the same value); only integers that drive a branch or an
             // address cross to SGPRs.  It returns -- before touching anything -- at the first step that is not such a
-            // hit, or whose decide() would have to reduce the band it leaves as it is (a kept minimum that slid out of its
-            // window): the general loop runs that step and comes back.  W = 512 only, and not the throughput flavour
-            // (its point is its register budget).
+            // hit, or whose decide() would have to reduce a band (a kept minimum that slid out of its window; a Both step's
+            // speculated argmin outside the step's window): the general loop runs that step and comes back.  W = 512 only,
+            // and not the throughput flavour (its point is its register budget).
             int2 *const path_row = reinterpret_cast<int2 *>(e.path) + (size_t)e.b * e.path_cap;
             const auto hit_steps = [&](auto v2_c, auto defer_c) __attribute__((always_inline)) {
                 constexpr bool V2 = decltype(v2_c)::value, DEFER = decltype(defer_c)::value;
+                // (-DRTS_OTW_NO_BOTH_LOOP: Both steps stay with the general loop, for A/B runs and the "before" stamps)
+#ifdef RTS_OTW_NO_BOTH_LOOP
+                constexpr bool kBothHere = false;
+#else
+                constexpr bool kBothHere = true;
+#endif
                 // every lane holds the same control state: said once here, the integers stay in SGPRs through the loop
 #define RTS_RFL_CTL(f) k.f = __builtin_amdgcn_readfirstlane(k.f)
                 RTS_RFL_CTL(t), RTS_RFL_CTL(j), RTS_RFL_CTL(dir), RTS_RFL_CTL(prev), RTS_RFL_CTL(run_count);
@@ -1735,62 +1797,149 @@ otw_advance_kernel(OtwArgs a) {
                     const int fl = __builtin_amdgcn_readfirstlane(pl.flags);
                     const int kind = fl & (kPlanHit | kPlanRow | kPlanCol | kPlanStop | kPlanExit | kPlanHitIf);
                     const bool is_row = kind == (kPlanHit | kPlanRow);
-                    if (!is_row && kind != (kPlanHit | kPlanCol)) return;
+                    // a Both step whose strips are the two shadows: planned as a hit (the band is still filling), or "hit
+                    // if the column speculation allows" (full band; otw_resolve_plan)
+                    const bool hit_if = kind == (kPlanHitIf | kPlanRow | kPlanCol);
+                    const bool is_both = kBothHere && (hit_if || kind == (kPlanHit | kPlanRow | kPlanCol));
+                    if (!is_row && !is_both && kind != (kPlanHit | kPlanCol)) return;
                     const int jn = is_row ? j0 : j0 + 1;
-                    // the band this step does not recompute keeps its minimum only while that stays inside the window
-                    const int keep_lo = is_row ? pt - c + 1 : jn - c + 1;
-                    const int keep_idx = __builtin_amdgcn_readfirstlane(is_row ? k.cb_idx : k.rb_idx);
-                    if (keep_idx < ((keep_lo > 0) ? keep_lo : 0)) return;
+                    double rmin, cmin, cl;
+                    int ridx, cidx;
+                    if (is_both) {
+                        // settle (otw_settle_hit_both): the two strips' last cells a = (pt, j0) and b = (pt-1, jn) and the
+                        // corner (pt, jn).  Nothing is written -- no LDS word, no control state -- before the step is known
+                        // to be a hit whose two argmins lie inside the step's windows; otherwise the general loop runs it
+                        // from the start (and resolves the plan for itself).
 #if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 1
-                    stamp_base = 0;
-                    stamp_sum[6] += 1;
+                        // (level-1 stamps: entry apart from settle, as in the branch below.  A step that then returns to the
+                        // general loop -- the rare band reduction, a "hit if" that is none -- leaves its entry in the hit slots.)
+                        stamp_base = 0;
 #endif
-                    RTS_STAMP(0);
-                    RTS_STAMP(1);
-                    // settle: the strip's last cell (otw_settle_hit)
-                    double *R = (fl & kPlanRi) ? SP.ShR : S.R, *C = (fl & kPlanCi) ? SP.ShC : S.C;
-                    const int pos = is_row ? j0 : pt;
-                    const int k1 = (pos - c + 1 > 0) ? pos - c + 1 : 0;
-                    const int n = pos - k1;
-                    double *band = is_row ? R : C, *other = is_row ? C : R;
-                    const OtwSpecOut *ex = is_row ? &SP.row[sp] : &SP.col[sp];
-                    if constexpr (DEFER) {  // livenote_v2.py:149-155
-                        if (k.pend_dir != -2) {
-                            k.run_count = (k.pend_dir == k.prev) ? k.run_count + 1 : 1;
-                            if (k.pend_dir != RTS_DIR_BOTH) k.prev = k.pend_dir;
-                            k.pend_dir = -2;
+                        RTS_STAMP(0);
+                        RTS_STAMP(1);
+                        const int flr = hit_if ? ((fl | kPlanHit) ^ (kPlanRi | kPlanCi)) : fl;  // as otw_resolve_plan, if it is a hit
+                        double *R = (flr & kPlanRi) ? SP.ShR : S.R, *C = (flr & kPlanCi) ? SP.ShC : S.C;
+                        const int t0 = pt - 1;
+                        const int k1r = (j0 - c + 1 > 0) ? j0 - c + 1 : 0, k1c = (pt - c + 1 > 0) ? pt - c + 1 : 0;
+                        const int lo_r = (jn - c + 1 > 0) ? jn - c + 1 : 0;  // the row band's window after the step
+                        const int k1c_s = (t0 - c + 1 > 0) ? t0 - c + 1 : 0;
+                        const OtwSpecOut *exr = &SP.row[sp], *exc = &SP.col[sp];
+                        // every LDS word of the step, the column speculation's verdict included, in one round trip
+                        const double pra = R[swz<W>(j0 - (j0 - k1r > 0 ? 1 : 0))], prb = C[swz<W>(t0 - (t0 - k1c > 0 ? 1 : 0))];
+                        const double d1_raw = exr->d, d2_raw = exc->d, d3_raw = exc->d2, rlm = exr->pmin[lane], clm = exc->pmin[lane];
+                        const int rml = exr->pidx[lane], cml = exc->pidx[lane];
+                        const int cflag = exc->flag;
+                        if (hit_if && !(pt < c || __builtin_amdgcn_readfirstlane(cflag) != 0)) return;  // a regular step
+                        // (uniform values through SGPRs, the three cells before the reductions: the loop's VGPR budget is tight)
+                        const double d1 = rfl(d1_raw), d2 = rfl(d2_raw), d3 = rfl(d3_raw);
+                        const double av = otw_last_cell_from(rfl(pra), j0, k1r, k.cA, k.cL, d1, sentinel);
+                        const double bv = otw_last_cell_from(rfl(prb), t0, k1c, k.cA, k.cU, d2, sentinel);
+                        const double cl_both = vmin(vmin(av + d3, k.cA + 2 * d3), bv + d3);  // acc[pt-1][j0] + 2 d(pt, jn): the diagonal
+                        double rsm, csm;
+                        int rsi, csi;
+                        // the speculated strips start where the plan says: row strip [k1r, j0-1], column strip [k1c_s, pt-2]
+                        otw_spec_argmin2<W>(rlm, rml, k1r, clm, cml, k1c_s, rsm, rsi, csm, csi);
+                        // the strips' last cells sit at the highest index: they win only if strictly smaller (np.argmin)
+                        const bool a_new = av < rsm, b_new = bv < csm;
+                        rmin = a_new ? av : rsm;
+                        cmin = b_new ? bv : csm;
+                        ridx = __builtin_amdgcn_readfirstlane(a_new ? j0 : rsi);
+                        cidx = __builtin_amdgcn_readfirstlane(b_new ? t0 : csi);
+                        // a speculated argmin on a cell outside the Both step's window needs a band reduction
+                        if (ridx < lo_r || cidx < k1c) return;
+#if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 1
+                        stamp_sum[6] += 1;
+#endif
+                        if constexpr (DEFER) {  // livenote_v2.py:149-155
+                            if (k.pend_dir != -2) {
+                                k.run_count = (k.pend_dir == k.prev) ? k.run_count + 1 : 1;
+                                if (k.pend_dir != RTS_DIR_BOTH) k.prev = k.pend_dir;
+                                k.pend_dir = -2;
+                            }
                         }
-                    }
-                    const double prev_raw = band[swz<W>(pos - (n > 0 ? 1 : 0))];
-                    const double d = ex->d, lm = ex->pmin[lane];
-                    const int ml = ex->pidx[lane], sk1 = ex->k1;
-                    double smin;
-                    int sidx;
-                    otw_spec_argmin<W>(lm, ml, __builtin_amdgcn_readfirstlane(sk1), smin, sidx);
-                    const double prev = (n > 0) ? prev_raw : ((k1 > 0) ? sentinel : inf);
-                    const double diag = (pos > 0) ? (is_row ? k.cL : k.cU) + 2 * d : inf;
-                    const double cl = vmin(vmin(k.cA + d, diag), prev + d);
-                    if (lane == 0) {
-                        band[swz<W>(pos)] = cl;
-                        other[swz<W>(is_row ? pt : jn)] = cl;  // column j0 gains row pt / row pt gains column jn
-                    }
-                    if (is_row) {
+                        cl = cl_both;
+                        if (lane == 0) {
+                            R[swz<W>(j0)] = av;
+                            C[swz<W>(t0)] = bv;
+                            R[swz<W>(jn)] = cl;
+                            C[swz<W>(pt)] = cl;
+                            if (k1c > k1c_s) {  // the dropped cell's slot, as an in-place strip leaves it
+                                double sv = sentinel;
+                                asm volatile("" : "+v"(sv));  // copied to a VGPR pair here, not held in one through the whole loop
+                                C[swz<W>(k1c - 1)] = sv;
+                            }
+                        }
                         k.rows += 1;
-                        k.consumed = pt + 1;
-                        k.cU = k.cA;
-                        k.cL = prev;
-                    } else {
                         k.cols += 1;
-                        k.cL = k.cA;
-                        k.cU = prev;
+                        k.consumed = pt + 1;
+                        k.cells += (j0 - k1r + 1) + (pt - k1c + 1);
+                        k.cU = bv;
+                        k.cL = av;
+                        k.cA = cl;
+                        RTS_STAMP(3);
+                    } else {
+                        // the band this step does not recompute keeps its minimum only while that stays inside the window
+                        const int keep_lo = is_row ? pt - c + 1 : jn - c + 1;
+                        const int keep_idx = __builtin_amdgcn_readfirstlane(is_row ? k.cb_idx : k.rb_idx);
+                        if (keep_idx < ((keep_lo > 0) ? keep_lo : 0)) return;
+#if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 1
+                        stamp_base = 0;
+                        stamp_sum[6] += 1;
+#endif
+                        RTS_STAMP(0);
+                        RTS_STAMP(1);
+                        // settle: the strip's last cell (otw_settle_hit)
+                        double *R = (fl & kPlanRi) ? SP.ShR : S.R, *C = (fl & kPlanCi) ? SP.ShC : S.C;
+                        const int pos = is_row ? j0 : pt;
+                        const int k1 = (pos - c + 1 > 0) ? pos - c + 1 : 0;
+                        const int n = pos - k1;
+                        double *band = is_row ? R : C, *other = is_row ? C : R;
+                        const OtwSpecOut *ex = is_row ? &SP.row[sp] : &SP.col[sp];
+                        if constexpr (DEFER) {  // livenote_v2.py:149-155
+                            if (k.pend_dir != -2) {
+                                k.run_count = (k.pend_dir == k.prev) ? k.run_count + 1 : 1;
+                                if (k.pend_dir != RTS_DIR_BOTH) k.prev = k.pend_dir;
+                                k.pend_dir = -2;
+                            }
+                        }
+                        const double prev_raw = band[swz<W>(pos - (n > 0 ? 1 : 0))];
+                        const double d = ex->d, lm = ex->pmin[lane];
+                        const int ml = ex->pidx[lane], sk1 = ex->k1;
+                        double smin;
+                        int sidx;
+                        otw_spec_argmin<W>(lm, ml, __builtin_amdgcn_readfirstlane(sk1), smin, sidx);
+                        const double prev = (n > 0) ? prev_raw : ((k1 > 0) ? sentinel : inf);
+                        const double diag = (pos > 0) ? (is_row ? k.cL : k.cU) + 2 * d : inf;
+                        cl = vmin(vmin(k.cA + d, diag), prev + d);
+                        if (lane == 0) {
+                            band[swz<W>(pos)] = cl;
+                            other[swz<W>(is_row ? pt : jn)] = cl;  // column j0 gains row pt / row pt gains column jn
+                        }
+                        if (is_row) {
+                            k.rows += 1;
+                            k.consumed = pt + 1;
+                            k.cU = k.cA;
+                            k.cL = prev;
+                        } else {
+                            k.cols += 1;
+                            k.cL = k.cA;
+                            k.cU = prev;
+                        }
+                        k.cA = cl;
+                        k.cells += n + 1;
+                        RTS_STAMP(3);
+                        // decide (otw_decide): the strip's band brings the speculated argmin, the other band keeps its
+                        // minimum
+                        rmin = is_row ? smin : k.rb_min, cmin = is_row ? k.cb_min : smin;
+                        ridx = is_row ? sidx : k.rb_idx, cidx = is_row ? k.cb_idx : sidx;
                     }
-                    k.cA = cl;
-                    k.cells += n + 1;
-                    RTS_STAMP(3);
-                    // decide (otw_decide): the strip's band brings the speculated argmin, the other band keeps its
-                    // minimum, and both gain `cl` at their top index (it wins only if strictly smaller)
-                    double rmin = is_row ? smin : k.rb_min, cmin = is_row ? k.cb_min : smin;
-                    int ridx = is_row ? sidx : k.rb_idx, cidx = is_row ? k.cb_idx : sidx;
+                    // a "hit if" step that was resolved to a hit: both shadows have become bands.  (Here, on the common path and
+                    // without a branch: k.ri / k.ci live in VGPRs, and a flip inside the Both branch cost three more copies of
+                    // the pair -- six registers, which put the kernel over the 128 that two workgroups per CU allow.)
+                    const int flip = (is_both && hit_if) ? 1 : 0;
+                    k.ri ^= flip;
+                    k.ci ^= flip;
+                    // both bands gain `cl` at their top index (it wins only if strictly smaller)
                     const bool r_new = cl < rmin, c_new = cl < cmin;
                     rmin = r_new ? cl : rmin;
                     ridx = r_new ? jn : ridx;
@@ -1838,7 +1987,7 @@ otw_advance_kernel(OtwArgs a) {
                     k.spec_valid = 1;
                     pl = otw_make_plan<W, RT>(S, k, e, true, sp ^ 1);
                     RTS_STAMP(5);
-                    RTS_W0_STEP_END(true);
+                    RTS_W0_STEP_END(is_both ? (hit_if ? 2 : 1) : 0);
                     sp ^= 1;
                 }
             };
@@ -1859,9 +2008,10 @@ otw_advance_kernel(OtwArgs a) {
                 // wave 0 wrote the plan itself; pinned to SGPRs so that the step's addressing and branches are scalar
                 const int pt = __builtin_amdgcn_readfirstlane(pl.t), j0 = __builtin_amdgcn_readfirstlane(pl.j0);
                 pl.flags = __builtin_amdgcn_readfirstlane(pl.flags);
-                const int pflags = otw_resolve_plan(pl.flags, pt, c, &SP.col[sp]);
+                const int praw = pl.flags;  // (this step's: `pl` is the next step's plan by the time the step ends)
+                const int pflags = otw_resolve_plan(praw, pt, c, &SP.col[sp]);
                 if (pflags & kPlanExit) break;
-                if ((pl.flags & kPlanHitIf) && (pflags & kPlanHit)) {  // resolved to a hit: both shadows become bands
+                if ((praw & kPlanHitIf) && (pflags & kPlanHit)) {  // resolved to a hit: both shadows become bands
                     k.ri ^= 1;
                     k.ci ^= 1;
                 }
@@ -1919,7 +2069,7 @@ otw_advance_kernel(OtwArgs a) {
                 k.spec_valid = !o.stop;  // the shadows being computed during this step belong to (k.t, k.j)
                 pl = otw_make_plan<W, RT>(S, k, e, true, sp ^ 1);
                 RTS_STAMP2(5);
-                RTS_W0_STEP_END(pflags & kPlanHit);
+                RTS_W0_STEP_END(RTS_STEP_KIND(praw, pflags));
                 sp ^= 1;
             }
 #undef RTS_W0_STEP_END
@@ -2118,12 +2268,17 @@ otw_advance_kernel(OtwArgs a) {
         for (int i = 0; i < 16; i++) a.debug[(size_t)e.b * 16 + i] = stamp_sum[i];
 #endif
 #if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 2
-    if (tid == 0 && a.debug) {
-        long long *dbg = a.debug + (size_t)e.b * 16;
-        dbg[0] = lw_hit, dbg[1] = lb_hit, dbg[2] = ln_hit, dbg[3] = lw_oth, dbg[4] = lb_oth, dbg[5] = ln_oth;
+    // [B][64]: 16 words per step kind -- 0 wave-0 work, 1 its end-of-step wait, 2 steps, 3..9 own work of waves 1..7;
+    // words 10, 11 of kind 0: the extra carry rounds of waves 1, 2 (all steps)
+    if (a.debug) {
+        long long *dbg = a.debug + (size_t)e.b * 64;
+        if (tid == 0) {
+            dbg[0] = lw_k0, dbg[1] = lb_k0, dbg[2] = ln_k0, dbg[16] = lw_k1, dbg[17] = lb_k1, dbg[18] = ln_k1;
+            dbg[32] = lw_k2, dbg[33] = lb_k2, dbg[34] = ln_k2, dbg[48] = lw_k3, dbg[49] = lb_k3, dbg[50] = ln_k3;
+        }
+        if (lane == 0 && wave >= 1 && wave <= 7) dbg[2 + wave] = lo_k0, dbg[18 + wave] = lo_k1, dbg[34 + wave] = lo_k2;
+        if (lane == 0 && wave >= 1 && wave <= 2) dbg[9 + wave] = lo_rounds;
     }
-    if (a.debug && lane == 0 && wave >= 1 && wave <= 7) a.debug[(size_t)e.b * 16 + 5 + wave] = lo_work;
-    if (a.debug && lane == 0 && wave >= 1 && wave <= 2) a.debug[(size_t)e.b * 16 + 12 + wave] = lo_rounds;
 #endif
     if (tid == 0) {
         st[RTS_ST_T] = k.t;
@@ -2889,12 +3044,15 @@ int rts_otw_read_bands(rts_otw *h, int b, double *row_band, double *col_band, vo
 }
 
 #ifdef RTS_OTW_STAMPS
-/* Diagnostic build only: caller-provided [B][16] int64 device buffer receiving per-phase cycle sums. */
+/* Diagnostic build only: caller-provided [B][rts_otw_debug_words()] int64 device buffer receiving per-phase cycle sums. */
 int rts_otw_set_debug(rts_otw *h, long long *debug_dev) {
     if (!h) return rts::set_error(RTS_ERR_INVALID, "handle is NULL");
     h->debug = debug_dev;
     return RTS_OK;
 }
+/* What this library was built with, so that the caller sizes the buffer by the library and not by its own settings. */
+int rts_otw_stamp_level(void) { return RTS_OTW_STAMPS; }
+int rts_otw_debug_words(void) { return (RTS_OTW_STAMPS == 2) ? 64 : 16; }
 #endif
 
 int rts_otw_device_views(rts_otw *h, int32_t **path_dev, int *path_cap, int32_t **state_dev) {

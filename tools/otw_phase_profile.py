@@ -1,20 +1,29 @@
 #!/usr/bin/env python3
 """Diagnostic (not shipped): build librtsync with -DRTS_OTW_STAMPS into tools/_diag/ and print
-the share of wave-0 cycles each phase of otw_advance_kernel takes on the bench workload."""
+the share of wave-0 cycles each phase of otw_advance_kernel takes on the bench workload.
+
+    RTS_DIAG_LEVEL=1|2 python tools/otw_phase_profile.py [--build] [--no-both-loop]
+
+--no-both-loop builds with -DRTS_OTW_NO_BOTH_LOOP (Both hits left to the general loop: the "before" of
+profiles/r05a_phase_L2_old.txt) into tools/_diag/librtsync_diag_nobothloop.so and runs that.  RTS_DIAG_LIB=<path> runs a
+diagnostic library built earlier.  The stamp level and the size of the debug buffer are the library's own
+(rts_otw_stamp_level / rts_otw_debug_words), whatever RTS_DIAG_LEVEL says when the tool runs."""
 import ctypes, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 DIAG = os.path.join(ROOT, "tools", "_diag")
+NO_BOTH = "--no-both-loop" in sys.argv
+DEFAULT_SO = os.path.join(DIAG, "librtsync_diag_nobothloop.so" if NO_BOTH else "librtsync_diag.so")
 
 
 def build():
     os.makedirs(DIAG, exist_ok=True)
-    so = os.path.join(DIAG, "librtsync_diag.so")
+    so = DEFAULT_SO
     src = [os.path.join(ROOT, "real_time_audio_sync_amd", "csrc", f) for f in ("common.cpp", "otw.hip")]
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
            "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-amdgpu-sched-strategy=max-ilp",  # as _build.PER_SOURCE_FLAGS["otw.hip"]
-           "-DRTS_OTW_STAMPS=%s" % os.environ.get("RTS_DIAG_LEVEL", "1"), "-o", so]
+           "-DRTS_OTW_STAMPS=%s" % os.environ.get("RTS_DIAG_LEVEL", "1")] + (["-DRTS_OTW_NO_BOTH_LOOP"] if NO_BOTH else []) + ["-o", so]
     for s in src:
         cmd += ["-x", "hip", s]
     subprocess.check_call(cmd)
@@ -22,7 +31,7 @@ def build():
 
 
 def main():
-    so = os.path.join(DIAG, "librtsync_diag.so")
+    so = os.environ.get("RTS_DIAG_LIB", DEFAULT_SO)  # a diagnostic library built earlier (A/B)
     if "--build" in sys.argv or not os.path.exists(so):
         build()
         if "--build" in sys.argv:
@@ -36,6 +45,9 @@ def main():
     L.rts_otw_set_debug.argtypes = [vp, vp]
     L.rts_otw_set_waves.argtypes = [vp, i32]
     L.rts_otw_read_states.argtypes = [vp, vp, vp]
+    L.rts_otw_stamp_level.restype = L.rts_otw_debug_words.restype = i32
+    LEVEL2 = L.rts_otw_stamp_level() == 2  # the library's, not this run's RTS_DIAG_LEVEL: the kernel writes what it was built for
+    words = L.rts_otw_debug_words()
     B, N, c = 64, 2200, 500
     ref = synth.synth_ref(N, seed=1000)
     lives = [synth.synth_live(ref, seed=1001 + b) for b in range(B)]
@@ -52,7 +64,7 @@ def main():
         h = vp()
         assert L.rts_otw_create(ref_d.data_ptr(), 0, 12, N, B, c, 3, 0, 0, ctypes.byref(h)) == 0
         L.rts_otw_set_waves(h, waves)
-        dbg = torch.zeros((B, 16), dtype=torch.int64, device=dev)
+        dbg = torch.zeros((B, words), dtype=torch.int64, device=dev)
         L.rts_otw_set_debug(h, dbg.data_ptr())
         for _ in range(2):
             L.rts_otw_run(h, live_d.data_ptr(), 0, tmax, len_d.data_ptr(), 0, None)
@@ -61,15 +73,24 @@ def main():
         L.rts_otw_read_states(h, st.ctypes.data, None)
         d = dbg.cpu().numpy().astype(np.float64)
         frames = st[:, 8].sum()
-        if os.environ.get("RTS_DIAG_LEVEL", "1") == "2":
-            for base, label in ((0, "hit steps"), (3, "other steps")):
-                n = max(d[:, base + 2].sum(), 1)
-                print("%s: %d  wave-0 work %.0f cycles, end-of-step barrier wait %.0f cycles" % (label, n, d[:, base].sum() / n, d[:, base + 1].sum() / n))
-            n = max(d[:, 2].sum(), 1)
+        if LEVEL2:
+            # [B][64]: 16 words per step kind (0 wave-0 work, 1 its end-of-step wait, 2 steps, 3..9 own work of waves 1..7)
+            kinds = ("single hits (Row-only / Column-only)", "Both hits while the band fills", "Both hits with a full band (\"hit if\")")
+            tot = d.reshape(B, 4, 16).sum(axis=0)
+            hits = tot[:3].sum(axis=0)
+            n = max(hits[2], 1)
+            print("hit steps: %d  wave-0 work %.0f cycles, end-of-step barrier wait %.0f cycles" % (hits[2], hits[0] / n, hits[1] / n))
+            n3 = max(tot[3, 2], 1)
+            print("other steps: %d  wave-0 work %.0f cycles, end-of-step barrier wait %.0f cycles" % (tot[3, 2], tot[3, 0] / n3, tot[3, 1] / n3))
             print("hit steps, own work: wave 1 (row speculation) %.0f, wave 2 (column speculation) %.0f, helper waves 3-7: %s"
-                  % (d[:, 6].sum() / n, d[:, 7].sum() / n, ", ".join("%.0f" % (d[:, 8 + i].sum() / n) for i in range(5))))
-            steps = max(d[:, 2].sum() + d[:, 5].sum(), 1)
-            print("extra carry rounds per speculative chain: row %.2f, column %.2f" % (d[:, 13].sum() / steps, d[:, 14].sum() / steps))
+                  % (hits[3] / n, hits[4] / n, ", ".join("%.0f" % (hits[5 + i] / n) for i in range(5))))
+            for kd, label in enumerate(kinds):
+                nk = max(tot[kd, 2], 1)
+                print("%s: %d  wave-0 work %.0f + wait %.0f, wave 1 %.0f, wave 2 %.0f, helper waves 3-7: %s"
+                      % (label, tot[kd, 2], tot[kd, 0] / nk, tot[kd, 1] / nk, tot[kd, 3] / nk, tot[kd, 4] / nk,
+                         ", ".join("%.0f" % (tot[kd, 5 + i] / nk) for i in range(5))))
+            steps = max(tot[:, 2].sum(), 1)
+            print("extra carry rounds per speculative chain: row %.2f, column %.2f" % (tot[0, 10] / steps, tot[0, 11] / steps))
             return
         nm = ["barrier-2 wait", "phase A (chain / install) | hit: step entry", "barrier-1 wait", "settle", "decide", "plan + refill"]
         for base, label in ((0, "hit steps"), (8, "other steps")):
