@@ -1,25 +1,24 @@
-// Windowed time warping for gfx950: the chroma-level half of wtw.WTW.insert
-// (/root/reference/wtw.py:92-128) with get_cost_matrix (:162-171), run_dtw (:173-217) and
-// find_path (:219-240), batched over B independent live streams against one reference chroma.
+// Windowed time warping for gfx950: the chroma-level half of wtw.WTW.insert (the reference's wtw.py:92-128) with
+// get_cost_matrix (:162-171), run_dtw (:173-217) and find_path (:219-240), batched over B independent live streams, each
+// against one reference chroma or against its own slice of a pool of references.
 //
-// One workgroup per stream walks its newly appended live chroma columns; whenever a full window
-// of W live frames is available it
-//   1. computes the W x W normalised-cosine cost with the reference's dot orders (norms: fma
-//      chain = x.dot(x) on a contiguous copy; cross term: OpenBLAS strided ddot order),
-//   2. sweeps the anti-diagonals of the unit-weight DP (candidates (i-1,j), (i,j-1), (i-1,j-1),
-//      strict '<' in that order, codes 3/1/2) with three rotating float64 diagonals in LDS -- all
-//      cells of a diagonal are independent, so D and B are bit-identical to the serial loops,
-//   3. backtracks B and applies the hand-over rule of wtw.py:107-128 (append sub-path points with
-//      l <= dtw_hop/hop, move (live_ptr, ref_ptr) to the last appended point) on one lane.
-// The back-pointer matrix lives in LDS for W <= 128 and in an HBM workspace above that.
+// Whenever a stream has a full window of W live frames, the window is the W x W normalised-cosine cost in the reference's
+// dot orders (sdp::WtwPolicy: norms as an fma chain = x.dot(x) on a contiguous copy, cross term in OpenBLAS's strided ddot
+// order), the unit-weight DP over it (candidates (i-1,j), (i,j-1), (i-1,j-1), strict '<' in that order), the walk back
+// from its last cell, and the hand-over rule of wtw.py:107-128 (append the sub-path points with l <= dtw_hop / hop, move
+// (live_ptr, ref_ptr) to the last appended point).  D, the paths and the pointers are bit-identical to the serial loops.
+// Two paths do this; wtw_select() picks one per handle, at create:
 //
-// Windows of more than 64 frames (wtw_live.py's W = 100 up to BASELINE configs[4]'s W = 10 000, where one window is
-// 1e8 cells) run as a strip DP (sdp.h) spread over many workgroups: per window one launch of
-// wtw_big_dp_kernel (a pipeline of row groups down the W x W matrix, step codes packed 2 bits per cell), the
-// backtrack kernels (wtw_big_hops_kernel, wtw_big_segment_kernel: every strip's path segment by its own wave) and
-// wtw_big_ctl_kernel (hand-over, then the column bookkeeping of
-// wtw.py:92-100 up to the next window).  The host enqueues as many such rounds as the pushed columns can
-// possibly complete windows; rounds with nothing pending return at once.  Everything stays asynchronous.
+// Windows of at most kWinW = 128 frames (tests.py:174's W = 20, wtw_live.py's W = 100): wtw_win_kernel, one workgroup per
+// stream, every window of a push in ONE launch, the cost matrix and the step codes in LDS (described at the kernel).
+//
+// Longer windows (up to BASELINE configs[4]'s W = 10 000, where one window is 1e8 cells; from 65 frames with
+// RTS_WTW_WIN=0) run as a strip DP (sdp.h) spread over many workgroups: per window one launch of wtw_big_dp_kernel (a
+// pipeline of row groups down the W x W matrix, step codes packed 2 bits per cell in HBM), the backtrack kernels
+// (wtw_big_hops_kernel, wtw_big_segment_kernel: every strip's path segment by its own wave; one wtw_big_tail_ctl_kernel
+// for windows of few strips) and wtw_big_ctl_kernel (hand-over, then the column bookkeeping of wtw.py:92-100 up to the
+// next window).  The host enqueues as many such rounds as the pushed columns can possibly complete windows; rounds with
+// nothing pending return at once.  Everything stays asynchronous.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -32,10 +31,6 @@
 namespace rts {
 
 constexpr int kWF = 12;
-constexpr int kWtwNT = 256;
-constexpr int kWtwLdsB = 128;  // largest W whose back-pointers stay in LDS
-constexpr int kWtwLdsW = 512;  // largest W whose window (features, norms, diagonals) stays in LDS
-constexpr int kWtwStripFrom = 64;  // windows above this many frames use the strip DP (sdp.h)
 constexpr int kWtwMaxW = 16384;
 
 struct WtwArgs {
@@ -44,9 +39,9 @@ struct WtwArgs {
     int32_t *appended;    // [B] columns written to `live` so far
     int32_t *state;       // [B][8]: chroma_ptr, live_ptr, ref_ptr, status, n_path, n_windows, cells_lo, cells_hi
     int32_t *path;        // [B][path_cap][2]
-    int8_t *bwork;        // [B][W][W] or NULL when W <= kWtwLdsB
+    int32_t *appended_next;  // [B] the other count array: the next append writes it, then the host swaps the two
     double *dlast;        // [B][W][W] last window's D (optional, NULL = not stored)
-    // W > kWtwLdsW (strip DP):
+    // the strip DP only (NULL on a handle that runs wtw_win_kernel):
     int32_t *ws_sub;           // [B][4W] ints: the window's sub-path, reversed
     int32_t *ws_scr;           // [B][scratch_pairs(W, W)][2]: its segments as walked (sdp::path_segment)
     int32_t *ctl;              // [B][8]: pending, live_ptr, ref_ptr, n, m of the window being computed
@@ -85,206 +80,7 @@ __device__ __forceinline__ WtwRef wtw_ref(const WtwArgs &g, int b) {
     return r;
 }
 
-__device__ __forceinline__ double wtw_dot_chain(const double *x, const double *y) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < kWF; i++) s = fma(x[i], y[i], s);
-    return s;
-}
-
-__device__ __forceinline__ double wtw_dot_strided(const double *x, const double *y) {
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < kWF; i += 4) {
-        const double m3 = y[i + 2] * x[i + 2];
-        const double m4 = y[i + 3] * x[i + 3];
-        const double a = fma(y[i], x[i], m3);
-        const double b = fma(y[i + 1], x[i + 1], m4);
-        t1 = t1 + a;
-        t2 = t2 + b;
-    }
-    return t1 + t2;
-}
-
-// Windows of up to kWtwLdsW frames: window state in LDS, 256 threads.  BL: back-pointers in LDS (W <= kWtwLdsB)
-// rather than HBM.  Compile-time, so that every pointer has a known address space.
-template <bool BL>
-__global__ void __launch_bounds__(256) wtw_advance_kernel(WtwArgs g) {
-    extern __shared__ __align__(16) unsigned char wtw_smem[];
-    const int W = g.W;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    double *xs_l = reinterpret_cast<double *>(wtw_smem);  // [W][F] live window
-    double *ys_l = xs_l + (size_t)W * kWF;                // [W][F] ref window
-    double *nx = ys_l + (size_t)W * kWF;                  // [W]
-    double *ny = nx + W;                                  // [W]
-    double *diag = ny + W;                                // [3][W]
-    int32_t *sub = reinterpret_cast<int32_t *>(diag + 3 * (size_t)W);  // [2W][2]
-    int8_t *bl = reinterpret_cast<int8_t *>(sub + 4 * (size_t)W);  // [W][W] when W <= kWtwLdsB
-    __shared__ int s_chroma_ptr, s_live_ptr, s_ref_ptr, s_status, s_n_path, s_n_windows, s_go;
-    __shared__ long long s_cells;
-
-    int32_t *st = g.state + (size_t)b * 8;
-    const double *live = g.live + (size_t)b * g.live_stride * kWF;
-    const WtwRef sr = wtw_ref(g, b);
-    auto Bm = [&]() {
-        if constexpr (BL)
-            return bl;
-        else
-            return g.bwork + (size_t)b * W * W;
-    }();
-    // `appended` may exceed the capacity N: the excess columns were dropped by the append kernel and mean
-    // "the next column does not fit" (wtw.py:92 would raise IndexError) once the stored ones are consumed
-    const int appended_raw = g.appended[b];
-    const int appended = appended_raw < sr.N ? appended_raw : sr.N;
-
-    if (tid == 0) {
-        s_chroma_ptr = st[0];
-        s_live_ptr = st[1];
-        s_ref_ptr = st[2];
-        s_status = st[3];
-        s_n_path = st[4];
-        s_n_windows = st[5];
-        s_cells = ((long long)(uint32_t)st[7] << 32) | (uint32_t)st[6];
-    }
-    __syncthreads();
-
-    for (;;) {
-        // ---- one new column (wtw.py:92-97), decided by lane 0, broadcast through s_go
-        if (tid == 0) {
-            int go = 0;
-            if (s_status == RTS_RUNNING && s_chroma_ptr < appended) {
-                s_chroma_ptr += 1;
-                if (s_ref_ptr >= (sr.M - 1 - W) || s_live_ptr >= (sr.N - 1 - W))
-                    s_status = RTS_STOP_REF_END;
-                else
-                    go = 1;
-            }
-            s_go = go;
-        }
-        __syncthreads();
-        if (!s_go) break;
-        // ---- windows (wtw.py:100-128)
-        while (s_chroma_ptr - s_live_ptr >= W) {  // uniform: shared values only change behind barriers
-            const int lp = s_live_ptr, rp = s_ref_ptr;
-            const int n = W;
-            int m = W;
-            if (rp + m > sr.M) m = sr.M - rp;  // numpy slice truncation of chroma_ref[:, rp:rp+W]
-            if (m <= 0) break;
-            for (int idx = tid; idx < n * kWF; idx += kWtwNT) xs_l[idx] = live[(size_t)lp * kWF + idx];
-            for (int idx = tid; idx < m * kWF; idx += kWtwNT) ys_l[idx] = sr.ref[(size_t)rp * kWF + idx];
-            const double *xs = xs_l, *ys = ys_l;
-            __syncthreads();
-            for (int i = tid; i < n; i += kWtwNT) nx[i] = sqrt(wtw_dot_chain(xs + i * kWF, xs + i * kWF));
-            for (int j = tid; j < m; j += kWtwNT) ny[j] = sqrt(wtw_dot_chain(ys + j * kWF, ys + j * kWF));
-            __syncthreads();
-            const int n_diag = n + m - 1;
-            for (int d = 0; d < n_diag; d++) {
-                double *cur = diag + (size_t)(d % 3) * W;
-                const double *p1 = diag + (size_t)((d + 2) % 3) * W;
-                const double *p2 = diag + (size_t)((d + 1) % 3) * W;
-                for (int i = tid; i < n; i += kWtwNT) {
-                    const int j = d - i;
-                    if (j < 0 || j >= m) continue;
-                    const double dot = wtw_dot_strided(xs + i * kWF, ys + j * kWF);
-                    const double c = 1.0 - dot / (nx[i] * ny[j]);  // wtw.py:169
-                    double dv;
-                    int8_t code;
-                    if (i == 0 && j == 0) {
-                        dv = c;
-                        code = 0;
-                    } else if (j == 0) {
-                        dv = p1[i - 1] + c;  // wtw.py:187-191
-                        code = 3;
-                    } else if (i == 0) {
-                        dv = p1[0] + c;  // wtw.py:194-198
-                        code = 1;
-                    } else {
-                        double mc = p1[i - 1];  // (i-1, j)
-                        code = 3;
-                        const double v1 = p1[i];  // (i, j-1)
-                        if (v1 < mc) {
-                            mc = v1;
-                            code = 1;
-                        }
-                        const double v2 = p2[i - 1];  // (i-1, j-1)
-                        if (v2 < mc) {
-                            mc = v2;
-                            code = 2;
-                        }
-                        dv = mc + c;
-                    }
-                    cur[i] = dv;
-                    Bm[(size_t)i * W + j] = code;
-                    if (g.dlast) g.dlast[((size_t)b * W + i) * W + j] = dv;
-                }
-                lds_barrier();  // diagonals in LDS: leave the back-pointer / D stores in flight
-            }
-            __syncthreads();  // back-pointers (HBM for W > 128) visible to the lane that walks them
-            if (tid == 0) {
-                // find_path (wtw.py:219-240): walk back from (n-1, m-1); sub[] holds it reversed
-                int i = n - 1, j = m - 1, len = 0;
-                sub[0] = i;
-                sub[1] = j;
-                len = 1;
-                while (!(i == 0 && j == 0) && len < 2 * W) {
-                    const int8_t p = Bm[(size_t)i * W + j];
-                    if (p == 1)
-                        j -= 1;
-                    else if (p == 2) {
-                        i -= 1;
-                        j -= 1;
-                    } else
-                        i -= 1;
-                    sub[2 * len] = i;
-                    sub[2 * len + 1] = j;
-                    len++;
-                }
-                // hand-over (wtw.py:107-128), iterating the sub-path forwards
-                int change = 0, idx_l = 0, idx_r = 0;
-                int32_t *path = g.path + (size_t)b * g.path_cap * 2;
-                for (int q = len - 1; q >= 0; q--) {
-                    const int l = sub[2 * q], r = sub[2 * q + 1];
-                    if (l <= g.hopf) {
-                        if (s_n_path < g.path_cap) {
-                            path[2 * s_n_path] = l + lp;
-                            path[2 * s_n_path + 1] = r + rp;
-                        }
-                        s_n_path += 1;
-                        idx_l = l;
-                        idx_r = r;
-                    } else {
-                        change = 1;
-                        break;
-                    }
-                }
-                if (change) {
-                    s_live_ptr = lp + idx_l;
-                    s_ref_ptr = rp + idx_r;
-                } else {
-                    s_live_ptr = lp + g.hopf;
-                    s_ref_ptr = rp + g.hopf;
-                }
-                s_n_windows += 1;
-                s_cells += (long long)n * m;
-            }
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        if (s_status == RTS_RUNNING && s_chroma_ptr >= sr.N && appended_raw > sr.N) s_status = RTS_LIVE_OVERFLOW;
-        st[0] = s_chroma_ptr;
-        st[1] = s_live_ptr;
-        st[2] = s_ref_ptr;
-        st[3] = s_status;
-        st[4] = s_n_path;
-        st[5] = s_n_windows;
-        st[6] = (int32_t)(uint32_t)(s_cells & 0xffffffffLL);
-        st[7] = (int32_t)(uint32_t)((unsigned long long)s_cells >> 32);
-    }
-}
-
-// ---- windows of at most kWinMaxW frames: every window of a push in ONE launch, one workgroup per stream -------------
+// ---- windows of at most kWinW frames: every window of a push in ONE launch, one workgroup per stream -------------
 //
 // wtw_live.py runs W = 100 / hop = 50, tests.py:174 W = 20 / hop = 10: thousands of small windows per stream, each one
 // depending on the hand-over of the one before.  wtw_win_kernel<R, STAGE> keeps a stream's whole window loop on the device.
@@ -309,8 +105,7 @@ __global__ void __launch_bounds__(256) wtw_advance_kernel(WtwArgs g) {
 //      (n-1, m-1) when the window is no taller than the hop -- with the position in SGPRs and the row's code word one
 //      v_readlane away (find_path, wtw.py:219-240), and appends it (wtw.py:107-117).
 // The column bookkeeping up to the next window is in closed form (the same rules as wtw_ctl_body below).
-constexpr int kWinMaxW = 128;   // what the kernel can do (RTS_WTW_WIN=1 forces it up to here)
-constexpr int kWinAutoW = 128;  // what it is chosen for by default
+constexpr int kWinW = 128;       // the largest window of this kernel: two DP waves of 64 rows (wtw_select)
 constexpr int kWinKW = 12;       // code words per lane: 64 + 127 - 1 steps at most
 constexpr int kWinPadFront = 64;  // doubles in front of / behind the cost matrix: lanes that are not on a valid cell read
 constexpr int kWinPadBack = 208;  // (and ignore) whatever their row pointer + step lands on
@@ -332,7 +127,7 @@ __host__ __device__ inline size_t win_lds_bytes(int W) {
     const size_t feat = sizeof(double) * ((size_t)W * kWF + (size_t)W);                    // xs, nx
     const size_t walk = sizeof(uint32_t) * 2 * kWinKW * 64 + sizeof(double) * (3 * (size_t)W + 32 + kWinBotPad) +  // codes; row 0, column 0 (padded), bottom row of wave 0 (padded)
                         sizeof(int32_t) * ((size_t)W + kWinBotPad) + sizeof(int32_t) * 4 * (size_t)W;  // its crossing columns (padded); sub-path
-    const size_t pref = (W <= kWinPrefW) ? sizeof(double) * (kWinPrefN * kWF + kWinPrefN) : 0;  // ypre, nypre
+    const size_t pref = (W <= kWinPrefW) ? sizeof(int32_t) * (W & 1) + sizeof(double) * (kWinPrefN * kWF + kWinPrefN) : 0;  // (alignment) ypre, nypre
     return sizeof(double) * ((size_t)W * win_ldc(W) + kWinPadFront + kWinPadBack) + feat + walk + pref + 128;
 }
 
@@ -423,7 +218,9 @@ __global__ void __launch_bounds__(R == 1 ? 256 : 512) wtw_win_kernel(WtwArgs g) 
     int32_t *botx = reinterpret_cast<int32_t *>(bot_dummy + kWinBotDummy) + kWinBotFront;  // [W] ... and its crossing columns, padded
     int32_t *botx_dummy = botx + W + kWinBotBack;                                 // [80]
     int32_t *sub = botx_dummy + kWinBotDummy;                                     // [2W][2], reversed
-    double *ypre = reinterpret_cast<double *>(sub + 4 * (size_t)W);              // [kWinPrefN][F] reference frames pref_rp .. (W <= kWinPrefW)
+    // the int32 run botx .. sub in front of ypre is 5 W + kWinBotPad words: one more for odd W keeps the doubles on 8 bytes
+    static_assert(kWinBotPad % 2 == 0, "wtw_win_kernel: the constant part of the int32 run in front of ypre must be an even count");
+    double *ypre = reinterpret_cast<double *>(sub + 4 * (size_t)W + (W & 1));    // [kWinPrefN][F] reference frames pref_rp .. (W <= kWinPrefW)
     double *nypre = ypre + kWinPrefN * kWF;                                       // [kWinPrefN] their norms
 
     int32_t *st = g.state + (size_t)b * 8;
@@ -582,7 +379,9 @@ __global__ void __launch_bounds__(R == 1 ? 256 : 512) wtw_win_kernel(WtwArgs g) 
             for (int q0 = 0; q0 < cnt; q0 += 16) {
                 double v[16];
 #pragma unroll
-                for (int q = 0; q < 16; q++) v[q] = src[q * stride];  // (past the end: the padding behind C)
+                // (past the end: row 0 into the padding behind C; column 0 up to 15 rows -- 15 ldc doubles -- past C,
+                // into xs / nx / codes, all inside this workgroup's LDS: read and never used)
+                for (int q = 0; q < 16; q++) v[q] = src[q * stride];
                 src += 16 * stride;
                 if (q0 == 0) {
                     acc = v[0];
@@ -712,7 +511,7 @@ __global__ void __launch_bounds__(R == 1 ? 256 : 512) wtw_win_kernel(WtwArgs g) 
     }
 }
 
-// ---- windows of more than kWtwLdsW frames: strip DP over many workgroups (sdp.h) ------------------------------
+// ---- windows of more than kWinW frames (from 65 with RTS_WTW_WIN=0): strip DP over many workgroups (sdp.h) ---------
 
 // H helper waves per strip: <.., 2> two strips per workgroup, <.., 3> one strip per workgroup (sdp::pick_config).
 template <bool STAGE, int H>
@@ -902,7 +701,7 @@ __global__ void wtw_precheck_kernel(int32_t *state, int B, int M, const int32_t 
 
 // Append n_new[b] columns from cols [B][n_max][F] to the live history; columns beyond the 2M capacity
 // are dropped (the reference would raise IndexError at that column) and reported as status
-// LIVE_OVERFLOW by the advance kernel once it has walked the columns that did fit.
+// LIVE_OVERFLOW by the window / control kernel once it has walked the columns that did fit.
 // grid (B, slices): a push of a whole recording is 200 KB per stream, so several workgroups share a stream's copy.  Every
 // slice reads the old count from `appended`; slice 0 writes the new one to `appended_next`, and the host swaps the two
 // arrays after the launch (the kernels that follow read the new one).  N is the history stride: with per-stream references
@@ -981,56 +780,45 @@ __global__ void __launch_bounds__(256) wtw_recent_kernel(const double *live, con
 
 }  // namespace rts
 
+// One launch signature for every kernel that takes the handle's arguments.
+typedef void (*rts_wtw_kernel)(rts::WtwArgs);
+
 struct rts_wtw {
-    const double *ref;
-    int M, B, W, hopf, path_cap;
-    int live_stride;  // frames per stream in `live`: 2M (2 M_max with per-stream references)
-    rts::RefTable refs;  // per-stream references (rts_wtw_create_refs): lengths M_b in the pool `ref` points to
-    double *live;
-    int32_t *appended, *appended_next, *state, *path;
-    int8_t *bwork;
-    double *dlast;
-    int32_t *ws_sub, *ws_scr, *ctl, *err, *ticket, *entb, *cross, *lens;
-    double *yrec;
-    uint32_t *codes;
-    unsigned long long *bnd;
-    int big_waves, big_helpers, n_rg, big_grid, use_big;
-    int use_win;  // windows of at most kWinMaxW frames: wtw_win_kernel (0: off, 1 / 2: DP waves)
+    rts::WtwArgs args;   // every buffer and size of the handle: what the kernels are launched with
+    rts::RefTable refs;  // per-stream references (rts_wtw_create_refs): owns args.ref_first / args.ref_len
+    int B;
     int device;  // the HIP device the handle's buffers live on
-    size_t smem;
+    // decided at create (wtw_select): the strip DP (dp != NULL) or the window kernel (win != NULL)
+    rts_wtw_kernel dp;   // wtw_big_dp_kernel<STAGE, H> for this handle's keep_last_d and helper count
+    rts_wtw_kernel win;  // wtw_win_kernel<R, STAGE> for its DP waves and keep_last_d
+    int grid, block;     // of `dp` (grid x B workgroups) or `win` (B workgroups)
+    size_t smem;         // their dynamic LDS
 };
 
 namespace rts {
 
-// Which kernels serve windows of W frames.  The defaults: at most kWinAutoW (128) frames, the one-launch window kernel
-// (measured, 64 streams, hop = W / 2: 3.2x faster than the anti-diagonal sweep at W = 20, 3.8x at W = 64, on a par with
-// the strip DP's launch-per-window rounds at W = 100); above that, being more than one strip (64 rows), the strip DP:
-// on 64 streams at wtw_live.py's W = 100 / hop = 50 it is twice as fast as the single-workgroup sweep despite its five
-// launches per window.  The knobs (tuning, tests and A/B runs; results do not depend on them): RTS_WTW_WIN=0, or 1 to
-// force the window kernel up to kWinMaxW; RTS_WTW_BIG_FROM, another strip-DP threshold (at most kWtwLdsW), which also
-// turns the window kernel off; RTS_WIN_FORCE_R2, two DP waves in the window kernel at any W.
-struct WtwSelect {
-    int use_win;  // 0: off; 1 / 2: DP waves (interior rows 1 .. W-1: one wave up to 65 frames)
-    int use_big;
-    int big_from;
-};
-static WtwSelect wtw_select(int W) {
-    const char *win_e = getenv("RTS_WTW_WIN"), *big_e = getenv("RTS_WTW_BIG_FROM"), *r2_e = getenv("RTS_WIN_FORCE_R2");
-    const int big_from = big_e ? (atoi(big_e) < kWtwLdsW ? atoi(big_e) : kWtwLdsW) : kWtwStripFrom;
-    const bool win = !big_e && (win_e ? (W <= kWinMaxW && atoi(win_e) != 0) : W <= kWinAutoW);
-    return {win ? ((W <= 65 && !r2_e) ? 1 : 2) : 0, !win && W > big_from, big_from};
+// Which kernels serve windows of W frames: wtw_win_kernel up to kWinW (128) frames, the strip DP above.  (Measured on 64
+// streams, hop = W / 2: the window kernel is on a par with the strip DP's launch-per-window rounds at W = 100 and ahead
+// of them below.)  The knobs (tests and A/B runs; results do not depend on them): RTS_WTW_WIN=0 sends windows of 65 to
+// kWinW frames to the strip DP, which keeps its one- and two-strip forms covered -- windows of at most kWinOnlyW frames
+// run on the window kernel whatever is set; RTS_WIN_FORCE_R2, two DP waves in the window kernel at any W.
+constexpr int kWinOnlyW = 64;
+// Returns the DP waves of wtw_win_kernel (interior rows 1 .. W-1: one wave up to 65 frames), 0 for the strip DP.
+static int wtw_select(int W) {
+    const char *win_e = getenv("RTS_WTW_WIN"), *r2_e = getenv("RTS_WIN_FORCE_R2");
+    if (W > kWinW || (W > kWinOnlyW && win_e && atoi(win_e) == 0)) return 0;
+    return (W <= 65 && !r2_e) ? 1 : 2;
 }
 
-// The kernel instantiations that ask for more dynamic LDS than the default limit: 160 KB for the strip-DP and window
-// kernels, 150 KB for the two sweep kernels behind them.
-constexpr int kWtwAttrs160 = 8;
-static const void *const kWtwLdsAttrFns[10] = {
-    reinterpret_cast<const void *>(&wtw_big_dp_kernel<false, 2>), reinterpret_cast<const void *>(&wtw_big_dp_kernel<false, 3>),
-    reinterpret_cast<const void *>(&wtw_big_dp_kernel<true, 2>),  reinterpret_cast<const void *>(&wtw_big_dp_kernel<true, 3>),
-    reinterpret_cast<const void *>(&wtw_win_kernel<1, false>),    reinterpret_cast<const void *>(&wtw_win_kernel<2, false>),
-    reinterpret_cast<const void *>(&wtw_win_kernel<1, true>),     reinterpret_cast<const void *>(&wtw_win_kernel<2, true>),
-    reinterpret_cast<const void *>(&wtw_advance_kernel<true>),    reinterpret_cast<const void *>(&wtw_advance_kernel<false>),
-};
+// The instantiations, [STAGE][...]: all of them ask for more dynamic LDS than the default limit (wtw_raise_lds).
+static const rts_wtw_kernel kWtwDpKernels[2][2] = {{wtw_big_dp_kernel<false, 3>, wtw_big_dp_kernel<false, 2>},  // [helpers == 2]
+                                                   {wtw_big_dp_kernel<true, 3>, wtw_big_dp_kernel<true, 2>}};
+static const rts_wtw_kernel kWtwWinKernels[2][2] = {{wtw_win_kernel<1, false>, wtw_win_kernel<2, false>},  // [DP waves - 1]
+                                                    {wtw_win_kernel<1, true>, wtw_win_kernel<2, true>}};
+
+static hipError_t wtw_raise_lds(rts_wtw_kernel k) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
 
 // The constructor behind rts_wtw_create (first_host == NULL: one reference of M frames) and rts_wtw_create_refs (M =
 // M_max, per-stream tables of B entries, already checked).  Every argument is checked before the first HIP call.
@@ -1046,78 +834,89 @@ static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win
         return set_error(RTS_ERR_UNSUPPORTED, "window of %d frames exceeds the supported %d", win_frames, kWtwMaxW);
     rts_wtw *h = (rts_wtw *)calloc(1, sizeof(rts_wtw));
     if (!h) return set_error(RTS_ERR_INVALID, "out of host memory");
-    h->ref = chroma_ref_dev;
+    WtwArgs &g = h->args;
+    g.ref = chroma_ref_dev;
     if (hipError_t ed = hipGetDevice(&h->device); ed != hipSuccess) {
         free(h);
         return set_error(RTS_ERR_HIP, "hipGetDevice failed: %s", hipGetErrorString(ed));
     }
-    h->M = M;
-    h->live_stride = 2 * M;  // wtw.py:52
+    g.M = M;
+    g.live_stride = 2 * M;  // wtw.py:52
     h->B = B;
-    h->W = win_frames;
-    h->hopf = hop_frames;
-    h->path_cap = (h->live_stride / hop_frames + 2) * (win_frames + hop_frames + 2);
-    const int W = win_frames;
-    const WtwSelect sel = wtw_select(W);
-    const bool win = sel.use_win != 0, big = sel.use_big != 0;
-    h->use_win = sel.use_win;
-    h->use_big = sel.use_big;
-    // (before the occupancy query below: it answers for the limit in force)
-    for (int k = 0; k < 10; k++) {
-        const hipError_t ea = hipFuncSetAttribute(kWtwLdsAttrFns[k], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (k < kWtwAttrs160 ? 160 : 150) * 1024);
-        if (ea != hipSuccess) {
-            free(h);
-            return set_error(RTS_ERR_HIP, "WTW allocation failed: %s", hipGetErrorString(ea));
-        }
-    }
+    g.W = win_frames;
+    g.hopf = hop_frames;
+    g.path_cap = (g.live_stride / hop_frames + 2) * (win_frames + hop_frames + 2);
+    const int W = win_frames, S = sdp::n_strips(W);
+    const int win_waves = wtw_select(W);
+    const bool big = win_waves == 0, stage = keep_last_d != 0;
+    hipError_t e = hipSuccess;
     if (big) {
-        int nw, nh, grid;
-        // workgroups of the one-strip / two-strip DP kernel this device holds at once (sdp::pick_config, "Residency")
-        const size_t pad = sdp::lds_pad();
-        const int res1 = keep_last_d ? sdp::resident_blocks(wtw_big_dp_kernel<true, 3>, 256, sdp::lds_bytes(1) + pad)
-                                     : sdp::resident_blocks(wtw_big_dp_kernel<false, 3>, 256, sdp::lds_bytes(1) + pad);
-        const int res2 = keep_last_d ? sdp::resident_blocks(wtw_big_dp_kernel<true, 2>, 384, sdp::lds_bytes(2) + pad)
-                                     : sdp::resident_blocks(wtw_big_dp_kernel<false, 2>, 384, sdp::lds_bytes(2) + pad);
-        if (res1 < 1 && res2 < 1) {
-            free(h);
-            return set_error(RTS_ERR_HIP, "the occupancy query reports no resident workgroup for the strip-DP kernel on this device");
+        // (the attribute before the occupancy query: it answers for the limit in force)
+        rts_wtw_kernel const k3 = kWtwDpKernels[stage][0], k2 = kWtwDpKernels[stage][1];
+        if ((e = wtw_raise_lds(k3)) == hipSuccess) e = wtw_raise_lds(k2);
+        if (e == hipSuccess) {
+            int nw, nh, grid;
+            // workgroups of the one-strip / two-strip DP kernel this device holds at once (sdp::pick_config, "Residency")
+            const size_t pad = sdp::lds_pad();
+            const int res1 = sdp::resident_blocks(k3, 256, sdp::lds_bytes(1) + pad);
+            const int res2 = sdp::resident_blocks(k2, 384, sdp::lds_bytes(2) + pad);
+            if (res1 < 1 && res2 < 1) {
+                free(h);
+                return set_error(RTS_ERR_HIP, "the occupancy query reports no resident workgroup for the strip-DP kernel on this device");
+            }
+            sdp::pick_config(S, B, res1, res2, nw, nh, grid);
+            h->dp = nh == 2 ? k2 : k3;
+            h->grid = grid;
+            h->block = 64 * nw * (1 + nh);
+            h->smem = sdp::lds_bytes(nw) + pad;
+            g.n_strips_wg = nw;
+            g.n_rg = (S + nw - 1) / nw;
+            g.fill_separate = ((size_t)(g.n_rg > 1 ? g.n_rg - 1 : 0) * W > (1u << 16)) ? 1 : 0;  // more than 0.5 MB of boundary words
         }
-        sdp::pick_config(sdp::n_strips(W), B, res1, res2, nw, nh, grid);
-        h->big_waves = nw;
-        h->big_helpers = nh;
-        h->n_rg = (sdp::n_strips(W) + nw - 1) / nw;
-        h->big_grid = grid;
-        h->smem = sdp::lds_bytes(nw) + pad;
-    } else if (win) {
-        h->smem = win_lds_bytes(W);
     } else {
-        h->smem = sizeof(double) * ((size_t)2 * W * kWF + 2 * W + 3 * W) + sizeof(int32_t) * 4 * W +
-                  (W <= kWtwLdsB ? (size_t)W * W : 0) + 64;
+        h->win = kWtwWinKernels[stage][win_waves - 1];
+        h->grid = B;
+        h->block = win_waves == 1 ? 256 : 512;
+        h->smem = win_lds_bytes(W);
+        e = wtw_raise_lds(h->win);
     }
-    hipError_t e;
-    if ((e = hipMalloc((void **)&h->live, sizeof(double) * kWF * (size_t)h->live_stride * B)) != hipSuccess ||
-        (first_host && (e = ref_table_upload(&h->refs, first_host, len_host, B)) != hipSuccess) ||
-        (e = hipMalloc((void **)&h->appended, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
-        (e = hipMalloc((void **)&h->appended_next, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
-        (e = hipMalloc((void **)&h->state, sizeof(int32_t) * 8 * (size_t)B)) != hipSuccess ||
-        (e = hipMalloc((void **)&h->path, sizeof(int32_t) * 2 * (size_t)h->path_cap * B)) != hipSuccess ||
-        (!big && !win && W > kWtwLdsB && (e = hipMalloc((void **)&h->bwork, (size_t)B * W * W)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->ws_sub, sizeof(int32_t) * 4 * (size_t)W * B)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->ws_scr, sizeof(int32_t) * 2 * sdp::scratch_pairs(W, W) * B)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->ctl, sizeof(int32_t) * 8 * (size_t)B)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->err, 16)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->ticket, sizeof(int32_t) * (size_t)B)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->codes, sizeof(uint32_t) * sdp::codes_words(W, W) * B)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->bnd, sizeof(unsigned long long) * (size_t)sdp::n_strips(W) * W * B)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->entb, sizeof(int32_t) * (size_t)sdp::n_strips(W) * W * B)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->cross, sizeof(int32_t) * (size_t)sdp::n_strips(W) * B)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->yrec, sizeof(double) * sdp::kYRec * (size_t)W * B)) != hipSuccess) ||
-        (big && (e = hipMalloc((void **)&h->lens, sizeof(int32_t) * (size_t)sdp::n_strips(W) * B)) != hipSuccess) ||
-        (keep_last_d && (e = hipMalloc((void **)&h->dlast, sizeof(double) * (size_t)B * W * W)) != hipSuccess)) {
+    if (e != hipSuccess) {
+        free(h);
+        return set_error(RTS_ERR_HIP, "WTW allocation failed: %s", hipGetErrorString(e));
+    }
+    const size_t nB = (size_t)B;
+    const struct {
+        bool wanted;
+        void **buf;
+        size_t bytes;
+    } allocs[] = {
+        {true, (void **)&g.live, sizeof(double) * kWF * (size_t)g.live_stride * nB},
+        {true, (void **)&g.appended, sizeof(int32_t) * nB},
+        {true, (void **)&g.appended_next, sizeof(int32_t) * nB},
+        {true, (void **)&g.state, sizeof(int32_t) * 8 * nB},
+        {true, (void **)&g.path, sizeof(int32_t) * 2 * (size_t)g.path_cap * nB},
+        {stage, (void **)&g.dlast, sizeof(double) * nB * W * W},
+        {big, (void **)&g.ws_sub, sizeof(int32_t) * 4 * (size_t)W * nB},
+        {big, (void **)&g.ws_scr, sizeof(int32_t) * 2 * sdp::scratch_pairs(W, W) * nB},
+        {big, (void **)&g.ctl, sizeof(int32_t) * 8 * nB},
+        {big, (void **)&g.err, 16},
+        {big, (void **)&g.ticket, sizeof(int32_t) * nB},
+        {big, (void **)&g.codes, sizeof(uint32_t) * sdp::codes_words(W, W) * nB},
+        {big, (void **)&g.bnd, sizeof(unsigned long long) * (size_t)S * W * nB},
+        {big, (void **)&g.entb, sizeof(int32_t) * (size_t)S * W * nB},
+        {big, (void **)&g.cross, sizeof(int32_t) * (size_t)S * nB},
+        {big, (void **)&g.lens, sizeof(int32_t) * (size_t)S * nB},
+        {big, (void **)&g.yrec, sizeof(double) * sdp::kYRec * (size_t)W * nB},
+    };
+    for (const auto &a : allocs)
+        if (e == hipSuccess && a.wanted) e = hipMalloc(a.buf, a.bytes);
+    if (e == hipSuccess && first_host) e = ref_table_upload(&h->refs, first_host, len_host, B);
+    if (e != hipSuccess) {
         rts_wtw_destroy(h);
         return set_error(RTS_ERR_HIP, "WTW allocation failed: %s", hipGetErrorString(e));
     }
+    g.ref_first = h->refs.first;
+    g.ref_len = h->refs.len;
     int rc = rts_wtw_reset(h, nullptr);
     if (rc != RTS_OK) {
         rts_wtw_destroy(h);
@@ -1164,8 +963,9 @@ int rts_wtw_create_refs(const double *chroma_refs_dev, int F, long long n_ref_fr
 int rts_wtw_destroy(rts_wtw *h) {
     if (!h) return RTS_OK;
     rts::ref_table_free(&h->refs);
-    void *const bufs[] = {h->live,   h->appended, h->appended_next, h->state, h->path, h->bwork, h->dlast, h->ws_sub, h->ws_scr,
-                          h->ctl,    h->err,      h->ticket,        h->codes, h->bnd,  h->entb,  h->cross, h->yrec,   h->lens};
+    const rts::WtwArgs &g = h->args;
+    void *const bufs[] = {g.live, g.appended, g.appended_next, g.state, g.path, g.dlast, g.ws_sub, g.ws_scr, g.ctl,
+                          g.err,  g.ticket,   g.codes,          g.bnd,   g.entb, g.cross, g.yrec,   g.lens};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     free(h);
@@ -1175,17 +975,18 @@ int rts_wtw_destroy(rts_wtw *h) {
 int rts_wtw_reset(rts_wtw *h, void *stream) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (h->state) {  // (rts_wtw_create resets before the handle is complete; the device is current there by construction)
+    const WtwArgs &g = h->args;
+    if (g.state) {  // (rts_wtw_create resets before the handle is complete; the device is current there by construction)
         if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     }
     hipStream_t s = (hipStream_t)stream;
-    RTS_HIP(hipMemsetAsync(h->appended, 0, sizeof(int32_t) * (size_t)h->B, s));
-    RTS_HIP(hipMemsetAsync(h->state, 0, sizeof(int32_t) * 8 * (size_t)h->B, s));
+    RTS_HIP(hipMemsetAsync(g.appended, 0, sizeof(int32_t) * (size_t)h->B, s));
+    RTS_HIP(hipMemsetAsync(g.state, 0, sizeof(int32_t) * 8 * (size_t)h->B, s));
     // wtw.py:55: chroma_live starts as zeros
-    RTS_HIP(hipMemsetAsync(h->live, 0, sizeof(double) * kWF * (size_t)h->live_stride * h->B, s));
-    if (h->ctl) RTS_HIP(hipMemsetAsync(h->ctl, 0, sizeof(int32_t) * 8 * (size_t)h->B, s));
-    if (h->err) RTS_HIP(hipMemsetAsync(h->err, 0, 16, s));
-    if (h->ticket) RTS_HIP(hipMemsetAsync(h->ticket, 0, sizeof(int32_t) * (size_t)h->B, s));
+    RTS_HIP(hipMemsetAsync(g.live, 0, sizeof(double) * kWF * (size_t)g.live_stride * h->B, s));
+    if (g.ctl) RTS_HIP(hipMemsetAsync(g.ctl, 0, sizeof(int32_t) * 8 * (size_t)h->B, s));
+    if (g.err) RTS_HIP(hipMemsetAsync(g.err, 0, 16, s));
+    if (g.ticket) RTS_HIP(hipMemsetAsync(g.ticket, 0, sizeof(int32_t) * (size_t)h->B, s));
     return RTS_OK;
 }
 
@@ -1194,15 +995,16 @@ int rts_wtw_restart(rts_wtw *h, const uint8_t *mask_host, const long long *first
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (!mask_host) return set_error(RTS_ERR_INVALID, "mask_host is NULL");
-    if (int rc = restart_check(h->B, mask_host, first_host, len_host, h->refs.first ? h->refs.n_frames : -1, h->M, "M_max");
+    if (int rc = restart_check(h->B, mask_host, first_host, len_host, h->refs.first ? h->refs.n_frames : -1, h->args.M, "M_max");
         rc != RTS_OK)
         return rc;
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
+    const WtwArgs &g = h->args;
     RestartSel sel;
     for (int pos = 0; restart_next_chunk(h->B, mask_host, first_host, len_host, &pos, &sel) > 0;) {
-        hipLaunchKernelGGL(wtw_restart_kernel, dim3(16, sel.n), dim3(256), 0, s, sel, h->state, h->appended, h->live,
-                           (long long)h->live_stride * kWF, h->ctl, h->ticket, h->refs.first, h->refs.len);
+        hipLaunchKernelGGL(wtw_restart_kernel, dim3(16, sel.n), dim3(256), 0, s, sel, g.state, g.appended, g.live,
+                           (long long)g.live_stride * kWF, g.ctl, g.ticket, h->refs.first, h->refs.len);
         RTS_HIP(hipGetLastError());
     }
     return RTS_OK;
@@ -1216,8 +1018,8 @@ int rts_wtw_recent(rts_wtw *h, int M_max, double *out_dev, int32_t *len_dev, con
     if (M_max < 1) return set_error(RTS_ERR_INVALID, "M_max must be >= 1 (got %d)", M_max);
     if (M_max > 256) return set_error(RTS_ERR_UNSUPPORTED, "M_max = %d exceeds the 256 frames rts_locate takes", M_max);
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
-    hipLaunchKernelGGL(wtw_recent_kernel, dim3(h->B), dim3(256), 0, (hipStream_t)stream, h->live, h->appended, h->live_stride,
-                       h->M, h->refs.len, M_max, out_dev, len_dev, mask_dev);
+    hipLaunchKernelGGL(wtw_recent_kernel, dim3(h->B), dim3(256), 0, (hipStream_t)stream, h->args.live, h->args.appended,
+                       h->args.live_stride, h->args.M, h->args.ref_len, M_max, out_dev, len_dev, mask_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
@@ -1231,92 +1033,41 @@ int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, co
     if (cols_dtype != RTS_F32 && cols_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad cols_dtype %d", cols_dtype);
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
+    WtwArgs &g = h->args;
+    const int B = h->B;
     if (precheck) {
-        hipLaunchKernelGGL(wtw_precheck_kernel, dim3((h->B + 63) / 64), dim3(64), 0, s, h->state, h->B, h->M, h->refs.len);
+        hipLaunchKernelGGL(wtw_precheck_kernel, dim3((B + 63) / 64), dim3(64), 0, s, g.state, B, g.M, g.ref_len);
         RTS_HIP(hipGetLastError());
     }
     if (n_max == 0) return RTS_OK;
-    hipLaunchKernelGGL(wtw_append_kernel, dim3(h->B, n_max >= 64 ? kWtwAppendSlices : 1), dim3(256), 0, s, h->live, h->appended,
-                       h->appended_next, h->state, cols_dev, cols_dtype == RTS_F64, n_new_dev, n_max, n_max, h->B, h->live_stride);
+    hipLaunchKernelGGL(wtw_append_kernel, dim3(B, n_max >= 64 ? kWtwAppendSlices : 1), dim3(256), 0, s, g.live, g.appended,
+                       g.appended_next, g.state, cols_dev, cols_dtype == RTS_F64, n_new_dev, n_max, n_max, B, g.live_stride);
     {
-        int32_t *t = h->appended;
-        h->appended = h->appended_next;
-        h->appended_next = t;
+        int32_t *t = g.appended;
+        g.appended = g.appended_next;
+        g.appended_next = t;
     }
     RTS_HIP(hipGetLastError());
-    WtwArgs g;
-    g.ref = h->ref;
-    g.live = h->live;
-    g.appended = h->appended;
-    g.state = h->state;
-    g.path = h->path;
-    g.bwork = h->bwork;
-    g.dlast = h->dlast;
-    g.ws_sub = h->ws_sub;
-    g.ws_scr = h->ws_scr;
-    g.ctl = h->ctl;
-    g.codes = h->codes;
-    g.bnd = h->bnd;
-    g.entb = h->entb;
-    g.cross = h->cross;
-    g.lens = h->lens;
-    g.yrec = h->yrec;
-    g.err = h->err;
-    g.ticket = h->ticket;
-    g.n_rg = h->n_rg;
-    g.fill_separate = ((size_t)(h->n_rg > 1 ? h->n_rg - 1 : 0) * h->W > (1u << 16)) ? 1 : 0;  // more than 0.5 MB of boundary words
-    g.n_strips_wg = h->big_waves;
-    g.M = h->M;
-    g.live_stride = h->live_stride;
-    g.ref_first = h->refs.first;
-    g.ref_len = h->refs.len;
-    g.W = h->W;
-    g.hopf = h->hopf;
-    g.path_cap = h->path_cap;
-    if (h->use_big) {
+    if (h->win) {
+        hipLaunchKernelGGL(h->win, dim3(h->grid), dim3(h->block), h->smem, s, g);
+    } else {
         // one (dp, ctl) round per window the new columns can complete: the first needs at least one column, every
         // further one dtw_hop / hop more (the live pointer advances by exactly that per window, wtw.py:118-128)
-        const int rounds = n_max / h->hopf + 1;
-        hipLaunchKernelGGL(wtw_big_ctl_kernel, dim3(h->B), dim3(1024), 0, s, g);
-        if (g.fill_separate) hipLaunchKernelGGL(wtw_big_fill_kernel, dim3(128, h->B), dim3(256), 0, s, g);
+        const int rounds = n_max / g.hopf + 1, S = sdp::n_strips(g.W);
+        hipLaunchKernelGGL(wtw_big_ctl_kernel, dim3(B), dim3(1024), 0, s, g);
+        if (g.fill_separate) hipLaunchKernelGGL(wtw_big_fill_kernel, dim3(128, B), dim3(256), 0, s, g);
         for (int r = 0; r < rounds; r++) {
-            const dim3 grid(h->big_grid, h->B), block(64 * h->big_waves * (1 + h->big_helpers));
-            if (h->big_helpers == 2) {
-                if (h->dlast)
-                    hipLaunchKernelGGL((wtw_big_dp_kernel<true, 2>), grid, block, h->smem, s, g);
-                else
-                    hipLaunchKernelGGL((wtw_big_dp_kernel<false, 2>), grid, block, h->smem, s, g);
+            hipLaunchKernelGGL(h->dp, dim3(h->grid, B), dim3(h->block), h->smem, s, g);
+            if (S <= sdp::kTailStrips) {
+                hipLaunchKernelGGL(wtw_big_tail_ctl_kernel, dim3(B), dim3(64 * S), sdp::tail_lds_bytes(S), s, g);
             } else {
-                if (h->dlast)
-                    hipLaunchKernelGGL((wtw_big_dp_kernel<true, 3>), grid, block, h->smem, s, g);
-                else
-                    hipLaunchKernelGGL((wtw_big_dp_kernel<false, 3>), grid, block, h->smem, s, g);
+                hipLaunchKernelGGL(wtw_big_hops_kernel, dim3(B), dim3(64), 0, s, g);
+                hipLaunchKernelGGL((wtw_big_segment_kernel<0>), dim3(S, B), dim3(64), 0, s, g);
+                hipLaunchKernelGGL((wtw_big_segment_kernel<1>), dim3(S, B), dim3(64), 0, s, g);
+                hipLaunchKernelGGL(wtw_big_ctl_kernel, dim3(B), dim3(1024), 0, s, g);
             }
-            if (sdp::n_strips(h->W) <= sdp::kTailStrips) {
-                hipLaunchKernelGGL(wtw_big_tail_ctl_kernel, dim3(h->B), dim3(64 * sdp::n_strips(h->W)),
-                                   sdp::tail_lds_bytes(sdp::n_strips(h->W)), s, g);
-            } else {
-                hipLaunchKernelGGL(wtw_big_hops_kernel, dim3(h->B), dim3(64), 0, s, g);
-                hipLaunchKernelGGL((wtw_big_segment_kernel<0>), dim3(sdp::n_strips(h->W), h->B), dim3(64), 0, s, g);
-                hipLaunchKernelGGL((wtw_big_segment_kernel<1>), dim3(sdp::n_strips(h->W), h->B), dim3(64), 0, s, g);
-                hipLaunchKernelGGL(wtw_big_ctl_kernel, dim3(h->B), dim3(1024), 0, s, g);
-            }
-            if (g.fill_separate) hipLaunchKernelGGL(wtw_big_fill_kernel, dim3(128, h->B), dim3(256), 0, s, g);
+            if (g.fill_separate) hipLaunchKernelGGL(wtw_big_fill_kernel, dim3(128, B), dim3(256), 0, s, g);
         }
-    } else if (h->use_win == 1) {
-        if (h->dlast)
-            hipLaunchKernelGGL((wtw_win_kernel<1, true>), dim3(h->B), dim3(256), h->smem, s, g);
-        else
-            hipLaunchKernelGGL((wtw_win_kernel<1, false>), dim3(h->B), dim3(256), h->smem, s, g);
-    } else if (h->use_win == 2) {
-        if (h->dlast)
-            hipLaunchKernelGGL((wtw_win_kernel<2, true>), dim3(h->B), dim3(512), h->smem, s, g);
-        else
-            hipLaunchKernelGGL((wtw_win_kernel<2, false>), dim3(h->B), dim3(512), h->smem, s, g);
-    } else if (h->W > kWtwLdsB) {
-        hipLaunchKernelGGL((wtw_advance_kernel<false>), dim3(h->B), dim3(kWtwNT), h->smem, s, g);
-    } else {
-        hipLaunchKernelGGL((wtw_advance_kernel<true>), dim3(h->B), dim3(kWtwNT), h->smem, s, g);
     }
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -1327,7 +1078,7 @@ int rts_wtw_read_states(rts_wtw *h, int32_t *states, void *stream) {
     if (!h || !states) return set_error(RTS_ERR_INVALID, "NULL argument");
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    RTS_HIP(hipMemcpyAsync(states, h->state, sizeof(int32_t) * 8 * (size_t)h->B, hipMemcpyDeviceToHost, s));
+    RTS_HIP(hipMemcpyAsync(states, h->args.state, sizeof(int32_t) * 8 * (size_t)h->B, hipMemcpyDeviceToHost, s));
     RTS_HIP(hipStreamSynchronize(s));
     return RTS_OK;
 }
@@ -1336,18 +1087,18 @@ int rts_wtw_read_path(rts_wtw *h, int b, int32_t *pairs, int cap_pairs, int *n, 
     using namespace rts;
     if (!h || !n) return set_error(RTS_ERR_INVALID, "NULL argument");
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
-    return read_path(h->state, 8, 4, h->path, h->path_cap, b, h->B, pairs, cap_pairs, n, (hipStream_t)stream);
+    return read_path(h->args.state, 8, 4, h->args.path, h->args.path_cap, b, h->B, pairs, cap_pairs, n, (hipStream_t)stream);
 }
 
 int rts_wtw_read_last_d(rts_wtw *h, int b, double *d_host, void *stream) {
     using namespace rts;
     if (!h || !d_host) return set_error(RTS_ERR_INVALID, "NULL argument");
     if (b < 0 || b >= h->B) return set_error(RTS_ERR_INVALID, "stream index %d out of range [0, %d)", b, h->B);
-    if (!h->dlast) return set_error(RTS_ERR_INVALID, "handle was created with keep_last_d = 0");
+    const int W = h->args.W;
+    if (!h->args.dlast) return set_error(RTS_ERR_INVALID, "handle was created with keep_last_d = 0");
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    RTS_HIP(hipMemcpyAsync(d_host, h->dlast + (size_t)b * h->W * h->W, sizeof(double) * (size_t)h->W * h->W,
-                           hipMemcpyDeviceToHost, s));
+    RTS_HIP(hipMemcpyAsync(d_host, h->args.dlast + (size_t)b * W * W, sizeof(double) * (size_t)W * W, hipMemcpyDeviceToHost, s));
     RTS_HIP(hipStreamSynchronize(s));
     return RTS_OK;
 }
@@ -1364,16 +1115,16 @@ int rts_wtw_read_win_stamps(long long *out) {
 int rts_wtw_state_view(rts_wtw *h, int32_t **state_dev) {
     using namespace rts;
     if (!h || !state_dev) return set_error(RTS_ERR_INVALID, "NULL argument");
-    *state_dev = h->state;
+    *state_dev = h->args.state;
     return RTS_OK;
 }
 
 int rts_wtw_device_views(rts_wtw *h, double **live_chroma_dev, int *live_capacity, double **last_d_dev) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (live_chroma_dev) *live_chroma_dev = h->live;
-    if (live_capacity) *live_capacity = h->live_stride;
-    if (last_d_dev) *last_d_dev = h->dlast;
+    if (live_chroma_dev) *live_chroma_dev = h->args.live;
+    if (live_capacity) *live_capacity = h->args.live_stride;
+    if (last_d_dev) *last_d_dev = h->args.dlast;
     return RTS_OK;
 }
 

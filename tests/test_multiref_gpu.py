@@ -201,9 +201,12 @@ def test_dense_mirror_refused():
     eng.close()
 
 
-@pytest.fixture(params=["win", "win_two_waves", "older"])
+@pytest.fixture(params=["win", "win_two_waves", "strip_65_128"])
 def wtw_path(request, monkeypatch):
-    monkeypatch.setenv("RTS_WTW_WIN", "0" if request.param == "older" else "1")
+    """As in test_wtw_gpu.py: the default selection, two DP waves in wtw_win_kernel at any W, and the strip DP for windows
+    of 65 to 128 frames (RTS_WTW_WIN=0)."""
+    if request.param == "strip_65_128":
+        monkeypatch.setenv("RTS_WTW_WIN", "0")
     if request.param == "win_two_waves":
         monkeypatch.setenv("RTS_WIN_FORCE_R2", "1")
     return request.param

@@ -54,13 +54,15 @@ def test_windows_against_reference_vectors(wtw_window_golden, wtw_path):
         eng.close()
 
 
-@pytest.fixture(params=["win", "win_two_waves", "older"])
+@pytest.fixture(params=["win", "win_two_waves", "strip_65_128"])
 def wtw_path(request, monkeypatch):
-    """Windows of at most 128 frames can run on wtw_win_kernel (every window of a push in one launch; the default up to
-    128 frames, and forced on up to there here); RTS_WTW_WIN=0 selects the older kernels (anti-diagonal sweep up to 64 frames,
-    strip DP above), which stay covered this way.  "win_two_waves" sends windows of 65 frames or fewer through the
-    two-wave form of the kernel as well (RTS_WIN_FORCE_R2: its second DP wave then has no rows)."""
-    monkeypatch.setenv("RTS_WTW_WIN", "0" if request.param == "older" else "1")
+    """Windows of at most 128 frames run on wtw_win_kernel (every window of a push in one launch), longer ones on the
+    strip DP: "win" is that default.  "strip_65_128" sets RTS_WTW_WIN=0, which sends windows of 65 to 128 frames to the
+    strip DP as well, so that its one- and two-strip forms stay covered; windows of 64 frames or fewer run on
+    wtw_win_kernel under every setting.  "win_two_waves" sends windows of 65 frames or fewer through the two-wave form
+    of the kernel as well (RTS_WIN_FORCE_R2: its second DP wave then has no rows)."""
+    if request.param == "strip_65_128":
+        monkeypatch.setenv("RTS_WTW_WIN", "0")
     if request.param == "win_two_waves":
         monkeypatch.setenv("RTS_WIN_FORCE_R2", "1")
     return request.param
@@ -102,7 +104,7 @@ def test_batched_streams_vs_oracle(wtw_path):
 # 768 / 800 frames: 12 strips (backtrack and control step in one launch) / 13 strips (separate kernels)
 @pytest.mark.parametrize("W,hopf,n_ref", [(700, 350, 2500), (2000, 1000, 5000), (768, 300, 2600), (800, 410, 2700)])
 def test_large_windows_hbm_resident(W, hopf, n_ref):
-    """Windows beyond the 512 frames that fit LDS run from an HBM workspace; results stay bit-exact."""
+    """Windows of many strips run on the strip DP from an HBM workspace; results stay bit-exact."""
     import oracle
     from real_time_audio_sync_amd import synth
     from real_time_audio_sync_amd.wtw import BatchedWTW
@@ -229,6 +231,39 @@ def test_randomized_small_windows(wtw_path):
         assert (st["live_ptr"], st["ref_ptr"], st["windows"]) == (so["live_ptr"], so["ref_ptr"], o.counters["windows"]), tag
         assert (st["status"] != 0) == (so["status"] != 0), tag
         eng.close()
+
+
+@pytest.mark.parametrize("W", [33, 63])
+def test_odd_window_prefetch_vs_oracle(wtw_path, W):
+    """Odd windows of at most 64 frames, hop = W // 3, two streams against a 400-frame reference, the whole live stream
+    in ONE push: one launch of wtw_win_kernel then runs many windows back to back, and from the second on their cost
+    phase reads what was fetched during the previous window's DP (ypre / nypre, which for odd W sit behind an odd
+    number of int32 words and are moved up to the next 8-byte boundary).  Only the one-wave kernel prefetches, so "win"
+    and "strip_65_128" (the same selection at these W) exercise ypre; "win_two_waves" runs the same windows without it."""
+    import oracle
+    from real_time_audio_sync_amd import synth
+    from real_time_audio_sync_amd.wtw import BatchedWTW
+    dev = torch.device("cuda:0")
+    hopf = W // 3
+    ref, lives = synth.synth_batch(400, 2, seed=17 + W)
+    tmax = max(l.shape[1] for l in lives)
+    cols = np.zeros((2, tmax, 12))
+    for b, l in enumerate(lives):
+        cols[b, : l.shape[1]] = l.T
+    n_new = torch.tensor([l.shape[1] for l in lives], dtype=torch.int32, device=dev)
+    eng = BatchedWTW(torch.from_numpy(np.ascontiguousarray(ref.T)).to(dev), W, hopf, 2)
+    eng.push(torch.from_numpy(cols).to(dev), n_new, precheck=True)
+    for b, l in enumerate(lives):
+        o = oracle.WtwOracle(ref, W, hopf)
+        for q in range(l.shape[1]):
+            if o.push_col(l[:, q]) != oracle.RUNNING:
+                break
+        st, so = eng.state(b), o.state
+        assert o.counters["windows"] >= 3, (W, b)
+        assert np.array_equal(eng.path(b), o.path), (W, b)
+        assert (st["live_ptr"], st["ref_ptr"], st["status"]) == (so["live_ptr"], so["ref_ptr"], so["status"]), (W, b)
+        assert st["windows"] == o.counters["windows"], (W, b)
+    eng.close()
 
 
 def test_wtw_argument_errors():
