@@ -1,0 +1,248 @@
+"""Inputs with digital silence (all-zero chroma columns) for every tracker, and what the CPU oracle says about them.
+
+synth.py adds noise so that no two accumulated costs are equal.  A silent column leaves that regime, differently for
+each tracker:
+
+  * OTW / LiveNote / LiveNoteV2 with the Euclidean cost: a zero live column against a zero reference column costs
+    exactly 0, accumulated costs repeat along the whole band and both band minima are tied -- np.argmin's first-minimum
+    rule and ``rmin < cmin`` decide every step (``silent_pair``, ``band_tie_census``);
+  * WTW: wtw.py:169 divides by the column norms, a zero column makes a NaN row or column of costs, and wtw.py:201-215
+    keeps a NaN that sits in (i-1, j) and ignores it elsewhere (``wtw_silence_case``);
+  * the dot cost: a zero frame costs exactly 1.0 against everything.
+
+Everything here runs on the CPU from the oracle alone; tests/test_silence_cpu.py pins what these inputs do, the GPU
+modules hold the kernels to the oracle on them."""
+import numpy as np
+
+import oracle
+from real_time_audio_sync_amd import synth
+
+VARIANTS = {"otw": oracle.OTW, "livenote": oracle.LIVENOTE, "livenote_v2": oracle.LIVENOTE_V2}
+
+# ---- the OTW inputs of tests/test_otw_ties_gpu.py: (c, seed); every one is silent_pair(2 * c + 100, c, seed, True)
+OTW_BOUNDARY_C = (20, 116, 117, 244, 245, 500)   # last / first band width of the 32-, 128-, 256- and 512-cell windows
+OTW_WIDE_C = (501, 1013)                         # first band width of the 1024- and 2048-cell windows
+OTW_DOT_C = (20, 245)
+
+
+def otw_seed(c):
+    return 7000 + c
+
+
+def silent_pair(n_ref, c, seed, euclid):
+    """-> (ref (12, n_ref), [full, cut, extended]) float64 arrays of float32 values.
+
+    The first c + 55 live frames and the first c + 48 reference frames are zero (the whole fill phase t < c and the
+    crossing of t = c see nothing but ties); a second silence of c + 7 frames starts at live frame c + 69 and at
+    reference frame c + 72.  ``cut`` ends inside the first silence (after t = c), ``extended`` runs past the reference
+    end."""
+    assert n_ref >= 2 * c + 100
+    base = synth.synth_ref(n_ref + 80, seed)         # the live stream is a rendition of a slightly longer piece
+    live = synth.synth_live(base, seed + 1)
+    ref = base[:, :n_ref].copy()
+    if euclid:
+        ref = synth._as_f32_values(np.abs(ref - 0.2))
+        live = synth._as_f32_values(np.abs(live - 0.2))
+    assert live.shape[1] >= 2 * c + 80
+    ref[:, : c + 48] = 0.0
+    live[:, : c + 55] = 0.0
+    ref[:, c + 72: 2 * c + 79] = 0.0
+    live[:, c + 69: 2 * c + 76] = 0.0
+    cut = live[:, : c + 21].copy()
+    ext = synth._as_f32_values(np.concatenate([live, np.repeat(live[:, -1:], 40, axis=1)], axis=1))
+    return ref, [live, cut, ext]
+
+
+def tie_euclid(n_frames, seed):
+    """synth.synth_tie's repeated frames through abs(x - 0.2): equal frames cost exactly 0 with the Euclidean cost."""
+    ref, live = synth.synth_tie(n_frames, seed=seed)
+    return synth._as_f32_values(np.abs(ref - 0.2)), synth._as_f32_values(np.abs(live - 0.2))
+
+
+def silent_pieces(c, seed):
+    """Three pieces for one ``with_references`` handle: the reference of ``silent_pair`` and two copies that start 7 and
+    19 frames later, so the pieces begin with c + 48, c + 41 and c + 29 silent frames and differ in length.
+    -> (refs, lives); stream b follows refs[b]."""
+    ref, lives = silent_pair(2 * c + 100 + 19, c, seed, True)
+    return [ref[:, :-19].copy(), ref[:, 7:-5].copy(), ref[:, 19:].copy()], lives
+
+
+def _ties(band):
+    v = band[~np.isnan(band)]
+    return int((v == v.min()).sum()), float(v.min())
+
+
+def band_tie_census(ref, live, c, mrc=3, variant="otw", euclid=False):
+    """Insert ``live`` frame by frame into the oracle and read ``OtwOracle.bands()`` after every insert.
+
+    -> dict(inserts, tied_fill, tied_steady, largest, equal_minima): the inserts made; those after which the row band
+    or the column band holds its minimum in more than one cell, for t < c and for t >= c; the largest number of cells
+    of one band sharing its minimum; the inserts after which the two band minima are equal."""
+    o = oracle.OtwOracle(ref, c, mrc, VARIANTS[variant], oracle.COST_EUCLID if euclid else oracle.COST_DOT)
+    out = dict(inserts=0, tied_fill=0, tied_steady=0, largest=1, equal_minima=0)
+    for i in range(live.shape[1]):
+        status = o.insert(live[:, i])
+        out["inserts"] += 1
+        if status != oracle.RUNNING or o.state["status"] != oracle.RUNNING:
+            break
+        rb, cb = o.bands()
+        (nr, rmin), (nc, cmin) = _ties(rb), _ties(cb)
+        if max(nr, nc) > 1:
+            out["tied_fill" if o.state["t"] < c else "tied_steady"] += 1
+        out["largest"] = max(out["largest"], nr, nc)
+        out["equal_minima"] += int(rmin == cmin)
+    return out
+
+
+# ---- audio with digital silence for the live ingestion -------------------------------------------------------------------
+LIVE_L, LIVE_HOP, LIVE_COLS = 512, 128, 140          # the smallest geometry of tests/test_live_model_cpu.py
+LIVE_SILENT_COLS = 30                                # longer than the trackers' band (10) and window (16 + 8)
+
+
+def silent_audio(seed=0):
+    """-> (pcm [4] int16, float32 = pcm / 32768 exactly, silences [4] of (first, last) sample or None).  Stream 0 is silent
+    from the first sample and its silence ends half a hop into a hop; stream 1 is silent for LIVE_SILENT_COLS whole frames
+    in the middle, from a hop boundary on; stream 2 the same half a hop later, so that the hops at both ends are half
+    silent; stream 3 holds no silence."""
+    from test_chroma_paths_gpu import synth as audio_synth
+    L, hop = LIVE_L, LIVE_HOP
+    n = L + LIVE_COLS * hop
+    span = L + (LIVE_SILENT_COLS - 1) * hop
+    sil = [(0, span + hop // 2), (40 * hop, 40 * hop + span), (40 * hop + hop // 2, 40 * hop + hop // 2 + span + hop), None]
+    pcm = []
+    for b in range(4):
+        x = np.round(audio_synth(n, hop, seed + 1000 * b).astype(np.float64) * 32768.0).astype(np.int16)
+        if sil[b]:
+            x[sil[b][0]: sil[b][1]] = 0
+        pcm.append(x)
+    return pcm, [p.astype(np.float32) / np.float32(32768.0) for p in pcm], sil
+
+
+def silent_columns(sil, n_cols):
+    """Indices of the chroma columns whose whole frame lies inside the silence (first, last)."""
+    if sil is None:
+        return []
+    return [m for m in range(n_cols) if sil[0] <= m * LIVE_HOP and m * LIVE_HOP + LIVE_L <= sil[1]]
+
+
+# ---- offline DTW ------------------------------------------------------------------------------------------------------
+DTW_SHAPES = ((130, 200), (200, 70))   # (rows, columns): three and four 64-row strips
+
+
+def dtw_silent_pair(M, N, seed):
+    """-> (a (12, M), b (12, N)) with zero frames: rows 0, 63, 64 and the last of ``a``; a run of 9 columns and both ends
+    of ``b``.  Under the dot cost a zero frame costs exactly 1.0 against everything."""
+    a, b = synth.synth_ref(M, seed), synth.synth_ref(N, seed + 1)
+    a[:, [0, 63, 64, M - 1]] = 0.0
+    b[:, N // 3: N // 3 + 9] = 0.0
+    b[:, [0, N - 1]] = 0.0
+    return a, b
+
+
+# ---- WTW ------------------------------------------------------------------------------------------------------------
+def wtw_silence_case(W, hop, rows=(), cols=(), run="live", seed=0, n_ref=None, clean_len=None, records=True):
+    """One reference and two or three live streams for a W-frame window with a hop of ``hop`` frames.
+
+    ``rows`` / ``cols``: silent live frames / reference frames, given as rows / columns of the FIRST window (live frame
+    r, reference frame c: the first window starts at (0, 0)).  ``run``: where a long silence sits later in the piece, from
+    frame 4 W on -- "live" (W + hop + 2 frames: live_ptr moves in steps of hop, so one window lies wholly inside), "ref"
+    (2 W + 1 frames: a window that holds a silent column moves ref_ptr on by W - 1, so the next one lies wholly inside) or
+    "both".  Stream 0 carries all of it and is long enough to reach the stop, stream 1 is stream 0 cut where its live
+    silence ends, stream 2 is another rendition without silent live frames (its first ``clean_len`` frames, if given).
+
+    -> (ref (12, M), lives, records).  records[b] = dict(windows=[(live_ptr, ref_ptr, share of NaN cells in C)],
+    status, live_ptr, ref_ptr): one entry per window the oracle ran, made from ``WtwOracle.state`` before the window and
+    ``oracle.wtw_cost_matrix`` of the two slices (None with ``records=False``)."""
+    M = int(n_ref or 16 * W)
+    ref = synth.synth_ref(M, seed)
+    rs = np.random.RandomState(seed + 5)
+    lives = []
+    for b in range(3):
+        lv = synth.synth_live(ref, seed + 1 + (0 if b < 2 else 1))
+        lv = lv * (0.5 + rs.rand(1, lv.shape[1]))            # un-normalised columns: the cosine cost renormalises
+        lives.append(lv)
+    ref = ref.copy()
+    a = 4 * W
+    for c in cols:
+        ref[:, c] = 0.0
+    if run in ("ref", "both"):
+        ref[:, a + 3: a + 3 + 2 * W + 1] = 0.0
+    for b in (0, 1):
+        for r in rows:
+            lives[b][:, r] = 0.0
+        if run in ("live", "both"):
+            lives[b][:, a: a + W + hop + 2] = 0.0
+    lives[1] = lives[1][:, : a + W + hop + 2].copy()
+    if clean_len:
+        lives[2] = lives[2][:, :clean_len].copy()
+    return ref, lives, [wtw_window_record(ref, lv, W, hop) for lv in lives] if records else None
+
+
+def wtw_window_record(ref, live, W, hop, starts=None):
+    o = oracle.WtwOracle(ref, W, hop)
+    wins = []
+    with np.errstate(all="ignore"):
+        for q in range(live.shape[1]):
+            if starts is not None and q in starts and o.insert_precheck() != oracle.RUNNING:
+                break
+            before, n = o.state, o.counters["windows"]
+            status = o.push_col(live[:, q])
+            if o.counters["windows"] > n:
+                lp, rp = before["live_ptr"], before["ref_ptr"]
+                C = oracle.wtw_cost_matrix(live[:, lp: lp + W], ref[:, rp: rp + W])
+                wins.append((lp, rp, float(np.isnan(C).mean())))
+            if status != oracle.RUNNING:
+                break
+    st = o.state
+    return dict(windows=wins, status=st["status"], live_ptr=st["live_ptr"], ref_ptr=st["ref_ptr"], path=o.path)
+
+
+def wtw_oracle(ref, live, W, hop):
+    """The finished oracle of one stream pushed column by column (one precheck-free run, like ``push`` of everything)."""
+    o = oracle.WtwOracle(ref, W, hop)
+    with np.errstate(all="ignore"):
+        for q in range(live.shape[1]):
+            if o.push_col(live[:, q]) != oracle.RUNNING:
+                break
+    return o
+
+
+def _rows_for(W, first=True):
+    """Rows 0 (with ``first``), 63/64 and 127/128 where a W-frame window has them, and the last."""
+    return tuple(r for r in (0, 63, 64, 127, 128, W - 1) if r < W and (first or r > 0))
+
+
+def wtw_cases():
+    """name -> dict(W, hop, rows, cols, run, seed): every WTW input of tests/test_wtw_silence_gpu.py.
+
+    A silent row r makes every row from r on NaN in D, a silent column c every column from c on, and the path then
+    climbs the last column of the window and walks back along row 0.  So what a case can show depends on its first silent
+    index: "rows" and "both" start at 0 (D is NaN throughout, later windows meet the other rows at other positions),
+    "cols" starts at 63 or at the last column, and "lastcol" has the last column alone: only there does a cell have a NaN
+    above it and finite neighbours to its left, which is where wtw.py:201-215's "a NaN in (i-1, j) stays" decides the
+    step, on the very column the path climbs."""
+    run_of = {"rows": "live", "cols": "ref", "both": "both", "lastcol": "ref"}
+    cases = {}
+
+    def add(W, kind, hop, seed, **kw):
+        rows = _rows_for(W) if kind in ("rows", "both") else ()
+        cols = {"rows": (), "cols": _rows_for(W, first=False), "both": _rows_for(W), "lastcol": (W - 1,)}[kind]
+        cases["w%d_%s" % (W, kind)] = dict(W=W, hop=hop, rows=rows, cols=cols, run=run_of[kind], seed=seed, **kw)
+
+    for k, W in enumerate((16, 33, 64, 65, 100, 128)):
+        add(W, ("rows", "cols", "both")[k % 3], max(1, W // 2 - (k % 3)), 300 + W)
+    # the placements once more on the other sizes, so that every kind meets windows of at most 64 frames (one wave) and of
+    # 65 to 128 (two waves / one and two strips)
+    add(100, "rows", 37, 411)
+    add(33, "both", 11, 412)
+    add(128, "cols", 64, 413)
+    add(64, "lastcol", 29, 414)
+    add(65, "lastcol", 32, 415)
+    add(128, "lastcol", 61, 416)
+    for k, W in enumerate((129, 130, 200)):          # three and four strips
+        add(W, ("both", "rows", "cols")[k], W // 2 - k, 500 + W)
+    add(130, "lastcol", 64, 417)
+    for W in (768, 800):   # 12 strips (backtrack in the DP launch) and 13 (separate kernels): one row, one column
+        cases["w%d_both" % W] = dict(W=W, hop=W // 2 + 5, rows=(W - 1,), cols=(W - 1,), run="live", seed=600 + W,
+                                     n_ref=12 * W, clean_len=3 * W)
+    return cases

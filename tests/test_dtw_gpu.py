@@ -58,6 +58,30 @@ def test_dtw_batch_shapes_and_backpointers():
         assert np.array_equal(acc[k].cpu().numpy(), oacc), k
 
 
+@pytest.mark.parametrize("tdt", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("M,N", [(130, 200), (200, 70)])
+def test_dtw_zero_frames(M, N, tdt):
+    """Digital silence (tests/silence_inputs.py): zero frames on rows 0, 63, 64 and the last, a run of zero columns and
+    both ends of the other sequence.  A zero frame costs exactly 1.0 against everything; two pairs per call."""
+    import oracle
+    import silence_inputs as si
+    from real_time_audio_sync_amd.dtw import dtw_batch
+    from real_time_audio_sync_amd.otw_batch import frames_tensor
+    dev = torch.device("cuda:0")
+    pairs = [si.dtw_silent_pair(M, N, seed) for seed in (M + N, M + N + 7)]
+    a = torch.stack([frames_tensor(x, dev, tdt) for x, _ in pairs])
+    b = torch.stack([frames_tensor(y, dev, tdt) for _, y in pairs])
+    cost, acc, back, path, plen = dtw_batch(a, b)
+    torch.cuda.synchronize()
+    for k, (x, y) in enumerate(pairs):
+        ocost, oacc, opath, oback = oracle.dtw(x, y)
+        assert (ocost[[0, 63, 64, M - 1]] == 1.0).all() and (ocost[:, [0, N // 3, N - 1]] == 1.0).all()
+        assert np.array_equal(cost[k].cpu().numpy(), ocost), k
+        assert np.array_equal(acc[k].cpu().numpy(), oacc), k
+        assert np.array_equal(back[k].cpu().numpy(), oback), k
+        assert np.array_equal(path[k, :int(plen[k])].cpu().numpy(), opath), k
+
+
 # 768 / 769 rows: 12 strips (whole backtrack in one launch) / 13 strips (a workgroup per strip)
 @pytest.mark.parametrize("M,N", [(1, 1), (1, 7), (9, 1), (2, 2), (513, 40), (1100, 90), (768, 130), (769, 130), (64, 700)])
 def test_dtw_edge_shapes(M, N):

@@ -130,6 +130,19 @@ def test_ragged_batch_tail_backtrack():
         _check_pair(path, plen, total, k, r["want"][k])
 
 
+@pytest.mark.parametrize("tdt", [torch.float32, torch.float64], ids=["f32", "f64"])
+def test_zero_frames(tdt):
+    """Digital silence (tests/silence_inputs.py): a 130 x 200 and a 200 x 70 pair in one call, zero frames on rows 0, 63, 64
+    and the last, a run of zero columns and both ends of the other sequence: rows and columns of cost exactly 1.0."""
+    import silence_inputs as si
+    pairs = [si.dtw_silent_pair(m, n, m + n) for m, n in si.DTW_SHAPES]
+    r = dict(shapes=list(si.DTW_SHAPES), a=[x for x, _ in pairs], b=[y for _, y in pairs],
+             want=[_oracle(x, y) for x, y in pairs])
+    path, plen, total = _run_ragged(r, tdt)
+    for k in range(len(pairs)):
+        _check_pair(path, plen, total, k, r["want"][k])
+
+
 @pytest.mark.parametrize("config,grid", [(1, 3), (2, 1), (1, 13)])
 def test_ragged_batch_forced_configurations(ragged13, config, grid):
     """Row groups are per pair: fewer workgroups than the longest pair's row groups, one workgroup for all of them, and

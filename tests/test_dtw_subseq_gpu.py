@@ -188,6 +188,17 @@ def test_ragged_batch_tail_backtrack():
     _check_batch(_run(r), r)
 
 
+@pytest.mark.parametrize("tdt", [torch.float32, torch.float64], ids=["f32", "f64"])
+def test_zero_frames(tdt):
+    """Digital silence (tests/silence_inputs.py): a 130 x 200 and a 200 x 70 pair in one call, zero frames on rows 0, 63, 64
+    and the last of the excerpt, a run of zero columns and both ends of the piece: rows and columns of cost exactly 1.0,
+    so whole stretches of the last row are equal and ``end`` is the first of them."""
+    import silence_inputs as si
+    pairs = [si.dtw_silent_pair(m, n, m + n) for m, n in si.DTW_SHAPES]
+    r = _batch([x for x, _ in pairs], [y for _, y in pairs])
+    _check_batch(_run(r, tdt), r)
+
+
 @pytest.mark.parametrize("shapes,seed", [(RAGGED_13, 500), (RAGGED_12, 600)], ids=["segment", "tail"])
 def test_planted_excerpts_in_ragged_batches(shapes, seed):
     """Both backtrack forms with ends and starts inside the piece, the chunk edges of EDGES among them."""

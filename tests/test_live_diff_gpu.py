@@ -363,3 +363,33 @@ def test_default_mode_is_untouched():
     finally:
         named.close()
         plain.close()
+
+
+@pytest.mark.parametrize("dtype", ["float32", "int16"])
+def test_silence_into_the_headline_configuration(dtype):
+    """Digital silence (tests/silence_inputs.py::silent_audio) into LiveNoteV2 on chroma_diff with the Euclidean cost,
+    against a reference whose audio also begins with silence: the difference of two silent columns is all zeros, zero
+    against zero costs exactly 0 and the band minima tie.  Columns, path, position and status equal the oracle chain
+    (chroma oracle -> clip-diff -> OtwOracle)."""
+    import oracle
+    import silence_inputs as si
+    from test_live_paths_gpu import run_silent_session
+    L, hop = si.LIVE_L, si.LIVE_HOP
+    ref = diff_reference(si.silent_audio()[1][0], L, hop)          # stream 0, silent from the first sample, at 1.25 hop
+    n_zero = int(np.argmax(ref.any(axis=0)))
+    assert n_zero > OTW_C and not ref[:, :n_zero].any()
+    sess = open_session(ref, L, hop)
+    try:
+        device, oracle_cols, info = run_silent_session(sess, dtype, diff=True)
+        for b in range(B):
+            sa = sess.otw.state(b)
+            for cols in (device[b], oracle_cols[b]):
+                o = oracle.OtwOracle(ref, OTW_C, OTW_MRC, variant=oracle.LIVENOTE_V2, cost=oracle.COST_EUCLID)
+                o.run(np.ascontiguousarray(cols.T))
+                assert np.array_equal(sess.path(b), o.path), b
+                assert (sa["t"], sa["j"], sa["status"]) == (o.state["t"], o.state["j"], o.state["status"]), b
+            assert tuple(info["positions"][b]) == (sa["t"], sa["j"]) and info["status"][b] == sa["status"], b
+        census = si.band_tie_census(ref, np.ascontiguousarray(oracle_cols[0].T), OTW_C, OTW_MRC, "livenote_v2", True)
+        assert census["tied_fill"] >= 1 and census["tied_steady"] >= 1 and census["largest"] == OTW_C + 1, census
+    finally:
+        sess.close()

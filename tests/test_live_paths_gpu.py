@@ -295,3 +295,111 @@ def test_otw_state_follows_the_offline_push_and_the_oracle(L, hop, dtype):
     finally:
         eng.close()
         sess.close()
+
+
+# ---- digital silence ------------------------------------------------------------------------------------------------------
+
+def run_silent_session(sess, dtype, diff=False):
+    """Feeds tests/silence_inputs.py::silent_audio to a 4-stream session in feeds of 421 samples and returns, per stream,
+    the columns the feeds handed to the tracker (read through last_columns after every feed), after checking them: bit for
+    bit ChromaPlan.frames on the same plan over all samples (their clip-diff with ``diff``), within the chroma gate of the
+    oracle's columns, and a column whose whole frame is silent exactly zero in both -- zero, not NaN."""
+    import silence_inputs as si
+    from test_live_diff_cpu import clip_diff
+    from test_live_diff_gpu import offline_chroma, oracle_chroma, read_columns
+    pcm, flt, sil = si.silent_audio()
+    src = pcm if dtype == "int16" else flt
+    L, hop = si.LIVE_L, si.LIVE_HOP
+    got = [[] for _ in range(4)]
+    n = len(flt[0])
+    for a in range(0, n, 421):
+        sess.feed([x[a:a + 421] for x in src])
+        cols, _ = read_columns(sess)
+        for b in range(4):
+            got[b].append(cols[b])
+    info = sess.poll()
+    assert info["feeds_done"] == info["feeds_submitted"] == (n + 420) // 421
+    device, oracle_cols = [], []
+    for b in range(4):
+        have = np.concatenate(got[b])
+        off = offline_chroma(sess.plan, flt[b], L, hop).cpu().numpy()
+        orc = oracle_chroma(flt[b], L, hop)
+        assert off.shape == orc.shape == (si.LIVE_COLS + 1, 12)
+        silent = si.silent_columns(sil[b], len(off))
+        assert len(silent) == (0 if sil[b] is None else si.LIVE_SILENT_COLS), b
+        assert not off[silent].any() and not orc[silent].any(), b      # exactly zero, and therefore not NaN
+        rest = [m for m in range(len(off)) if m not in silent]
+        assert off[rest].any(axis=1).all() and not np.isnan(off).any() and not np.isnan(orc).any(), b
+        assert np.abs(off - orc).max() <= CHROMA_ATOL, b
+        if diff:
+            off, orc = clip_diff(off), clip_diff(orc)
+        assert bit_equal(have, off), b
+        device.append(have)
+        oracle_cols.append(orc)
+    return device, oracle_cols, info
+
+
+@pytest.mark.parametrize("dtype", ["float32", "int16"])
+def test_silence_into_an_otw_session(dtype):
+    """int16 zeros and float32 zeros from the first sample, for 30 frames in the middle, and beginning and ending half a
+    hop into a hop: the silent chroma columns are all zeros, cost exactly 1.0 against every reference frame, and the OTW
+    session equals the oracle chain (chroma oracle -> OtwOracle) in path, position and status."""
+    import oracle
+    import silence_inputs as si
+    from oracle import chroma_oracle as co
+    from real_time_audio_sync_amd.live import LiveSession
+    L, hop = si.LIVE_L, si.LIVE_HOP
+    x, h2 = si.silent_audio()[1][3], hop * 5 // 4                # the stream without silence at another tempo
+    ref = np.ascontiguousarray(co.live_loop_columns([x[m * h2:m * h2 + L] for m in range((len(x) - L) // h2 + 1)], L, FS).T)
+    sess = LiveSession(ref, batch=4, c=OTW_C, max_run_count=OTW_MRC, fft_len=L, hop_size=hop, fs=FS,
+                       max_pending=L + 5 * hop + 77)
+    try:
+        device, oracle_cols, info = run_silent_session(sess, dtype)
+        for b in range(4):
+            sa = sess.otw.state(b)
+            for cols in (device[b], oracle_cols[b]):
+                o = oracle.OtwOracle(ref, OTW_C, OTW_MRC)
+                o.run(np.ascontiguousarray(cols.T))
+                assert np.array_equal(sess.path(b), o.path), b
+                assert (sa["t"], sa["j"], sa["status"]) == (o.state["t"], o.state["j"], o.state["status"]), b
+            assert tuple(info["positions"][b]) == (sa["t"], sa["j"]) and info["status"][b] == sa["status"], b
+    finally:
+        sess.close()
+
+
+@pytest.mark.parametrize("dtype", ["float32", "int16"])
+def test_silence_into_a_wtw_session(dtype):
+    """The same audio into a WTW session: a silent column is all zeros in the history, its costs are NaN (wtw.py:169), and
+    windows that lie partly and wholly inside the silence run.  History, path, pointers and status equal the oracle chain
+    (chroma oracle -> WtwOracle)."""
+    import oracle
+    import silence_inputs as si
+    from real_time_audio_sync_amd import synth as rsynth
+    from real_time_audio_sync_amd.live import LiveSession
+    L, hop = si.LIVE_L, si.LIVE_HOP
+    k = si.LIVE_COLS + 1
+    ref = rsynth.synth_ref((k // WTW_HOPF + 1) * (WTW_W - 1) + WTW_W + 8 + k // 4, seed=L + hop)   # wtw_ref_frames
+    sess = LiveSession(ref, batch=4, fft_len=L, hop_size=hop, fs=FS, max_pending=L + 5 * hop + 77,
+                       wtw_params={'dtw_win_size': WTW_W * hop, 'dtw_hop_size': WTW_HOPF * hop})
+    try:
+        device, oracle_cols, info = run_silent_session(sess, dtype)
+        lc, rows = ctypes.c_void_p(), ctypes.c_int()
+        from real_time_audio_sync_amd import _native as nat
+        nat.check(nat.lib.rts_wtw_device_views(sess.wtw._h, ctypes.byref(lc), ctypes.byref(rows), None))
+        hist = _device_to_host(lc.value, (4, rows.value, 12))
+        shares = []
+        for b in range(4):
+            st = sess.wtw.state(b)
+            assert st["chroma_ptr"] == k and bit_equal(hist[b, :k], device[b]) and not hist[b, k:].any(), b
+            for cols in (device[b], oracle_cols[b]):
+                rec = si.wtw_window_record(ref, np.ascontiguousarray(cols.T), WTW_W, WTW_HOPF)
+                assert np.array_equal(sess.wtw.path(b), rec["path"]), b
+                assert (st["live_ptr"], st["ref_ptr"], st["status"], st["windows"]) == (
+                    rec["live_ptr"], rec["ref_ptr"], rec["status"], len(rec["windows"])), b
+            assert tuple(info["positions"][b]) == (st["live_ptr"], st["ref_ptr"]) and info["status"][b] == st["status"], b
+            shares.append([w[2] for w in rec["windows"]])
+        for b in range(3):
+            assert any(0 < s < 1 for s in shares[b]) and any(s == 1 for s in shares[b]), (b, shares[b])
+        assert not any(shares[3])
+    finally:
+        sess.close()

@@ -54,8 +54,10 @@ def test_reference_shorter_than_the_band(mods, mode, c):
 @pytest.mark.parametrize("variant", ["otw", "livenote_v2"])
 @pytest.mark.parametrize("c", [245, 300])
 def test_exact_ties_in_the_fill(mods, variant, c):
-    """synth_tie: exactly equal costs, so the two reductions tie between lanes and the three cells of a Both step tie with
-    the strips' minima -- np.argmin's first-minimum rule decides."""
+    """synth_tie: exactly equal costs, so the three predecessors of a cell tie (56 436 of the 226 676 cells at c = 245) and
+    the order of the candidates decides.  Under the dot cost the minimum of a band is never tied, after none of the
+    inserts (tests/test_silence_cpu.py pins that); tied band minima, where np.argmin's first-minimum rule decides, are in
+    tests/test_otw_ties_gpu.py."""
     oracle, ob, synth = mods
     ref, live = synth.synth_tie(2 * c + 100, seed=13)
     lives = [live, live[:, : c - 3].copy(), live[:, : c + 1].copy()]
