@@ -250,9 +250,15 @@ int rts_dtw_workspace_bytes(int M, int N, int B, size_t *bytes);
  *          consecutive pairs (0 = every pair shares one a); b_dev / b_stride likewise, [B][N][F].
  *   cost_dev, acc_dev: double [B][M][N] outputs (dtw.py:11, :14); back_dev: optional (may be NULL) int8
  *          [B][M][N], the reference's internal `back` matrix: step codes 0 = (0,-1), 1 = (-1,0),
- *          2 = (-1,-1) (dtw.py:30); path_dev: int32 [B][M+N][2], pairs (i, j) from (0,0) to (M-1,N-1);
+ *          2 = (-1,-1) (dtw.py:30); path_dev: int32 [B][M+N][2], pairs (i, j) from (0,0) to (M-1,N-1) in the first
+ *          path_len_dev[k] rows of pair k, the rows behind them are left untouched;
  *          path_len_dev: int32 [B] (-1 if the device pipeline reported a fault).
- *   ws_dev / ws_bytes: caller-owned, 16-byte aligned scratch of at least rts_dtw_workspace_bytes(M, N, B).
+ *   ws_dev / ws_bytes: caller-owned, 16-byte aligned scratch of at least rts_dtw_workspace_bytes(M, N, B).  16 bytes is
+ *          all the alignment it needs (ws_dev + 16 is as good as a 256-byte aligned address), ws_bytes is all the room:
+ *          nothing is written outside [ws_dev, ws_dev + rts_dtw_workspace_bytes), and no result depends on what the
+ *          workspace or the outputs held before the call.
+ *   Alignment of the outputs: path_dev 8 bytes (the path is stored as (i, j) pairs, RTS_ERR_INVALID otherwise); every
+ *          other output that of its element type.  The same holds for rts_dtw_paths and rts_dtw_subseq_paths.
  * Any M, N >= 1 (a long pair is spread over many workgroups).  B <= 65535.  Asynchronous on `stream`;
  * no allocation, no synchronisation (graph-capturable). */
 int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_dev, int b_dtype,
@@ -283,7 +289,7 @@ int rts_dtw_paths_workspace_bytes(int M_max, int N_max, int B, size_t *bytes);
  *   ws_dev / ws_bytes: caller-owned, 16-byte aligned scratch of at least rts_dtw_paths_workspace_bytes(M_max, N_max, B).
  * Limits and errors as rts_dtw: F == 12 (RTS_ERR_UNSUPPORTED otherwise), M_max, N_max, B >= 1, B <= 65535, the same
  * bound on M_max * N_max; RTS_ERR_INVALID names the argument (a NULL a_dev, b_dev, path_dev, path_len_dev, total_dev or
- * ws_dev, a stride between 1 and the maximum, a short or misaligned workspace).
+ * ws_dev, a stride between 1 and the maximum, a short or misaligned workspace, a path_dev that is not 8-byte aligned).
  * Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable). */
 int rts_dtw_paths(const void *a_dev, int a_dtype, long long a_stride, const int32_t *a_len_dev, const void *b_dev,
                   int b_dtype, long long b_stride, const int32_t *b_len_dev, int F, int M_max, int N_max, int B,
@@ -322,8 +328,8 @@ int rts_dtw_subseq_paths_workspace_bytes(int M_max, int N_max, int B, size_t *by
  *          rts_dtw_subseq_paths_workspace_bytes(M_max, N_max, B).
  * Limits and errors as rts_dtw_paths: F == 12 (RTS_ERR_UNSUPPORTED otherwise), M_max, N_max, B >= 1, B <= 65535;
  * RTS_ERR_INVALID names the argument (a NULL a_dev, b_dev, path_dev, path_len_dev, total_dev, start_dev, end_dev or
- * ws_dev, a stride between 1 and the maximum, a short or misaligned workspace); all of them are reported before any
- * HIP call.
+ * ws_dev, a stride between 1 and the maximum, a short or misaligned workspace, a path_dev that is not 8-byte aligned);
+ * all of them are reported before any HIP call.
  * Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable). */
 int rts_dtw_subseq_paths(const void *a_dev, int a_dtype, long long a_stride, const int32_t *a_len_dev,
                          const void *b_dev, int b_dtype, long long b_stride, const int32_t *b_len_dev,
@@ -391,7 +397,8 @@ int rts_chroma_destroy(rts_chroma *h);
  * per-hop chroma of WTW.insert (wtw.py:81-90).  Frame m covers samples [m*hop - pad_left, +fft_len),
  * indices < 0 read as zero (pad_left = fft_len/2 for create_stft's centred framing, 0 for live
  * buffers).  `chroma_out_dev`: [n_frames][12] (out_dtype) or NULL; `stft_out_dev`: optional
- * [n_frames][fft_len/2+1] complex doubles (re, im) -- create_stft's return value, frame-major.
+ * [n_frames][fft_len/2+1] complex doubles (re, im) -- create_stft's return value, frame-major; 16-byte aligned, the
+ * alignment of one complex double (RTS_ERR_INVALID otherwise).  chroma_out_dev needs the alignment of its element type.
  * normalize = 0 gives create_chroma(ft, normalize=False). */
 int rts_chroma_frames(rts_chroma *h, const void *samples_dev, int sample_dtype, long long n_samples,
                       int pad_left, int n_frames, int normalize, void *chroma_out_dev, int out_dtype,
@@ -516,7 +523,12 @@ int rts_wtw_recent(rts_wtw *h, int M_max, double *out_dev, int32_t *len_dev, con
 
 int rts_wtw_read_states(rts_wtw *h, int32_t *states /* [B][RTS_WTW_STATE_LEN] */, void *stream);
 int rts_wtw_read_path(rts_wtw *h, int b, int32_t *pairs, int cap_pairs, int *n, void *stream);
-/* The last window's accumulated-cost matrix D, [W][W] doubles (needs keep_last_d). */
+/* The last window's accumulated-cost matrix D, [W][W] doubles (needs keep_last_d).  A window of n live frames against m
+ * reference frames writes D[i][j] for i < n, j < m with leading dimension W and nothing else.  Today every window is
+ * W x W: wtw.py:96-97 stops a stream while ref_ptr + W is still inside the reference, so the slice wtw.py:102 takes is
+ * never cut short.  Were one cut short (m < W), the cells outside its n x m part would keep what the stream's earlier
+ * windows wrote there -- within a run m only shrinks, so column j >= m holds the D of the last window that reached
+ * it.  Before a stream's first window since create the buffer is unspecified. */
 int rts_wtw_read_last_d(rts_wtw *h, int b, double *d_host, void *stream);
 /* Device views: live chroma history [B][2M][F] float64 and (if kept) the last window's D [B][W][W]. */
 int rts_wtw_device_views(rts_wtw *h, double **live_chroma_dev, int *live_capacity, double **last_d_dev);

@@ -876,6 +876,8 @@ int rts_chroma_frames(rts_chroma *h, const void *samples_dev, int sample_dtype, 
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (!samples_dev) return set_error(RTS_ERR_INVALID, "samples_dev is NULL");
     if (!chroma_out_dev && !stft_out_dev) return set_error(RTS_ERR_INVALID, "no output requested");
+    // a bin leaves the kernels as one (re, im) pair, a 16-byte store
+    if (((uintptr_t)stft_out_dev & 15) != 0) return set_error(RTS_ERR_INVALID, "stft_out_dev must be 16-byte aligned");
     if ((sample_dtype != RTS_F32 && sample_dtype != RTS_F64) || (out_dtype != RTS_F32 && out_dtype != RTS_F64))
         return set_error(RTS_ERR_INVALID, "bad dtype");
     if (n_frames < 0 || pad_left < 0 || n_samples < 0) return set_error(RTS_ERR_INVALID, "negative size");

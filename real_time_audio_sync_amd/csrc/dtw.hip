@@ -317,10 +317,11 @@ static int dtw_workspace(int M, int N, int B, size_t *bytes, const char *m_name,
     return RTS_OK;
 }
 
-// The argument checks rts_dtw and rts_dtw_paths share (M, N: the call's maxima), workspace included: `ws_size` is the
-// caller's own rts_*_workspace_bytes, `ws_fn` its name for the message.
-static int dtw_check(int a_dtype, int b_dtype, int F, int M, int N, int B, const void *ws_dev, size_t ws_bytes,
-                     const char *m_name, const char *n_name, int (*ws_size)(int, int, int, size_t *), const char *ws_fn) {
+// The argument checks rts_dtw and rts_dtw_paths share (M, N: the call's maxima), workspace and the alignment of path_dev
+// included: `ws_size` is the caller's own rts_*_workspace_bytes, `ws_fn` its name for the message.
+static int dtw_check(int a_dtype, int b_dtype, int F, int M, int N, int B, const void *path_dev, const void *ws_dev,
+                     size_t ws_bytes, const char *m_name, const char *n_name, int (*ws_size)(int, int, int, size_t *),
+                     const char *ws_fn) {
     if (F != kDtwF) return set_error(RTS_ERR_UNSUPPORTED, "F must be 12 chroma bins (got %d)", F);
     if (M < 1 || N < 1 || B < 1)
         return set_error(RTS_ERR_INVALID, "%s, %s, B must be >= 1 (got %d %d %d)", m_name, n_name, M, N, B);
@@ -333,6 +334,8 @@ static int dtw_check(int a_dtype, int b_dtype, int F, int M, int N, int B, const
     if (ws_bytes < need)
         return set_error(RTS_ERR_INVALID, "workspace of %zu bytes is smaller than %s = %zu", ws_bytes, ws_fn, need);
     if (((uintptr_t)ws_dev & 15) != 0) return set_error(RTS_ERR_INVALID, "workspace must be 16-byte aligned");
+    // sdp::path_segment copies a segment to its place as (i, j) pairs, one 8-byte store each
+    if (((uintptr_t)path_dev & 7) != 0) return set_error(RTS_ERR_INVALID, "path_dev must be 8-byte aligned");
     return RTS_OK;
 }
 
@@ -426,7 +429,7 @@ int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_de
     using namespace rts;
     if (!a_dev || !b_dev || !cost_dev || !acc_dev || !path_dev || !path_len_dev || !ws_dev)
         return set_error(RTS_ERR_INVALID, "NULL device buffer");
-    if (int rc = dtw_check(a_dtype, b_dtype, F, M, N, B, ws_dev, ws_bytes, "M", "N", rts_dtw_workspace_bytes,
+    if (int rc = dtw_check(a_dtype, b_dtype, F, M, N, B, path_dev, ws_dev, ws_bytes, "M", "N", rts_dtw_workspace_bytes,
                            "rts_dtw_workspace_bytes");
         rc != RTS_OK)
         return rc;
@@ -468,8 +471,8 @@ int rts_dtw_paths(const void *a_dev, int a_dtype, long long a_stride, const int3
     if (!path_len_dev) return set_error(RTS_ERR_INVALID, "path_len_dev is NULL");
     if (!total_dev) return set_error(RTS_ERR_INVALID, "total_dev is NULL");
     if (!ws_dev) return set_error(RTS_ERR_INVALID, "ws_dev is NULL");
-    if (int rc = dtw_check(a_dtype, b_dtype, F, M_max, N_max, B, ws_dev, ws_bytes, "M_max", "N_max",
-                           rts_dtw_paths_workspace_bytes, "rts_dtw_paths_workspace_bytes");
+    if (int rc = dtw_check(a_dtype, b_dtype, F, M_max, N_max, B, path_dev, ws_dev, ws_bytes, "M_max",
+                           "N_max", rts_dtw_paths_workspace_bytes, "rts_dtw_paths_workspace_bytes");
         rc != RTS_OK)
         return rc;
     if (a_stride != 0 && a_stride < M_max)
@@ -517,8 +520,8 @@ int rts_dtw_subseq_paths(const void *a_dev, int a_dtype, long long a_stride, con
     if (!start_dev) return set_error(RTS_ERR_INVALID, "start_dev is NULL");
     if (!end_dev) return set_error(RTS_ERR_INVALID, "end_dev is NULL");
     if (!ws_dev) return set_error(RTS_ERR_INVALID, "ws_dev is NULL");
-    if (int rc = dtw_check(a_dtype, b_dtype, F, M_max, N_max, B, ws_dev, ws_bytes, "M_max", "N_max",
-                           rts_dtw_subseq_paths_workspace_bytes, "rts_dtw_subseq_paths_workspace_bytes");
+    if (int rc = dtw_check(a_dtype, b_dtype, F, M_max, N_max, B, path_dev, ws_dev, ws_bytes, "M_max",
+                           "N_max", rts_dtw_subseq_paths_workspace_bytes, "rts_dtw_subseq_paths_workspace_bytes");
         rc != RTS_OK)
         return rc;
     if (a_stride != 0 && a_stride < M_max)

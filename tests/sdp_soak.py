@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Soak test of the strip DP (csrc/sdp.h) on the GPU box: seeded random DTW shapes (1 .. ~1500 rows / columns, batches,
 float32 / float64 inputs, shared or per-pair b) and WTW windows of 65 .. 900 frames, against the CPU oracle --
-cost, acc_cost, back-pointers, paths, pointers, bit for bit.  The pytest suite runs a shortened form.
+cost, acc_cost, back-pointers, paths, pointers and, on the handles created with keep_last_d, the last window's D, bit
+for bit.  The pytest suite runs a shortened form.
 
     python3 tests/sdp_soak.py [n_trials] [seed]
 """
@@ -15,17 +16,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(n_trials=60, seed=5, verbose=True):
+def run(n_trials=60, seed=5, verbose=True, stats=None):
+    """-> problems checked.  ``stats`` (a dict, optional) receives ``last_d``: how many kept D matrices were compared."""
     import torch
     import oracle
     from real_time_audio_sync_amd import synth
     from real_time_audio_sync_amd.dtw import dtw_batch
     from real_time_audio_sync_amd.otw_batch import frames_tensor
     from real_time_audio_sync_amd.wtw import BatchedWTW
+    import silence_inputs as si
     dev = torch.device("cuda:0")
     rs = np.random.RandomState(seed)
     t0 = time.time()
-    checked = 0
+    checked = d_checked = 0
     for trial in range(n_trials):
         if trial % 3 != 2:
             # ---- DTW
@@ -86,26 +89,48 @@ def run(n_trials=60, seed=5, verbose=True):
                 eng.push(torch.from_numpy(cols[:, cut:].copy()).to(dev), torch.clamp(n_new - cut, min=0), precheck=True)
             for k, l in enumerate(lives):
                 o = oracle.WtwOracle(ref, W, hopf)
+                wins = []   # (live_ptr, ref_ptr) of every window the oracle ran
                 with np.errstate(all="ignore"):
                     for q in range(l.shape[1]):
                         if q == 0 or q == cut:
                             if o.insert_precheck() != oracle.RUNNING:
                                 break
-                        if o.push_col(l[:, q]) != oracle.RUNNING:
+                        before, n_before = o.state, o.counters["windows"]
+                        status = o.push_col(l[:, q])
+                        if o.counters["windows"] > n_before:
+                            wins.append((before["live_ptr"], before["ref_ptr"]))
+                        if status != oracle.RUNNING:
                             break
                 st, so = eng.state(k), o.state
                 tag = ("wtw", trial, W, hopf, Mref, B, k, cut)
                 assert np.array_equal(eng.path(k), o.path), tag
                 assert (st["live_ptr"], st["ref_ptr"], st["windows"]) == (so["live_ptr"], so["ref_ptr"], o.counters["windows"]), tag
                 assert (st["status"] != 0) == (so["status"] != 0), tag
+                assert len(wins) == o.counters["windows"], tag
+                if keep and wins:
+                    # the kept D (the STAGE instantiations of wtw_win_kernel / wtw_big_dp_kernel): the n x m part the
+                    # last window defines, then whatever earlier windows left around a window cut short at the
+                    # reference end (include/rtsync.h, rts_wtw_read_last_d)
+                    got = eng.last_d(k)
+                    lp, rp = wins[-1]
+                    n, m = min(W, l.shape[1] - lp), min(W, Mref - rp)
+                    D, known = si.wtw_last_d(ref, l, wins[-1:], W)
+                    assert known[:n, :m].all() and known.sum() == n * m, tag
+                    assert np.array_equal(got[:n, :m], D[:n, :m], equal_nan=True), tag
+                    D, known = si.wtw_last_d(ref, l, wins, W)
+                    assert np.array_equal(got[known], D[known], equal_nan=True), tag
+                    d_checked += 1
                 checked += 1
             eng.close()
         if verbose and trial % 10 == 9:
             print("trial %d: %d problems checked, %.0f s" % (trial + 1, checked, time.time() - t0), flush=True)
+    if stats is not None:
+        stats["last_d"] = d_checked
     return checked
 
 
 if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-    print("checked", run(n, seed), "problems bit-exact against the oracle")
+    st = {}
+    print("checked", run(n, seed, stats=st), "problems bit-exact against the oracle,", st["last_d"], "kept D matrices among them")

@@ -197,6 +197,28 @@ def wtw_window_record(ref, live, W, hop, starts=None):
     return dict(windows=wins, status=st["status"], live_ptr=st["live_ptr"], ref_ptr=st["ref_ptr"], path=o.path)
 
 
+def wtw_last_d(ref, live, windows, W):
+    """What rts_wtw_read_last_d holds after a stream has run ``windows`` -- (live_ptr, ref_ptr, ...) of every window since
+    create, in order -- as the header states it: window k writes D[i][j] of ``oracle.wtw_run_dtw`` on its n x m cost
+    matrix (m < W where ``ref[:, rp:rp + W]`` is cut short by the reference's end) into a [W][W] buffer with leading
+    dimension W, and a cell keeps what the last window that covered it wrote.
+    -> (D [W][W] float64, known [W][W] bool: the cells some window has written; the others are unspecified).  NaN
+    positions belong to the value, NaN payloads do not: compare with ``np.array_equal(..., equal_nan=True)``."""
+    D = np.full((W, W), np.nan)
+    known = np.zeros((W, W), dtype=bool)
+    for w in reversed(windows):
+        lp, rp = int(w[0]), int(w[1])
+        with np.errstate(all="ignore"):
+            d = oracle.wtw_run_dtw(oracle.wtw_cost_matrix(live[:, lp: lp + W], ref[:, rp: rp + W]))[0]
+        n, m = d.shape
+        new = ~known[:n, :m]
+        D[:n, :m][new] = d[new]
+        known[:n, :m] = True
+        if known.all():
+            break
+    return D, known
+
+
 def wtw_oracle(ref, live, W, hop):
     """The finished oracle of one stream pushed column by column (one precheck-free run, like ``push`` of everything)."""
     o = oracle.WtwOracle(ref, W, hop)

@@ -173,7 +173,10 @@ def test_dtw_batched_pipelines_side_by_side():
 
 def test_strip_dp_soak_short():
     """tests/sdp_soak.py, shortened: seeded random DTW shapes / batches / dtypes and WTW windows on the strip-DP path,
-    everything bit-exact against the oracle (cost, acc_cost, back-pointers, paths, pointers).  (The long form, run by
-    hand when sdp.h changes: 600 trials = 1 038 problems at the end of round 2.)"""
+    everything bit-exact against the oracle (cost, acc_cost, back-pointers, paths, pointers, and the last window's D of
+    the six streams whose handle keeps it: windows of 66 frames on wtw_win_kernel, of 66, 127 and 900 on the strip DP).
+    (The long form, run by hand when sdp.h changes: 600 trials = 1 038 problems at the end of round 2.)"""
     import sdp_soak
-    assert sdp_soak.run(45, seed=17, verbose=False) >= 45
+    stats = {}
+    assert sdp_soak.run(45, seed=17, verbose=False, stats=stats) >= 45
+    assert stats["last_d"] >= 6
