@@ -210,6 +210,13 @@ int rts_otw_read_path(rts_otw *h, int b, int32_t *pairs, int cap_pairs, int *n, 
  * not consumed a frame since create / rts_otw_restart; rts_otw_reset and rts_otw_run leave the bands of such a stream as
  * they were). */
 int rts_otw_read_bands(rts_otw *h, int b, double *row_band, double *col_band, void *stream);
+/* Which streams had their band filled by the dense wavefront kernel in the handle's last rts_otw_run / rts_otw_insert /
+ * rts_otw_push: took[b] = 1 if stream b was fresh and that call brought it at least c frames (c <= 500, reference of at
+ * least c frames, no dense mirror; set_live: more than c frames), so that otw_bandfill_kernel evaluated the square
+ * [0, c-1] x [0, c-1] in front of the step loop; 0 where the step loop ran alone.  Results do not depend on it: the
+ * environment variable RTS_OTW_FILL=0, read by rts_otw_create, leaves every stream to the step loop (A/B measurements,
+ * tests).  `took`: host int32 [B]. */
+int rts_otw_read_fill(rts_otw *h, int32_t *took /* [B] */, void *stream);
 /* Device-side views for zero-copy consumers (torch): path buffer [B][path_cap][2] int32 and state
  * [B][RTS_STATE_LEN] int32. */
 int rts_otw_device_views(rts_otw *h, int32_t **path_dev, int *path_cap, int32_t **state_dev);

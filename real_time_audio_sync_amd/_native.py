@@ -72,6 +72,7 @@ _decl("rts_otw_read_state", _i32, [_vp, _i32, _vp, _vp])
 _decl("rts_otw_read_states", _i32, [_vp, _vp, _vp])
 _decl("rts_otw_read_path", _i32, [_vp, _i32, _vp, _i32, _pi32, _vp])
 _decl("rts_otw_read_bands", _i32, [_vp, _i32, _vp, _vp, _vp])
+_decl("rts_otw_read_fill", _i32, [_vp, _vp, _vp])
 _decl("rts_otw_device_views", _i32, [_vp, ctypes.POINTER(_vp), _pi32, ctypes.POINTER(_vp)])
 _decl("rts_otw_set_waves", _i32, [_vp, _i32])
 _decl("rts_otw_set_dense", _i32, [_vp, _vp, _vp, _vp])

@@ -2475,6 +2475,9 @@ __global__ void __launch_bounds__(256) otw_path_cost_kernel(PathCostArgs a) {
 
 }  // namespace rts
 
+// The band fill of a fresh stream as a dense wavefront (otw_bandfill_kernel), enqueued in front of otw_advance_kernel.
+#include "otw_fill.h"
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -2495,6 +2498,9 @@ struct rts_otw {
     int device;         // the HIP device the handle's buffers live on (one handle = one device)
     int cus;            // its compute units
     int tp_from;        // batches of at least tp_from streams per CU take the residency-oriented kernel flavour
+    int fill;           // RTS_OTW_FILL: 1 = a launch that can bring c frames to a fresh stream runs otw_bandfill_kernel first
+    int fill_last;      // the handle's last launch enqueued it (host-side: which kernels ran is decided per call)
+    int32_t *fill_took; // [B]: 1 where the stream's band was filled by that kernel (written by it, for every stream)
     const void *attr_fn[8];  // kernel instantiations whose dynamic-LDS limit is already raised on `device`
     // what the handle has consumed since the last reset, for rts_otw_replay_dense
     int src_kind;       // 0 nothing, 1 the buffers of the last rts_otw_run, 2 the handle-owned history, 3 mixed
@@ -2573,8 +2579,18 @@ static int launch_w(rts_otw *h, const OtwArgs &args, int B, int waves, hipStream
     return set_error(RTS_ERR_INVALID, "waves must be 1, 2, 4 or 8 (got %d)", waves);
 }
 
-static int launch(rts_otw *h, const OtwArgs &args, hipStream_t s) {
+// max_new: the largest number of new frames the call can bring to any stream (a host-side hint).  Only a launch that can
+// bring a fresh stream its first c frames pays for the band-fill kernel; which streams it fills is decided on the device
+// (otw_fill_eligible), every other stream is left to the step loop untouched.
+static int launch(rts_otw *h, const OtwArgs &args, hipStream_t s, int max_new) {
     if ((uintptr_t)args.live & 15) return set_error(RTS_ERR_INVALID, "live features must be 16-byte aligned");
+    const bool fill = h->fill && max_new >= h->c && h->c >= 2 && h->W <= 512 && !args.dense_acc;
+    if (args.state == h->state) h->fill_last = fill;  // (the dense replay runs on scratch state and never fills)
+    if (fill) {
+        const dim3 block(otw_fill_threads(h->c));
+        hipLaunchKernelGGL(otw_bandfill_kernel, dim3(h->B), block, 0, s, args, h->fill_took);
+        RTS_HIP(hipGetLastError());
+    }
     switch (h->W) {
         case 64: return launch_w<64>(h, args, h->B, h->waves, s);
         case 128: return launch_w<128>(h, args, h->B, h->waves, s);
@@ -2649,12 +2665,13 @@ static void fill_dense(const rts_otw *h, double *acc, double *cost, const Restar
 // the faster one at every batch size measured; RTS_OTW_SPEC=0 selects the plain kernel (A/B runs, tests).  Batches of at
 // least RTS_OTW_TP_FROM streams per CU take the residency-oriented flavour (tests: 0 selects it at any batch size).
 // Results are identical.
+// RTS_OTW_FILL=0 leaves the band fill of fresh streams to the step loop (otw_bandfill_kernel is never enqueued).
 struct OtwKnobs {
-    int spec, tp_from;
+    int spec, tp_from, fill;
 };
 static OtwKnobs otw_knobs() {
-    const char *sp = getenv("RTS_OTW_SPEC"), *tp = getenv("RTS_OTW_TP_FROM");
-    return {sp ? (atoi(sp) != 0) : 1, tp ? atoi(tp) : 2};
+    const char *sp = getenv("RTS_OTW_SPEC"), *tp = getenv("RTS_OTW_TP_FROM"), *fl = getenv("RTS_OTW_FILL");
+    return {sp ? (atoi(sp) != 0) : 1, tp ? atoi(tp) : 2, fl ? (atoi(fl) != 0) : 1};
 }
 
 // The constructor behind rts_otw_create (first_host == NULL: one reference of N frames) and rts_otw_create_refs (N =
@@ -2692,6 +2709,7 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
     const OtwKnobs knobs = otw_knobs();
     h->spec = knobs.spec;
     h->tp_from = knobs.tp_from;
+    h->fill = knobs.fill;
     h->hist_stride = 2 * N;
     h->path_cap = 3 * N + 8;  // one point per decide(); decides <= row strips + column strips <= 2N + N
     hipError_t e;
@@ -2704,6 +2722,7 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
         (e = hipMalloc((void **)&h->path, sizeof(int32_t) * 2 * (size_t)h->path_cap * B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->bands, sizeof(double) * 2 * (size_t)(c + 1) * B)) != hipSuccess ||
         (e = hipMalloc((void **)&h->hist_len, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
+        (e = hipMalloc((void **)&h->fill_took, sizeof(int32_t) * (size_t)B)) != hipSuccess ||
         (first_host && (e = ref_table_upload(&h->refs, first_host, len_host, B)) != hipSuccess)) {
         rts_otw_destroy(h);
         return set_error(RTS_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
@@ -2766,6 +2785,7 @@ int rts_otw_destroy(rts_otw *h) {
     if (h->bands) (void)hipFree(h->bands);
     if (h->hist) (void)hipFree(h->hist);
     if (h->hist_len) (void)hipFree(h->hist_len);
+    if (h->fill_took) (void)hipFree(h->fill_took);
     rts::ref_table_free(&h->refs);
     if (h->rp_state) (void)hipFree(h->rp_state);
     if (h->rp_path) (void)hipFree(h->rp_path);
@@ -2876,7 +2896,7 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
         a.mode = h->run_mode;
         a.clamp_len = 1;
     }
-    int rc = launch(h, a, s);
+    int rc = launch(h, a, s, 0);  // the dense mirror: always the step loop
     if (rc != RTS_OK) return rc;
     RTS_HIP(hipStreamSynchronize(s));
     return RTS_OK;
@@ -2915,7 +2935,7 @@ int rts_otw_run(rts_otw *h, const void *live_dev, int live_dtype, int T_max, con
     h->run_dtype = live_dtype;
     h->run_T = T_max;
     h->run_mode = mode;
-    return launch(h, a, s);
+    return launch(h, a, s, T_max);
 }
 
 int rts_otw_insert(rts_otw *h, const void *frames_dev, int frames_dtype, const uint8_t *active_dev, void *stream) {
@@ -2929,7 +2949,7 @@ int rts_otw_insert(rts_otw *h, const void *frames_dev, int frames_dtype, const u
     hipLaunchKernelGGL(otw_append_kernel, dim3(h->B), dim3(64), 0, s, h->hist, h->hist_len, frames_dev,
                        frames_dtype == RTS_F64, active_dev, h->B, h->hist_stride);
     RTS_HIP(hipGetLastError());
-    return launch(h, hist_args(h), s);
+    return launch(h, hist_args(h), s, 1);
 }
 
 int rts_otw_push(rts_otw *h, const void *frames_dev, int frames_dtype, int n_max, const int32_t *n_new_dev,
@@ -2946,7 +2966,8 @@ int rts_otw_push(rts_otw *h, const void *frames_dev, int frames_dtype, int n_max
     hipLaunchKernelGGL(otw_append_many_kernel, dim3(h->B), dim3(128), 0, s, h->hist, h->hist_len, frames_dev,
                        frames_dtype == RTS_F64, n_new_dev, n_max, n_max, h->B, h->hist_stride);
     RTS_HIP(hipGetLastError());
-    return launch(h, hist_args(h), s);
+    // n_max: a restarted or late-joining stream may catch up from a long excerpt in one call
+    return launch(h, hist_args(h), s, n_max);
 }
 
 // rts_otw_recent / rts_otw_path_cost read the handle-owned history: frames of an rts_otw_run are the caller's memory.
@@ -3029,6 +3050,19 @@ int rts_otw_read_path(rts_otw *h, int b, int32_t *pairs, int cap_pairs, int *n, 
     if (!h || !n) return set_error(RTS_ERR_INVALID, "NULL argument");
     return read_path(h->state, RTS_STATE_LEN, RTS_ST_N_PATH, h->path, h->path_cap, b, h->B, pairs, cap_pairs, n,
                      (hipStream_t)stream);
+}
+
+int rts_otw_read_fill(rts_otw *h, int32_t *took, void *stream) {
+    using namespace rts;
+    if (!h || !took) return set_error(RTS_ERR_INVALID, "NULL argument");
+    if (!h->fill_last) {  // the last launch ran the step loop alone
+        memset(took, 0, sizeof(int32_t) * (size_t)h->B);
+        return RTS_OK;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    RTS_HIP(hipMemcpyAsync(took, h->fill_took, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, s));
+    RTS_HIP(hipStreamSynchronize(s));
+    return RTS_OK;
 }
 
 int rts_otw_read_bands(rts_otw *h, int b, double *row_band, double *col_band, void *stream) {

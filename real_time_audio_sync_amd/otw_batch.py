@@ -205,6 +205,14 @@ class BatchedOTW(_BatchedHandle):
         return rb, cb
 
     @_on_device
+    def fill_taken(self):
+        """int32 [B]: 1 where the stream's band was filled by the dense wavefront kernel in the last run / insert / push
+        (rts_otw_read_fill), 0 where the step loop ran alone."""
+        out = np.zeros(self.B, dtype=np.int32)
+        nat.check(nat.lib.rts_otw_read_fill(self._h, out.ctypes.data, self._stream()))
+        return out
+
+    @_on_device
     def enable_dense(self):
         """Allocate and attach the reference's dense (2N x N) acc_cost / cost matrices per stream
         (float64 device tensors [B][2N][N]); every evaluated cell is mirrored into them."""
