@@ -235,8 +235,9 @@ int rts_otw_set_dense(rts_otw *h, double *acc_dev, double *cost_dev, void *strea
  * (otw_eran.py:23,27) are made of. */
 int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T_max, const int32_t *live_len_dev,
                          double *acc_dev, double *cost_dev, void *stream);
-/* Tuning knob, not semantics: waves per stream workgroup (1, 2, 4 or 8; default 8).  Results are identical.
- * With 8 waves and no dense mirror the library runs its pipelined kernel (the next step's strips are computed
+/* Formerly a tuning knob (waves per stream workgroup); every kernel now runs 8 waves.  8 is accepted and changes
+ * nothing, the retired counts 1, 2 and 4 return RTS_ERR_UNSUPPORTED, anything else RTS_ERR_INVALID.
+ * Without a dense mirror the library runs its pipelined kernel (the next step's strips are computed
  * beside this step's control work); the environment variable RTS_OTW_SPEC=0, read by rts_otw_create, selects
  * the plain kernel instead (A/B measurements, tests). */
 int rts_otw_set_waves(rts_otw *h, int waves);

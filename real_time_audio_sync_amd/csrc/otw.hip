@@ -4,7 +4,7 @@
 // livenote_v2.py:43-236 (restated on the CPU, for tests only, in oracle/rtsync_oracle.c).
 //
 // Design:
-//   * one workgroup (NW waves) per live stream; the whole per-stream state lives in LDS for the
+//   * one workgroup (8 waves) per live stream; the whole per-stream state lives in LDS for the
 //     duration of a launch: the two live accumulated-cost bands (row t over columns [j-c, j] and
 //     column j over rows [t-c, t]), ring windows of the last W live (and, plain kernel, reference)
 //     chroma frames, and the cost strips the helper waves prepare ahead of time;
@@ -1375,25 +1375,19 @@ __device__ __forceinline__ OtwSettled otw_settle_hit(double *R, double *C, const
 // The barrier of the pipelined step loops.  The waves of a stream talk to each other through LDS only (bands, cost
 // buffers, plan); what they send to global memory -- wave 0's path points, the dense mirror -- is read by nobody before
 // the launch ends.  __syncthreads() would also drain those stores (a full release: vmcnt(0)) once per step.
-// -DRTS_OTW_FULL_BARRIER restores it for A/B runs.
-#ifdef RTS_OTW_FULL_BARRIER
-#define RTS_STEP_BARRIER() __syncthreads()
-#else
 #define RTS_STEP_BARRIER() ::rts::lds_barrier()
-#endif
 
-template <int W, int NW, bool DENSE, typename RT, bool SPEC>
+template <int W, bool DENSE, typename RT, bool SPEC>
 // (the throughput flavour exists for its residency -- three workgroups of eight waves per CU, i.e. at most 80 VGPRs: said to
 // the compiler here, because the ILP-first scheduling this file is built with otherwise spends 87)
-__global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kThroughput<RT> ? 6 : 1)))
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(kThroughput<RT> ? 6 : 1)))
 otw_advance_kernel(OtwArgs a) {
-    static_assert(!SPEC || (NW >= 8 && !DENSE), "the pipelined kernel needs 8 waves and no dense mirror");
-    constexpr int NT = 64 * NW;
+    static_assert(!SPEC || !DENSE, "the pipelined kernel writes no dense mirror");
+    constexpr int NT = 512;  // eight waves
     // Waves >= HW0 pre-compute the next step's cell costs while waves 0/1 run the chains (pipelined kernel:
-    // wave 2 runs the speculative column strip).  With fewer than 4 waves there are no spare ones and every
-    // wave does its share after its chain.
-    constexpr int HW0 = SPEC ? 3 : (NW >= 4) ? 2 : 0;
-    constexpr int NHELP = 64 * (NW - HW0);
+    // wave 2 runs the speculative column strip).
+    constexpr int HW0 = SPEC ? 3 : 2;
+    constexpr int NHELP = NT - 64 * HW0;
 #if defined(RTS_OTW_STAMPS) && RTS_OTW_STAMPS == 1
     long long stamp_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int stamp_base = 0;
@@ -1634,14 +1628,6 @@ otw_advance_kernel(OtwArgs a) {
     __syncthreads();
 
     int sp = 0;  // pipelined kernel: step parity (plan slot read this step; speculation results go to [sp ^ 1])
-#ifdef RTS_OTW_PRIO_W0
-    // experiment (profiles/experiments/README.md): the waves that pace a step -- control wave 0, chain waves 1 / 2 -- each
-    // share a SIMD with a helper wave; a static priority lets them win every issue arbitration
-    if constexpr (SPEC) {
-        if (wave == 0) __builtin_amdgcn_s_setprio(RTS_OTW_PRIO_W0);
-        if (wave == 1 || wave == 2) __builtin_amdgcn_s_setprio(RTS_OTW_PRIO_W12);
-    }
-#endif
     if constexpr (SPEC) {
         // ---- pipelined step loops.  While wave 0 runs the control work of a step, wave 1 already runs the row strip
         // the next step needs if it turns out Row-only and wave 2 the column strip it needs if it turns out
@@ -1779,12 +1765,6 @@ otw_advance_kernel(OtwArgs a) {
             int2 *const path_row = reinterpret_cast<int2 *>(e.path) + (size_t)e.b * e.path_cap;
             const auto hit_steps = [&](auto v2_c, auto defer_c) __attribute__((always_inline)) {
                 constexpr bool V2 = decltype(v2_c)::value, DEFER = decltype(defer_c)::value;
-                // (-DRTS_OTW_NO_BOTH_LOOP: Both steps stay with the general loop, for A/B runs and the "before" stamps)
-#ifdef RTS_OTW_NO_BOTH_LOOP
-                constexpr bool kBothHere = false;
-#else
-                constexpr bool kBothHere = true;
-#endif
                 // every lane holds the same control state: said once here, the integers stay in SGPRs through the loop
 #define RTS_RFL_CTL(f) k.f = __builtin_amdgcn_readfirstlane(k.f)
                 RTS_RFL_CTL(t), RTS_RFL_CTL(j), RTS_RFL_CTL(dir), RTS_RFL_CTL(prev), RTS_RFL_CTL(run_count);
@@ -1800,7 +1780,7 @@ otw_advance_kernel(OtwArgs a) {
                     // a Both step whose strips are the two shadows: planned as a hit (the band is still filling), or "hit
                     // if the column speculation allows" (full band; otw_resolve_plan)
                     const bool hit_if = kind == (kPlanHitIf | kPlanRow | kPlanCol);
-                    const bool is_both = kBothHere && (hit_if || kind == (kPlanHit | kPlanRow | kPlanCol));
+                    const bool is_both = hit_if || kind == (kPlanHit | kPlanRow | kPlanCol);
                     if (!is_row && !is_both && kind != (kPlanHit | kPlanCol)) return;
                     const int jn = is_row ? j0 : j0 + 1;
                     double rmin, cmin, cl;
@@ -2074,7 +2054,7 @@ otw_advance_kernel(OtwArgs a) {
             }
 #undef RTS_W0_STEP_END
         }
-    } else if constexpr (NW >= 4) {
+    } else {
         // ---- role-specialised step loops.  Every wave runs only its own role's code between the two barriers of
         // a step (a step = one row strip and/or one column strip + one decide()), so each loop keeps only its own
         // values live: helpers pre-compute costs, wave 1 runs the column strip of Both steps, wave 0 runs the
@@ -2126,119 +2106,6 @@ otw_advance_kernel(OtwArgs a) {
                 __syncthreads();
                 buf ^= 1;
             }
-        }
-    } else {
-        // ---- step loop: one iteration = one row strip and/or one column strip + one decide()
-        for (;;) {
-            RTS_STAMP(0);
-            const int pt = __builtin_amdgcn_readfirstlane(S.plan_t[0]), j0 = __builtin_amdgcn_readfirstlane(S.plan_j0[0]),
-                      pflags = __builtin_amdgcn_readfirstlane(S.plan_flags[0]);
-            if (pflags & kPlanExit) break;
-            const bool do_row = (pflags & kPlanRow) != 0, do_col = (pflags & kPlanCol) != 0;
-            const bool stop = (pflags & kPlanStop) != 0;
-            const int jn = j0 + (do_col ? 1 : 0);
-            const int k1r = (j0 - c + 1 > 0) ? j0 - c + 1 : 0, nr = j0 - k1r + 1;  // row strip: columns
-            const int k1c = (pt - c + 1 > 0) ? pt - c + 1 : 0, nc = pt - k1c + 1;  // column strip: rows
-            const bool col_active = do_col && !stop;
-            double *Dr = S.Dr[buf], *Dc = S.Dc[buf];
-
-            // -- chain phase: row strip on wave 0, column strip on wave 1; spare waves pre-compute the
-            //    next step's costs meanwhile
-            const int col_wave = (NW > 1 && do_row) ? 1 : 0;
-            double rf_min = inf;
-            int rf_idx = 0x7fffffff;
-            if (do_row && wave == 0) {
-                const double x_in = (k1r > 0) ? sentinel : inf;  // (t, k1r-1) was never evaluated
-                const int lo_arg = (jn - c + 1 > 0) ? jn - c + 1 : 0;  // row band's lower end at decide()
-                const long long dro = ((long long)e.b * e.live_cap + pt) * N + k1r;  // cell (pt, k1r)
-                strip_chain<W, DENSE>(Dr, S.R, S.R, k1r, nr, x_in, lane, lo_arg, rf_min, rf_idx, DENSE ? a.dense_acc + dro : nullptr,
-                                      DENSE ? a.dense_cost + dro : nullptr, 1);
-                if (lane == 0 && k1r > 0) S.R[swz<W>(k1r - 1)] = sentinel;
-            }
-            if (col_active && wave == col_wave) {
-                const double x_in = (k1c > 0) ? sentinel : inf;  // (k1c-1, jn) was never evaluated
-                const int ncc = nc - (do_row ? 1 : 0);            // corner cell waits for the row strip
-                double fm;
-                int fi;
-                // the corner's diagonal term needs column jn-1 at row t-1, which the chain is about to overwrite
-                const double dcorner = Dc[swz<W>(pt)];
-                const double pa = (do_row && pt > 0) ? S.C[swz<W>(pt - 1)] + 2 * dcorner : inf;
-                const long long dco = ((long long)e.b * e.live_cap + k1c) * N + jn;  // cell (k1c, jn)
-                strip_chain<W, DENSE>(Dc, S.C, S.C, k1c, ncc, x_in, lane, k1c, fm, fi, DENSE ? a.dense_acc + dco : nullptr,
-                                      DENSE ? a.dense_cost + dco : nullptr, N);
-                if (lane == 0) {
-                    S.corner_pa = pa;
-                    S.corner_d = dcorner;
-                    if (k1c > 0) S.C[swz<W>(k1c - 1)] = sentinel;
-                    S.cfresh_min = fm;
-                    S.cfresh_idx = fi;
-                }
-            }
-            RTS_STAMP(3);
-            if (!stop && wave >= HW0)
-                otw_precompute<W, RT>(S, e, pt, jn, S.Dr[buf ^ 1], S.Dc[buf ^ 1], tid - 64 * HW0, NHELP);
-            RTS_STAMP(4);
-            __syncthreads();
-            RTS_STAMP(5);
-
-            // -- corner fix-up, decide, next plan (wave 0, register state)
-            if (wave == 0) {
-                if (!stop && e.deferred_update && k.pend_dir != -2) {  // livenote_v2.py:149-155
-                    k.run_count = (k.pend_dir == k.prev) ? k.run_count + 1 : 1;
-                    if (k.pend_dir != RTS_DIR_BOTH) k.prev = k.pend_dir;
-                    k.pend_dir = -2;
-                }
-                if (do_row) {
-                    k.rows += 1;
-                    k.cells += nr;
-                    k.consumed = pt + 1;
-                }
-                double cl = 0.0, cf_min = inf;
-                int cf_idx = 0x7fffffff;
-                // last cell of the row strip = acc[t][j0]; of the column chain = acc[t-1][jn] (Both) or acc[t][jn]
-                const double row_last = do_row ? rfl(S.R[swz<W>(j0)]) : 0.0;
-                if (do_row && !col_active && lane == 0) S.C[swz<W>(pt)] = row_last;  // column j0 gains row t
-                if (col_active) {
-                    const int ncc = nc - (do_row ? 1 : 0);
-                    cl = (ncc > 0) ? rfl(S.C[swz<W>(k1c + ncc - 1)]) : ((k1c > 0) ? sentinel : inf);
-                    cf_min = rfl(S.cfresh_min);
-                    cf_idx = __builtin_amdgcn_readfirstlane(S.cfresh_idx);
-                    if (do_row) {
-                        const double d = rfl(S.corner_d);
-                        const double av = vmin(row_last + d, rfl(S.corner_pa));
-                        cl = vmin(av, cl + d);  // cl was the value of (t-1, jn), or the sentinel carry
-                        if (lane == 0) {
-                            S.C[swz<W>(pt)] = cl;
-                            if (DENSE) {
-                                const long long o = ((long long)e.b * e.live_cap + pt) * N + jn;
-                                a.dense_acc[o] = cl;
-                                a.dense_cost[o] = d;
-                            }
-                        }
-                    }
-                    if (lane == 0) S.R[swz<W>(jn)] = cl;  // row t gains column jn
-                    k.cols += 1;
-                    k.cells += nc;
-                }
-                RTS_STAMP(6);
-                if (stop) {
-                    k.status = RTS_STOP_REF_END;
-                    k.t = pt;
-                    k.j = jn;
-                    k.pending_col = 0;
-                } else {
-                    // row band: fresh from this step's row strip, plus the corner a column strip appended;
-                    // column band: fresh from this step's column strip (its corner cell is outside the
-                    // chain), or the old band plus the row strip's last cell
-                    otw_decide<W, RT>(S.R, S.C, k, e, pt, jn, do_row, rf_min, rf_idx, col_active, cf_min, cf_idx, col_active, cl,
-                                  do_row, col_active ? cl : row_last, false);
-                }
-                RTS_STAMP(7);
-                otw_make_plan<W, RT>(S, k, e);
-            }
-            RTS_STAMP(8);
-            __syncthreads();
-            buf ^= 1;
         }
     }
     __syncthreads();
@@ -2473,6 +2340,14 @@ __global__ void __launch_bounds__(256) otw_path_cost_kernel(PathCostArgs a) {
     }
 }
 
+// One otw_advance_kernel instantiation as the handle launches it: eight waves -- wave 0: control (+ chains of steps that
+// are not hits), waves 1/2: chains, 3..7: cost strips, ring refill -- per stream.  fn == NULL: the handle has no kernel
+// for that kind of launch, which is refused.
+struct OtwKernel {
+    const void *fn;
+    size_t smem;  // dynamic LDS
+};
+
 }  // namespace rts
 
 // The band fill of a fresh stream as a dense wavefront (otw_bandfill_kernel), enqueued in front of otw_advance_kernel.
@@ -2484,7 +2359,7 @@ __global__ void __launch_bounds__(256) otw_path_cost_kernel(PathCostArgs a) {
 struct rts_otw {
     const void *ref;
     int ref_dtype, F, N, B, c, max_run_count, variant, cost_kind;
-    int W, waves, path_cap;
+    int W, path_cap;
     int hist_stride;    // frames per stream in `hist`: 2N (2 N_max with per-stream references)
     int32_t *state;     // [B][16]
     int32_t *path;      // [B][path_cap][2]
@@ -2494,14 +2369,15 @@ struct rts_otw {
     int32_t *hist_len;  // [B]
     long long *debug;   // diagnostic builds only
     double *dense_acc, *dense_cost;  // caller-owned, optional
-    int spec;           // 1: pipelined kernel (needs 8 waves and no dense mirror); 0: plain kernel
+    int spec;           // 1: pipelined kernel (no dense mirror); 0: plain kernel
     int device;         // the HIP device the handle's buffers live on (one handle = one device)
     int cus;            // its compute units
     int tp_from;        // batches of at least tp_from streams per CU take the residency-oriented kernel flavour
     int fill;           // RTS_OTW_FILL: 1 = a launch that can bring c frames to a fresh stream runs otw_bandfill_kernel first
     int fill_last;      // the handle's last launch enqueued it (host-side: which kernels ran is decided per call)
     int32_t *fill_took; // [B]: 1 where the stream's band was filled by that kernel (written by it, for every stream)
-    const void *attr_fn[8];  // kernel instantiations whose dynamic-LDS limit is already raised on `device`
+    // the handle's kernels (resolve_kernels, at create): the dense mirror's, and the others by [live input is float64]
+    rts::OtwKernel k_dense, k_plain[2];
     // what the handle has consumed since the last reset, for rts_otw_replay_dense
     int src_kind;       // 0 nothing, 1 the buffers of the last rts_otw_run, 2 the handle-owned history, 3 mixed
     int run_dtype, run_T, run_mode;  // of the last rts_otw_run (the buffers themselves are the caller's and not remembered)
@@ -2511,72 +2387,65 @@ struct rts_otw {
 
 namespace rts {
 
-// The dynamic-LDS limit is a per-device function attribute: remembered per handle (a handle lives on one device),
-// not per process.
-static int ensure_lds_attr(rts_otw *h, const void *fn, size_t smem) {
-    for (int k = 0; k < 8; k++)
-        if (h->attr_fn[k] == fn) return RTS_OK;
-    RTS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    for (int k = 0; k < 8; k++)
-        if (!h->attr_fn[k]) {
-            h->attr_fn[k] = fn;
-            break;
-        }
-    return RTS_OK;
-}
-
-template <int W, int NW, bool DENSE, typename RT, bool SPEC>
-static int launch_advance_d(rts_otw *h, const OtwArgs &args, int B, hipStream_t s) {
+// Resolves one entry of the handle's kernel table.  The dynamic-LDS limit is a per-device function attribute: raised
+// here, at create, on the handle's device (a handle lives on one device).
+template <int W, bool DENSE, typename RT, bool SPEC>
+static int set_kernel(OtwKernel *k) {
     using LdsT = OtwLds<W, RT>;
-    const size_t smem = SPEC ? ((offsetof(LdsT, refw) + 15) & ~(size_t)15) + sizeof(OtwSpecLds<W>)
-                             : (kHasLiveRing<RT> ? sizeof(LdsT) : ((offsetof(LdsT, refw) + 15) & ~(size_t)15));
-    const int rc = ensure_lds_attr(h, reinterpret_cast<const void *>(&otw_advance_kernel<W, NW, DENSE, RT, SPEC>), smem);
-    if (rc != RTS_OK) return rc;
-    hipLaunchKernelGGL((otw_advance_kernel<W, NW, DENSE, RT, SPEC>), dim3(B), dim3(64 * NW), smem, s, args);
-    RTS_HIP(hipGetLastError());
+    k->fn = reinterpret_cast<const void *>(&otw_advance_kernel<W, DENSE, RT, SPEC>);
+    k->smem = SPEC ? ((offsetof(LdsT, refw) + 15) & ~(size_t)15) + sizeof(OtwSpecLds<W>)
+                   : (kHasLiveRing<RT> ? sizeof(LdsT) : ((offsetof(LdsT, refw) + 15) & ~(size_t)15));
+    RTS_HIP(hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k->smem));
     return RTS_OK;
 }
 
+// The handle's kernels, chosen once at create: everything the choice depends on is fixed then, except whether a launch
+// writes a dense mirror and whether its live input is float64 (rts_otw_run's dtype; the history is always float64).
 // The dense mirror is a separate instantiation so that the default kernel carries none of its code.
-template <int W, int NW>
-static int launch_advance(rts_otw *h, const OtwArgs &args, int B, hipStream_t s) {
+template <int W>
+static int resolve_kernels(rts_otw *h) {
+    const int B = h->B;
     if constexpr (W >= 1024) {
         // no ring fits beside a 1024-cell window's bands: every frame is read from global memory.  The dense mirror
-        // (otw_eran.py:23,27) runs the plain role-specialised kernel that way, in its 8-wave form whatever rts_otw_set_waves says
-        if (args.dense_acc) return launch_advance_d<W, 8, true, LiveFromGlobal, false>(h, args, B, s);
-        if constexpr (NW >= 8) {
-            if (args.spec) return launch_advance_d<W, NW, false, LiveFromGlobal, true>(h, args, B, s);
-        }
-        return set_error(RTS_ERR_UNSUPPORTED, "band widths above 500 (c=%d) run only on the pipelined 8-wave kernel", h->c);
+        // (otw_eran.py:23,27) runs the plain role-specialised kernel that way
+        if (int rc = set_kernel<W, true, LiveFromGlobal, false>(&h->k_dense); rc != RTS_OK) return rc;
+        if (!h->spec) return RTS_OK;  // RTS_OTW_SPEC=0: no plain entry, launch() refuses
+        if (int rc = set_kernel<W, false, LiveFromGlobal, true>(&h->k_plain[0]); rc != RTS_OK) return rc;
+        h->k_plain[1] = h->k_plain[0];
+        return RTS_OK;
     } else {  // (an else branch, so that none of the ring kernels below is instantiated for the wide windows)
-        if (args.dense_acc) return launch_advance_d<W, NW, true, double, false>(h, args, B, s);
-        // float32 rings only when both inputs are float32: every value then widens back exactly
-        const bool f32 = !args.ref_f64 && !args.live_f64;
-        if constexpr (NW >= 8) {
-            if (args.spec) {
+        if (int rc = set_kernel<W, true, double, false>(&h->k_dense); rc != RTS_OK) return rc;
+        for (int live_f64 = 0; live_f64 < 2; live_f64++) {
+            OtwKernel *k = &h->k_plain[live_f64];
+            // float32 rings only when both inputs are float32: every value then widens back exactly
+            const bool f32 = h->ref_dtype != RTS_F64 && !live_f64;
+            int rc;
+            if (h->spec) {
                 // two streams per CU or more: the 73-register flavour, three workgroups per CU
-                if (B >= h->tp_from * h->cus && B > 0) return launch_advance_d<W, NW, false, LiveFromGlobalLean, true>(h, args, B, s);
-                if (f32) return launch_advance_d<W, NW, false, float, true>(h, args, B, s);
+                if (B >= h->tp_from * h->cus && B > 0) rc = set_kernel<W, false, LiveFromGlobalLean, true>(k);
+                else if (f32) rc = set_kernel<W, false, float, true>(k);
                 // float64 features: the ring (one workgroup per CU at W = 512) while every stream has a CU to itself
                 // (B = 64: 4.67 vs 4.93 ms), no ring and up to four workgroups per CU beyond
-                return (B <= h->cus) ? launch_advance_d<W, NW, false, double, true>(h, args, B, s)
-                                     : launch_advance_d<W, NW, false, LiveFromGlobal, true>(h, args, B, s);
+                else rc = (B <= h->cus) ? set_kernel<W, false, double, true>(k) : set_kernel<W, false, LiveFromGlobal, true>(k);
+            } else {
+                rc = f32 ? set_kernel<W, false, float, false>(k) : set_kernel<W, false, double, false>(k);
             }
+            if (rc != RTS_OK) return rc;
         }
-        return f32 ? launch_advance_d<W, NW, false, float, false>(h, args, B, s)
-                   : launch_advance_d<W, NW, false, double, false>(h, args, B, s);
+        return RTS_OK;
     }
 }
 
-template <int W>
-static int launch_w(rts_otw *h, const OtwArgs &args, int B, int waves, hipStream_t s) {
-    switch (waves) {
-        case 1: return launch_advance<W, 1>(h, args, B, s);
-        case 2: return launch_advance<W, 2>(h, args, B, s);
-        case 4: return launch_advance<W, 4>(h, args, B, s);
-        case 8: return launch_advance<W, 8>(h, args, B, s);
+static int resolve_kernels(rts_otw *h) {
+    switch (h->W) {
+        case 64: return resolve_kernels<64>(h);
+        case 128: return resolve_kernels<128>(h);
+        case 256: return resolve_kernels<256>(h);
+        case 512: return resolve_kernels<512>(h);
+        case 1024: return resolve_kernels<1024>(h);  // c up to 1012: one workgroup per CU
+        case 2048: return resolve_kernels<2048>(h);  // c up to 2036: 32 cells per lane in the chains
     }
-    return set_error(RTS_ERR_INVALID, "waves must be 1, 2, 4 or 8 (got %d)", waves);
+    return set_error(RTS_ERR_UNSUPPORTED, "no kernel for window %d", h->W);
 }
 
 // max_new: the largest number of new frames the call can bring to any stream (a host-side hint).  Only a launch that can
@@ -2591,15 +2460,11 @@ static int launch(rts_otw *h, const OtwArgs &args, hipStream_t s, int max_new) {
         hipLaunchKernelGGL(otw_bandfill_kernel, dim3(h->B), block, 0, s, args, h->fill_took);
         RTS_HIP(hipGetLastError());
     }
-    switch (h->W) {
-        case 64: return launch_w<64>(h, args, h->B, h->waves, s);
-        case 128: return launch_w<128>(h, args, h->B, h->waves, s);
-        case 256: return launch_w<256>(h, args, h->B, h->waves, s);
-        case 512: return launch_w<512>(h, args, h->B, h->waves, s);
-        case 1024: return launch_w<1024>(h, args, h->B, h->waves, s);  // c up to 1012: one workgroup per CU
-        case 2048: return launch_w<2048>(h, args, h->B, h->waves, s);  // c up to 2036: 32 cells per lane in the chains
-    }
-    return set_error(RTS_ERR_UNSUPPORTED, "no kernel for window %d", h->W);
+    const OtwKernel &k = args.dense_acc ? h->k_dense : h->k_plain[args.live_f64 != 0];
+    if (!k.fn) return set_error(RTS_ERR_UNSUPPORTED, "band widths above 500 (c=%d) run only on the pipelined 8-wave kernel", h->c);
+    void *params[] = {const_cast<OtwArgs *>(&args)};
+    RTS_HIP(hipLaunchKernel(k.fn, dim3(h->B), dim3(512), params, k.smem, s));
+    return RTS_OK;
 }
 
 static OtwArgs base_args(const rts_otw *h) {
@@ -2705,7 +2570,6 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
     h->cost_kind = cost_kind;
     h->W = 64;
     while (h->W < c + 12) h->W *= 2;
-    h->waves = 8;  // wave 0: control (+ chains of steps that are not hits), waves 1/2: chains, 3..7: cost strips, ring refill
     const OtwKnobs knobs = otw_knobs();
     h->spec = knobs.spec;
     h->tp_from = knobs.tp_from;
@@ -2727,7 +2591,8 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
         rts_otw_destroy(h);
         return set_error(RTS_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
     }
-    int rc = rts_otw_reset(h, nullptr);
+    int rc = resolve_kernels(h);
+    if (rc == RTS_OK) rc = rts_otw_reset(h, nullptr);
     if (rc != RTS_OK) {
         rts_otw_destroy(h);
         return rc;
@@ -2905,9 +2770,9 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
 int rts_otw_set_waves(rts_otw *h, int waves) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (waves != 1 && waves != 2 && waves != 4 && waves != 8)
-        return set_error(RTS_ERR_INVALID, "waves must be 1, 2, 4 or 8 (got %d)", waves);
-    h->waves = waves;
+    if (waves == 1 || waves == 2 || waves == 4)
+        return set_error(RTS_ERR_UNSUPPORTED, "wave counts below 8 were retired: every kernel runs 8 waves per stream (got %d)", waves);
+    if (waves != 8) return set_error(RTS_ERR_INVALID, "waves must be 8 (got %d)", waves);
     return RTS_OK;
 }
 

@@ -65,10 +65,13 @@ def test_golden_cases(gpu, otw_golden, dtype):
     assert recomputes > 0
 
 
-@pytest.mark.parametrize("waves", [1, 2, 4, 8])
+@pytest.mark.parametrize("waves", [8])
 def test_wave_count_does_not_change_results(gpu, otw_golden, waves):
+    """Every kernel runs 8 waves per stream.  Passing 8 explicitly changes nothing; the retired counts 1, 2, 4 are
+    refused with RTS_ERR_UNSUPPORTED (-2), anything else with RTS_ERR_INVALID (-1), and a refusal leaves the handle
+    as it was."""
     g = otw_golden
-    ob = gpu["ob"]
+    ob, nat, synth, oracle = gpu["ob"], gpu["nat"], gpu["synth"], gpu["oracle"]
     for cid in ("A_otw_c50_insert", "B_otw_c500_insert", "D_otw_tie_c10_insert", "C_livenote_v2_euclid_c50_insert",
                 "F_otw_stop_c20_insert", "E_otw_overflow_c10_insert", "A_livenote_v2_c10_set_live"):
         case = parse_case([m for m in g["cases"] if str(m).split("|")[0] == cid][0])
@@ -80,6 +83,29 @@ def test_wave_count_does_not_change_results(gpu, otw_golden, waves):
         eng.run(lv, ln, mode=case["mode"])
         _check_against_golden(g, case, eng)
         eng.close()
+    # the smallest handle that can be created
+    ref = synth.synth_ref(8, seed=68)
+    live = synth.synth_live(ref, seed=69)
+    eng = ob.BatchedOTW(ref, 2, 3, batch=1, dtype=torch.float64)
+    for retired in (1, 2, 4):
+        with pytest.raises(nat.RtsyncError, match=r"rtsync error -2: .*retired"):
+            eng.set_waves(retired)
+    with pytest.raises(nat.RtsyncError, match="rtsync error -1: "):
+        eng.set_waves(3)
+    eng.set_waves(8)
+    lv, ln = eng.pack([live])
+    eng.run(lv, ln)
+    o = oracle.OtwOracle(ref, 2, 3)
+    n = o.run(live)
+    st = eng.state(0)
+    assert np.array_equal(eng.path(0), o.path)
+    for k in ("t", "j", "direction", "previous", "run_count", "status"):
+        assert st[k] == o.state[k], k
+    assert st["consumed"] == n
+    rb, cb = eng.bands(0)
+    orb, ocb = o.bands()
+    assert np.array_equal(rb, orb, equal_nan=True) and np.array_equal(cb, ocb, equal_nan=True)
+    eng.close()
 
 
 @pytest.mark.parametrize("spec", ["0", "1"])
@@ -280,7 +306,7 @@ def test_argument_errors(gpu):
 
 def test_randomized_small_configs(gpu):
     """Seeded sweep over the corners the fixed cases do not reach: band widths down to c=1, references
-    and live sequences of a few frames, every variant / cost / mode / wave count, exact ties.  Each
+    and live sequences of a few frames, every variant / cost / mode, exact ties.  Each
     configuration must match the dense CPU oracle bit for bit."""
     ob, synth, oracle = gpu["ob"], gpu["synth"], gpu["oracle"]
     rs = np.random.RandomState(20261004)
@@ -293,7 +319,8 @@ def test_randomized_small_configs(gpu):
         variant = str(rs.choice(["otw", "livenote", "livenote_v2"]))
         euclid = bool(variant == "livenote_v2" and rs.rand() < 0.4)
         mode = "set_live" if rs.rand() < 0.3 else "insert"
-        waves = int(rs.choice([1, 2, 4, 8]))
+        rs.choice([1, 2, 4, 8])  # once the wave count: still drawn, so that the seeded configurations stay the same ones
+        waves = 8
         batch = int(rs.choice([1, 3]))
         if rs.rand() < 0.25:
             ref, base_live = synth.synth_tie(max(n_ref, 2), seed=trial)

@@ -2,10 +2,9 @@
 """Diagnostic (not shipped): build librtsync with -DRTS_OTW_STAMPS into tools/_diag/ and print
 the share of wave-0 cycles each phase of otw_advance_kernel takes on the bench workload.
 
-    RTS_DIAG_LEVEL=1|2 python tools/otw_phase_profile.py [--build] [--no-both-loop]
+    RTS_DIAG_LEVEL=1|2 python tools/otw_phase_profile.py [--build]
 
---no-both-loop builds with -DRTS_OTW_NO_BOTH_LOOP (Both hits left to the general loop: the "before" of
-profiles/r05a_phase_L2_old.txt) into tools/_diag/librtsync_diag_nobothloop.so and runs that.  RTS_DIAG_LIB=<path> runs a
+RTS_DIAG_LIB=<path> runs a
 diagnostic library built earlier.  The stamp level and the size of the debug buffer are the library's own
 (rts_otw_stamp_level / rts_otw_debug_words), whatever RTS_DIAG_LEVEL says when the tool runs."""
 import ctypes, os, subprocess, sys
@@ -13,8 +12,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 DIAG = os.path.join(ROOT, "tools", "_diag")
-NO_BOTH = "--no-both-loop" in sys.argv
-DEFAULT_SO = os.path.join(DIAG, "librtsync_diag_nobothloop.so" if NO_BOTH else "librtsync_diag.so")
+DEFAULT_SO = os.path.join(DIAG, "librtsync_diag.so")
 
 
 def build():
@@ -23,7 +21,7 @@ def build():
     src = [os.path.join(ROOT, "real_time_audio_sync_amd", "csrc", f) for f in ("common.cpp", "otw.hip")]
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
            "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-amdgpu-sched-strategy=max-ilp",  # as _build.PER_SOURCE_FLAGS["otw.hip"]
-           "-DRTS_OTW_STAMPS=%s" % os.environ.get("RTS_DIAG_LEVEL", "1")] + (["-DRTS_OTW_NO_BOTH_LOOP"] if NO_BOTH else []) + ["-o", so]
+           "-DRTS_OTW_STAMPS=%s" % os.environ.get("RTS_DIAG_LEVEL", "1"), "-o", so]
     for s in src:
         cmd += ["-x", "hip", s]
     subprocess.check_call(cmd)
