@@ -235,6 +235,36 @@ int rts_otw_set_dense(rts_otw *h, double *acc_dev, double *cost_dev, void *strea
  * (otw_eran.py:23,27) are made of. */
 int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T_max, const int32_t *live_len_dev,
                          double *acc_dev, double *cost_dev, void *stream);
+/* The backward path (Dixon's MATCH): from a stream's current best point back to (0, 0) over the
+ * accumulated-cost cells the tracker has evaluated -- a monotone, gap-free warping path, optimal inside the explored
+ * band, where .path is causal and may jump.  Defined on the reference's dense matrices acc / cost (otw_eran.py:23,27):
+ *   end cell: best_point (otw_eran.py:192-211) at the end position (t, j), t clamped to the last row consumed and j to
+ *     N - 1 (a stop or an overflow leaves one index one past the end);
+ *   predecessor of (x, y) != (0, 0), d = cost[x][y]: the first of (x, y-1) with acc + d, (x-1, y) with acc + d and
+ *     (x-1, y-1) with acc + 2 d, in-range candidates only, whose sum == acc[x][y];
+ *   path: the predecessors from the end cell down to (0, 0), in forward order; total = acc[end].
+ * The matrices are never built: the call replays what the handle has consumed (the source rules of rts_otw_replay_dense:
+ * live_dev = NULL after rts_otw_insert / rts_otw_push or on a fresh handle, that call's buffers again after rts_otw_run,
+ * RTS_ERR_UNSUPPORTED for the mixed state; a restarted stream shows what it consumed since its restart) on scratch state
+ * into a per-strip log in the caller's workspace, 8 bytes per evaluated cell, and walks the log on the device.  Works on
+ * rts_otw_create_refs handles: each stream uses its own range and N_b, indices are relative to the range.  Every
+ * supported band width; not affected by RTS_OTW_SPEC.  The handle's state, path, bands and history are only read.
+ *   path_dev [B][3 N_max + 8][2] (8-byte aligned): stream b gets path_len_dev[b] rows from (0, 0) to end_dev[b]; rows
+ *     behind them are left untouched.  total_dev[b] = acc[end] bit for bit.  acc_dev: optional [B][3 N_max + 8], acc at
+ *     every path point.  A stream that has consumed no frame: path_len 0, total NaN, end (-1, -1).
+ *   ws_dev / ws_bytes: caller-owned, 16-byte aligned scratch of at least rts_otw_backward_workspace_bytes(N_max, c, B)
+ *     (pure host arithmetic, linear in N_max: at most B (3 N_max + 8) (8 (c + 1) + 16) bytes plus a fixed header).
+ * Features must be finite: a NaN frame makes that stream's result unspecified (path_len stays within [0, 3 N_max + 8],
+ * nothing is read or written out of bounds).  Asynchronous on `stream`; the first call on a handle allocates its scratch
+ * state, later calls neither allocate nor synchronise.  Every argument is checked before anything is enqueued. */
+int rts_otw_backward_workspace_bytes(int N_max, int c, int B, size_t *bytes);
+int rts_otw_backward(rts_otw *h, const void *live_dev, int live_dtype, int T_max, const int32_t *live_len_dev,
+                     int32_t *path_dev /* [B][3 N_max + 8][2] */, int32_t *path_len_dev /* [B] */,
+                     double *total_dev /* [B] */, int32_t *end_dev /* [B][2] */,
+                     double *acc_dev /* optional [B][3 N_max + 8] */, void *ws_dev, size_t ws_bytes, void *stream);
+/* Device time of the handle's last rts_otw_backward, split into its two parts (HIP events the call records on its
+ * stream): the trace replay and the backtrace.  Waits for that call to finish. */
+int rts_otw_backward_times(rts_otw *h, float *replay_ms, float *backtrace_ms);
 /* Formerly a tuning knob (waves per stream workgroup); every kernel now runs 8 waves.  8 is accepted and changes
  * nothing, the retired counts 1, 2 and 4 return RTS_ERR_UNSUPPORTED, anything else RTS_ERR_INVALID.
  * Without a dense mirror the library runs its pipelined kernel (the next step's strips are computed

@@ -70,6 +70,15 @@ class OtwDropIn(object):
             return p.astype(np.int64)
         return [(int(x), int(y)) for x, y in p]
 
+    def backward_path(self):
+        """The backward path (BatchedOTW.backward): from the current best point back to (0, 0) over the evaluated
+        cells, in forward order and shaped like ``.path`` -- the monotone, gap-free alignment that is optimal inside
+        the band the tracker explored."""
+        p = self._eng.backward()[0][0]
+        if self._path_is_array:
+            return p.astype(np.int64)
+        return [(int(x), int(y)) for x, y in p]
+
     def _st(self):
         return self._eng.state(0)
 

@@ -77,6 +77,9 @@ _decl("rts_otw_device_views", _i32, [_vp, ctypes.POINTER(_vp), _pi32, ctypes.POI
 _decl("rts_otw_set_waves", _i32, [_vp, _i32])
 _decl("rts_otw_set_dense", _i32, [_vp, _vp, _vp, _vp])
 _decl("rts_otw_replay_dense", _i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp])
+_decl("rts_otw_backward_workspace_bytes", _i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_size_t)])
+_decl("rts_otw_backward", _i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp])
+_decl("rts_otw_backward_times", _i32, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)])
 _decl("rts_otw_kernel_name", ctypes.c_char_p, [_vp])
 _decl("rts_dtw_workspace_bytes", _i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_size_t)])
 _decl("rts_dtw", _i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,

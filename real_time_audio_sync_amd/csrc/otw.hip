@@ -66,7 +66,24 @@ struct OtwArgs {
     // quantity from OtwEnv (e.ref, e.N, e.live_cap), which the prologue fills from these or from ref / N / live_cap.
     const long long *ref_first;
     const int32_t *ref_len;
+    // trace replay (rts_otw_backward, otw_backward.h): the compact per-strip log of accumulated costs, NULL = off.
+    // Stream b owns slots [b * 3 N_max, (b + 1) * 3 N_max): row strip x in slot x, column strip y in slot trace_rows + y.
+    int2 *trace_hdr;      // per slot: (first index, cells) -- first column of a row strip, first row of a column strip
+    double *trace_cells;  // per slot: c + 1 doubles
+    int trace_rows;       // 2 N_max
 };
+
+// What a kernel instantiation mirrors of the cells it evaluates (the DENSE template argument): nothing, the reference's
+// dense matrices (rts_otw_set_dense / rts_otw_replay_dense), or the per-strip log of rts_otw_backward.
+constexpr int kMirrorDense = 1, kMirrorTrace = 2;
+
+// Trace replay: where the cells of stream b's slot go, and its header (one lane calls otw_trace_open).
+__device__ __forceinline__ double *otw_trace_slot(const OtwArgs &a, int b, int slot) {
+    return a.trace_cells + ((size_t)b * 3 * (a.trace_rows / 2) + slot) * (size_t)(a.c + 1);
+}
+__device__ __forceinline__ void otw_trace_open(const OtwArgs &a, int b, int slot, int first, int n) {
+    a.trace_hdr[(size_t)b * 3 * (a.trace_rows / 2) + slot] = make_int2(first, n);
+}
 
 // RT = element type of the feature rings: double, or float when both inputs are float32 (their values
 // widen back exactly, so results are identical while the plain kernel's LDS drops from 131 KB to 74 KB at
@@ -311,7 +328,7 @@ __device__ __forceinline__ void chain_store(unsigned oA, unsigned oB, const doub
 // corner slot, which the fix-up rewrites; every band position is written with its real value
 // before it is ever read (rows/columns only grow at the top index).  Valid cells are always finite:
 // each has a computed predecessor in the previous row (row strip) or column (column strip).
-template <int W, bool DENSE, bool GUARD = false, bool ALT = false, bool SPLIT = false>
+template <int W, int DENSE, bool GUARD = false, bool ALT = false, bool SPLIT = false>
 __device__ __forceinline__ void strip_chain(const double *__restrict__ Dv, const double *band, double *band_out, int k1,
                                             int n, double x_in, int lane, int lo_arg, double &fmin_out, int &fidx_out,
                                             double *dense_acc, double *dense_cost, long long dense_stride,
@@ -429,7 +446,7 @@ __device__ __forceinline__ void strip_chain(const double *__restrict__ Dv, const
 #pragma unroll
         for (int m = 0; m < L; m++) band_out[slot[m + 1]] = v[m];
     }
-    if (DENSE) {  // optional: mirror the strip into the reference's dense matrices (cell i at base + i*stride)
+    if (DENSE == kMirrorDense) {  // optional: mirror the strip into the reference's dense matrices (cell i at base + i*stride)
 #pragma unroll
         for (int m = 0; m < L; m++) {
             if (m < nloc) {
@@ -438,6 +455,11 @@ __device__ __forceinline__ void strip_chain(const double *__restrict__ Dv, const
                 dense_cost[off] = D[m];
             }
         }
+    }
+    if (DENSE == kMirrorTrace) {  // trace replay: the strip's accumulated costs into its log slot, cell i at base + i
+#pragma unroll
+        for (int m = 0; m < L; m++)
+            if (m < nloc) dense_acc[L * lane + m] = v[m];
     }
     // first minimum over positions >= lo_arg: lo_arg is k1 or k1 + 1, so at most the very first
     // cell is excluded
@@ -839,7 +861,7 @@ __device__ __forceinline__ OtwPlan otw_make_plan(OtwLds<W, RT> &S, OtwCtl &k, co
 
 // This step's row strip (t, [k1r, j0]) on the calling wave; returns its argmin restricted to the row
 // band decide() will look at.
-template <int W, bool DENSE, typename RT>
+template <int W, int DENSE, typename RT>
 __device__ __forceinline__ void otw_row_strip(double *R, const OtwArgs &a, const OtwEnv &e, const double *Dr,
                                               int pt, int j0, int jn, double sentinel, double &rf_min, int &rf_idx) {
     const int c = e.c;
@@ -847,14 +869,19 @@ __device__ __forceinline__ void otw_row_strip(double *R, const OtwArgs &a, const
     const double x_in = (k1r > 0) ? sentinel : (double)INFINITY;  // (t, k1r-1) was never evaluated
     const int lo_arg = (jn - c + 1 > 0) ? jn - c + 1 : 0;        // row band's lower end at decide()
     const long long dro = ((long long)e.b * e.live_cap + pt) * e.N + k1r;  // cell (pt, k1r)
-    strip_chain<W, DENSE>(Dr, R, R, k1r, nr, x_in, e.lane, lo_arg, rf_min, rf_idx, DENSE ? a.dense_acc + dro : nullptr,
-                          DENSE ? a.dense_cost + dro : nullptr, 1);
+    double *mirror = (DENSE == kMirrorDense) ? a.dense_acc + dro : nullptr;
+    if (DENSE == kMirrorTrace) {  // row pt's slot: columns k1r .. j0 (a Both step's corner joins it in otw_settle)
+        mirror = otw_trace_slot(a, e.b, pt);
+        if (e.lane == 0) otw_trace_open(a, e.b, pt, k1r, nr);
+    }
+    strip_chain<W, DENSE>(Dr, R, R, k1r, nr, x_in, e.lane, lo_arg, rf_min, rf_idx, mirror,
+                          (DENSE == kMirrorDense) ? a.dense_cost + dro : nullptr, 1);
     if (e.lane == 0 && k1r > 0) R[swz<W>(k1r - 1)] = sentinel;
 }
 
 // This step's column strip ([k1c, pt or pt-1], jn) on the calling wave; in a Both step (with_row) the corner
 // cell (pt, jn) is left to the fix-up and its diagonal term is stashed before column jn-1 is overwritten.
-template <int W, bool DENSE, typename RT>
+template <int W, int DENSE, typename RT>
 __device__ __forceinline__ void otw_col_strip(OtwLds<W, RT> &S, double *C, const OtwArgs &a, const OtwEnv &e,
                                               const double *Dc, int pt, int jn, bool with_row, double sentinel) {
     const int c = e.c;
@@ -866,8 +893,13 @@ __device__ __forceinline__ void otw_col_strip(OtwLds<W, RT> &S, double *C, const
     const double dcorner = Dc[swz<W>(pt)];
     const double pa = (with_row && pt > 0) ? C[swz<W>(pt - 1)] + 2 * dcorner : (double)INFINITY;
     const long long dco = ((long long)e.b * e.live_cap + k1c) * e.N + jn;  // cell (k1c, jn)
-    strip_chain<W, DENSE>(Dc, C, C, k1c, ncc, x_in, e.lane, k1c, fm, fi, DENSE ? a.dense_acc + dco : nullptr,
-                          DENSE ? a.dense_cost + dco : nullptr, e.N);
+    double *mirror = (DENSE == kMirrorDense) ? a.dense_acc + dco : nullptr;
+    if (DENSE == kMirrorTrace) {  // column jn's slot: rows k1c .. pt, without the corner in a Both step
+        mirror = otw_trace_slot(a, e.b, a.trace_rows + jn);
+        if (e.lane == 0) otw_trace_open(a, e.b, a.trace_rows + jn, k1c, ncc);
+    }
+    strip_chain<W, DENSE>(Dc, C, C, k1c, ncc, x_in, e.lane, k1c, fm, fi, mirror,
+                          (DENSE == kMirrorDense) ? a.dense_cost + dco : nullptr, e.N);
     if (e.lane == 0) {
         S.corner_pa = pa;
         S.corner_d = dcorner;
@@ -885,7 +917,7 @@ struct OtwSettled {
 };
 
 // First half of the control phase of a regular step (wave 0): counters and the corner fix-up.
-template <int W, bool DENSE, typename RT>
+template <int W, int DENSE, typename RT>
 __device__ __forceinline__ OtwSettled otw_settle(OtwLds<W, RT> &S, double *R, double *C, OtwCtl &k, const OtwArgs &a,
                                                  const OtwEnv &e, int pt, int j0, int pflags, double rf_min, int rf_idx,
                                                  double sentinel) {
@@ -929,10 +961,14 @@ __device__ __forceinline__ OtwSettled otw_settle(OtwLds<W, RT> &S, double *R, do
             cl = vmin(av, cl + d);  // cl was the value of (t-1, jn), or the sentinel carry
             if (lane == 0) {
                 C[swz<W>(pt)] = cl;
-                if (DENSE) {
+                if (DENSE == kMirrorDense) {
                     const long long o = ((long long)e.b * e.live_cap + pt) * e.N + jn;
                     a.dense_acc[o] = cl;
                     a.dense_cost[o] = d;
+                }
+                if (DENSE == kMirrorTrace) {  // the corner (pt, jn = j0 + 1) closes row pt's slot
+                    otw_trace_slot(a, e.b, pt)[nr] = cl;
+                    otw_trace_open(a, e.b, pt, k1r, nr + 1);
                 }
             }
         }
@@ -1377,7 +1413,7 @@ __device__ __forceinline__ OtwSettled otw_settle_hit(double *R, double *C, const
 // the launch ends.  __syncthreads() would also drain those stores (a full release: vmcnt(0)) once per step.
 #define RTS_STEP_BARRIER() ::rts::lds_barrier()
 
-template <int W, bool DENSE, typename RT, bool SPEC>
+template <int W, int DENSE, typename RT, bool SPEC>
 // (the throughput flavour exists for its residency -- three workgroups of eight waves per CU, i.e. at most 80 VGPRs: said to
 // the compiler here, because the ILP-first scheduling this file is built with otherwise spends 87)
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(kThroughput<RT> ? 6 : 1)))
@@ -1569,9 +1605,13 @@ otw_advance_kernel(OtwArgs a) {
             if (lane == 0) {
                 S.R[swz<W>(0)] = d;
                 S.C[swz<W>(0)] = d;
-                if (DENSE) {
+                if (DENSE == kMirrorDense) {
                     a.dense_acc[(long long)e.b * e.live_cap * N] = d;
                     a.dense_cost[(long long)e.b * e.live_cap * N] = d;
+                }
+                if (DENSE == kMirrorTrace) {  // cell (0, 0): row 0's slot
+                    otw_trace_slot(a, e.b, 0)[0] = d;
+                    otw_trace_open(a, e.b, 0, 0, 1);
                 }
             }
             k.first = 0;
@@ -2378,18 +2418,20 @@ struct rts_otw {
     int32_t *fill_took; // [B]: 1 where the stream's band was filled by that kernel (written by it, for every stream)
     // the handle's kernels (resolve_kernels, at create): the dense mirror's, and the others by [live input is float64]
     rts::OtwKernel k_dense, k_plain[2];
+    rts::OtwKernel k_trace;  // the trace replay of rts_otw_backward: the plain kernel at every band width, whatever RTS_OTW_SPEC
     // what the handle has consumed since the last reset, for rts_otw_replay_dense
     int src_kind;       // 0 nothing, 1 the buffers of the last rts_otw_run, 2 the handle-owned history, 3 mixed
     int run_dtype, run_T, run_mode;  // of the last rts_otw_run (the buffers themselves are the caller's and not remembered)
-    int32_t *rp_state, *rp_path;     // scratch state of rts_otw_replay_dense, allocated on first use
+    int32_t *rp_state, *rp_path;     // scratch state of rts_otw_replay_dense / rts_otw_backward, allocated on first use
     double *rp_bands;
+    hipEvent_t bw_ev[3];             // rts_otw_backward: before the replay, between its two parts, behind the backtrace
 };
 
 namespace rts {
 
 // Resolves one entry of the handle's kernel table.  The dynamic-LDS limit is a per-device function attribute: raised
 // here, at create, on the handle's device (a handle lives on one device).
-template <int W, bool DENSE, typename RT, bool SPEC>
+template <int W, int DENSE, typename RT, bool SPEC>
 static int set_kernel(OtwKernel *k) {
     using LdsT = OtwLds<W, RT>;
     k->fn = reinterpret_cast<const void *>(&otw_advance_kernel<W, DENSE, RT, SPEC>);
@@ -2408,13 +2450,15 @@ static int resolve_kernels(rts_otw *h) {
     if constexpr (W >= 1024) {
         // no ring fits beside a 1024-cell window's bands: every frame is read from global memory.  The dense mirror
         // (otw_eran.py:23,27) runs the plain role-specialised kernel that way
-        if (int rc = set_kernel<W, true, LiveFromGlobal, false>(&h->k_dense); rc != RTS_OK) return rc;
+        if (int rc = set_kernel<W, kMirrorDense, LiveFromGlobal, false>(&h->k_dense); rc != RTS_OK) return rc;
+        if (int rc = set_kernel<W, kMirrorTrace, LiveFromGlobal, false>(&h->k_trace); rc != RTS_OK) return rc;
         if (!h->spec) return RTS_OK;  // RTS_OTW_SPEC=0: no plain entry, launch() refuses
-        if (int rc = set_kernel<W, false, LiveFromGlobal, true>(&h->k_plain[0]); rc != RTS_OK) return rc;
+        if (int rc = set_kernel<W, 0, LiveFromGlobal, true>(&h->k_plain[0]); rc != RTS_OK) return rc;
         h->k_plain[1] = h->k_plain[0];
         return RTS_OK;
     } else {  // (an else branch, so that none of the ring kernels below is instantiated for the wide windows)
-        if (int rc = set_kernel<W, true, double, false>(&h->k_dense); rc != RTS_OK) return rc;
+        if (int rc = set_kernel<W, kMirrorDense, double, false>(&h->k_dense); rc != RTS_OK) return rc;
+        if (int rc = set_kernel<W, kMirrorTrace, double, false>(&h->k_trace); rc != RTS_OK) return rc;
         for (int live_f64 = 0; live_f64 < 2; live_f64++) {
             OtwKernel *k = &h->k_plain[live_f64];
             // float32 rings only when both inputs are float32: every value then widens back exactly
@@ -2422,13 +2466,13 @@ static int resolve_kernels(rts_otw *h) {
             int rc;
             if (h->spec) {
                 // two streams per CU or more: the 73-register flavour, three workgroups per CU
-                if (B >= h->tp_from * h->cus && B > 0) rc = set_kernel<W, false, LiveFromGlobalLean, true>(k);
-                else if (f32) rc = set_kernel<W, false, float, true>(k);
+                if (B >= h->tp_from * h->cus && B > 0) rc = set_kernel<W, 0, LiveFromGlobalLean, true>(k);
+                else if (f32) rc = set_kernel<W, 0, float, true>(k);
                 // float64 features: the ring (one workgroup per CU at W = 512) while every stream has a CU to itself
                 // (B = 64: 4.67 vs 4.93 ms), no ring and up to four workgroups per CU beyond
-                else rc = (B <= h->cus) ? set_kernel<W, false, double, true>(k) : set_kernel<W, false, LiveFromGlobal, true>(k);
+                else rc = (B <= h->cus) ? set_kernel<W, 0, double, true>(k) : set_kernel<W, 0, LiveFromGlobal, true>(k);
             } else {
-                rc = f32 ? set_kernel<W, false, float, false>(k) : set_kernel<W, false, double, false>(k);
+                rc = f32 ? set_kernel<W, 0, float, false>(k) : set_kernel<W, 0, double, false>(k);
             }
             if (rc != RTS_OK) return rc;
         }
@@ -2453,14 +2497,14 @@ static int resolve_kernels(rts_otw *h) {
 // (otw_fill_eligible), every other stream is left to the step loop untouched.
 static int launch(rts_otw *h, const OtwArgs &args, hipStream_t s, int max_new) {
     if ((uintptr_t)args.live & 15) return set_error(RTS_ERR_INVALID, "live features must be 16-byte aligned");
-    const bool fill = h->fill && max_new >= h->c && h->c >= 2 && h->W <= 512 && !args.dense_acc;
-    if (args.state == h->state) h->fill_last = fill;  // (the dense replay runs on scratch state and never fills)
+    const bool fill = h->fill && max_new >= h->c && h->c >= 2 && h->W <= 512 && !args.dense_acc && !args.trace_cells;
+    if (args.state == h->state) h->fill_last = fill;  // (the dense and trace replays run on scratch state and never fill)
     if (fill) {
         const dim3 block(otw_fill_threads(h->c));
         hipLaunchKernelGGL(otw_bandfill_kernel, dim3(h->B), block, 0, s, args, h->fill_took);
         RTS_HIP(hipGetLastError());
     }
-    const OtwKernel &k = args.dense_acc ? h->k_dense : h->k_plain[args.live_f64 != 0];
+    const OtwKernel &k = args.trace_cells ? h->k_trace : args.dense_acc ? h->k_dense : h->k_plain[args.live_f64 != 0];
     if (!k.fn) return set_error(RTS_ERR_UNSUPPORTED, "band widths above 500 (c=%d) run only on the pipelined 8-wave kernel", h->c);
     void *params[] = {const_cast<OtwArgs *>(&args)};
     RTS_HIP(hipLaunchKernel(k.fn, dim3(h->B), dim3(512), params, k.smem, s));
@@ -2509,6 +2553,22 @@ static int begin_append(rts_otw *h) {
         RTS_HIP(hipMalloc((void **)&h->hist, sizeof(double) * kF * (size_t)h->hist_stride * h->B));
     }
     h->src_kind = (h->src_kind == 0 || h->src_kind == 2) ? 2 : 3;
+    return RTS_OK;
+}
+
+// Scratch state of the replays (rts_otw_replay_dense, rts_otw_backward), so that the handle itself is not disturbed:
+// allocated on the first replay, kept with the handle.
+static int replay_scratch(rts_otw *h) {
+    if (h->rp_state) return RTS_OK;
+    hipError_t e;
+    if ((e = hipMalloc((void **)&h->rp_state, sizeof(int32_t) * RTS_STATE_LEN * (size_t)h->B)) != hipSuccess ||
+        (e = hipMalloc((void **)&h->rp_path, sizeof(int32_t) * 2 * (size_t)h->path_cap * h->B)) != hipSuccess ||
+        (e = hipMalloc((void **)&h->rp_bands, sizeof(double) * 2 * (size_t)(h->c + 1) * h->B)) != hipSuccess) {
+        if (h->rp_state) (void)hipFree(h->rp_state);
+        if (h->rp_path) (void)hipFree(h->rp_path);
+        h->rp_state = h->rp_path = nullptr;
+        return set_error(RTS_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
+    }
     return RTS_OK;
 }
 
@@ -2655,6 +2715,8 @@ int rts_otw_destroy(rts_otw *h) {
     if (h->rp_state) (void)hipFree(h->rp_state);
     if (h->rp_path) (void)hipFree(h->rp_path);
     if (h->rp_bands) (void)hipFree(h->rp_bands);
+    for (int i = 0; i < 3; i++)
+        if (h->bw_ev[i]) (void)hipEventDestroy(h->bw_ev[i]);
     free(h);
     return RTS_OK;
 }
@@ -2734,18 +2796,7 @@ int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T
     fill_dense(h, acc_dev, cost_dev, nullptr, s);
     RTS_HIP(hipGetLastError());
     if (h->src_kind == 0) return RTS_OK;  // freshly constructed: the matrices are all sentinel (otw_eran.py:23,27)
-    // scratch state so that the handle itself is not disturbed; allocated on the first replay, kept with the handle
-    if (!h->rp_state) {
-        hipError_t e;
-        if ((e = hipMalloc((void **)&h->rp_state, sizeof(int32_t) * RTS_STATE_LEN * (size_t)h->B)) != hipSuccess ||
-            (e = hipMalloc((void **)&h->rp_path, sizeof(int32_t) * 2 * (size_t)h->path_cap * h->B)) != hipSuccess ||
-            (e = hipMalloc((void **)&h->rp_bands, sizeof(double) * 2 * (size_t)(h->c + 1) * h->B)) != hipSuccess) {
-            if (h->rp_state) (void)hipFree(h->rp_state);
-            if (h->rp_path) (void)hipFree(h->rp_path);
-            h->rp_state = h->rp_path = nullptr;
-            return set_error(RTS_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
-        }
-    }
+    if (int rc = replay_scratch(h); rc != RTS_OK) return rc;
     hipLaunchKernelGGL(otw_reset_kernel, dim3((h->B + 63) / 64), dim3(64), 0, s, h->rp_state, h->B, h->variant);
     OtwArgs a = h->src_kind == 1 ? base_args(h) : hist_args(h);
     a.state = h->rp_state;
@@ -2964,3 +3015,6 @@ int rts_otw_device_views(rts_otw *h, int32_t **path_dev, int *path_cap, int32_t 
 }
 
 }  // extern "C"
+
+// rts_otw_backward: the trace replay's host side and the backtrace kernel.
+#include "otw_backward.h"

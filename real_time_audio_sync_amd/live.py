@@ -301,6 +301,20 @@ class LiveSession(object):
                                               self._conf_n.ctypes.data if mean is not None else None, ctypes.byref(done)))
         return dict(mean=self._conf_mean.copy(), n=self._conf_n.copy(), feeds_done=done.value)
 
+    def backward(self, streams=None):
+        """The backward path of every stream (or the listed ones) through the bound OTW tracker
+        (``BatchedOTW.backward``): ``(paths, totals, ends)`` for everything the microphones' columns have brought the
+        tracker so far; streams not listed get an empty path.  Waits for the feeds in flight.  OTW family only: a WTW
+        window re-decides its own path."""
+        if self.otw is None:
+            raise nat.RtsyncError("backward needs an OTW tracker (this session is bound to WTW)")
+        self.sync()
+        paths, totals, ends = self.otw.backward()
+        if streams is not None:
+            keep = set(int(b) for b in streams)
+            paths = [p if b in keep else p[:0] for b, p in enumerate(paths)]
+        return paths, totals, ends
+
     def path(self, b=0):
         return (self.otw or self.wtw).path(b)
 

@@ -243,6 +243,45 @@ class BatchedOTW(_BatchedHandle):
         return acc, cost
 
     @_on_device
+    def backward(self, live_dev=None, live_len_dev=None, want_acc=False):
+        """The backward path of every stream (rts_otw_backward): from its current best point back to (0, 0) over the
+        cells the tracker has evaluated -- monotone, gap-free and optimal inside the explored band, where ``path`` is
+        causal and may jump.  Returns ``(paths, totals, ends)``: a list of (n_b, 2) int32 arrays from (0, 0) to
+        ``ends[b]``, float64 [B] accumulated cost at the end cell, int32 [B][2]; with ``want_acc`` also a list of
+        float64 (n_b,) arrays, the accumulated cost at every path point.  A stream that has consumed nothing: an empty
+        path, NaN, (-1, -1).  After ``run`` the frames are that call's (kept by this object; ``live_dev`` /
+        ``live_len_dev`` override them); after ``insert`` / ``push`` they are the handle's history.  Works with
+        per-stream references.  The tracker itself is not disturbed."""
+        cap = 3 * self.N + 8
+        need = ctypes.c_size_t()
+        nat.check(nat.lib.rts_otw_backward_workspace_bytes(self.N, self.c, self.B, ctypes.byref(need)))
+        ws = getattr(self, "_bw_ws", None)
+        if ws is None or ws.numel() < need.value:
+            ws = self._bw_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        path = torch.empty((self.B, cap, 2), dtype=torch.int32, device=self.device)
+        plen = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        total = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        end = torch.empty((self.B, 2), dtype=torch.int32, device=self.device)
+        acc = torch.empty((self.B, cap), dtype=torch.float64, device=self.device) if want_acc else None
+        if live_dev is None and self._keep is not None:
+            live_dev, live_len_dev = self._keep
+        if live_dev is not None:
+            src = (live_dev.data_ptr(), _np_dtype_code(live_dev.dtype), int(live_dev.shape[1]), live_len_dev.data_ptr())
+        else:
+            src = (None, nat.F64, 0, None)
+        nat.check(nat.lib.rts_otw_backward(self._h, src[0], src[1], src[2], src[3], path.data_ptr(), plen.data_ptr(),
+                                           total.data_ptr(), end.data_ptr(), acc.data_ptr() if want_acc else None,
+                                           ws.data_ptr(), ws.numel(), self._stream()))
+        n = plen.cpu().numpy()
+        path_h = path.cpu().numpy()
+        paths = [path_h[b, :n[b]].copy() for b in range(self.B)]
+        out = (paths, total.cpu().numpy(), end.cpu().numpy())
+        if want_acc:
+            acc_h = acc.cpu().numpy()
+            out += ([acc_h[b, :n[b]].copy() for b in range(self.B)],)
+        return out
+
+    @_on_device
     def set_waves(self, waves):
         nat.check(nat.lib.rts_otw_set_waves(self._h, int(waves)))
 

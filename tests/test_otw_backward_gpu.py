@@ -1,0 +1,496 @@
+"""rts_otw_backward on the GPU, through the C ABI, against its definition in numpy (tests/otw_backward_model.py over the
+CPU oracle's dense matrices).  Indices, end, total and acc are compared with ==: the device walks the very values the
+oracle computes, there is no tolerance to choose."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+import oracle  # noqa: E402
+from guarded import FILLS, guarded, holds_fill, same_bytes  # noqa: E402
+from otw_backward_model import from_oracle  # noqa: E402
+from real_time_audio_sync_amd import synth  # noqa: E402
+from silence_inputs import VARIANTS, silent_pair, tie_euclid  # noqa: E402
+
+DEV = "cuda:0"
+INVALID, UNSUPPORTED = -1, -2
+I32, F32, F64, U8 = torch.int32, torch.float32, torch.float64, torch.uint8
+MRC = 3
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+
+
+def _nat():
+    from real_time_audio_sync_amd import _native
+    return _native
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _err():
+    return _nat().lib.rts_last_error().decode()
+
+
+class _Env(object):
+    def __init__(self, **kw):
+        self.kw = kw
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.kw}
+        os.environ.update({k: str(v) for k, v in self.kw.items()})
+
+    def __exit__(self, *a):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+class Raw(object):
+    """One rts_otw handle driven through the C ABI alone.  ``pool`` (12, P); without ``first`` / ``lens`` every one of the
+    ``B`` streams follows the whole pool, with them stream b follows pool[:, first[b]:first[b] + lens[b]]
+    (rts_otw_create_refs)."""
+
+    def __init__(self, pool, c, variant="otw", euclid=False, B=1, first=None, lens=None, dtype=F64, mrc=MRC):
+        nat = _nat()
+        self.nat, self.c, self.variant, self.euclid, self.mrc = nat, c, variant, euclid, mrc
+        self.pool = pool
+        self.pool_t = torch.from_numpy(np.ascontiguousarray(pool.T)).to(dtype).to(DEV)
+        code = nat.F32 if dtype == F32 else nat.F64
+        cost = nat.COST_EUCLID if euclid else nat.COST_DOT
+        self.h = ctypes.c_void_p()
+        P = pool.shape[1]
+        if first is None:
+            self.B, self.first, self.lens = B, [0] * B, [P] * B
+            nat.check(nat.lib.rts_otw_create(self.pool_t.data_ptr(), code, 12, P, B, c, mrc, VARIANTS[variant], cost,
+                                             ctypes.byref(self.h)))
+        else:
+            self.B, self.first, self.lens = len(first), list(first), list(lens)
+            f, l = np.array(first, dtype=np.int64), np.array(lens, dtype=np.int32)
+            nat.check(nat.lib.rts_otw_create_refs(self.pool_t.data_ptr(), code, 12, P, f.ctypes.data, l.ctypes.data, self.B, c,
+                                                  mrc, VARIANTS[variant], cost, ctypes.byref(self.h)))
+        self.N = max(self.lens)
+        self.cap = 3 * self.N + 8
+        self.keep = None
+        n = ctypes.c_size_t()
+        nat.check(nat.lib.rts_otw_backward_workspace_bytes(self.N, c, self.B, ctypes.byref(n)))
+        self.ws_bytes = n.value
+
+    def close(self):
+        if self.h:
+            torch.cuda.synchronize()
+            self.nat.lib.rts_otw_destroy(self.h)
+            self.h = None
+
+    def ref(self, b):
+        return self.pool[:, self.first[b]:self.first[b] + self.lens[b]]
+
+    def _pack(self, lives, dtype):
+        tmax = max(1, max(l.shape[1] for l in lives))
+        buf = torch.zeros((self.B, tmax, 12), dtype=dtype)
+        for b, l in enumerate(lives):
+            buf[b, :l.shape[1]] = torch.from_numpy(np.ascontiguousarray(l.T)).to(dtype)
+        return buf.to(DEV), torch.tensor([l.shape[1] for l in lives], dtype=I32).to(DEV)
+
+    def run(self, lives, mode="insert", dtype=F64):
+        nat = self.nat
+        lv, ln = self._pack(lives, dtype)
+        self.keep = (lv, nat.F32 if dtype == F32 else nat.F64, int(lv.shape[1]), ln)
+        nat.check(nat.lib.rts_otw_run(self.h, lv.data_ptr(), self.keep[1], self.keep[2], ln.data_ptr(),
+                                      nat.MODE_SET_LIVE if mode == "set_live" else nat.MODE_INSERT_LOOP, _stream()))
+
+    def push(self, lives, dtype=F64):
+        nat = self.nat
+        lv, ln = self._pack(lives, dtype)
+        nat.check(nat.lib.rts_otw_push(self.h, lv.data_ptr(), nat.F32 if dtype == F32 else nat.F64, int(lv.shape[1]),
+                                       ln.data_ptr(), _stream()))
+
+    def restart(self, b, first, length):
+        mask = np.zeros(self.B, dtype=np.uint8)
+        mask[b] = 1
+        f, l = np.array(self.first, dtype=np.int64), np.array(self.lens, dtype=np.int32)
+        f[b], l[b] = first, length
+        self.nat.check(self.nat.lib.rts_otw_restart(self.h, mask.ctypes.data, f.ctypes.data, l.ctypes.data, _stream()))
+        self.first[b], self.lens[b] = first, length
+
+    def snapshot(self):
+        """Everything the handle shows of its streams: states, forward paths, bands."""
+        nat = self.nat
+        st = np.zeros((self.B, nat.STATE_LEN), dtype=np.int32)
+        nat.check(nat.lib.rts_otw_read_states(self.h, st.ctypes.data, _stream()))
+        out = [st]
+        for b in range(self.B):
+            n = ctypes.c_int()
+            p = np.zeros((self.cap, 2), dtype=np.int32)
+            nat.check(nat.lib.rts_otw_read_path(self.h, b, p.ctypes.data, self.cap, ctypes.byref(n), _stream()))
+            rb, cb = np.empty(self.c + 1), np.empty(self.c + 1)
+            nat.check(nat.lib.rts_otw_read_bands(self.h, b, rb.ctypes.data, cb.ctypes.data, _stream()))
+            out += [p[:min(n.value, self.cap)].copy(), rb, cb]
+        return out
+
+    def buffers(self, fill=0x55, ws_offset=0, want_acc=True):
+        t, checks = {}, {}
+        for name, shape, dt, off in (("path", (self.B, self.cap, 2), I32, 0), ("len", (self.B,), I32, 0),
+                                     ("total", (self.B,), F64, 0), ("end", (self.B, 2), I32, 0),
+                                     ("acc", (self.B, self.cap), F64, 0), ("ws", (self.ws_bytes,), U8, ws_offset)):
+            if name == "acc" and not want_acc:
+                continue
+            t[name], checks[name] = guarded(shape, dt, DEV, fill, offset_bytes=off)
+        return t, checks
+
+    def call(self, t, src="keep", ws_bytes=None, **override):
+        """rts_otw_backward on the buffers ``t``; ``src``: 'keep' = the buffers of the last run (or NULL without one)."""
+        lv, code, T, ln = self.keep if (src == "keep" and self.keep) else (None, self.nat.F64, 0, None)
+        p = dict(h=self.h, live=lv.data_ptr() if lv is not None else None, code=code, T=T,
+                 ln=ln.data_ptr() if ln is not None else None, path=t["path"].data_ptr(), len=t["len"].data_ptr(),
+                 total=t["total"].data_ptr(), end=t["end"].data_ptr(), acc=t["acc"].data_ptr() if "acc" in t else None,
+                 ws=t["ws"].data_ptr(), ws_bytes=self.ws_bytes if ws_bytes is None else ws_bytes)
+        p.update(override)
+        return self.nat.lib.rts_otw_backward(p["h"], p["live"], p["code"], p["T"], p["ln"], p["path"], p["len"], p["total"],
+                                             p["end"], p["acc"], p["ws"], p["ws_bytes"], _stream())
+
+    def backward(self, fill=0x55, ws_offset=0, src="keep"):
+        """-> per stream dict(path, total, end, acc), every guard checked, rows behind path_len still the fill."""
+        t, checks = self.buffers(fill, ws_offset)
+        rc = self.call(t, src)
+        assert rc == 0, _err()
+        torch.cuda.synchronize()
+        for name, check in checks.items():
+            check(name)
+        n = t["len"].cpu().numpy()
+        path, acc, total, end = (t[k].cpu().numpy() for k in ("path", "acc", "total", "end"))
+        out = []
+        for b in range(self.B):
+            assert 0 <= n[b] <= self.cap
+            assert holds_fill(path[b, n[b]:], fill) and holds_fill(acc[b, n[b]:], fill), "rows behind path_len were written"
+            out.append(dict(path=path[b, :n[b]].copy(), acc=acc[b, :n[b]].copy(), total=total[b], end=end[b].copy()))
+        return out
+
+
+def model(ref, live, c, variant, euclid, mode="insert", mrc=MRC):
+    return from_oracle(ref, live, c, mrc, VARIANTS[variant], oracle.COST_EUCLID if euclid else oracle.COST_DOT, mode)
+
+
+def assert_same(got, want, what):
+    assert np.array_equal(got["path"], want["path"]), "%s: path" % (what,)
+    assert tuple(got["end"]) == tuple(want["end"]), "%s: end" % (what,)
+    assert same_bytes(np.float64(got["total"]), np.float64(want["total"])) or \
+        (np.isnan(got["total"]) and np.isnan(want["total"])), "%s: total %r != %r" % (what, got["total"], want["total"])
+    assert np.array_equal(got["acc"], want["acc"]), "%s: acc" % (what,)
+
+
+def _pair(c, seed, euclid, n=None):
+    n = n or max(8, 2 * c + 20)
+    ref = synth.synth_ref(n, seed)
+    live = synth.synth_live(ref, seed + 1)
+    if euclid:
+        ref, live = synth._as_f32_values(np.abs(ref - 0.2)), synth._as_f32_values(np.abs(live - 0.2))
+    return ref, live
+
+
+# ---- band widths on both sides of every window size --------------------------------------------------------------------
+SMALL_C = (1, 2, 3, 15, 16, 17, 52, 53, 116, 117)     # both sides of the 64- and 128-cell windows: everything
+WIDE_C = (244, 245, 500, 501, 1012, 1013)             # 256 .. 2048 cells: one variant per cost
+
+
+@pytest.mark.parametrize("c", SMALL_C)
+def test_small_widths_every_variant_cost_mode_dtype(c):
+    for variant in sorted(VARIANTS):
+        for euclid in (False, True):
+            ref, live = _pair(c, 100 + c, euclid)
+            lives = [live, live[:, :max(1, live.shape[1] // 2)]]
+            for dtype in (F32, F64):
+                r = Raw(ref, c, variant, euclid, B=2, dtype=dtype)
+                try:
+                    for mode in ("insert", "set_live"):
+                        r.run(lives, mode, dtype)
+                        got = r.backward()
+                        for b in range(2):
+                            assert_same(got[b], model(ref, lives[b], c, variant, euclid, mode)[0],
+                                        (c, variant, euclid, mode, dtype, b))
+                finally:
+                    r.close()
+
+
+@pytest.mark.parametrize("c", WIDE_C)
+def test_wide_widths(c):
+    i = WIDE_C.index(c)
+    for euclid in (False, True):
+        variant = sorted(VARIANTS)[(i + euclid) % 3]
+        mode = ("insert", "set_live")[(i + euclid) % 2]
+        dtype = (F32, F64)[i % 2]
+        ref, live = _pair(c, 300 + c, euclid)
+        r = Raw(ref, c, variant, euclid, B=1, dtype=dtype)
+        try:
+            r.run([live], mode, dtype)
+            assert_same(r.backward()[0], model(ref, live, c, variant, euclid, mode)[0], (c, variant, euclid, mode))
+        finally:
+            r.close()
+
+
+def test_plain_kernel_selection_does_not_disable_it():
+    ref, live = _pair(17, 77, False)
+    with _Env(RTS_OTW_SPEC=0):
+        r = Raw(ref, 17, "otw", False)
+    try:
+        r.run([live])
+        assert_same(r.backward()[0], model(ref, live, 17, "otw", False)[0], "RTS_OTW_SPEC=0")
+    finally:
+        r.close()
+
+
+# ---- ties: the first-minimum order ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("euclid", [False, True])
+def test_ties(euclid):
+    for c, variant in ((20, "otw"), (20, "livenote_v2"), (117, "livenote")):
+        ref, lives = silent_pair(2 * c + 100, c, 7000 + c, euclid)
+        r = Raw(ref, c, variant, euclid, B=3)
+        try:
+            for mode in ("insert", "set_live"):
+                r.run(lives, mode)
+                got = r.backward()
+                for b in range(3):
+                    assert_same(got[b], model(ref, lives[b], c, variant, euclid, mode)[0], ("silent", c, variant, mode, b))
+        finally:
+            r.close()
+    for c, variant in ((5, "otw"), (16, "livenote"), (16, "livenote_v2")):
+        ref, live = tie_euclid(2 * c + 30, 31 + c) if euclid else synth.synth_tie(2 * c + 30, seed=31 + c)
+        r = Raw(ref, c, variant, euclid)
+        try:
+            r.run([live])
+            assert_same(r.backward()[0], model(ref, live, c, variant, euclid)[0], ("tie", c, variant))
+        finally:
+            r.close()
+
+
+# ---- ends and ragged batches --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["insert", "set_live"])
+def test_ends_and_ragged_batch(mode):
+    c = 12
+    ref, live = _pair(c, 500, False, n=60)
+    # past the reference end: the live stream goes on after its last frame
+    ext = np.concatenate([live, np.repeat(live[:, -1:], 60, axis=1)], axis=1)
+    # stuck on the first reference frame for more than 2N frames: runs out of live rows before the reference ends
+    stuck = np.repeat(ref[:, :1], 2 * 60 + 5, axis=1)
+    lives = [ext, stuck, live[:, :1], live[:, :c - 1], live[:, :c], live[:, :0], live]
+    r = Raw(ref, c, "otw", False, B=len(lives), mrc=50)
+    try:
+        r.run(lives, mode)
+        got = r.backward()
+        statuses = []
+        for b, lv in enumerate(lives):
+            m, o = model(ref, lv, c, "otw", False, mode, mrc=50)
+            statuses.append(o.state["status"])
+            assert_same(got[b], m, (mode, b))
+        assert statuses[0] == oracle.STOP_REF_END and statuses[1] == oracle.LIVE_OVERFLOW    # the cases are what they say
+        assert np.array_equal(got[2]["path"], [[0, 0]])
+        assert len(got[5]["path"]) == 0 and np.isnan(got[5]["total"]) and tuple(got[5]["end"]) == (-1, -1)
+    finally:
+        r.close()
+
+
+def test_sources_refs_and_restart():
+    c = 9
+    pool = synth.synth_ref(120, 900)
+    first, lens = [0, 10, 25, 40], [60, 45, 35, 80]          # overlapping ranges of different lengths
+    r = Raw(pool, c, "livenote", False, first=first, lens=lens)
+    try:
+        # fresh: nothing consumed
+        for g in r.backward():
+            assert len(g["path"]) == 0 and np.isnan(g["total"]) and tuple(g["end"]) == (-1, -1)
+        # run: the buffers are passed again
+        lives = [synth.synth_live(r.ref(b), 910 + b) for b in range(4)]
+        lives[3] = lives[3][:, :1]
+        r.run(lives)
+        got = r.backward()
+        for b in range(4):
+            assert_same(got[b], model(r.ref(b), lives[b], c, "livenote", False)[0], ("run", b))
+        # mixed: a push behind the run
+        r.push([lv[:, :2] for lv in lives])
+        t, _ = r.buffers()
+        before = {k: v.clone() for k, v in t.items()}
+        assert r.call(t) == UNSUPPORTED and "rts_otw_run" in _err()
+        torch.cuda.synchronize()
+        assert all(torch.equal(before[k], t[k]) for k in t)
+        # insert / push only (NULL), ragged, then stream 1 restarted onto another range and pushed again
+        r.nat.check(r.nat.lib.rts_otw_reset(r.h, _stream()))
+        r.keep = None
+        heard = [lv[:, :n] for lv, n in zip(lives, (30, 0, 17, 1))]
+        r.push(heard)
+        got = r.backward()
+        for b in range(4):
+            assert_same(got[b], model(r.ref(b), heard[b], c, "livenote", False)[0], ("push", b))
+        r.restart(1, 30, 50)
+        got = r.backward()
+        assert len(got[1]["path"]) == 0 and tuple(got[1]["end"]) == (-1, -1)
+        assert_same(got[0], model(r.ref(0), heard[0], c, "livenote", False)[0], "beside a restarted stream")
+        again = synth.synth_live(r.ref(1), 950)[:, :40]
+        empty = again[:, :0]
+        r.push([empty, again, empty, empty])
+        got = r.backward()
+        assert_same(got[1], model(r.ref(1), again, c, "livenote", False)[0], "restarted onto pool[30:80], then pushed")
+        assert_same(got[2], model(r.ref(2), heard[2], c, "livenote", False)[0], "beside it")
+    finally:
+        r.close()
+
+
+# ---- the handle is only read ----------------------------------------------------------------------------------------------
+def test_handle_untouched():
+    c = 14
+    ref, live = _pair(c, 1200, True, n=70)
+    lives = [live[:, :40], live[:, :23]]
+    more = [live[:, 40:55], live[:, 23:50]]
+    r, ctl = Raw(ref, c, "livenote_v2", True, B=2), Raw(ref, c, "livenote_v2", True, B=2)
+    try:
+        for h in (r, ctl):
+            h.push(lives)
+        before = r.snapshot()
+        got = r.backward()
+        after = r.snapshot()
+        assert all(same_bytes(x, y) for x, y in zip(before, after))
+        for b in range(2):
+            assert_same(got[b], model(ref, lives[b], c, "livenote_v2", True)[0], b)
+        for h in (r, ctl):
+            h.push(more)
+        assert all(same_bytes(x, y) for x, y in zip(r.snapshot(), ctl.snapshot()))
+    finally:
+        r.close()
+        ctl.close()
+
+
+# ---- caller memory ----------------------------------------------------------------------------------------------------------
+def test_caller_memory_fills_and_offset_workspace():
+    c = 21
+    ref, live = _pair(c, 1300, False)
+    lives = [live, live[:, :5], live[:, :0]]
+    r = Raw(ref, c, "otw", False, B=3, dtype=F32)
+    try:
+        r.run(lives, "insert", F32)
+        want = [model(ref, lv, c, "otw", False)[0] for lv in lives]
+        for fill in FILLS:
+            for ws_offset in (0, 16):
+                got = r.backward(fill=fill, ws_offset=ws_offset)      # guards and the rows behind path_len are checked inside
+                for b in range(3):
+                    assert_same(got[b], want[b], (hex(fill), ws_offset, b))
+    finally:
+        r.close()
+
+
+# ---- argument errors --------------------------------------------------------------------------------------------------------
+def test_argument_errors():
+    c = 6
+    ref, live = _pair(c, 1400, False, n=30)
+    r = Raw(ref, c, "otw", False)
+    try:
+        r.run([live])
+        t, checks = r.buffers(0x55)
+        before = {k: v.clone() for k, v in t.items()}
+        cases = [(dict(h=None), "handle"), (dict(path=None), "path_dev"), (dict(len=None), "path_len_dev"),
+                 (dict(total=None), "total_dev"), (dict(end=None), "end_dev"), (dict(ws=None), "ws_dev"),
+                 (dict(ws_bytes=r.ws_bytes - 1), "ws_bytes"), (dict(ws=t["ws"].data_ptr() + 8, ws_bytes=r.ws_bytes - 8), "ws_dev"),
+                 (dict(path=t["path"].data_ptr() + 4), "path_dev"), (dict(live=None), "live_dev"), (dict(ln=None), "live_len_dev"),
+                 (dict(code=r.nat.F32), "live_dtype"), (dict(T=r.keep[2] + 1), "T_max"), (dict(code=7), "live_dtype")]
+        for override, name in cases:
+            assert r.call(t, **override) == INVALID, name
+            assert name in _err(), (name, _err())
+        if torch.cuda.device_count() > 1:
+            with torch.cuda.device(1):
+                assert r.call(t) == INVALID and "device" in _err()
+        # frames of the handle's own history: live_dev must be NULL
+        r.nat.check(r.nat.lib.rts_otw_reset(r.h, _stream()))
+        r.push([live[:, :10]])
+        assert r.call(t) == INVALID and "live_dev" in _err()          # still hands the run's buffers in
+        torch.cuda.synchronize()
+        for name, check in checks.items():
+            check(name)
+        assert all(torch.equal(before[k], t[k]) for k in t), "a refused call wrote something"
+        r.keep = None
+        assert_same(r.backward()[0], model(ref, live[:, :10], c, "otw", False)[0], "after the refusals")
+    finally:
+        r.close()
+
+
+# ---- Python surface ---------------------------------------------------------------------------------------------------------
+def test_python_surface_batched_and_dropin():
+    from real_time_audio_sync_amd.otw_batch import BatchedOTW
+    from real_time_audio_sync_amd.otw_eran import OnlineTimeWarping
+    c = 10
+    ref, lives = synth.synth_batch(50, 3, seed=21)
+    eng = BatchedOTW(ref, c, MRC, batch=3, dtype=F64)
+    try:
+        lv, ln = eng.pack(lives)
+        eng.run(lv, ln)
+        paths, totals, ends, accs = eng.backward(want_acc=True)
+        assert len(eng.backward()) == 3
+        for b in range(3):
+            assert_same(dict(path=paths[b], total=totals[b], end=ends[b], acc=accs[b]), model(ref, lives[b], c, "otw", False)[0], b)
+    finally:
+        eng.close()
+    o = OnlineTimeWarping(ref, {'c': c, 'max_run_count': MRC})
+    for i in range(25):
+        o.insert(lives[0][:, i])
+    want = model(ref, lives[0][:, :25], c, "otw", False)[0]["path"]
+    got = o.backward_path()
+    assert isinstance(got, list) and got == [(int(x), int(y)) for x, y in want]
+    o.set_live(lives[1])
+    got = o.backward_path()
+    want = model(ref, lives[1], c, "otw", False, "set_live")[0]["path"]
+    assert isinstance(got, np.ndarray) and got.dtype == np.int64 and np.array_equal(got, want)
+
+
+def _tones(n, seed, fs=22050):
+    """Synthetic audio: a new three-tone chord every fifth of a second, a little noise."""
+    rs = np.random.RandomState(seed)
+    x = np.zeros(n)
+    t = np.arange(n) / float(fs)
+    seg = fs // 5
+    for s in range(0, n, seg):
+        for f in 110.0 * 2 ** (rs.randint(0, 36, size=3) / 12.0):
+            x[s:s + seg] += np.sin(2 * np.pi * f * t[s:s + seg])
+    return (0.2 * x + 0.01 * rs.randn(n)).astype(np.float32)
+
+
+def test_python_surface_live_session():
+    from real_time_audio_sync_amd import _native as nat
+    from real_time_audio_sync_amd.live import LiveSession
+    c = 15
+    ref = synth.synth_ref(90, 33)
+    mics = [_tones(150000, 1), _tones(90000, 2)]
+    sess = LiveSession(ref, batch=2, c=c, max_run_count=MRC)
+    try:
+        pos = [0, 0]
+        while any(pos[b] < len(mics[b]) for b in range(2)):
+            bufs = []
+            for b, size in enumerate((4096, 7001)):
+                n = min(size, len(mics[b]) - pos[b])
+                bufs.append(mics[b][pos[b]:pos[b] + n] if n > 0 else None)
+                pos[b] += max(n, 0)
+            sess.feed(bufs)
+        paths, totals, ends = sess.backward()
+        frames, lens = sess.otw.recent(256)
+        frames, lens = frames.cpu().numpy(), lens.cpu().numpy()
+        for b in range(2):
+            assert 20 < lens[b] < 256      # the whole history
+            m = model(ref, np.ascontiguousarray(frames[b, :lens[b]].T), c, "otw", False)[0]
+            assert np.array_equal(paths[b], m["path"]) and totals[b] == m["total"] and tuple(ends[b]) == tuple(m["end"]), b
+        only = sess.backward(streams=[1])[0]
+        assert len(only[0]) == 0 and np.array_equal(only[1], paths[1])
+    finally:
+        sess.close()
+    wtw = LiveSession(ref, batch=2, wtw_params=dict(dtw_win_size=4096 * 10, dtw_hop_size=2048 * 10))
+    try:
+        with pytest.raises(nat.RtsyncError):
+            wtw.backward()
+    finally:
+        wtw.close()
