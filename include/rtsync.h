@@ -231,6 +231,8 @@ int rts_otw_set_dense(rts_otw *h, double *acc_dev, double *cost_dev, void *strea
  * rts_otw_run are the caller's memory and the library keeps no pointer to them: pass that call's live_dev, live_dtype,
  * T_max and live_len_dev again (dtype and T_max are checked against the run being replayed).  The handle's own state is
  * not touched, so the streams keep running on the pipelined kernel.  Every supported band width.  Synchronises `stream`.
+ * Every argument is checked before anything is enqueued, as in rts_otw_backward, whose source rules these are: a refused
+ * call (live_dev must also be 16-byte aligned) leaves acc_dev / cost_dev untouched.
  * What the drop-in classes' .acc_cost / .cost
  * (otw_eran.py:23,27) are made of. */
 int rts_otw_replay_dense(rts_otw *h, const void *live_dev, int live_dtype, int T_max, const int32_t *live_len_dev,

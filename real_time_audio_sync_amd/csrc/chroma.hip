@@ -878,7 +878,7 @@ int rts_chroma_frames(rts_chroma *h, const void *samples_dev, int sample_dtype, 
     if (!chroma_out_dev && !stft_out_dev) return set_error(RTS_ERR_INVALID, "no output requested");
     // a bin leaves the kernels as one (re, im) pair, a 16-byte store
     if (((uintptr_t)stft_out_dev & 15) != 0) return set_error(RTS_ERR_INVALID, "stft_out_dev must be 16-byte aligned");
-    if ((sample_dtype != RTS_F32 && sample_dtype != RTS_F64) || (out_dtype != RTS_F32 && out_dtype != RTS_F64))
+    if (!dtype_ok(sample_dtype) || !dtype_ok(out_dtype))
         return set_error(RTS_ERR_INVALID, "bad dtype");
     if (n_frames < 0 || pad_left < 0 || n_samples < 0) return set_error(RTS_ERR_INVALID, "negative size");
     if ((long long)n_frames > rts_chroma_num_frames(n_samples, h->L, h->hop, pad_left))
@@ -938,7 +938,7 @@ int rts_chroma_frames_batch(rts_chroma *h, const void *samples_dev, int sample_d
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (!samples_dev || !n_samples_dev || !n_frames_dev || !chroma_out_dev)
         return set_error(RTS_ERR_INVALID, "NULL device buffer");
-    if ((sample_dtype != RTS_F32 && sample_dtype != RTS_F64) || (out_dtype != RTS_F32 && out_dtype != RTS_F64))
+    if (!dtype_ok(sample_dtype) || !dtype_ok(out_dtype))
         return set_error(RTS_ERR_INVALID, "bad dtype");
     if (B < 1 || n_frames_max < 0 || pad_left < 0 || sample_stride < 0) return set_error(RTS_ERR_INVALID, "bad size");
     if (n_frames_max == 0) return RTS_OK;
@@ -990,7 +990,7 @@ int rts_chroma_project(rts_chroma *h, const double *spec_dev, int n_frames, int 
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (!spec_dev || !chroma_out_dev) return set_error(RTS_ERR_INVALID, "NULL device buffer");
-    if (out_dtype != RTS_F32 && out_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad dtype");
+    if (!dtype_ok(out_dtype)) return set_error(RTS_ERR_INVALID, "bad dtype");
     if (n_frames < 0) return set_error(RTS_ERR_INVALID, "negative size");
     if (n_frames == 0) return RTS_OK;
     ChromaArgs g;
@@ -1019,7 +1019,7 @@ int rts_chroma_read_stamps(long long *out) {
 int rts_chroma_diff(const void *chroma_dev, int dtype, int n_frames, void *out_dev, void *stream) {
     using namespace rts;
     if (!chroma_dev || !out_dev) return set_error(RTS_ERR_INVALID, "NULL device buffer");
-    if (dtype != RTS_F32 && dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad dtype");
+    if (!dtype_ok(dtype)) return set_error(RTS_ERR_INVALID, "bad dtype");
     if (n_frames < 2) return RTS_OK;
     const long long n_out = (long long)(n_frames - 1) * kCh;
     hipLaunchKernelGGL(chroma_diff_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream,

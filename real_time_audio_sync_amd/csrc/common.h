@@ -11,6 +11,8 @@ namespace rts {
 char *last_error_buf();  // thread-local, 512 bytes
 int set_error(int code, const char *fmt, ...);
 
+inline bool dtype_ok(int dtype) { return dtype == RTS_F32 || dtype == RTS_F64; }  // a floating-point dtype code of the ABI
+
 // Streams of a tracker handle (rts_live_create checks that it binds one of its own size).  Library-internal.
 __attribute__((visibility("hidden"))) int otw_batch(const rts_otw *h);
 __attribute__((visibility("hidden"))) int wtw_batch(const rts_wtw *h);

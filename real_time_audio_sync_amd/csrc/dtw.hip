@@ -325,7 +325,7 @@ static int dtw_check(int a_dtype, int b_dtype, int F, int M, int N, int B, const
     if (F != kDtwF) return set_error(RTS_ERR_UNSUPPORTED, "F must be 12 chroma bins (got %d)", F);
     if (M < 1 || N < 1 || B < 1)
         return set_error(RTS_ERR_INVALID, "%s, %s, B must be >= 1 (got %d %d %d)", m_name, n_name, M, N, B);
-    if ((a_dtype != RTS_F32 && a_dtype != RTS_F64) || (b_dtype != RTS_F32 && b_dtype != RTS_F64))
+    if (!dtype_ok(a_dtype) || !dtype_ok(b_dtype))
         return set_error(RTS_ERR_INVALID, "bad dtype");
     if ((long long)M * N > 0x7fffffffLL * 4) return set_error(RTS_ERR_INVALID, "%s*%s too large", m_name, n_name);
     if (B > 65535) return set_error(RTS_ERR_INVALID, "at most 65535 pairs per call");

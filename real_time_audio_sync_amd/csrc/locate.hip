@@ -282,8 +282,8 @@ int rts_locate(const void *queries_dev, int q_dtype, int M_max, const int32_t *q
     if (B < 1 || B > 65535) return set_error(RTS_ERR_INVALID, "B must be in [1, 65535] (got %d)", B);
     if (P < 1 || P > 65535) return set_error(RTS_ERR_INVALID, "P must be in [1, 65535] (got %d)", P);
     if (n_pool_frames < 1) return set_error(RTS_ERR_INVALID, "n_pool_frames must be >= 1 (got %lld)", n_pool_frames);
-    if (q_dtype != RTS_F32 && q_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad q_dtype %d", q_dtype);
-    if (pool_dtype != RTS_F32 && pool_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad pool_dtype %d", pool_dtype);
+    if (!dtype_ok(q_dtype)) return set_error(RTS_ERR_INVALID, "bad q_dtype %d", q_dtype);
+    if (!dtype_ok(pool_dtype)) return set_error(RTS_ERR_INVALID, "bad pool_dtype %d", pool_dtype);
     if (cost_kind != RTS_COST_DOT && cost_kind != RTS_COST_EUCLID)
         return set_error(RTS_ERR_INVALID, "bad cost_kind %d", cost_kind);
     LocArgs g;

@@ -1,6 +1,5 @@
 // rts_otw_backward: the backward path of on-line time warping -- from a stream's current best point back
-// to (0, 0) over the accumulated-cost cells the tracker has evaluated.  Included by otw.hip behind the host side of the
-// tracker, whose handle, launch() and argument builders it uses.
+// to (0, 0) over the accumulated-cost cells the tracker has evaluated.
 //
 // Two device parts:
 //   1. trace replay: the plain 8-wave otw_advance_kernel in its kMirrorTrace instantiation, run on the handle's scratch
@@ -15,6 +14,8 @@
 //      a (K + 1) x (K + 1) tile of the log behind the current cell in LDS together with the tile's K x K costs, one thread
 //      walks until it leaves the tile (at least K steps), and the next tile is staged behind the cell it stopped at.
 #pragma once
+#include "otw_device.h"  // the tracker's cost code: otw_live_frame, otw_ref_frame, cell_cost
+#include "otw_host.h"    // the handle, replay_source() and launch()
 
 namespace rts {
 
@@ -288,44 +289,18 @@ int rts_otw_backward(rts_otw *h, const void *live_dev, int live_dtype, int T_max
     if (ws_bytes < l.total)
         return set_error(RTS_ERR_INVALID, "ws_bytes = %zu is less than rts_otw_backward_workspace_bytes = %zu", ws_bytes, l.total);
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
-    if (h->src_kind == 3)
-        return set_error(RTS_ERR_UNSUPPORTED, "rts_otw_insert / rts_otw_push after rts_otw_run without a reset: nothing to replay from");
-    if (h->src_kind == 1) {  // the source rules of rts_otw_replay_dense
-        if (!live_dev || !live_len_dev)
-            return set_error(RTS_ERR_INVALID, "the handle's frames came from rts_otw_run: pass that call's live_dev / live_len_dev again");
-        if (live_dtype != RTS_F32 && live_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad live_dtype %d", live_dtype);
-        if (live_dtype != h->run_dtype || T_max != h->run_T)
-            return set_error(RTS_ERR_INVALID, "live_dtype / T_max differ from the rts_otw_run being replayed (%d / %d then)", h->run_dtype, h->run_T);
-        if ((uintptr_t)live_dev & 15) return set_error(RTS_ERR_INVALID, "live_dev must be 16-byte aligned");
-    } else if (live_dev) {
-        return set_error(RTS_ERR_INVALID, "the handle's frames came through rts_otw_insert / rts_otw_push (or it is fresh): live_dev must be NULL");
-    }
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = replay_scratch(h); rc != RTS_OK) return rc;  // first call only
+    OtwArgs a;
+    if (int rc = replay_source(h, live_dev, live_dtype, T_max, live_len_dev, s, &a); rc != RTS_OK) return rc;
     if (!h->bw_ev[0]) {
         for (int i = 0; i < 3; i++) RTS_HIP(hipEventCreate(&h->bw_ev[i]));
     }
     char *ws = static_cast<char *>(ws_dev);
-    RTS_HIP(hipEventRecord(h->bw_ev[0], s));
+    RTS_HIP(hipEventRecord(h->bw_ev[0], s));  // (behind the reset of the scratch state: B threads)
     RTS_HIP(hipMemsetAsync(ws + l.hdr_off, 0, l.hdr_bytes, s));  // every slot: no cells
-    hipLaunchKernelGGL(otw_reset_kernel, dim3((h->B + 63) / 64), dim3(64), 0, s, h->rp_state, h->B, h->variant);
-    RTS_HIP(hipGetLastError());
-    OtwArgs a = h->src_kind == 1 ? base_args(h) : hist_args(h);
-    a.state = h->rp_state;
-    a.path = h->rp_path;
-    a.bands = h->rp_bands;
-    a.dense_acc = a.dense_cost = nullptr;
     a.trace_hdr = reinterpret_cast<int2 *>(ws + l.hdr_off);
     a.trace_cells = reinterpret_cast<double *>(ws + l.cells_off);
     a.trace_rows = 2 * h->N;
-    if (h->src_kind == 1) {
-        a.live = live_dev;
-        a.live_len = live_len_dev;
-        a.live_stride = T_max;
-        a.live_f64 = live_dtype == RTS_F64;
-        a.mode = h->run_mode;
-        a.clamp_len = 1;
-    }
     if (h->src_kind != 0) {  // (a fresh handle has consumed nothing: the scratch state says so to the kernel below)
         if (int rc = launch(h, a, s, 0); rc != RTS_OK) return rc;
     }

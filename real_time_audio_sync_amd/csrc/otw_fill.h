@@ -1,8 +1,5 @@
 // Band fill of a fresh OTW stream as one dense anti-diagonal wavefront ("band fill").
 //
-// Included by otw.hip behind otw_advance_kernel: it uses that file's cell_cost, otw_load_feat, otw_live_frame, vmin,
-// wave_shift_up and OtwArgs, so the bit patterns cannot drift.
-//
 // While the band fills (t < c) otw_decide returns Both unconditionally, so the first c-1 steps of a fresh stream are
 // fixed in advance: t = j = s, both strips start at 0, no decision feeds back into the arithmetic.  The cells they
 // evaluate are the dense DTW matrix of the square [0, c-1] x [0, c-1]; the two band argmins of step s are the first
@@ -52,6 +49,7 @@
 // that is a number, whatever the order, so the value does not depend on it.  Missing predecessors of the cells of row 0
 // and column 0 are +inf for every variant, as in the chains while their strips start at 0 (x_in = inf, prevb[0] = inf).
 #pragma once
+#include "otw_device.h"  // OtwArgs, cell_cost, vmin, the wave shifts, otw_load_feat, otw_live_frame: the step kernel's own
 
 namespace rts {
 

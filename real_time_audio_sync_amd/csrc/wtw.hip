@@ -1030,7 +1030,7 @@ int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, co
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
     if (n_max < 0) return set_error(RTS_ERR_INVALID, "n_max < 0");
     if (n_max > 0 && !cols_dev) return set_error(RTS_ERR_INVALID, "cols_dev is NULL");
-    if (cols_dtype != RTS_F32 && cols_dtype != RTS_F64) return set_error(RTS_ERR_INVALID, "bad cols_dtype %d", cols_dtype);
+    if (!dtype_ok(cols_dtype)) return set_error(RTS_ERR_INVALID, "bad cols_dtype %d", cols_dtype);
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     WtwArgs &g = h->args;

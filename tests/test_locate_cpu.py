@@ -137,7 +137,8 @@ def test_argument_errors_come_before_any_hip_call(nat):
 
 
 def test_product_does_not_import_the_oracle():
-    for fn in ("locate.py", "_handle.py", "csrc/locate.hip", "csrc/cost.h"):
+    for fn in ("locate.py", "_handle.py", "csrc/locate.hip", "csrc/cost.h", "csrc/otw_device.h", "csrc/otw_stamps.h",
+               "csrc/otw_host.h"):
         src = open(os.path.join(ROOT, "real_time_audio_sync_amd", fn)).read()
         assert "import oracle" not in src and "from oracle" not in src and "liboracle" not in src, fn
 

@@ -421,6 +421,52 @@ def test_argument_errors():
         r.close()
 
 
+def test_dense_replay_refusals_leave_the_matrices_alone():
+    """rts_otw_replay_dense follows the same source rules (one function in the library) and, like rts_otw_backward, makes
+    every refusal before its first enqueue: the caller's matrices keep their bytes, the misaligned live_dev included --
+    that one used to be noticed only at the launch, behind the fill of both matrices."""
+    c, fill = 6, 0x55
+    ref, live = _pair(c, 1400, False, n=30)
+    N = ref.shape[1]
+    r = Raw(ref, c, "otw", False)
+    try:
+        nat = r.nat
+        acc, check_acc = guarded((1, 2 * N, N), F64, DEV, fill)
+        cost, check_cost = guarded((1, 2 * N, N), F64, DEV, fill)
+
+        def replay(**override):
+            lv, code, T, ln = r.keep if r.keep else (None, nat.F64, 0, None)
+            p = dict(live=lv.data_ptr() if lv is not None else None, code=code, T=T, ln=ln.data_ptr() if ln is not None else None)
+            p.update(override)
+            return nat.lib.rts_otw_replay_dense(r.h, p["live"], p["code"], p["T"], p["ln"], acc.data_ptr(), cost.data_ptr(),
+                                                _stream())
+
+        r.run([live])
+        for override, name in [(dict(live=None), "live_dev"), (dict(ln=None), "live_len_dev"), (dict(code=nat.F32), "live_dtype"),
+                               (dict(code=7), "live_dtype"), (dict(T=r.keep[2] + 1), "T_max"),
+                               (dict(live=r.keep[0].data_ptr() + 8), "live_dev")]:
+            assert replay(**override) == INVALID, name
+            assert name in _err(), (name, _err())
+        r.push([live[:, :10]])                                     # behind a run, without a reset: nothing to replay from
+        assert replay() == UNSUPPORTED, _err()
+        nat.check(nat.lib.rts_otw_reset(r.h, _stream()))
+        r.push([live[:, :10]])
+        assert replay() == INVALID and "live_dev" in _err()       # still hands the run's buffers in
+        torch.cuda.synchronize()
+        check_acc("acc_dev")
+        check_cost("cost_dev")
+        assert holds_fill(acc, fill) and holds_fill(cost, fill), "a refused call wrote into the caller's matrices"
+        r.keep = None
+        assert replay() == 0, _err()
+        check_acc("acc_dev")
+        check_cost("cost_dev")
+        want = model(ref, live[:, :10], c, "otw", False)[0]
+        assert same_bytes(acc[0].cpu().numpy(), want["acc_matrix"]), "acc after the refusals"
+        assert same_bytes(cost[0].cpu().numpy(), want["cost_matrix"]), "cost after the refusals"
+    finally:
+        r.close()
+
+
 # ---- Python surface ---------------------------------------------------------------------------------------------------------
 def test_python_surface_batched_and_dropin():
     from real_time_audio_sync_amd.otw_batch import BatchedOTW

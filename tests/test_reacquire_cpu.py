@@ -142,7 +142,8 @@ def test_argument_errors_come_before_any_hip_call(nat):
 
 def test_product_does_not_import_the_oracle():
     for fn in ("_handle.py", "otw_batch.py", "wtw.py", "live.py", "locate.py", "_native.py", "csrc/otw.hip", "csrc/wtw.hip",
-               "csrc/live.hip", "csrc/cost.h"):
+               "csrc/live.hip", "csrc/cost.h", "csrc/otw_device.h", "csrc/otw_stamps.h", "csrc/otw_fill.h", "csrc/otw_host.h",
+               "csrc/otw_backward.h"):
         src = open(os.path.join(ROOT, "real_time_audio_sync_amd", fn)).read()
         assert "import oracle" not in src and "from oracle" not in src and "liboracle" not in src, fn
     tool = open(os.path.join(ROOT, "tools", "bench_live.py")).read()
