@@ -123,7 +123,6 @@ __global__ void __launch_bounds__(256) dtw_cost_kernel(DtwArgs g) {
     }
 }
 
-
 __global__ void __launch_bounds__(256) dtw_prep_kernel(DtwArgs g) {
     const int pair = blockIdx.y;
     const int j = blockIdx.x * 256 + threadIdx.x;
@@ -277,60 +276,26 @@ __global__ void __launch_bounds__(256) dtw_back_decode_kernel(DtwArgs g) {
     g.back[((size_t)pair * g.M + i) * g.N + j] = (int8_t)((w >> (2 * (t & 15))) & 3);
 }
 
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Workgroups of the strip-DP kernel K3 (one strip each) / K2 (two strips each) the current device holds at once; queried
-// once per kernel pair, device and LDS padding (sdp::pick_config, "Residency").
-template <void (*K3)(DtwArgs), void (*K2)(DtwArgs)>
-static int dtw_residency(int &r1, int &r2) {
-    static int cache[16][3];  // [device]: pad + 1, r1, r2
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const size_t pad = sdp::lds_pad();
-    int *c = (dev >= 0 && dev < 16) ? cache[dev] : nullptr;
-    if (c && c[0] == (int)pad + 1) {
-        r1 = c[1];
-        r2 = c[2];
-        return RTS_OK;
-    }
-    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K2), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K3), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    r1 = sdp::resident_blocks(K3, 256, sdp::lds_bytes(1) + pad);
-    r2 = sdp::resident_blocks(K2, 384, sdp::lds_bytes(2) + pad);
-    if (c) {
-        c[1] = r1;
-        c[2] = r2;
-        c[0] = (int)pad + 1;
-    }
-    return RTS_OK;
-}
-
-// The one workspace formula behind rts_dtw_workspace_bytes and rts_dtw_paths_workspace_bytes (dtw_enqueue carves it).
+// The one size function behind rts_dtw_workspace_bytes, rts_dtw_paths_workspace_bytes and
+// rts_dtw_subseq_paths_workspace_bytes: the sections are sdp_plan.h's table, which dtw_enqueue carves.
 static int dtw_workspace(int M, int N, int B, size_t *bytes, const char *m_name, const char *n_name) {
     if (!bytes) return set_error(RTS_ERR_INVALID, "bytes is NULL");
     if (M < 1 || N < 1 || B < 1) return set_error(RTS_ERR_INVALID, "%s, %s, B must be >= 1", m_name, n_name);
-    const size_t strips = (size_t)B * sdp::n_strips(M);
-    *bytes = 256 + align256(sizeof(unsigned long long) * strips * N) + align256(sizeof(int32_t) * strips * N) +
-             2 * align256(sizeof(int32_t) * strips) + align256(sizeof(double) * (size_t)B * N * sdp::kYRec) +
-             align256(sizeof(uint32_t) * (size_t)B * sdp::codes_words(M, N)) +
-             align256(sizeof(int32_t) * 2 * (size_t)B * sdp::scratch_pairs(M, N)) + align256(sizeof(int32_t) * (size_t)B);
+    *bytes = sdp::workspace_bytes(M, N, B);
     return RTS_OK;
 }
 
-// The argument checks rts_dtw and rts_dtw_paths share (M, N: the call's maxima), workspace and the alignment of path_dev
-// included: `ws_size` is the caller's own rts_*_workspace_bytes, `ws_fn` its name for the message.
+// The argument checks the three calls share (M, N: the call's maxima), workspace and the alignment of path_dev
+// included: `ws_fn` is the name of the caller's own rts_*_workspace_bytes, for the message.
 static int dtw_check(int a_dtype, int b_dtype, int F, int M, int N, int B, const void *path_dev, const void *ws_dev,
-                     size_t ws_bytes, const char *m_name, const char *n_name, int (*ws_size)(int, int, int, size_t *),
-                     const char *ws_fn) {
+                     size_t ws_bytes, const char *m_name, const char *n_name, const char *ws_fn) {
     if (F != kDtwF) return set_error(RTS_ERR_UNSUPPORTED, "F must be 12 chroma bins (got %d)", F);
     if (M < 1 || N < 1 || B < 1)
         return set_error(RTS_ERR_INVALID, "%s, %s, B must be >= 1 (got %d %d %d)", m_name, n_name, M, N, B);
-    if (!dtype_ok(a_dtype) || !dtype_ok(b_dtype))
-        return set_error(RTS_ERR_INVALID, "bad dtype");
+    if (!dtype_ok(a_dtype) || !dtype_ok(b_dtype)) return set_error(RTS_ERR_INVALID, "bad dtype");
     if ((long long)M * N > 0x7fffffffLL * 4) return set_error(RTS_ERR_INVALID, "%s*%s too large", m_name, n_name);
     if (B > 65535) return set_error(RTS_ERR_INVALID, "at most 65535 pairs per call");
-    size_t need = 0;
-    ws_size(M, N, B, &need);
+    const size_t need = sdp::workspace_bytes(M, N, B);
     if (ws_bytes < need)
         return set_error(RTS_ERR_INVALID, "workspace of %zu bytes is smaller than %s = %zu", ws_bytes, ws_fn, need);
     if (((uintptr_t)ws_dev & 15) != 0) return set_error(RTS_ERR_INVALID, "workspace must be 16-byte aligned");
@@ -339,47 +304,55 @@ static int dtw_check(int a_dtype, int b_dtype, int F, int M, int N, int B, const
     return RTS_OK;
 }
 
+// The caller's buffers, sizes and dtypes as the kernels get them (the workspace fields: dtw_enqueue).  rts_dtw has no
+// length tables and no total / start / end / row; the path-only calls have no cost / acc / back.
+static DtwArgs dtw_args(const void *a_dev, int a_dtype, long long a_stride, const int32_t *a_len_dev, const void *b_dev,
+                        int b_dtype, long long b_stride, const int32_t *b_len_dev, int M, int N, double *cost_dev,
+                        double *acc_dev, int8_t *back_dev, int32_t *path_dev, int32_t *path_len_dev, double *total_dev,
+                        int32_t *start_dev, int32_t *end_dev, double *row_dev) {
+    DtwArgs g;
+    g.a = a_dev;
+    g.b = b_dev;
+    g.cost = cost_dev;
+    g.acc = acc_dev;
+    g.back = back_dev;
+    g.path = path_dev;
+    g.path_len = path_len_dev;
+    g.a_stride = a_stride;
+    g.b_stride = b_stride;
+    g.M = M;
+    g.N = N;
+    g.a_f64 = a_dtype == RTS_F64;
+    g.b_f64 = b_dtype == RTS_F64;
+    g.a_len = a_len_dev;
+    g.b_len = b_len_dev;
+    g.total = total_dev;
+    g.start = start_dev;
+    g.end = end_dev;
+    g.row = row_dev;
+    return g;
+}
+
 // Carves the workspace and enqueues the pipeline; `g` arrives with the caller's buffers, sizes and dtypes filled in.
 // DENSE: rts_dtw (cost and acc_cost are written); otherwise rts_dtw_paths or, with SUBSEQ, rts_dtw_subseq_paths.
 template <bool DENSE, bool SUBSEQ = false>
 static int dtw_enqueue(DtwArgs g, int B, void *ws_dev, hipStream_t s) {
     static_assert(!(DENSE && SUBSEQ), "the subsequence form has no dense outputs");
-    constexpr auto k_sdp3 = SUBSEQ ? &dtw_subseq_sdp_kernel<3> : &dtw_sdp_kernel<3, DENSE>;
-    constexpr auto k_sdp2 = SUBSEQ ? &dtw_subseq_sdp_kernel<2> : &dtw_sdp_kernel<2, DENSE>;
-    const int M = g.M, N = g.N;
-    const int strips = sdp::n_strips(M);
-    int NS, H, G, res1 = 0, res2 = 0;
-    if (int rc = dtw_residency<k_sdp3, k_sdp2>(res1, res2); rc != RTS_OK) return rc;
-    if (res1 < 1 && res2 < 1)
-        return set_error(RTS_ERR_HIP, "the occupancy query reports no resident workgroup for the strip-DP kernel on this device");
-    sdp::pick_config(strips, B, res1, res2, NS, H, G);
-    const int n_rg = (strips + NS - 1) / NS;
-    unsigned char *ws = reinterpret_cast<unsigned char *>(ws_dev);
-    g.err = reinterpret_cast<int32_t *>(ws);
-    {
-        unsigned char *p = ws + 256;
-        g.bnd = reinterpret_cast<unsigned long long *>(p);
-        p += align256(sizeof(unsigned long long) * (size_t)B * strips * N);
-        g.entb = reinterpret_cast<int32_t *>(p);
-        p += align256(sizeof(int32_t) * (size_t)B * strips * N);
-        g.cross = reinterpret_cast<int32_t *>(p);
-        p += align256(sizeof(int32_t) * (size_t)B * strips);
-        g.lens = reinterpret_cast<int32_t *>(p);
-        p += align256(sizeof(int32_t) * (size_t)B * strips);
-        g.yrec = reinterpret_cast<double *>(p);
-        p += align256(sizeof(double) * (size_t)B * N * sdp::kYRec);
-        g.codes = reinterpret_cast<uint32_t *>(p);
-        p += align256(sizeof(uint32_t) * (size_t)B * sdp::codes_words(M, N));
-        g.pscr = reinterpret_cast<int32_t *>(p);
-        p += align256(sizeof(int32_t) * 2 * (size_t)B * sdp::scratch_pairs(M, N));
-        g.ticket = reinterpret_cast<int32_t *>(p);
-    }
-    g.n_rg = n_rg;
-    g.n_strips_wg = NS;
+    // one strip per workgroup / two (sdp::pick_config); their residency is asked once per device and LDS padding
+    void (*const k_sdp1)(DtwArgs) = SUBSEQ ? &dtw_subseq_sdp_kernel<3> : &dtw_sdp_kernel<3, DENSE>;
+    void (*const k_sdp2)(DtwArgs) = SUBSEQ ? &dtw_subseq_sdp_kernel<2> : &dtw_sdp_kernel<2, DENSE>;
+    static int residency[sdp::kResidencyDevices][3];
+    const int M = g.M, N = g.N, strips = sdp::n_strips(M);
+    sdp::Plan plan;
+    void (*k_sdp)(DtwArgs);
+    if (int rc = sdp::launch_plan(k_sdp1, k_sdp2, strips, B, residency, &plan, &k_sdp); rc != RTS_OK) return rc;
+    const sdp::WorkspaceLayout ws = sdp::workspace_carve(ws_dev, M, N, B, &g, &g.pscr);
+    g.n_rg = plan.n_rg;
+    g.n_strips_wg = plan.NS;
     RTS_HIP(hipMemsetAsync(g.err, 0, 16, s));
     RTS_HIP(hipMemsetAsync(g.ticket, 0, sizeof(int32_t) * (size_t)B, s));
     // (n_rg is the longest pair's: with per-pair lengths, whenever any pair can have more than one row group)
-    if (n_rg > 1) RTS_HIP(hipMemsetD32Async((hipDeviceptr_t)g.bnd, (int)sdp::kSentinel32, (size_t)2 * B * strips * N, s));
+    if (plan.n_rg > 1) RTS_HIP(hipMemsetD32Async((hipDeviceptr_t)g.bnd, (int)sdp::kSentinel32, ws.len[sdp::kBnd] / 4, s));
     if (DENSE) {
         const dim3 grid((N + 255) / 256, (M + kCostRows - 1) / kCostRows, B);
         if (g.a_f64 && g.b_f64)
@@ -393,11 +366,7 @@ static int dtw_enqueue(DtwArgs g, int B, void *ws_dev, hipStream_t s) {
         RTS_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(dtw_prep_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, g);
-    const size_t smem = sdp::lds_bytes(NS) + sdp::lds_pad();
-    if (H == 2)
-        hipLaunchKernelGGL(k_sdp2, dim3(G, B), dim3(64 * NS * 3), smem, s, g);
-    else
-        hipLaunchKernelGGL(k_sdp3, dim3(G, B), dim3(64 * NS * 4), smem, s, g);
+    hipLaunchKernelGGL(k_sdp, dim3(plan.grid, B), dim3(plan.block), plan.smem, s, g);
     RTS_HIP(hipGetLastError());
     if (strips <= sdp::kTailStrips) {
         hipLaunchKernelGGL(dtw_tail_kernel<SUBSEQ>, dim3(B), dim3(64 * strips), sdp::tail_lds_bytes(strips), s, g);
@@ -412,6 +381,33 @@ static int dtw_enqueue(DtwArgs g, int B, void *ws_dev, hipStream_t s) {
         RTS_HIP(hipGetLastError());
     }
     return RTS_OK;
+}
+
+// rts_dtw_paths (SUBSEQ = false: start_dev, end_dev and row_dev are absent) and rts_dtw_subseq_paths.
+template <bool SUBSEQ>
+static int dtw_paths_call(const void *a_dev, int a_dtype, long long a_stride, const int32_t *a_len_dev, const void *b_dev,
+                          int b_dtype, long long b_stride, const int32_t *b_len_dev, int F, int M_max, int N_max, int B,
+                          int32_t *path_dev, int32_t *path_len_dev, double *total_dev, int32_t *start_dev, int32_t *end_dev,
+                          double *row_dev, void *ws_dev, size_t ws_bytes, void *stream) {
+    if (!a_dev) return set_error(RTS_ERR_INVALID, "a_dev is NULL");
+    if (!b_dev) return set_error(RTS_ERR_INVALID, "b_dev is NULL");
+    if (!path_dev) return set_error(RTS_ERR_INVALID, "path_dev is NULL");
+    if (!path_len_dev) return set_error(RTS_ERR_INVALID, "path_len_dev is NULL");
+    if (!total_dev) return set_error(RTS_ERR_INVALID, "total_dev is NULL");
+    if (SUBSEQ && !start_dev) return set_error(RTS_ERR_INVALID, "start_dev is NULL");
+    if (SUBSEQ && !end_dev) return set_error(RTS_ERR_INVALID, "end_dev is NULL");
+    if (!ws_dev) return set_error(RTS_ERR_INVALID, "ws_dev is NULL");
+    if (int rc = dtw_check(a_dtype, b_dtype, F, M_max, N_max, B, path_dev, ws_dev, ws_bytes, "M_max", "N_max",
+                           SUBSEQ ? "rts_dtw_subseq_paths_workspace_bytes" : "rts_dtw_paths_workspace_bytes");
+        rc != RTS_OK)
+        return rc;
+    if (a_stride != 0 && a_stride < M_max)
+        return set_error(RTS_ERR_INVALID, "a_stride must be 0 (shared) or >= M_max (got %lld)", a_stride);
+    if (b_stride != 0 && b_stride < N_max)
+        return set_error(RTS_ERR_INVALID, "b_stride must be 0 (shared) or >= N_max (got %lld)", b_stride);
+    const DtwArgs g = dtw_args(a_dev, a_dtype, a_stride, a_len_dev, b_dev, b_dtype, b_stride, b_len_dev, M_max, N_max, nullptr,
+                               nullptr, nullptr, path_dev, path_len_dev, total_dev, start_dev, end_dev, row_dev);
+    return dtw_enqueue<false, SUBSEQ>(g, B, ws_dev, (hipStream_t)stream);
 }
 
 }  // namespace rts
@@ -429,29 +425,11 @@ int rts_dtw(const void *a_dev, int a_dtype, long long a_stride, const void *b_de
     using namespace rts;
     if (!a_dev || !b_dev || !cost_dev || !acc_dev || !path_dev || !path_len_dev || !ws_dev)
         return set_error(RTS_ERR_INVALID, "NULL device buffer");
-    if (int rc = dtw_check(a_dtype, b_dtype, F, M, N, B, path_dev, ws_dev, ws_bytes, "M", "N", rts_dtw_workspace_bytes,
-                           "rts_dtw_workspace_bytes");
+    if (int rc = dtw_check(a_dtype, b_dtype, F, M, N, B, path_dev, ws_dev, ws_bytes, "M", "N", "rts_dtw_workspace_bytes");
         rc != RTS_OK)
         return rc;
-    DtwArgs g;
-    g.a = a_dev;
-    g.b = b_dev;
-    g.cost = cost_dev;
-    g.acc = acc_dev;
-    g.back = back_dev;
-    g.path = path_dev;
-    g.path_len = path_len_dev;
-    g.a_stride = a_stride;
-    g.b_stride = b_stride;
-    g.M = M;
-    g.N = N;
-    g.a_f64 = a_dtype == RTS_F64;
-    g.b_f64 = b_dtype == RTS_F64;
-    g.a_len = nullptr;
-    g.b_len = nullptr;
-    g.total = nullptr;
-    g.start = g.end = nullptr;
-    g.row = nullptr;
+    const DtwArgs g = dtw_args(a_dev, a_dtype, a_stride, nullptr, b_dev, b_dtype, b_stride, nullptr, M, N, cost_dev, acc_dev,
+                               back_dev, path_dev, path_len_dev, nullptr, nullptr, nullptr, nullptr);
     return dtw_enqueue<true>(g, B, ws_dev, (hipStream_t)stream);
 }
 
@@ -464,41 +442,9 @@ int rts_dtw_paths(const void *a_dev, int a_dtype, long long a_stride, const int3
                   int b_dtype, long long b_stride, const int32_t *b_len_dev, int F, int M_max, int N_max, int B,
                   int32_t *path_dev, int32_t *path_len_dev, double *total_dev, void *ws_dev, size_t ws_bytes,
                   void *stream) {
-    using namespace rts;
-    if (!a_dev) return set_error(RTS_ERR_INVALID, "a_dev is NULL");
-    if (!b_dev) return set_error(RTS_ERR_INVALID, "b_dev is NULL");
-    if (!path_dev) return set_error(RTS_ERR_INVALID, "path_dev is NULL");
-    if (!path_len_dev) return set_error(RTS_ERR_INVALID, "path_len_dev is NULL");
-    if (!total_dev) return set_error(RTS_ERR_INVALID, "total_dev is NULL");
-    if (!ws_dev) return set_error(RTS_ERR_INVALID, "ws_dev is NULL");
-    if (int rc = dtw_check(a_dtype, b_dtype, F, M_max, N_max, B, path_dev, ws_dev, ws_bytes, "M_max",
-                           "N_max", rts_dtw_paths_workspace_bytes, "rts_dtw_paths_workspace_bytes");
-        rc != RTS_OK)
-        return rc;
-    if (a_stride != 0 && a_stride < M_max)
-        return set_error(RTS_ERR_INVALID, "a_stride must be 0 (shared) or >= M_max (got %lld)", a_stride);
-    if (b_stride != 0 && b_stride < N_max)
-        return set_error(RTS_ERR_INVALID, "b_stride must be 0 (shared) or >= N_max (got %lld)", b_stride);
-    DtwArgs g;
-    g.a = a_dev;
-    g.b = b_dev;
-    g.cost = nullptr;
-    g.acc = nullptr;
-    g.back = nullptr;
-    g.path = path_dev;
-    g.path_len = path_len_dev;
-    g.a_stride = a_stride;
-    g.b_stride = b_stride;
-    g.M = M_max;
-    g.N = N_max;
-    g.a_f64 = a_dtype == RTS_F64;
-    g.b_f64 = b_dtype == RTS_F64;
-    g.a_len = a_len_dev;
-    g.b_len = b_len_dev;
-    g.total = total_dev;
-    g.start = g.end = nullptr;
-    g.row = nullptr;
-    return dtw_enqueue<false>(g, B, ws_dev, (hipStream_t)stream);
+    return rts::dtw_paths_call<false>(a_dev, a_dtype, a_stride, a_len_dev, b_dev, b_dtype, b_stride, b_len_dev, F, M_max,
+                                      N_max, B, path_dev, path_len_dev, total_dev, nullptr, nullptr, nullptr, ws_dev,
+                                      ws_bytes, stream);
 }
 
 // The workspace is rts_dtw_paths': the last row lives in the boundary slot of a pair's last row group, which that call
@@ -511,44 +457,9 @@ int rts_dtw_subseq_paths(const void *a_dev, int a_dtype, long long a_stride, con
                          int b_dtype, long long b_stride, const int32_t *b_len_dev, int F, int M_max, int N_max, int B,
                          int32_t *path_dev, int32_t *path_len_dev, double *total_dev, int32_t *start_dev,
                          int32_t *end_dev, double *row_dev, void *ws_dev, size_t ws_bytes, void *stream) {
-    using namespace rts;
-    if (!a_dev) return set_error(RTS_ERR_INVALID, "a_dev is NULL");
-    if (!b_dev) return set_error(RTS_ERR_INVALID, "b_dev is NULL");
-    if (!path_dev) return set_error(RTS_ERR_INVALID, "path_dev is NULL");
-    if (!path_len_dev) return set_error(RTS_ERR_INVALID, "path_len_dev is NULL");
-    if (!total_dev) return set_error(RTS_ERR_INVALID, "total_dev is NULL");
-    if (!start_dev) return set_error(RTS_ERR_INVALID, "start_dev is NULL");
-    if (!end_dev) return set_error(RTS_ERR_INVALID, "end_dev is NULL");
-    if (!ws_dev) return set_error(RTS_ERR_INVALID, "ws_dev is NULL");
-    if (int rc = dtw_check(a_dtype, b_dtype, F, M_max, N_max, B, path_dev, ws_dev, ws_bytes, "M_max",
-                           "N_max", rts_dtw_subseq_paths_workspace_bytes, "rts_dtw_subseq_paths_workspace_bytes");
-        rc != RTS_OK)
-        return rc;
-    if (a_stride != 0 && a_stride < M_max)
-        return set_error(RTS_ERR_INVALID, "a_stride must be 0 (shared) or >= M_max (got %lld)", a_stride);
-    if (b_stride != 0 && b_stride < N_max)
-        return set_error(RTS_ERR_INVALID, "b_stride must be 0 (shared) or >= N_max (got %lld)", b_stride);
-    DtwArgs g;
-    g.a = a_dev;
-    g.b = b_dev;
-    g.cost = nullptr;
-    g.acc = nullptr;
-    g.back = nullptr;
-    g.path = path_dev;
-    g.path_len = path_len_dev;
-    g.a_stride = a_stride;
-    g.b_stride = b_stride;
-    g.M = M_max;
-    g.N = N_max;
-    g.a_f64 = a_dtype == RTS_F64;
-    g.b_f64 = b_dtype == RTS_F64;
-    g.a_len = a_len_dev;
-    g.b_len = b_len_dev;
-    g.total = total_dev;
-    g.start = start_dev;
-    g.end = end_dev;
-    g.row = row_dev;
-    return dtw_enqueue<false, true>(g, B, ws_dev, (hipStream_t)stream);
+    return rts::dtw_paths_call<true>(a_dev, a_dtype, a_stride, a_len_dev, b_dev, b_dtype, b_stride, b_len_dev, F, M_max,
+                                     N_max, B, path_dev, path_len_dev, total_dev, start_dev, end_dev, row_dev, ws_dev,
+                                     ws_bytes, stream);
 }
 
 }  // extern "C"

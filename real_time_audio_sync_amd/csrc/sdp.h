@@ -35,20 +35,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "common.h"
+#include "sdp_plan.h"  // strip / chunk counts, LDS sizes, the workspace's sections, the launch plan: no HIP in there
 
 namespace rts {
 namespace sdp {
 
 constexpr int kF = 12;
 constexpr int kChunk = 16;     // steps between two workgroup barriers
+static_assert(kChunk == kSteps, "sdp_plan.h sizes the step codes and the LDS for chunks of kChunk steps");
 constexpr int kLag = 5;        // chunks wave w+1 runs behind wave w: lane 63 finishes column 16m+15 at step 16m+78
-constexpr int kYRec = 14;      // doubles per prepared column record: 12 features, norm, pad (112 bytes)
-constexpr int kRing = 96;      // steps of the LDS cost ring: a helper runs one chunk ahead and a column spans 64 steps
-constexpr int kStageLd = 65;   // leading dimension of the [16][64] output tiles
-constexpr int kTiles = 3;      // output tiles per strip: written in chunk m, read in chunks m+1 and m+2
 constexpr int kMaxStrips = 2;  // strips per workgroup (LDS: 77 696 bytes per strip)
 constexpr unsigned long long kSentinel = 0x7FF4DEAD7FF4DEADull;  // signalling NaN: never an arithmetic result
 constexpr uint32_t kSentinel32 = 0x7FF4DEADu;                    // the same as a 32-bit fill pattern
@@ -59,49 +56,6 @@ constexpr int kLeft = 0;  // from (i, j-1)
 constexpr int kUp = 1;    // from (i-1, j)
 constexpr int kDiag = 2;  // from (i-1, j-1)
 
-__host__ __device__ inline int n_strips(int M) { return (M + 63) / 64; }
-__host__ __device__ inline int n_chunks(int N) { return (N + 63 + kChunk - 1) / kChunk; }  // per strip
-__host__ __device__ inline size_t lds_core_bytes(int NS) {
-    return sizeof(double) * (size_t)NS * ((size_t)kRing * 64 + (size_t)kTiles * kChunk * kStageLd + 2 * kChunk * kYRec + 64 + 2 * kChunk);
-}
-// + 16 bytes behind the strips' buffers: the workgroup's current ticket (for_each_rowgroup).  All of it is dynamic LDS --
-// the kernels declare no static LDS, so that the dynamic limit can be raised to the full 160 KB.
-__host__ __device__ inline size_t lds_bytes(int NS) { return lds_core_bytes(NS) + 16; }
-// Strips per workgroup / helper waves per strip / workgroups of one problem's pipeline.  One strip per workgroup
-// (3 helpers; the DP wave, which sets the pace, has a SIMD to itself; 77 KB of LDS, so two workgroups share a CU) when
-// every strip of every problem can have a resident workgroup of its own; otherwise two strips per workgroup (2 helpers
-// each), which halves the number of passes a workgroup makes over the columns.
-//
-// Residency.  A problem's row groups wait for one another inside the launch (run_rowgroup polls the bottom row of the
-// row group above).  That is deadlock-free WHATEVER the residency, because row groups are not bound to workgroups:
-// a workgroup takes the next row group of its problem from a ticket counter when it starts and whenever it finishes
-// one (for_each_rowgroup), so row group r - 1 was always taken by a workgroup that is already running -- by induction it
-// finishes, and r with it.  `resident1` / `resident2` (workgroups of the one-strip / two-strip kernel the device holds
-// at once: compute units x hipOccupancyMaxActiveBlocksPerMultiprocessor, queried by the caller for the instantiation
-// it launches) only size the grid: workgroups beyond residency would just queue behind the running ones.
-// RTS_SDP_CONFIG=1|2 forces the strips per workgroup, RTS_SDP_GRID=n the workgroups per problem (tuning and tests;
-// results do not depend on either).
-inline void pick_config(int strips, int B, int resident1, int resident2, int &NS, int &H, int &grid) {
-    if (resident1 < 1) resident1 = 1;
-    if (resident2 < 1) resident2 = 1;
-    NS = ((long long)strips * B <= resident1) ? 1 : 2;
-    if (const char *e = getenv("RTS_SDP_CONFIG")) NS = (atoi(e) == 1) ? 1 : 2;
-    if (NS > strips) NS = strips;
-    H = (NS == 1) ? 3 : 2;
-    const int n_rg = (strips + NS - 1) / NS;
-    const int resident = (NS == 1) ? resident1 : resident2;
-    grid = resident / B;
-    if (grid < 1) grid = 1;
-    if (grid > n_rg) grid = n_rg;
-    if (const char *e = getenv("RTS_SDP_GRID")) grid = atoi(e) > 0 ? atoi(e) : grid;
-}
-// Test knob: extra bytes of dynamic LDS per workgroup (lowers the residency the occupancy query reports and the
-// hardware grants, e.g. 80000 -> one workgroup per CU); 0 in production.
-inline size_t lds_pad() {
-    const char *e = getenv("RTS_SDP_LDS_PAD");
-    const long v = e ? atol(e) : 0;
-    return v > 0 && v < 80 * 1024 ? (size_t)v : 0;
-}
 // Workgroups of `kernel` (block threads, smem bytes of dynamic LDS) resident on the current device at once.
 template <typename K>
 inline int resident_blocks(K kernel, int block, size_t smem) {
@@ -113,7 +67,31 @@ inline int resident_blocks(K kernel, int block, size_t smem) {
     }
     return cus * per_cu;
 }
-__host__ __device__ inline size_t codes_words(int M, int N) { return (size_t)n_strips(M) * n_chunks(N) * 64; }
+constexpr int kResidencyDevices = 16;  // devices a residency cache covers; beyond them launch_plan asks every time
+// The launch plan of the strip-DP kernel pair k1 (one strip per workgroup) / k2 (two): raises both kernels' dynamic-LDS
+// limit (before the occupancy query: it answers for the limit in force), asks how many workgroups of each the current
+// device holds at once and plans for `strips` strips of each of B problems (pick_config); *kernel is the one to launch.
+// `cache` (may be NULL: ask every time; zero-initialised) keeps the answers for ONE kernel pair, per device: pad + 1,
+// resident1, resident2.  The environment knobs are read on every call either way.
+template <typename K>
+inline int launch_plan(K k1, K k2, int strips, int B, int (*cache)[3], Plan *plan, K *kernel) {
+    int dev = 0, fresh[3] = {0, 0, 0};
+    (void)hipGetDevice(&dev);
+    const size_t pad = lds_pad();
+    int *c = (cache && dev >= 0 && dev < kResidencyDevices) ? cache[dev] : fresh;
+    if (c[0] != (int)pad + 1) {
+        RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        RTS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        c[1] = resident_blocks(k1, block_threads(1), lds_bytes(1) + pad);
+        c[2] = resident_blocks(k2, block_threads(2), lds_bytes(2) + pad);
+        c[0] = (int)pad + 1;
+    }
+    if (c[1] < 1 && c[2] < 1)
+        return set_error(RTS_ERR_HIP, "the occupancy query reports no resident workgroup for the strip-DP kernel on this device");
+    *plan = pick_config(strips, B, c[1], c[2], pad);
+    *kernel = plan->H == 2 ? k2 : k1;
+    return RTS_OK;
+}
 
 struct Problem {
     const void *x;        // row features [M][12]
@@ -785,7 +763,6 @@ __device__ __forceinline__ void run_rowgroup(const Problem &pb, int rg, int n_rg
 // current 16-step chunk in a register and the step code is one v_readlane away, so no step waits for memory.  A
 // window of kBtChunks chunks of the strip is staged in LDS (`win`: [2][kBtChunks][64] dwords) and the next window to
 // the left is fetched into registers while the current one is being walked.
-constexpr int kBtChunks = 8;
 
 // Walks from (i, j) while the position stays inside strip (i >> 6) and has not reached (0, 0).  The k-th visited point
 // (the start included, the first point outside the strip excluded) is written to out[2 * (out_base + k)] when `out` is
@@ -939,7 +916,6 @@ __device__ __forceinline__ void path_hops(const uint32_t *codes, const int32_t *
 // forward order; *total (if not null, strip 0 only) receives the path length.
 // FREE ends: strip 0's walk stops at the first cell of row 0 it reaches and reports that cell's column as the path's
 // start (a segment of strip 0 then has at most 64 + cross[0] - start points: the parking places hold as before).
-__host__ __device__ inline size_t scratch_pairs(int M, int N) { return (size_t)64 * n_strips(M) + N; }
 template <bool FREE = false>
 __device__ __forceinline__ void path_segment(const uint32_t *codes, int M, int N, int s, const int32_t *cross,
                                              int32_t *lens, int pass, int32_t *path, int32_t *total, uint32_t *win,
@@ -978,7 +954,6 @@ __device__ __forceinline__ void path_segment(const uint32_t *codes, int M, int N
 // long ones keep a workgroup per strip (path_hops / path_segment from separate kernels).  `win`: the workgroup's
 // dynamic LDS, 2 * kBtChunks * 64 dwords per wave.
 constexpr int kTailStrips = 12;  // 48 KB of dynamic LDS: below the 64 KB a launch gets without an attribute, static LDS included
-__host__ __device__ inline size_t tail_lds_bytes(int S) { return sizeof(uint32_t) * 2 * kBtChunks * 64 * (size_t)S; }
 template <bool FREE = false>
 __device__ __forceinline__ void path_tail(const uint32_t *codes, const int32_t *entb, int M, int N, int32_t *cross,
                                           int32_t *lens, int32_t *path, int32_t *total, uint32_t *win, int32_t *scratch,

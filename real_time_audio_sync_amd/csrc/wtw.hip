@@ -789,10 +789,10 @@ struct rts_wtw {
     int B;
     int device;  // the HIP device the handle's buffers live on
     // decided at create (wtw_select): the strip DP (dp != NULL) or the window kernel (win != NULL)
-    rts_wtw_kernel dp;   // wtw_big_dp_kernel<STAGE, H> for this handle's keep_last_d and helper count
-    rts_wtw_kernel win;  // wtw_win_kernel<R, STAGE> for its DP waves and keep_last_d
-    int grid, block;     // of `dp` (grid x B workgroups) or `win` (B workgroups)
-    size_t smem;         // their dynamic LDS
+    rts_wtw_kernel dp;    // wtw_big_dp_kernel<STAGE, H> for this handle's keep_last_d and helper count
+    rts_wtw_kernel win;   // wtw_win_kernel<R, STAGE> for its DP waves and keep_last_d
+    rts::sdp::Plan plan;  // of `dp` (plan.grid x B workgroups; args.n_rg / n_strips_wg repeat it) or `win` (B workgroups)
+    void *sdp_ws;         // the strip DP's workspace, one allocation: what args.err .. args.ticket point into (sdp_plan.h)
 };
 
 namespace rts {
@@ -810,15 +810,11 @@ static int wtw_select(int W) {
     return (W <= 65 && !r2_e) ? 1 : 2;
 }
 
-// The instantiations, [STAGE][...]: all of them ask for more dynamic LDS than the default limit (wtw_raise_lds).
+// The instantiations, [STAGE][...]: all of them ask for more dynamic LDS than the default limit (raised at create).
 static const rts_wtw_kernel kWtwDpKernels[2][2] = {{wtw_big_dp_kernel<false, 3>, wtw_big_dp_kernel<false, 2>},  // [helpers == 2]
                                                    {wtw_big_dp_kernel<true, 3>, wtw_big_dp_kernel<true, 2>}};
 static const rts_wtw_kernel kWtwWinKernels[2][2] = {{wtw_win_kernel<1, false>, wtw_win_kernel<2, false>},  // [DP waves - 1]
                                                     {wtw_win_kernel<1, true>, wtw_win_kernel<2, true>}};
-
-static hipError_t wtw_raise_lds(rts_wtw_kernel k) {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
 
 // The constructor behind rts_wtw_create (first_host == NULL: one reference of M frames) and rts_wtw_create_refs (M =
 // M_max, per-stream tables of B entries, already checked).  Every argument is checked before the first HIP call.
@@ -846,39 +842,26 @@ static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win
     g.W = win_frames;
     g.hopf = hop_frames;
     g.path_cap = (g.live_stride / hop_frames + 2) * (win_frames + hop_frames + 2);
-    const int W = win_frames, S = sdp::n_strips(W);
+    const int W = win_frames;
     const int win_waves = wtw_select(W);
     const bool big = win_waves == 0, stage = keep_last_d != 0;
     hipError_t e = hipSuccess;
     if (big) {
-        // (the attribute before the occupancy query: it answers for the limit in force)
-        rts_wtw_kernel const k3 = kWtwDpKernels[stage][0], k2 = kWtwDpKernels[stage][1];
-        if ((e = wtw_raise_lds(k3)) == hipSuccess) e = wtw_raise_lds(k2);
-        if (e == hipSuccess) {
-            int nw, nh, grid;
-            // workgroups of the one-strip / two-strip DP kernel this device holds at once (sdp::pick_config, "Residency")
-            const size_t pad = sdp::lds_pad();
-            const int res1 = sdp::resident_blocks(k3, 256, sdp::lds_bytes(1) + pad);
-            const int res2 = sdp::resident_blocks(k2, 384, sdp::lds_bytes(2) + pad);
-            if (res1 < 1 && res2 < 1) {
-                free(h);
-                return set_error(RTS_ERR_HIP, "the occupancy query reports no resident workgroup for the strip-DP kernel on this device");
-            }
-            sdp::pick_config(S, B, res1, res2, nw, nh, grid);
-            h->dp = nh == 2 ? k2 : k3;
-            h->grid = grid;
-            h->block = 64 * nw * (1 + nh);
-            h->smem = sdp::lds_bytes(nw) + pad;
-            g.n_strips_wg = nw;
-            g.n_rg = (S + nw - 1) / nw;
-            g.fill_separate = ((size_t)(g.n_rg > 1 ? g.n_rg - 1 : 0) * W > (1u << 16)) ? 1 : 0;  // more than 0.5 MB of boundary words
+        // once per handle, so without sdp::launch_plan's residency cache: the occupancy queries are made at every create
+        const int rc = sdp::launch_plan(kWtwDpKernels[stage][0], kWtwDpKernels[stage][1], sdp::n_strips(W), B, nullptr, &h->plan, &h->dp);
+        if (rc != RTS_OK) {
+            free(h);
+            return rc;
         }
+        g.n_strips_wg = h->plan.NS;
+        g.n_rg = h->plan.n_rg;
+        g.fill_separate = ((size_t)(g.n_rg > 1 ? g.n_rg - 1 : 0) * W > (1u << 16)) ? 1 : 0;  // more than 0.5 MB of boundary words
     } else {
         h->win = kWtwWinKernels[stage][win_waves - 1];
-        h->grid = B;
-        h->block = win_waves == 1 ? 256 : 512;
-        h->smem = win_lds_bytes(W);
-        e = wtw_raise_lds(h->win);
+        h->plan.grid = B;
+        h->plan.block = win_waves == 1 ? 256 : 512;
+        h->plan.smem = win_lds_bytes(W);
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(h->win), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
     if (e != hipSuccess) {
         free(h);
@@ -897,19 +880,12 @@ static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win
         {true, (void **)&g.path, sizeof(int32_t) * 2 * (size_t)g.path_cap * nB},
         {stage, (void **)&g.dlast, sizeof(double) * nB * W * W},
         {big, (void **)&g.ws_sub, sizeof(int32_t) * 4 * (size_t)W * nB},
-        {big, (void **)&g.ws_scr, sizeof(int32_t) * 2 * sdp::scratch_pairs(W, W) * nB},
         {big, (void **)&g.ctl, sizeof(int32_t) * 8 * nB},
-        {big, (void **)&g.err, 16},
-        {big, (void **)&g.ticket, sizeof(int32_t) * nB},
-        {big, (void **)&g.codes, sizeof(uint32_t) * sdp::codes_words(W, W) * nB},
-        {big, (void **)&g.bnd, sizeof(unsigned long long) * (size_t)S * W * nB},
-        {big, (void **)&g.entb, sizeof(int32_t) * (size_t)S * W * nB},
-        {big, (void **)&g.cross, sizeof(int32_t) * (size_t)S * nB},
-        {big, (void **)&g.lens, sizeof(int32_t) * (size_t)S * nB},
-        {big, (void **)&g.yrec, sizeof(double) * sdp::kYRec * (size_t)W * nB},
+        {big, &h->sdp_ws, big ? sdp::workspace_bytes(W, W, B) : 0},  // every window is at most W x W
     };
     for (const auto &a : allocs)
         if (e == hipSuccess && a.wanted) e = hipMalloc(a.buf, a.bytes);
+    if (e == hipSuccess && big) sdp::workspace_carve(h->sdp_ws, W, W, B, &g, &g.ws_scr);
     if (e == hipSuccess && first_host) e = ref_table_upload(&h->refs, first_host, len_host, B);
     if (e != hipSuccess) {
         rts_wtw_destroy(h);
@@ -964,8 +940,7 @@ int rts_wtw_destroy(rts_wtw *h) {
     if (!h) return RTS_OK;
     rts::ref_table_free(&h->refs);
     const rts::WtwArgs &g = h->args;
-    void *const bufs[] = {g.live, g.appended, g.appended_next, g.state, g.path, g.dlast, g.ws_sub, g.ws_scr, g.ctl,
-                          g.err,  g.ticket,   g.codes,          g.bnd,   g.entb, g.cross, g.yrec,   g.lens};
+    void *const bufs[] = {g.live, g.appended, g.appended_next, g.state, g.path, g.dlast, g.ws_sub, g.ctl, h->sdp_ws};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     free(h);
@@ -1049,7 +1024,7 @@ int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, co
     }
     RTS_HIP(hipGetLastError());
     if (h->win) {
-        hipLaunchKernelGGL(h->win, dim3(h->grid), dim3(h->block), h->smem, s, g);
+        hipLaunchKernelGGL(h->win, dim3(h->plan.grid), dim3(h->plan.block), h->plan.smem, s, g);
     } else {
         // one (dp, ctl) round per window the new columns can complete: the first needs at least one column, every
         // further one dtw_hop / hop more (the live pointer advances by exactly that per window, wtw.py:118-128)
@@ -1057,7 +1032,7 @@ int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, co
         hipLaunchKernelGGL(wtw_big_ctl_kernel, dim3(B), dim3(1024), 0, s, g);
         if (g.fill_separate) hipLaunchKernelGGL(wtw_big_fill_kernel, dim3(128, B), dim3(256), 0, s, g);
         for (int r = 0; r < rounds; r++) {
-            hipLaunchKernelGGL(h->dp, dim3(h->grid, B), dim3(h->block), h->smem, s, g);
+            hipLaunchKernelGGL(h->dp, dim3(h->plan.grid, B), dim3(h->plan.block), h->plan.smem, s, g);
             if (S <= sdp::kTailStrips) {
                 hipLaunchKernelGGL(wtw_big_tail_ctl_kernel, dim3(B), dim3(64 * S), sdp::tail_lds_bytes(S), s, g);
             } else {

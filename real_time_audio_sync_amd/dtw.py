@@ -84,19 +84,54 @@ def _infer_pairs(a_dev, b_dev, a_len, b_len):
     return 1 if given is None else int(torch.as_tensor(given).numel())
 
 
-def _paths_call(a_dev, b_dev, a_len, b_len, B, path, plen, total):
+def _paths_call(a_dev, b_dev, a_len, b_len, B, path, plen, total, start=None, end=None, row=None):
+    """rts_dtw_paths, or with start / end (and optionally row) rts_dtw_subseq_paths: the same arguments but for those."""
     dev = a_dev.device
     M, N = a_dev.shape[-2], b_dev.shape[-2]
+    name = "rts_dtw_paths" if start is None else "rts_dtw_subseq_paths"
+    ends = () if start is None else (start.data_ptr(), end.data_ptr(), row.data_ptr() if row is not None else None)
     nbytes = ctypes.c_size_t(0)
-    nat.check(nat.lib.rts_dtw_paths_workspace_bytes(M, N, B, ctypes.byref(nbytes)))
+    nat.check(getattr(nat.lib, name + "_workspace_bytes")(M, N, B, ctypes.byref(nbytes)))
     ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
-    nat.check(nat.lib.rts_dtw_paths(a_dev.data_ptr(), _np_dtype_code(a_dev.dtype), 0 if a_dev.dim() == 2 else M,
-                                    a_len.data_ptr() if a_len is not None else None,
-                                    b_dev.data_ptr(), _np_dtype_code(b_dev.dtype), 0 if b_dev.dim() == 2 else N,
-                                    b_len.data_ptr() if b_len is not None else None,
-                                    12, M, N, B, path.data_ptr(), plen.data_ptr(), total.data_ptr(),
-                                    ws.data_ptr(), nbytes.value,
-                                    ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    nat.check(getattr(nat.lib, name)(
+        a_dev.data_ptr(), _np_dtype_code(a_dev.dtype), 0 if a_dev.dim() == 2 else M,
+        a_len.data_ptr() if a_len is not None else None,
+        b_dev.data_ptr(), _np_dtype_code(b_dev.dtype), 0 if b_dev.dim() == 2 else N,
+        b_len.data_ptr() if b_len is not None else None,
+        12, M, N, B, path.data_ptr(), plen.data_ptr(), total.data_ptr(), *ends, ws.data_ptr(), nbytes.value,
+        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+
+def _align(who, name, seqs_a, seqs_b, device, dtype, n_tables):
+    """The body of align_pairs (n_tables = 1: path_len) and align_excerpts (3: path_len, start, end): pads, uploads once,
+    makes one call and one read-back.  Returns (path [B][M+N][2], total [B] float64, the int32 tables), on the host."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("%s needs a ROCm GPU (no CPU fallback)" % who)
+    dev = torch.device(device)
+    a_one, b_one = isinstance(seqs_a, (np.ndarray, torch.Tensor)), isinstance(seqs_b, (np.ndarray, torch.Tensor))
+    B = 1 if (a_one and b_one) else (len(seqs_b) if a_one else len(seqs_a))
+    if B < 1:
+        return None
+    a, a_len = _pad_frames(seqs_a, B, dtype, who)
+    b, b_len = _pad_frames(seqs_b, B, dtype, who)
+    a, b = a.to(dev), b.to(dev)
+    M, N = a.shape[-2], b.shape[-2]
+    # one int32 buffer for all outputs, so that one copy brings them back: total (as float64), then the int32 tables
+    # (padded together to an even count: the path is written in 8-byte pairs), path
+    head = 2 * B + n_tables * B + (n_tables * B & 1)
+
+    def unpack(buf, view64):
+        return (buf[head:].reshape(B, M + N, 2), view64(buf[:2 * B]),
+                [buf[(2 + t) * B:(3 + t) * B] for t in range(n_tables)])
+
+    out = torch.zeros((head + B * (M + N) * 2,), dtype=torch.int32, device=dev)
+    path, total, tables = unpack(out, lambda x: x.view(torch.float64))
+    _paths_call(a, b, _lengths(a_len, B, dev, "a_len"), _lengths(b_len, B, dev, "b_len"), B, path, tables[0], total,
+                *tables[1:])
+    path, total, tables = unpack(out.cpu().numpy(), lambda x: x.view(np.float64))
+    if int(tables[0].min()) < 0:
+        raise nat.RtsyncError("%s: the device pipeline reported a fault" % name)
+    return path, total, tables
 
 
 def dtw_paths(a_dev, b_dev, a_len=None, b_len=None, check=False):
@@ -153,45 +188,11 @@ def align_pairs(seqs_a, seqs_b, device="cuda:0", dtype=torch.float64):
     side is shared by all pairs.  Pads, uploads once, makes one ``rts_dtw_paths`` call and one read-back.
     Returns [(path (P_k, 2) int64 ndarray, total float), ...], each path what ``DTW(seqs_a[k], seqs_b[k])[2]`` is and
     ready for ``evaluate.AlignmentError(ref_csv, live_csv, path)``; total is acc_cost[-1, -1]."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("align_pairs needs a ROCm GPU (no CPU fallback)")
-    dev = torch.device(device)
-    a_one, b_one = isinstance(seqs_a, (np.ndarray, torch.Tensor)), isinstance(seqs_b, (np.ndarray, torch.Tensor))
-    B = 1 if (a_one and b_one) else (len(seqs_b) if a_one else len(seqs_a))
-    if B < 1:
+    got = _align("align_pairs", "rts_dtw_paths", seqs_a, seqs_b, device, dtype, 1)
+    if got is None:
         return []
-    a, a_len = _pad_frames(seqs_a, B, dtype)
-    b, b_len = _pad_frames(seqs_b, B, dtype)
-    a, b = a.to(dev), b.to(dev)
-    M, N = a.shape[-2], b.shape[-2]
-    # one int32 buffer for all three outputs, so that one copy brings them back: total (as float64), path_len (padded
-    # to an even count: the path is written in 8-byte pairs), path
-    Bp = B + (B & 1)
-    out = torch.zeros((2 * B + Bp + B * (M + N) * 2,), dtype=torch.int32, device=dev)
-    total, plen, path = out[:2 * B].view(torch.float64), out[2 * B:2 * B + B], out[2 * B + Bp:].view(B, M + N, 2)
-    _paths_call(a, b, _lengths(a_len, B, dev, "a_len"), _lengths(b_len, B, dev, "b_len"), B, path, plen, total)
-    host = out.cpu().numpy()
-    total_h, plen_h = host[:2 * B].view(np.float64), host[2 * B:2 * B + B]
-    path_h = host[2 * B + Bp:].reshape(B, M + N, 2)
-    if int(plen_h.min()) < 0:
-        raise nat.RtsyncError("rts_dtw_paths: the device pipeline reported a fault")
-    return [(path_h[k, :int(plen_h[k])].astype(np.int64), float(total_h[k])) for k in range(B)]
-
-
-def _subseq_call(a_dev, b_dev, a_len, b_len, B, path, plen, total, start, end, row):
-    dev = a_dev.device
-    M, N = a_dev.shape[-2], b_dev.shape[-2]
-    nbytes = ctypes.c_size_t(0)
-    nat.check(nat.lib.rts_dtw_subseq_paths_workspace_bytes(M, N, B, ctypes.byref(nbytes)))
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
-    nat.check(nat.lib.rts_dtw_subseq_paths(
-        a_dev.data_ptr(), _np_dtype_code(a_dev.dtype), 0 if a_dev.dim() == 2 else M,
-        a_len.data_ptr() if a_len is not None else None,
-        b_dev.data_ptr(), _np_dtype_code(b_dev.dtype), 0 if b_dev.dim() == 2 else N,
-        b_len.data_ptr() if b_len is not None else None,
-        12, M, N, B, path.data_ptr(), plen.data_ptr(), total.data_ptr(), start.data_ptr(), end.data_ptr(),
-        row.data_ptr() if row is not None else None, ws.data_ptr(), nbytes.value,
-        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    path, total, (plen,) = got
+    return [(path[k, :int(plen[k])].astype(np.int64), float(total[k])) for k in range(len(plen))]
 
 
 def dtw_subseq_paths(a_dev, b_dev, a_len=None, b_len=None, want_row=False, check=False):
@@ -222,7 +223,7 @@ def dtw_subseq_paths(a_dev, b_dev, a_len=None, b_len=None, want_row=False, check
     start = torch.empty((B,), dtype=torch.int32, device=dev)
     end = torch.empty((B,), dtype=torch.int32, device=dev)
     row = torch.empty((B, N), dtype=torch.float64, device=dev) if want_row else None
-    _subseq_call(a_dev, b_dev, a_len, b_len, B, path, plen, total, start, end, row)
+    _paths_call(a_dev, b_dev, a_len, b_len, B, path, plen, total, start, end, row)
     if check and int(plen.min().item()) < 0:
         raise nat.RtsyncError("rts_dtw_subseq_paths: the device pipeline reported a fault (path_len = -1)")
     return (path, plen, total, start, end, row) if want_row else (path, plen, total, start, end)
@@ -238,31 +239,9 @@ def align_excerpts(excerpts, pieces, device="cuda:0", dtype=torch.float64):
     frames, path[:, 1] the piece's, from (0, start) to (M_k-1, end) -- ready for
     ``evaluate.AlignmentError(excerpt_csv, piece_csv, path)``.  A pair without frames on either side gives an empty
     path, total inf and start = end = -1."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("align_excerpts needs a ROCm GPU (no CPU fallback)")
-    dev = torch.device(device)
-    a_one, b_one = isinstance(excerpts, (np.ndarray, torch.Tensor)), isinstance(pieces, (np.ndarray, torch.Tensor))
-    B = 1 if (a_one and b_one) else (len(pieces) if a_one else len(excerpts))
-    if B < 1:
+    got = _align("align_excerpts", "rts_dtw_subseq_paths", excerpts, pieces, device, dtype, 3)
+    if got is None:
         return []
-    a, a_len = _pad_frames(excerpts, B, dtype, "align_excerpts")
-    b, b_len = _pad_frames(pieces, B, dtype, "align_excerpts")
-    a, b = a.to(dev), b.to(dev)
-    M, N = a.shape[-2], b.shape[-2]
-    # one int32 buffer for all outputs, so that one copy brings them back: total (as float64), then path_len, start and
-    # end (padded together to an even count: the path is written in 8-byte pairs), path
-    Bp = 3 * B + (B & 1)
-    out = torch.zeros((2 * B + Bp + B * (M + N) * 2,), dtype=torch.int32, device=dev)
-    total = out[:2 * B].view(torch.float64)
-    plen, start, end = out[2 * B:3 * B], out[3 * B:4 * B], out[4 * B:5 * B]
-    path = out[2 * B + Bp:].view(B, M + N, 2)
-    _subseq_call(a, b, _lengths(a_len, B, dev, "a_len"), _lengths(b_len, B, dev, "b_len"), B, path, plen, total, start,
-                 end, None)
-    host = out.cpu().numpy()
-    total_h = host[:2 * B].view(np.float64)
-    plen_h, start_h, end_h = host[2 * B:3 * B], host[3 * B:4 * B], host[4 * B:5 * B]
-    path_h = host[2 * B + Bp:].reshape(B, M + N, 2)
-    if int(plen_h.min()) < 0:
-        raise nat.RtsyncError("rts_dtw_subseq_paths: the device pipeline reported a fault")
-    return [(path_h[k, :int(plen_h[k])].astype(np.int64), float(total_h[k]), int(start_h[k]), int(end_h[k]))
-            for k in range(B)]
+    path, total, (plen, start, end) = got
+    return [(path[k, :int(plen[k])].astype(np.int64), float(total[k]), int(start[k]), int(end[k]))
+            for k in range(len(plen))]

@@ -16,9 +16,12 @@ by tests/guarded.py between two guards.  Three properties per entry point, next 
                     more than their element type's alignment (path_dev: 8 bytes, stft_out_dev: 16) are refused below
                     it, and the refusals are tested here instead of the stores.
 
-What a green run does NOT show: the workspace is one allocation that dtw_enqueue carves into eight sections, and a
-section that spills into the next one hits no guard.  Such an overrun is seen only through (b) and the reference
-comparison -- as a result that is wrong or that changes with the fill -- never as a guard that tripped."""
+What a green run does NOT show: the workspace is one allocation of eight sections behind a header, and a section that
+spills into the next one hits no guard.  That the carve agrees with the size function is checked elsewhere: both walk
+one table (csrc/sdp_plan.h), and tests/test_sdp_plan_cpu.py holds every section's offset and length, and the total,
+against a model of the arrays' shapes.  A kernel that writes past the end of a section it was handed correctly is
+still seen only through (b) and the reference comparison -- as a result that is wrong or that changes with the fill --
+never as a guard that tripped."""
 import ctypes
 import os
 import re
@@ -32,6 +35,7 @@ torch = pytest.importorskip("torch")
 from dtw_subseq_model import subseq  # noqa: E402
 from guarded import FILLS, guarded, holds_fill, same_bytes  # noqa: E402
 from resample_model import out_len, resample_model  # noqa: E402
+from scoped_env import Env  # noqa: E402
 from test_chroma_gpu import CHROMA_ATOL, STFT_RTOL  # noqa: E402
 from test_reacquire_cpu import path_cost_ref  # noqa: E402
 
@@ -68,22 +72,6 @@ def _stream():
 def _nat():
     from real_time_audio_sync_amd import _native
     return _native
-
-
-class _Env(object):
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update({k: str(v) for k, v in self.kw.items()})
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 class _Bufs(object):
@@ -334,7 +322,7 @@ def test_paths_confined_and_independent_of_stale_contents(M, N, B, tdt, subseq_f
     first = None
     for fill, env, want_row in runs:
         tag = "fill 0x%02X %s" % (fill, env or "")
-        with _Env(**env):
+        with Env(**env):
             out = _run_paths(M, N, B, tdt, fill, subseq_form, want_row=want_row)
         _check_paths(out, M, N, B, tdt, fill, subseq_form, tag)
         first = first or out

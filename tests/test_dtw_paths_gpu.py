@@ -5,10 +5,11 @@ pairs of different lengths in one call.  Bar: every pair's path and acc_cost[-1]
 The padding behind a pair's own frames is NaN in these tests: a kernel that read a frame beyond a pair's length could
 not produce the oracle's result."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
+
+from scoped_env import Env
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -20,22 +21,6 @@ FILL = -7   # what the path buffer holds before a call
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-class _Env(object):
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update({k: str(v) for k, v in self.kw.items()})
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _widen(x, tdt):
@@ -148,7 +133,7 @@ def test_ragged_batch_forced_configurations(ragged13, config, grid):
     """Row groups are per pair: fewer workgroups than the longest pair's row groups, one workgroup for all of them, and
     one per strip of the longest pair (most of which find no row group in a short pair).  Same bits as the default."""
     base = _run_ragged(ragged13)
-    with _Env(RTS_SDP_CONFIG=config, RTS_SDP_GRID=grid):
+    with Env(RTS_SDP_CONFIG=config, RTS_SDP_GRID=grid):
         path, plen, total = _run_ragged(ragged13)
     assert (plen > 0).all(), plen
     assert np.array_equal(plen, base[1]) and np.array_equal(path, base[0])

@@ -6,10 +6,11 @@ and row cells behind a pair's own N untouched; the same doubles as rts_locate an
 The padding behind a pair's own frames is NaN in these tests: a kernel that read a frame beyond a pair's length could
 not produce the model's result.  Every model result is computed once (module fixtures)."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
+
+from scoped_env import Env
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -25,22 +26,6 @@ DEV = "cuda:0"
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-class _Env(object):
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update({k: str(v) for k, v in self.kw.items()})
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _padded(seqs, n_max, tdt):
@@ -217,7 +202,7 @@ def test_ragged_batch_forced_configurations(ragged13, config, grid):
     """Fewer workgroups than the longest pair's row groups, one workgroup for all of them, and one per strip of the
     longest pair: the last row is parked in the pair's own last row group's slot whatever the configuration."""
     base = _run(ragged13)
-    with _Env(RTS_SDP_CONFIG=config, RTS_SDP_GRID=grid):
+    with Env(RTS_SDP_CONFIG=config, RTS_SDP_GRID=grid):
         out = _run(ragged13)
     assert (out["plen"] > 0).all(), out["plen"]
     _same_bits(out, base)

@@ -2,10 +2,11 @@
 CPU oracle's dense matrices).  Indices, end, total and acc are compared with ==: the device walks the very values the
 oracle computes, there is no tolerance to choose."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
+
+from scoped_env import Env
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -39,22 +40,6 @@ def _stream():
 
 def _err():
     return _nat().lib.rts_last_error().decode()
-
-
-class _Env(object):
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update({k: str(v) for k, v in self.kw.items()})
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 class Raw(object):
@@ -241,7 +226,7 @@ def test_wide_widths(c):
 
 def test_plain_kernel_selection_does_not_disable_it():
     ref, live = _pair(17, 77, False)
-    with _Env(RTS_OTW_SPEC=0):
+    with Env(RTS_OTW_SPEC=0):
         r = Raw(ref, 17, "otw", False)
     try:
         r.run([live])

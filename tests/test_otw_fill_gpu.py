@@ -11,13 +11,13 @@ filled its band, and the tests assert it for every stream: a case that silently 
 
 Shapes are the smallest at which the kernel can go wrong: c = 2 (three stages), 5, 63 / 64 / 65 (one wave, its last lane,
 the lane-63 -> lane-0 hand-over), 129 (two hand-overs) and 500 once (the largest band, all eight waves)."""
-import os
 
 import numpy as np
 import pytest
 
 import silence_inputs as si
 from guarded import guarded, same_bytes
+from scoped_env import Env
 from test_otw_hitloop_gpu import _check, mods  # noqa: F401  (mods: the module fixture)
 
 pytestmark = pytest.mark.gpu
@@ -29,27 +29,11 @@ VARIANTS = ["otw", "livenote", "livenote_v2"]
 MODES = ["insert", "set_live"]
 
 
-class _Env(object):
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update({k: str(v) for k, v in self.kw.items()})
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def _pair(make):
     """The same handle twice: with the fill kernel (RTS_OTW_FILL is read at create) and with the step loop alone."""
-    with _Env(RTS_OTW_FILL=1):
+    with Env(RTS_OTW_FILL=1):
         on = make()
-    with _Env(RTS_OTW_FILL=0):
+    with Env(RTS_OTW_FILL=0):
         off = make()
     return on, off
 
@@ -76,7 +60,7 @@ def _segmented(make, lv, lens, took, c):
     """A step-loop handle (RTS_OTW_FILL=0) whose launches begin where the fill handle's kernels do: the packed frames
     ``lv`` through rts_otw_push, c frames first for the streams that took the fill (everything for the others), then the
     rest.  Insert mode only (push is the insert loop)."""
-    with _Env(RTS_OTW_FILL=0):
+    with Env(RTS_OTW_FILL=0):
         seg = make()
     first = [c if t else n for t, n in zip(took, lens)]
     for lo, hi in (([0] * len(lens), first), (first, lens)):
@@ -182,7 +166,7 @@ def test_the_hand_over_state_is_the_oracles_after_c_frames(mods):
     c = 65
     ref, lives = synth.synth_batch(2 * c + 40, 1, seed=6601)
     live = lives[0][:, :c].copy()
-    with _Env(RTS_OTW_FILL=1):
+    with Env(RTS_OTW_FILL=1):
         eng = ob.BatchedOTW(ref, c, 3, batch=1, dtype=torch.float64)
     lv, ln = eng.pack([live])
     eng.run(lv, ln)

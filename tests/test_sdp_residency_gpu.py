@@ -5,10 +5,11 @@ The row groups of one DTW / WTW problem wait for one another inside a single lau
 no particular residency.  These tests force the situations the round-2 review named: fewer resident workgroups than the
 grid (LDS padding: one workgroup per CU; forced grid larger than that), and another kernel occupying the CUs on a second
 stream while the pipeline runs.  Results must be bit-exact and no fault may be reported."""
-import os
 
 import numpy as np
 import pytest
+
+from scoped_env import Env
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -18,22 +19,6 @@ torch = pytest.importorskip("torch")
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-class _Env(object):
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update({k: str(v) for k, v in self.kw.items()})
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _dtw_pairs_vs_oracle(a_list, b, tdt=torch.float32):
@@ -59,12 +44,12 @@ def test_more_workgroups_than_the_device_holds():
     from real_time_audio_sync_amd import synth
     b = synth.synth_ref(260, seed=31)
     a_list = [synth.synth_ref(5050, seed=40 + k) for k in range(6)]
-    with _Env(RTS_SDP_LDS_PAD=80000, RTS_SDP_CONFIG=1, RTS_SDP_GRID=79):
+    with Env(RTS_SDP_LDS_PAD=80000, RTS_SDP_CONFIG=1, RTS_SDP_GRID=79):
         _dtw_pairs_vs_oracle(a_list, b)
     # and the opposite corner: far fewer workgroups than row groups (each takes many tickets in turn)
-    with _Env(RTS_SDP_CONFIG=1, RTS_SDP_GRID=3):
+    with Env(RTS_SDP_CONFIG=1, RTS_SDP_GRID=3):
         _dtw_pairs_vs_oracle(a_list[:2], b)
-    with _Env(RTS_SDP_CONFIG=2, RTS_SDP_GRID=1):
+    with Env(RTS_SDP_CONFIG=2, RTS_SDP_GRID=1):
         _dtw_pairs_vs_oracle(a_list[:1], b)
 
 
@@ -77,7 +62,7 @@ def test_wtw_windows_with_padded_lds_and_forced_grid():
     dev = torch.device("cuda:0")
     B, W, hopf = 30, 700, 350
     ref, lives = synth.synth_batch(1800, B, seed=55)
-    with _Env(RTS_SDP_LDS_PAD=80000, RTS_SDP_CONFIG=1, RTS_SDP_GRID=11):
+    with Env(RTS_SDP_LDS_PAD=80000, RTS_SDP_CONFIG=1, RTS_SDP_GRID=11):
         eng = BatchedWTW(torch.from_numpy(np.ascontiguousarray(ref.T)).to(dev), W, hopf, B)
         tmax = max(l.shape[1] for l in lives)
         cols = np.zeros((B, tmax, 12))
