@@ -688,6 +688,56 @@ int rts_live_poll(rts_live *h, int32_t *status /* [B] */, int32_t *positions /* 
 int rts_live_watch(rts_live *h, int K);
 int rts_live_confidence(rts_live *h, double *mean_cost /* [B] */, int32_t *n_points /* [B] */, int *feeds_done);
 
+/* The level gate: keeps the columns of a microphone nobody plays into away from its tracker, per stream, without a
+ * read-back.  The reference never tracks silence: an operator presses `r` when the music starts (livenote_live.py:145-150,
+ * :162) and watches a microphone meter (livenote_live.py:170-177, wtw_live.py:192-197).  On a silent column every
+ * reference frame costs the same, so the OTW family ties and walks the diagonal while nothing is played, and WTW's cosine
+ * cost is NaN; a session opened before the downbeat, or running across the gap between two movements, loses its place.
+ *
+ * Level of a column: column m of stream b in a feed is framed from the L = fft_len pending samples x[0..L) at offset
+ * m * hop of the stream's buffer (after PCM scaling and after the resampler: on a resampling handle these are plan-rate
+ * samples; the same offset in the hop > fft_len geometry).  Its level is (sum_i (double)x[i] * (double)x[i]) / L, the mean
+ * square, un-windowed; 10 log10(level) is the reference meter's 20 log10(rms).  Every product is exact in float64 and the
+ * order of the sum depends on the index i alone, so the same frame has the same level however the audio was cut into feeds.
+ * Decision: every stream carries q, the length of its current run of quiet columns, saturating at hold + 1; a fresh stream
+ * is closed (q = hold + 1), waiting for the first sound.  For every new chroma column in order: loud = level >= min_level
+ * (a NaN level is quiet); loud: q = 0 and the column passes; otherwise q = min(q + 1, hold + 1) and the column passes iff
+ * q <= hold.  So with hold = 0 a column passes iff it is loud, a rest of up to `hold` columns inside the music is kept
+ * whole, a longer rest passes its first `hold` columns and then pauses the stream until the next loud column, and a stream
+ * that has never heard a loud column passes nothing.
+ * What the tracker gets.  RTS_FEATURE_CHROMA: the passing columns in order, packed to the front of a second buffer with
+ * the feed's row stride, their counts as the push's n_new_dev.  RTS_FEATURE_CHROMA_DIFF: the difference step runs unchanged
+ * on all chroma columns (carry and first-column skip as without the gate); the difference column of chroma columns
+ * (m - 1, m) is handed on iff both passed, "the previous column passed" being one more device word per stream for a
+ * feed's first column, zero whenever the stream has no carry.  Samples dropped per column, rts_live_pending and the
+ * staging ring are as without the gate.  A feed in which every column of every stream is dropped still calls the push,
+ * with counts of zero, which leaves the trackers alone.
+ * Ordinals.  seen[b] counts the chroma columns stream b has completed since create, reset or its last restart, passed[b]
+ * the columns handed to its tracker in that time.  The handle keeps the ordinal (the value of `seen` before the column,
+ * for a difference column that of the later chroma column) of every column handed on, as long as the bound tracker's
+ * history (2 N_max for OTW, 2 M_max for WTW): the counts run on past it, nothing is stored past it.  Live frame t of a
+ * tracker's path thus ended at (ordinal[t] * hop + fft_len) / fs seconds of the stream's run.
+ *
+ * rts_live_gate: min_level > 0 and finite switches the gate on (buffers are made on first use), min_level == 0 off;
+ * 0 <= hold <= 65535.  Allowed only before the first feed after create or after rts_live_reset: later it returns
+ * RTS_ERR_INVALID, the message says so, and nothing changes.  With the gate on every feed enqueues two more launches
+ * between the chroma (difference) step and the push (one in a feed without a column); with it off, or never called, a
+ * feed enqueues exactly what it enqueues without this function.  Either tracker, either feature kind, resampling
+ * handles too.  rts_live_reset keeps the setting and closes every stream; rts_live_restart closes the selected
+ * streams: q, the previous-passed word, seen and passed start again, their ordinals are empty, their words republished.
+ *   RTS_ERR_INVALID: NULL handle, negative / NaN / infinite min_level, hold out of range, after a feed, a failed handle.
+ * rts_live_levels: the non-blocking look at a third host-mapped block, like rts_live_confidence and with the same
+ * guarantee (when *feeds_done >= k, every word read reflects a feed >= k): level[b] of the stream's most recent chroma
+ * column (NaN before its first), open[b] whether that column passed, seen[b], passed[b].  Any pointer may be NULL.
+ * RTS_ERR_INVALID before the first rts_live_gate(min_level > 0).
+ * rts_live_gate_columns: synchronises `stream`; *n = passed[b]; copies min(*n, cap, history length) ordinals of stream b
+ * to ordinals_host (may be NULL).  RTS_ERR_INVALID: NULL handle or n, b out of range, before the first
+ * rts_live_gate(min_level > 0). */
+int rts_live_gate(rts_live *h, double min_level, int hold);
+int rts_live_levels(rts_live *h, double *level /* [B] */, int32_t *open /* [B] */, int32_t *seen /* [B] */,
+                    int32_t *passed /* [B] */, int *feeds_done);
+int rts_live_gate_columns(rts_live *h, int b, int32_t *ordinals_host, int cap, int *n, void *stream);
+
 /* Device views of the columns the most recently submitted feed handed to the tracker, and of their per-stream counts
  * (zero-copy consumers, tests): *cols_dev is float64, stream b's column i at cols_dev[(b * *cols_stride + i) * 12],
  * i < (*n_cols_dev)[b].  *cols_stride, the rows per stream, is the largest number of chroma columns any stream completed
@@ -695,8 +745,10 @@ int rts_live_confidence(rts_live *h, double *mean_cost /* [B] */, int32_t *n_poi
  * and the tracker push share, so it changes from feed to feed and is returned here from the host mirror; it never
  * exceeds *cols_cap = (max_pending - fft_len) / hop + 1, the rows per stream the buffer has room for.  Valid for both
  * feature kinds: RTS_FEATURE_CHROMA views the chroma columns and the counts rts_chroma_frames_batch was given,
- * RTS_FEATURE_CHROMA_DIFF the difference columns and their counts.  The pointers stay the same for the handle's
- * life; the contents belong to the last feed in stream order, the caller synchronises.  Any pointer may be NULL. */
+ * RTS_FEATURE_CHROMA_DIFF the difference columns and their counts; with the gate on (rts_live_gate) either kind views
+ * the gated buffer and its counts, at the same row stride -- the columns the feed handed to the tracker.  The pointers
+ * stay the same for the handle's life (two sets: gate off, gate on); the contents belong to the last feed in stream
+ * order, the caller synchronises.  Any pointer may be NULL. */
 int rts_live_columns_view(rts_live *h, double **cols_dev, int *cols_cap, int *cols_stride, int32_t **n_cols_dev);
 /* Samples pending per stream after everything submitted so far (the host-side mirror; exact). */
 int rts_live_pending(rts_live *h, long long *pending_host /* [B] */);

@@ -139,6 +139,9 @@ _decl("rts_live_poll", _i32, [_vp, _vp, _vp, _pi32, _pi32])
 _decl("rts_live_pending", _i32, [_vp, _vp])
 _decl("rts_live_watch", _i32, [_vp, _i32])
 _decl("rts_live_confidence", _i32, [_vp, _vp, _vp, _pi32])
+_decl("rts_live_gate", _i32, [_vp, ctypes.c_double, _i32])
+_decl("rts_live_levels", _i32, [_vp, _vp, _vp, _vp, _vp, _pi32])
+_decl("rts_live_gate_columns", _i32, [_vp, _i32, _vp, _i32, _pi32, _vp])
 
 
 def check(rc):

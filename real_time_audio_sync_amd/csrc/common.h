@@ -16,6 +16,9 @@ inline bool dtype_ok(int dtype) { return dtype == RTS_F32 || dtype == RTS_F64; }
 // Streams of a tracker handle (rts_live_create checks that it binds one of its own size).  Library-internal.
 __attribute__((visibility("hidden"))) int otw_batch(const rts_otw *h);
 __attribute__((visibility("hidden"))) int wtw_batch(const rts_wtw *h);
+// Frames per stream of a tracker's own history, 2 N_max / 2 M_max (rts_live_gate keeps one ordinal per history frame).
+__attribute__((visibility("hidden"))) int otw_history(const rts_otw *h);
+__attribute__((visibility("hidden"))) int wtw_history(const rts_wtw *h);
 
 // A handle (`noun`: "handle", or "plan" for rts_chroma) belongs to the device that was current when it was created;
 // driving it with another device current would launch against foreign buffers.

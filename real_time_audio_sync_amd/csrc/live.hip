@@ -24,6 +24,10 @@
 //   live_diff_kernel      RTS_FEATURE_CHROMA_DIFF only: the columns become max(chroma[m+1] - chroma[m], 0)
 //                         (np.clip(np.diff(chroma), 0, inf), chroma.py:85-90) in a second buffer; the last chroma
 //                         column of every stream is carried on the device from feed to feed
+//   live_level_kernel, live_gate_kernel   only after rts_live_gate(min_level > 0) (csrc/live_gate.h): the mean square of
+//                         every column's frame, then per stream the decision which columns its tracker gets, those
+//                         packed into a second buffer with their counts, and the meter words of rts_live_levels into a
+//                         third host-mapped block; the push below then takes that buffer and those counts
 //   rts_otw_push | rts_wtw_push   the columns into the alignment state (insert semantics, column by column)
 //   rts_otw_path_cost     only after rts_live_watch(K > 0): the tracker's mean cell cost over its last K path points into a
 //                         second host-mapped block -- rts_live_confidence reads it like rts_live_poll reads the status words
@@ -166,10 +170,17 @@ __global__ void __launch_bounds__(256) live_diff_kernel(LiveArgs g) {
     }
 }
 
+}  // namespace rts
+
+#include "live_gate.h"
+
+namespace rts {
+
 // rts_live_restart, after the bound tracker's own restart: the selected streams' pending samples are dropped and their
 // status / position words republished from the (now fresh) tracker state.  The feed number is left alone: the words
-// still reflect every feed submitted before the restart.  In diff mode the carried chroma column goes with the samples.
-__global__ void live_restart_kernel(RestartSel sel, LiveArgs g) {
+// still reflect every feed submitted before the restart.  In diff mode the carried chroma column goes with the samples,
+// and once rts_live_gate has made its buffers (t.q != NULL) the stream's gate closes.
+__global__ void live_restart_kernel(RestartSel sel, LiveArgs g, GateArgs t) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= sel.n) return;
     const int b = sel.idx[i];
@@ -184,6 +195,7 @@ __global__ void live_restart_kernel(RestartSel sel, LiveArgs g) {
         g.conf_n[b] = 0;
         g.conf_mean[b] = __longlong_as_double(0x7ff8000000000000LL);
     }
+    if (t.q) live_gate_restart(t, b);
     __threadfence_system();
 }
 
@@ -226,6 +238,11 @@ struct rts_live {
     float *rs_tail;  // [2][B][rs_T]: the copy feed k reads and the one it writes, alternating (rs_cur)
     int rs_cur;
     long long *rs_tot;
+    // rts_live_gate: on / off, what its two launches take (buffers from the first rts_live_gate(min_level > 0)), and the
+    // third host-mapped block, double level[B] then int32 {open, seen, passed}[B]
+    int gate_on;
+    rts::GateArgs gate;
+    unsigned char *gate_host;
 };
 
 namespace rts {
@@ -256,6 +273,24 @@ static int live_watch_launch(rts_live *h, void *stream) {
     return rts_otw_path_cost(h->otw, h->watch_k, h->args.conf_mean, h->args.conf_n, nullptr, stream);
 }
 
+static void live_gate_clear(rts_live *h) {
+    double *level = reinterpret_cast<double *>(h->gate_host);
+    for (int b = 0; b < h->geo.B; b++) level[b] = __builtin_nan("");
+    memset(level + h->geo.B, 0, sizeof(int32_t) * kGateWords * (size_t)h->geo.B);
+}
+
+// With the gate on, two more launches per feed between the chroma (and difference) step and the tracker push, in a feed
+// without a column the second alone (it writes the feed's zero counts).  `g` is the feed's copy of the arguments.
+static int live_gate_launch(rts_live *h, const LiveArgs &g, int n_max, hipStream_t s) {
+    if (n_max > 0) {
+        hipLaunchKernelGGL(live_level_kernel, dim3(n_max, h->geo.B), dim3(256), 0, s, g, h->gate);
+        RTS_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(live_gate_kernel, dim3(h->geo.B), dim3(256), 0, s, g, h->gate);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+
 static int live_refuse(const rts_live *h, LiveRefusal why, const FeedPlan &p, const int32_t *counts) {
     const int b = p.stream;
     if (why == kLiveNegativeCount) return set_error(RTS_ERR_INVALID, "stream %d: negative sample count", b);
@@ -274,7 +309,8 @@ static int live_refuse(const rts_live *h, LiveRefusal why, const FeedPlan &p, co
 // chroma column too: it writes the feed's n_cols); rts_chroma_frames_batch and rts_otw_push return at once when their
 // n_max is 0, rts_wtw_push after its entry check, which wtw.py:76-77 runs on every insert(), new column or not; in diff
 // mode the tracker is pushed only when some stream hands it a column (n_max_diff > 0; the rows still lie n_max apart);
-// the watch launch follows rts_live_watch.  The compaction and the publication end every feed.
+// the watch launch follows rts_live_watch, the two gate launches rts_live_gate: with the gate on the push takes the gated
+// buffer and its counts, and nothing else moves.  The compaction and the publication end every feed.
 static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, void *stream) {
     const int B = h->geo.B;
     hipStream_t s = (hipStream_t)stream;
@@ -311,6 +347,11 @@ static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, 
     }
     const double *cols = h->geo.diff ? h->args.dcols : h->args.cols;
     const int32_t *n_new = h->geo.diff ? h->args.n_cols : h->args.n_frames;
+    if (h->gate_on) {
+        if (int rc = live_gate_launch(h, g, p.n_max, s); rc != RTS_OK) return rc;
+        cols = h->gate.gcols;
+        n_new = h->gate.n_gated;
+    }
     const int n_push = h->geo.diff && p.n_max_diff == 0 ? 0 : p.n_max;
     if (int rc = h->otw ? rts_otw_push(h->otw, cols, RTS_F64, n_push, n_new, stream)
                         : rts_wtw_push(h->wtw, cols, RTS_F64, n_push, n_new, 1, stream);
@@ -369,11 +410,14 @@ int rts_live_destroy(rts_live *h) {
     }
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     void *dev[] = {h->args.buf,   h->args.pending,   h->args.n_samples, h->args.n_frames, h->args.cols,    h->args.dcols,
-                   h->args.carry, h->args.has_carry, h->args.n_cols,    h->rs_stage, h->rs_tail, h->rs_tot};
+                   h->args.carry, h->args.has_carry, h->args.n_cols,    h->rs_stage, h->rs_tail, h->rs_tot,
+                   h->gate.lev,   h->gate.gcols,     h->gate.n_gated,   h->gate.q,   h->gate.prev, h->gate.seen,
+                   h->gate.passed, h->gate.ord};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     if (h->pub_host) (void)hipHostFree(h->pub_host);
     if (h->conf_host) (void)hipHostFree(h->conf_host);
+    if (h->gate_host) (void)hipHostFree(h->gate_host);
     free(h);  // the mirrors with it
     return RTS_OK;
 }
@@ -515,9 +559,15 @@ int rts_live_reset(rts_live *h, void *stream) {
         RTS_HIP(hipMemsetAsync(h->rs_tail, 0, sizeof(float) * 2 * nB * h->rs_T, (hipStream_t)stream));
         RTS_HIP(hipMemsetAsync(h->rs_tot, 0, sizeof(long long) * 4 * nB, (hipStream_t)stream));
     }
+    if (h->gate_host) {  // every stream closed and at ordinal 0 again; the setting stays
+        RTS_HIP(hipMemsetD32Async((hipDeviceptr_t)h->gate.q, kGateClosed, nB, (hipStream_t)stream));
+        for (int32_t *w : {h->gate.prev, h->gate.seen, h->gate.passed})
+            RTS_HIP(hipMemsetAsync(w, 0, sizeof(int32_t) * nB, (hipStream_t)stream));
+    }
     memset(h + 1, 0, kMirrorBytes * nB);
     memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * nB);
     if (h->conf_host) live_conf_clear(h);
+    if (h->gate_host) live_gate_clear(h);
     memset(h->used, 0, sizeof(h->used));
     h->slot = -1;
     h->feeds = 0;
@@ -540,7 +590,7 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
         return rc;
     RestartSel sel;
     for (int pos = 0; restart_next_chunk(h->geo.B, mask_host, nullptr, nullptr, &pos, &sel) > 0;) {
-        hipLaunchKernelGGL(live_restart_kernel, dim3((sel.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, sel, h->args);
+        hipLaunchKernelGGL(live_restart_kernel, dim3((sel.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, sel, h->args, h->gate);
         RTS_HIP(hipGetLastError());
         if (h->rs) {
             if (int rc = resample_live_restart_enqueue(h->rs, sel, h->geo.B, h->rs_tail, h->rs_tot, (hipStream_t)stream); rc != RTS_OK)
@@ -668,13 +718,99 @@ int rts_live_confidence(rts_live *h, double *mean_cost, int32_t *n_points, int *
     return RTS_OK;
 }
 
+int rts_live_gate(rts_live *h, double min_level, int hold) {
+    using namespace rts;
+    if (int rc = live_usable(h); rc != RTS_OK) return rc;
+    if (!(min_level >= 0.0) || min_level > 1.7976931348623157e308)
+        return set_error(RTS_ERR_INVALID, "min_level must be a finite mean square >= 0 (0 = gate off)");
+    if (hold < 0 || hold > kGateMaxHold) return set_error(RTS_ERR_INVALID, "hold must be in [0, %d] (got %d)", kGateMaxHold, hold);
+    if (h->feeds != 0)
+        return set_error(RTS_ERR_INVALID, "rts_live_gate after %d feeds: the gate is set before the first feed after create or "
+                                          "rts_live_reset, so that every ordinal counts from a closed stream", h->feeds);
+    if (min_level > 0.0 && !h->gate_host) {
+        if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+        const size_t nB = (size_t)h->geo.B;
+        GateArgs t = {};
+        t.ord_len = h->otw ? otw_history(h->otw) : wtw_history(h->wtw);
+        unsigned char *host = nullptr;
+        void *dev = nullptr;
+        hipError_t e = hipMalloc((void **)&t.lev, sizeof(double) * nB * h->cols_cap);
+        if (e == hipSuccess) e = hipMalloc((void **)&t.gcols, sizeof(double) * kLiveF * nB * h->cols_cap);
+        e = live_dev_zeroed(e, &t.n_gated, nB);
+        if (e == hipSuccess) e = hipMalloc((void **)&t.q, sizeof(int32_t) * nB);
+        if (e == hipSuccess) e = hipMemsetD32((hipDeviceptr_t)t.q, kGateClosed, nB);
+        e = live_dev_zeroed(e, &t.prev, nB);
+        e = live_dev_zeroed(e, &t.seen, nB);
+        e = live_dev_zeroed(e, &t.passed, nB);
+        e = live_dev_zeroed(e, &t.ord, nB * (size_t)t.ord_len);
+        if (e == hipSuccess)
+            e = hipHostMalloc((void **)&host, (sizeof(double) + sizeof(int32_t) * kGateWords) * nB,
+                              hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&dev, host, 0);
+        if (e != hipSuccess) {
+            for (void *p : {(void *)t.lev, (void *)t.gcols, (void *)t.n_gated, (void *)t.q, (void *)t.prev, (void *)t.seen,
+                            (void *)t.passed, (void *)t.ord})
+                if (p) (void)hipFree(p);
+            if (host) (void)hipHostFree(host);
+            return set_error(RTS_ERR_HIP, "rts_live_gate: %s", hipGetErrorString(e));
+        }
+        t.pub_level = reinterpret_cast<double *>(dev);
+        t.pub_words = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(dev) + sizeof(double) * nB);
+        h->gate = t;
+        h->gate_host = host;
+        live_gate_clear(h);
+    }
+    h->gate.min_level = min_level;
+    h->gate.hold = hold;
+    h->gate.diff = h->geo.diff;
+    h->gate_on = min_level > 0.0;
+    return RTS_OK;
+}
+
+int rts_live_levels(rts_live *h, double *level, int32_t *open, int32_t *seen, int32_t *passed, int *feeds_done) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!h->gate_host) return set_error(RTS_ERR_INVALID, "rts_live_levels before any rts_live_gate(min_level > 0)");
+    const volatile double *lv = reinterpret_cast<const volatile double *>(h->gate_host);
+    const volatile int32_t *w = reinterpret_cast<const volatile int32_t *>(h->gate_host + sizeof(double) * (size_t)h->geo.B);
+    const int fd = live_read_published(h, [=](int b) {
+        if (level) level[b] = lv[b];
+        if (open) open[b] = w[(size_t)b * kGateWords + 0];
+        if (seen) seen[b] = w[(size_t)b * kGateWords + 1];
+        if (passed) passed[b] = w[(size_t)b * kGateWords + 2];
+    });
+    if (feeds_done) *feeds_done = fd;
+    return RTS_OK;
+}
+
+int rts_live_gate_columns(rts_live *h, int b, int32_t *ordinals_host, int cap, int *n, void *stream) {
+    using namespace rts;
+    if (!h || !n) return set_error(RTS_ERR_INVALID, "NULL argument");
+    if (!h->gate_host) return set_error(RTS_ERR_INVALID, "rts_live_gate_columns before any rts_live_gate(min_level > 0)");
+    if (b < 0 || b >= h->geo.B) return set_error(RTS_ERR_INVALID, "stream %d out of range [0, %d)", b, h->geo.B);
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    int32_t passed = 0;
+    RTS_HIP(hipMemcpyAsync(&passed, h->gate.passed + b, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    RTS_HIP(hipStreamSynchronize(s));
+    *n = passed;
+    int k = passed < h->gate.ord_len ? passed : h->gate.ord_len;
+    if (k > cap) k = cap;
+    if (k > 0 && ordinals_host) {
+        RTS_HIP(hipMemcpyAsync(ordinals_host, h->gate.ord + (size_t)b * h->gate.ord_len, sizeof(int32_t) * (size_t)k,
+                               hipMemcpyDeviceToHost, s));
+        RTS_HIP(hipStreamSynchronize(s));
+    }
+    return RTS_OK;
+}
+
 int rts_live_columns_view(rts_live *h, double **cols_dev, int *cols_cap, int *cols_stride, int32_t **n_cols_dev) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (cols_dev) *cols_dev = h->geo.diff ? h->args.dcols : h->args.cols;
+    if (cols_dev) *cols_dev = h->gate_on ? h->gate.gcols : h->geo.diff ? h->args.dcols : h->args.cols;
     if (cols_cap) *cols_cap = h->cols_cap;
     if (cols_stride) *cols_stride = h->last_stride;
-    if (n_cols_dev) *n_cols_dev = h->geo.diff ? h->args.n_cols : h->args.n_frames;
+    if (n_cols_dev) *n_cols_dev = h->gate_on ? h->gate.n_gated : h->geo.diff ? h->args.n_cols : h->args.n_frames;
     return RTS_OK;
 }
 

@@ -522,6 +522,7 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
 }
 
 int otw_batch(const rts_otw *h) { return h->B; }
+int otw_history(const rts_otw *h) { return h->hist_stride; }
 
 }  // namespace rts
 

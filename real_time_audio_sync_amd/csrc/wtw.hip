@@ -907,6 +907,7 @@ static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win
 }
 
 int wtw_batch(const rts_wtw *h) { return h->B; }
+int wtw_history(const rts_wtw *h) { return h->args.live_stride; }
 
 }  // namespace rts
 

@@ -117,6 +117,9 @@ class LiveSession(object):
         self._h = h
         self._status = np.zeros(self.B, dtype=np.int32)
         self._pos = np.zeros((self.B, 2), dtype=np.int32)
+        self.fs = int(fs)
+        self._gated = False                                  # gate() has made the handle's gate buffers
+        self._direct = np.zeros(self.B, dtype=np.int64)      # frames reacquire() pushed into the tracker since a restart
 
     # ---- feeding ----------------------------------------------------------------------------------------------
     def _stream(self):
@@ -217,6 +220,7 @@ class LiveSession(object):
         """Every stream starts again: pending samples, the carried chroma column of ``features='chroma_diff'`` and the
         tracker state are dropped."""
         nat.check(nat.lib.rts_live_reset(self._h, self._stream()))
+        self._direct[:] = 0
 
     @nat.on_device
     def restart(self, streams, refs=None, offsets=None):
@@ -242,6 +246,7 @@ class LiveSession(object):
         if self.otw:
             self.otw._version += 1
         eng._restarted(first, lens, pieces)
+        self._direct[mask != 0] = 0
 
     def locate(self, queries, q_len=None, euclid=None):
         """Where in the repertoire is each microphone?  ``BatchedOTW.locate`` / ``BatchedWTW.locate`` of the bound
@@ -278,7 +283,58 @@ class LiveSession(object):
             raise ValueError("reacquire needs per-stream references (a list as ref_chroma)")
         eng = self.otw or self.wtw
         out = eng._reacquire(streams, M, self._restart_known)
+        if self._gated:   # frame_columns: the excerpt's frames come first in the restarted streams' trackers
+            for b, e in out.items():
+                if e is not None:
+                    self._direct[b] = eng.state(b)["consumed" if self.otw else "chroma_ptr"]
         return {b: (self._given(e) if e is not None else None) for b, e in out.items()}
+
+    # ---- the level gate ---------------------------------------------------------------------------------------
+    @nat.on_device
+    def gate(self, min_db, hold=0):
+        """Keep silence away from the trackers (rts_live_gate): a chroma column is handed on iff the mean square of its
+        frame is at least ``10 ** (min_db / 10)`` -- ``min_db`` on the scale of the reference's microphone meter,
+        20 log10(rms) (livenote_live.py:170-177) -- or it is among the first ``hold`` columns of a rest.  Every stream
+        starts closed and opens with its first loud column: a session may be opened before the downbeat and left
+        running between two movements.  With ``features='chroma_diff'`` a difference column is handed on iff both its
+        chroma columns passed.  ``gate(None)`` switches the gate off.  Only before the first feed, or right after
+        ``reset()``; ``reset`` keeps the setting, ``restart`` closes the listed streams.  Two more small launches per
+        feed; nothing is read back."""
+        level = 0.0 if min_db is None else 10.0 ** (float(min_db) / 10.0)
+        nat.check(nat.lib.rts_live_gate(self._h, level, int(hold)))
+        self._gated = self._gated or level > 0.0
+
+    def levels(self):
+        """Non-blocking: {'level' float64 [B] (mean square of the frame of every stream's latest chroma column, NaN
+        before its first), 'level_db' (10 log10 of it, clipped like the reference's meter clips the rms to
+        [1e-10, 1]), 'open' bool [B] (that column passed), 'seen', 'passed' int32 [B] (chroma columns completed /
+        columns handed to the tracker since create, reset or the stream's restart), 'feeds_done'} as last published by
+        the device.  Needs ``gate(min_db)`` first."""
+        level = np.zeros(self.B, dtype=np.float64)
+        words = np.zeros((3, self.B), dtype=np.int32)
+        done = ctypes.c_int()
+        nat.check(nat.lib.rts_live_levels(self._h, level.ctypes.data, words[0].ctypes.data, words[1].ctypes.data,
+                                          words[2].ctypes.data, ctypes.byref(done)))
+        with np.errstate(invalid="ignore"):
+            db = 10.0 * np.log10(np.clip(level, 1e-20, 1.0))
+        return dict(level=level, level_db=db, open=words[0] != 0, seen=words[1].copy(), passed=words[2].copy(),
+                    feeds_done=done.value)
+
+    @nat.on_device
+    def frame_columns(self, b=0):
+        """int32 array aligned with the live frames of stream b's tracker: entry t is the ordinal, among the chroma
+        columns the stream has completed since create, reset or its restart, of the column that became live frame t (for
+        a difference column the later of its two), so that frame t ended ``(ordinal * hop_size + fft_len) / fs``
+        seconds into the stream's run.  Frames that ``reacquire`` pushed into the tracker itself come first and read
+        -1.  As long as the tracker's history at most.  Waits for the feeds in flight.  Needs ``gate(min_db)`` first."""
+        n = ctypes.c_int()
+        nat.check(nat.lib.rts_live_gate_columns(self._h, int(b), None, 0, ctypes.byref(n), self._stream()))
+        history = 2 * (self.otw.N if self.otw else self.wtw.M)   # ordinals are kept for as many frames as the tracker keeps
+        out = np.zeros(min(max(n.value, 0), history), dtype=np.int32)
+        if len(out):
+            nat.check(nat.lib.rts_live_gate_columns(self._h, int(b), out.ctypes.data, len(out), ctypes.byref(n),
+                                                    self._stream()))
+        return np.concatenate([np.full(int(self._direct[b]), -1, dtype=np.int32), out])
 
     @nat.on_device
     def watch(self, K):
