@@ -455,7 +455,9 @@ int rts_chroma_frames_batch(rts_chroma *h, const void *samples_dev, int sample_d
 /* fft_len and hop of a plan (either pointer may be NULL). */
 int rts_chroma_plan_info(const rts_chroma *h, int *fft_len, int *hop);
 
-/* create_chroma(ft) for a power spectrum that is already on the device: spec_dev [n_frames][fft_len/2+1]. */
+/* create_chroma(ft) for a power spectrum that is already on the device: spec_dev [n_frames][fft_len/2+1].  Like
+ * rts_chroma_frames and rts_chroma_frames_batch it refuses (RTS_ERR_INVALID) a plan whose device is not the current
+ * one. */
 int rts_chroma_project(rts_chroma *h, const double *spec_dev, int n_frames, int normalize, void *chroma_out_dev,
                        int out_dtype, void *stream);
 

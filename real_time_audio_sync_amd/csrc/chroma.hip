@@ -1,7 +1,7 @@
 // Chroma front end for gfx950: frame -> Hann -> real FFT -> |.|^2 -> 12-bin filterbank -> L2 normalise.
 //
-// Reference: /root/reference/chroma.py:35-90 (create_stft, create_chroma, wav_to_chroma_col,
-// wav_to_chroma_diff) and the per-hop half of wtw.WTW (wtw.py:37-41, :81-90).
+// Reference: chroma.py:35-90 (create_stft, create_chroma, wav_to_chroma_col, wav_to_chroma_diff) and the per-hop half
+// of wtw.WTW (wtw.py:37-41, :81-90).  Which kernel a call gets, every kernel's LDS layout and the grids: chroma_plan.h.
 //
 //   chroma_frames_kernel   one team of 256 threads per frame, two teams (two frames in flight) per workgroup,
 //                          persistent over groups of four frames:
@@ -12,9 +12,9 @@
 //       3. real-FFT untangling -> the L/2+1 rfft bins, optionally stored (create_stft's output),
 //          power spectrum -> LDS;
 //       4. projection onto the 12 x (L/2+1) filterbank: each thread owns bins k = tid (mod 256)
-//          with 12 running sums, a cross-wave LDS reduction finishes them (a 12-row GEMV per
-//          frame: MFMA would run at the fp64 vector rate with 3/4 of a 16-wide tile empty, so a
-//          plain reduction it is);
+//          with 12 running sums; DPP row sums of 16 lanes and [12][16] row totals per frame through LDS finish
+//          them (a 12-row GEMV per frame: MFMA would run at the fp64 vector rate with 3/4 of a 16-wide tile
+//          empty, so a plain reduction it is);
 //       5. column L2 normalisation with librosa's tiny-norm rule (chroma.py:74).
 //   chroma_project_kernel  steps 4-5 from a power spectrum already in HBM (create_chroma(ft)).
 //   chroma_diff_kernel     clip(diff(chroma), 0, inf)  (chroma.py:85-90).
@@ -28,25 +28,28 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "chroma_plan.h"
 #include "common.h"
 
 namespace rts {
+using namespace chroma_plan;
 
-constexpr int kCh = 12;
-constexpr int kChromaNT = 256;
+constexpr int kChromaFR = 4;  // frames of a group: they share one pass over the filterbank, fft_len <= 4096
+constexpr int kBigFR = 2;     // the same for fft_len 8192
+static_assert(kChromaFR == group(kGeneric) && kChromaFR == group(k4096) && kChromaFR == group(kProject) &&
+              kBigFR == group(kBig), "chroma_plan.h sizes the spectra and the grids by these");
 
 struct ChromaArgs {
     const void *samples;     // [n_samples]
     const double *window;    // [L]
     const double2 *twiddle;  // [L/2]  exp(-2 pi i n / L)
-    const double *fb;        // [12][L/2+1]
-    const double *fbt;       // [L/2+1][12]: the same, bin-major (a thread's 12 weights of one bin are 96 contiguous bytes)
+    const double *fbt;       // [L/2+1][12] filterbank, bin-major (a thread's 12 weights of one bin are 96 contiguous bytes)
     void *chroma_out;        // [n_frames][12]
     double2 *stft_out;       // [n_frames][L/2+1] or NULL
     const double *spec_in;   // projection-only entry: [n_frames][L/2+1]
     long long n_samples;
     long long frame_offset;  // sample index of frame 0, element 0 (= -pad_left)
-    int L, logL2, hop, n_frames, normalize, samples_f64, out_f64;
+    int L, hop, n_frames, normalize, out_f64;
     // batched form (blockIdx.y = stream): per-stream sample counts / frame counts, strides in elements
     const int32_t *n_samples_b;  // [B] or NULL
     const int32_t *n_frames_b;   // [B] or NULL
@@ -57,8 +60,51 @@ struct ChromaArgs {
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
     return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
+__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ double2 mul_mi(double2 a) { return make_double2(a.y, -a.x); }  // * (-i)
 
-constexpr int kChromaFR = 4;  // frames sharing one pass over the filterbank
+// The workgroup's dynamic LDS.  Every kernel chains its pointers through the sections of chroma_plan.h's layout, in its
+// order and from its shapes (`lds`): FFT buffers, twiddles, spectra, scratch.
+extern __shared__ __align__(16) unsigned char ch_smem[];
+
+// Batched launch (n_frames_b set): narrows the arguments to stream `sb` = blockIdx.y.  The caller tests n_frames_b.
+template <typename ST>
+__device__ __forceinline__ void select_stream(ChromaArgs &g, int sb) {
+    g.n_frames = g.n_frames_b[sb];
+    g.n_samples = g.n_samples_b[sb];
+    g.samples = reinterpret_cast<const ST *>(g.samples) + (long long)sb * g.sample_stride;
+    const long long oo = (long long)sb * g.out_frames_stride * kCh;
+    g.chroma_out = g.out_f64 ? (void *)(reinterpret_cast<double *>(g.chroma_out) + oo)
+                             : (void *)(reinterpret_cast<float *>(g.chroma_out) + oo);
+}
+
+// exp(-2 pi i t / L), t < L/2, from the quarter-circle table twq[n], n < NQ = L/4: exp(-i (x + pi/2)) = -i exp(-i x)
+__device__ __forceinline__ double2 quarter_tw(const double2 *twq, int NQ, int t) {
+    const double2 w = twq[t & (NQ - 1)];
+    return (t & NQ) ? make_double2(w.y, -w.x) : w;
+}
+
+// Radix-4 butterfly of the twiddled inputs u0..u3 (decimation in time), outputs in natural order in o.
+__device__ __forceinline__ void radix4(double2 u0, double2 u1, double2 u2, double2 u3, double2 (&o)[4]) {
+    const double2 a0 = cadd(u0, u2), a1 = csub(u0, u2), a2 = cadd(u1, u3), a3 = mul_mi(csub(u1, u3));
+    o[0] = cadd(a0, a2);
+    o[1] = cadd(a1, a3);
+    o[2] = csub(a0, a2);
+    o[3] = csub(a1, a3);
+}
+
+// Real-FFT untangling of one bin: X[k] = E[k] + W_L^k O[k] with E = (Z[k] + conj Z[N2-k]) / 2 and
+// O = (Z[k] - conj Z[N2-k]) / (2i); a = Z[k], bq = Z[N2-k] (Z[N2] == Z[0]), w = W_L^k.
+__device__ __forceinline__ double2 untangle(double2 a, double2 bq, double2 w) {
+    const double2 b = make_double2(bq.x, -bq.y);  // conj
+    const double2 e = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y + b.y));
+    const double2 dm = make_double2(a.x - b.x, a.y - b.y);
+    const double2 o = make_double2(0.5 * dm.y, -0.5 * dm.x);  // dm / (2i)
+    const double2 wo = cmul(w, o);
+    return make_double2(e.x + wo.x, e.y + wo.y);
+}
+
 #ifdef RTS_CHROMA_STAMPS
 __device__ long long g_chroma_stamps[8];
 #define CH_STAMP(i)                                                        \
@@ -197,38 +243,22 @@ constexpr int kChromaWG = 2 * kChromaNT;
 
 template <typename ST>  // sample type in HBM: float or double
 __global__ void __launch_bounds__(kChromaWG) chroma_frames_kernel(ChromaArgs g) {
-    extern __shared__ __align__(16) unsigned char ch_smem[];
     const int L = g.L, N2 = L / 2, NQ = N2 / 2;
-    const int sstride = N2 + 2;                               // doubles per power spectrum in LDS
+    const Lds lds = lds_layout(kGeneric, L);
+    const int sstride = lds.sstride;                          // doubles per power spectrum in LDS
     const int team = threadIdx.x >> 8, tid = threadIdx.x & (kChromaNT - 1);
-    double2 *zbase = reinterpret_cast<double2 *>(ch_smem);    // [2][N2] FFT work buffers, one per team
-    double2 *z = zbase + (size_t)team * N2;
-    double2 *twh = zbase + 2 * (size_t)N2;                    // [N2/2]  exp(-2 pi i n / L), n < L/4
-    double *spec = reinterpret_cast<double *>(twh + NQ);      // [kChromaFR][sstride]
-    // reduction scratch of a team ([12][256] + [192] doubles): its FFT buffer when that is large enough (it is free by
-    // then), a region of its own for short transforms
-    double *red = (2 * N2 >= 3264) ? reinterpret_cast<double *>(z)
-                                   : spec + (size_t)kChromaFR * sstride + (size_t)team * 3264;
+    double2 *zbase = reinterpret_cast<double2 *>(ch_smem);
+    double2 *z = zbase + (size_t)team * lds.z_team;             // [N2] the team's FFT work buffer
+    double2 *twh = zbase + lds.teams * (size_t)lds.z_team;      // [NQ] quarter-circle twiddle table
+    double *spec = reinterpret_cast<double *>(twh + lds.tw_slots);  // [kChromaFR][sstride]
+    double *red = lds.red_in_z() ? reinterpret_cast<double *>(z)      // the team's reduction scratch
+                               : spec + (size_t)lds.frames * sstride + (size_t)team * lds.red_team;
 
-    // quarter-circle twiddle table; the second quarter follows by a rotation: exp(-i (x + pi/2)) = -i exp(-i x)
     for (int n = threadIdx.x; n < NQ; n += kChromaWG) twh[n] = g.twiddle[n];
     __syncthreads();
-    auto tw = [&](int t) {  // t < N2
-        const double2 w = twh[t & (NQ - 1)];
-        return (t & NQ) ? make_double2(w.y, -w.x) : w;
-    };
+    auto tw = [&](int t) { return quarter_tw(twh, NQ, t); };  // t < N2
 
-    // batched launch: this workgroup's stream
-    const int sb = blockIdx.y;
-    if (g.n_frames_b) {
-        g.n_frames = g.n_frames_b[sb];
-        g.n_samples = g.n_samples_b[sb];
-        const long long so = (long long)sb * g.sample_stride;
-        g.samples = reinterpret_cast<const ST *>(g.samples) + so;
-        const long long oo = (long long)sb * g.out_frames_stride * kCh;
-        g.chroma_out = g.out_f64 ? (void *)(reinterpret_cast<double *>(g.chroma_out) + oo)
-                                 : (void *)(reinterpret_cast<float *>(g.chroma_out) + oo);
-    }
+    if (g.n_frames_b) select_stream<ST>(g, blockIdx.y);
 
     // (the window coefficients are read from the L2-resident table where they are used: keeping 16 of them per thread in
     // registers, next to the prefetched samples, pushed this kernel into scratch -- 176 B per lane with float64 samples)
@@ -326,18 +356,7 @@ __global__ void __launch_bounds__(kChromaWG) chroma_frames_kernel(ChromaArgs g) 
                         const double2 w1 = tw(t1), w2 = tw(t2);
                         double2 w3 = tw(t3 & (N2 - 1));
                         if (t3 >= N2) w3 = make_double2(-w3.x, -w3.y);  // exp(-i (pi + x)) = -exp(-i x)
-                        const double2 u0 = z[i];
-                        const double2 u1 = cmul(w1, z[i + q]);
-                        const double2 u2 = cmul(w2, z[i + 2 * q]);
-                        const double2 u3 = cmul(w3, z[i + 3 * q]);
-                        const double2 a0 = make_double2(u0.x + u2.x, u0.y + u2.y);
-                        const double2 a1 = make_double2(u0.x - u2.x, u0.y - u2.y);
-                        const double2 a2 = make_double2(u1.x + u3.x, u1.y + u3.y);
-                        const double2 a3 = make_double2(u1.y - u3.y, -(u1.x - u3.x));  // -i (u1 - u3)
-                        o[r][0] = make_double2(a0.x + a2.x, a0.y + a2.y);
-                        o[r][1] = make_double2(a1.x + a3.x, a1.y + a3.y);
-                        o[r][2] = make_double2(a0.x - a2.x, a0.y - a2.y);
-                        o[r][3] = make_double2(a1.x - a3.x, a1.y - a3.y);
+                        radix4(z[i], cmul(w1, z[i + q]), cmul(w2, z[i + 2 * q]), cmul(w3, z[i + 3 * q]), o[r]);
                         jj[r] = ((i - k) << 2) + k;
                     }
                 }
@@ -355,20 +374,12 @@ __global__ void __launch_bounds__(kChromaWG) chroma_frames_kernel(ChromaArgs g) 
                 lds_barrier();
             }
             CH_STAMP(2);
-            // 3. untangle: X[k] = E[k] + W_L^k O[k], E = (Z[k] + conj Z[N2-k]) / 2, O = (Z[k] - conj Z[N2-k]) / (2i)
+            // 3. untangle -> the L/2 + 1 rfft bins, power spectrum
             const int nb = N2 + 1;
             double *sp = spec + (size_t)f * sstride;
             if (live) {
                 for (int k = tid; k < nb; k += kChromaNT) {
-                    const double2 a = z[k & (N2 - 1)];          // Z[N2] == Z[0]
-                    const double2 bq = z[(N2 - k) & (N2 - 1)];
-                    const double2 b = make_double2(bq.x, -bq.y);  // conj
-                    const double2 e = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y + b.y));
-                    const double2 dm = make_double2(a.x - b.x, a.y - b.y);
-                    const double2 o = make_double2(0.5 * dm.y, -0.5 * dm.x);  // dm / (2i)
-                    const double2 w = (k < N2) ? tw(k) : make_double2(-1.0, 0.0);
-                    const double2 wo = cmul(w, o);
-                    const double2 x = make_double2(e.x + wo.x, e.y + wo.y);
+                    const double2 x = untangle(z[k & (N2 - 1)], z[(N2 - k) & (N2 - 1)], (k < N2) ? tw(k) : make_double2(-1.0, 0.0));
                     if (g.stft_out) g.stft_out[(size_t)frame * nb + k] = x;
                     sp[k] = x.x * x.x + x.y * x.y;
                 }
@@ -376,10 +387,10 @@ __global__ void __launch_bounds__(kChromaWG) chroma_frames_kernel(ChromaArgs g) 
             lds_barrier();
             CH_STAMP(3);
         }
-        // 4-5: each team projects its frames (f = team, team + 2) in one pass over the filterbank; its own FFT buffer
-        //      is free now and serves as reduction scratch
+        // 4-5: each team projects its frames (f = team, team + 2) in one pass over the filterbank (its FFT buffer is
+        //      free now: where the layout puts the scratch there, nothing else reads or writes it)
         if (g.chroma_out)
-            project_normalize<kChromaFR / 2>(g, spec, sstride, red, frame0, nf, team, 2, tid, [] { lds_barrier(); });
+            project_normalize<proj_frames(kGeneric)>(g, spec, sstride, red, frame0, nf, team, 2, tid, [] { lds_barrier(); });
         fetch_frame((long long)frame0 + (long long)gridDim.x * kChromaFR + team);  // the next group's first frame
         CH_STAMP(4);
     }
@@ -392,31 +403,19 @@ __global__ void __launch_bounds__(kChromaWG) chroma_frames_kernel(ChromaArgs g) 
 // ---- fft_len = 8192 (wtw.py:27 takes any length; the reference's own configurations stop at 4096) --------------------
 // The 4096 packed complex points of one frame fill 64 KB of LDS, so a workgroup is ONE team of 256 threads with one
 // frame in flight; two consecutive frames share a pass over the (394 KB, L2-resident) filterbank.  No sample prefetch
-// and the twiddles come from the L2-resident table instead of an LDS copy (the work buffer, two power spectra and the
-// reduction scratch leave no room for it): this kernel exists for completeness, not for speed.
-constexpr int kBigFR = 2;
-
+// and the twiddles come from the L2-resident table instead of an LDS copy (the work buffer and two power spectra, 128 KB,
+// leave no room for its 32 KB; the reduction scratch is the work buffer): this kernel exists for completeness, not speed.
 template <typename ST>
 __global__ void __launch_bounds__(kChromaNT) chroma_frames_big_kernel(ChromaArgs g) {
-    extern __shared__ __align__(16) unsigned char ch_smem[];
     const int L = g.L, N2 = L / 2, NQ = N2 / 2;  // 8192, 4096, 2048
-    const int sstride = N2 + 2;
     const int tid = threadIdx.x;
-    double2 *z = reinterpret_cast<double2 *>(ch_smem);             // [N2] FFT work buffer; reduction scratch afterwards
-    double *spec = reinterpret_cast<double *>(z + N2);             // [kBigFR][sstride]
-    auto tw = [&](int t) {  // t < N2: quarter-circle symmetry as in the kernels above, from the table in L2
-        const double2 w = g.twiddle[t & (NQ - 1)];
-        return (t & NQ) ? make_double2(w.y, -w.x) : w;
-    };
-    const int sb = blockIdx.y;
-    if (g.n_frames_b) {
-        g.n_frames = g.n_frames_b[sb];
-        g.n_samples = g.n_samples_b[sb];
-        g.samples = reinterpret_cast<const ST *>(g.samples) + (long long)sb * g.sample_stride;
-        const long long oo = (long long)sb * g.out_frames_stride * kCh;
-        g.chroma_out = g.out_f64 ? (void *)(reinterpret_cast<double *>(g.chroma_out) + oo)
-                                 : (void *)(reinterpret_cast<float *>(g.chroma_out) + oo);
-    }
+    const Lds lds = lds_layout(kBig, L);
+    const int sstride = lds.sstride;
+    static_assert(lds_layout(kBig, 8192).red_in_z(), "the reduction scratch is the FFT buffer");
+    double2 *z = reinterpret_cast<double2 *>(ch_smem);               // [N2] FFT work buffer; reduction scratch afterwards
+    double *spec = reinterpret_cast<double *>(z + lds.z_team + lds.tw_slots);  // [kBigFR][sstride]; no twiddle section
+    auto tw = [&](int t) { return quarter_tw(g.twiddle, NQ, t); };  // t < N2, from the table in L2
+    if (g.n_frames_b) select_stream<ST>(g, blockIdx.y);
     constexpr int kMaxBf4 = 4;  // N2/4/256 butterflies per thread and stage
     for (int frame0 = blockIdx.x * kBigFR; frame0 < g.n_frames; frame0 += gridDim.x * kBigFR) {
         const int nf = (g.n_frames - frame0 < kBigFR) ? g.n_frames - frame0 : kBigFR;
@@ -444,18 +443,7 @@ __global__ void __launch_bounds__(kChromaNT) chroma_frames_big_kernel(ChromaArgs
                     const double2 w1 = tw(t1), w2 = tw(t2);
                     double2 w3 = tw(t3 & (N2 - 1));
                     if (t3 >= N2) w3 = make_double2(-w3.x, -w3.y);
-                    const double2 u0 = z[i];
-                    const double2 u1 = cmul(w1, z[i + q]);
-                    const double2 u2 = cmul(w2, z[i + 2 * q]);
-                    const double2 u3 = cmul(w3, z[i + 3 * q]);
-                    const double2 a0 = make_double2(u0.x + u2.x, u0.y + u2.y);
-                    const double2 a1 = make_double2(u0.x - u2.x, u0.y - u2.y);
-                    const double2 a2 = make_double2(u1.x + u3.x, u1.y + u3.y);
-                    const double2 a3 = make_double2(u1.y - u3.y, -(u1.x - u3.x));
-                    o[r][0] = make_double2(a0.x + a2.x, a0.y + a2.y);
-                    o[r][1] = make_double2(a1.x + a3.x, a1.y + a3.y);
-                    o[r][2] = make_double2(a0.x - a2.x, a0.y - a2.y);
-                    o[r][3] = make_double2(a1.x - a3.x, a1.y - a3.y);
+                    radix4(z[i], cmul(w1, z[i + q]), cmul(w2, z[i + 2 * q]), cmul(w3, z[i + 3 * q]), o[r]);
                     jj[r] = ((i - k) << 2) + k;
                 }
                 __syncthreads();
@@ -472,22 +460,14 @@ __global__ void __launch_bounds__(kChromaNT) chroma_frames_big_kernel(ChromaArgs
             const int nb = N2 + 1;
             double *sp = spec + (size_t)f * sstride;
             for (int k = tid; k < nb; k += kChromaNT) {
-                const double2 a = z[k & (N2 - 1)];
-                const double2 bq = z[(N2 - k) & (N2 - 1)];
-                const double2 b = make_double2(bq.x, -bq.y);
-                const double2 e = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y + b.y));
-                const double2 dm = make_double2(a.x - b.x, a.y - b.y);
-                const double2 od = make_double2(0.5 * dm.y, -0.5 * dm.x);
-                const double2 w = (k < N2) ? tw(k) : make_double2(-1.0, 0.0);
-                const double2 wo = cmul(w, od);
-                const double2 x = make_double2(e.x + wo.x, e.y + wo.y);
+                const double2 x = untangle(z[k & (N2 - 1)], z[(N2 - k) & (N2 - 1)], (k < N2) ? tw(k) : make_double2(-1.0, 0.0));
                 if (g.stft_out) g.stft_out[(size_t)frame * nb + k] = x;
                 sp[k] = x.x * x.x + x.y * x.y;
             }
             __syncthreads();
         }
         if (g.chroma_out)
-            project_normalize<kBigFR>(g, spec, sstride, reinterpret_cast<double *>(z), frame0, nf, 0, 1, tid, [] { __syncthreads(); });
+            project_normalize<proj_frames(kBig)>(g, spec, sstride, reinterpret_cast<double *>(z), frame0, nf, 0, 1, tid, [] { __syncthreads(); });
         else
             __syncthreads();
     }
@@ -501,13 +481,10 @@ __global__ void __launch_bounds__(kChromaNT) chroma_frames_big_kernel(ChromaArgs
 // conflicts, samples are indexed with 32-bit arithmetic, and all compile-time strides fold into immediates.
 namespace c4k {
 constexpr int L = 4096, N2 = 2048, NQ = 1024;        // real length, packed complex length, quarter-circle table
-constexpr int ZSLOTS = N2 + N2 / 8;                  // padded work buffer (double2 slots)
-constexpr int SSTRIDE = N2 + 2;
-__device__ __forceinline__ constexpr int zi(int n) { return n + (n >> 3); }
-
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 mul_mi(double2 a) { return make_double2(a.y, -a.x); }  // * (-i)
+constexpr Lds LDS = lds_layout(k4096, L);
+constexpr int SSTRIDE = LDS.sstride;
+__device__ __forceinline__ constexpr int zi(int n) { return n + (n >> 3); }  // slot of point n in the padded work buffer
+static_assert(zi(N2 - 1) < k4096Slots && SSTRIDE > N2, "the layout holds the padded buffer and L/2 + 1 bins");
 
 // exp(-2 pi i t / 4096), 0 <= t < 4096, from the quarter table (t < 1024): every quarter turn multiplies by -i
 __device__ __forceinline__ double2 twf(const double2 *twq, int t) {
@@ -566,27 +543,19 @@ __device__ __forceinline__ void pass8(double2 *z, const double2 *twq, int tid, B
 template <typename ST>
 __global__ void __launch_bounds__(kChromaWG) chroma_frames4096_kernel(ChromaArgs g) {
     using namespace c4k;
-    extern __shared__ __align__(16) unsigned char ch_smem[];
     const int team = threadIdx.x >> 8, tid = threadIdx.x & (kChromaNT - 1);
-    double2 *zbase = reinterpret_cast<double2 *>(ch_smem);       // [2][ZSLOTS]
-    double2 *z = zbase + (size_t)team * ZSLOTS;
-    double2 *twq = zbase + 2 * (size_t)ZSLOTS;                   // [NQ]
-    double *spec = reinterpret_cast<double *>(twq + NQ);         // [kChromaFR][SSTRIDE]
-    double *red = reinterpret_cast<double *>(z);                 // the team's reduction scratch (26 KB of its 36 KB)
+    static_assert(LDS.red_in_z(), "the reduction scratch is the FFT buffer");
+    double2 *zbase = reinterpret_cast<double2 *>(ch_smem);
+    double2 *z = zbase + (size_t)team * LDS.z_team;             // [k4096Slots] the team's FFT work buffer
+    double2 *twq = zbase + LDS.teams * (size_t)LDS.z_team;      // [NQ]
+    double *spec = reinterpret_cast<double *>(twq + LDS.tw_slots);  // [kChromaFR][SSTRIDE]
+    double *red = reinterpret_cast<double *>(z);                // the team's reduction scratch
     auto bar = [] { lds_barrier(); };
 
     for (int n = threadIdx.x; n < NQ; n += kChromaWG) twq[n] = g.twiddle[n];
     __syncthreads();
 
-    const int sb = blockIdx.y;  // batched launch: this workgroup's stream
-    if (g.n_frames_b) {
-        g.n_frames = g.n_frames_b[sb];
-        g.n_samples = g.n_samples_b[sb];
-        g.samples = reinterpret_cast<const ST *>(g.samples) + (long long)sb * g.sample_stride;
-        const long long oo = (long long)sb * g.out_frames_stride * kCh;
-        g.chroma_out = g.out_f64 ? (void *)(reinterpret_cast<double *>(g.chroma_out) + oo)
-                                 : (void *)(reinterpret_cast<float *>(g.chroma_out) + oo);
-    }
+    if (g.n_frames_b) select_stream<ST>(g, blockIdx.y);
     const ST *samples = reinterpret_cast<const ST *>(g.samples);
     const int n_samples = (int)g.n_samples;  // the host routes longer signals to the generic kernel
     const int off0 = (int)g.frame_offset, hop = g.hop;
@@ -653,15 +622,8 @@ __global__ void __launch_bounds__(kChromaWG) chroma_frames4096_kernel(ChromaArgs
 #pragma unroll
                 for (int r = 0; r < 2; r++) {
                     const int i = tid + r * kChromaNT;  // k = i (P = 512 = N2/4)
-                    const double2 u0 = z[zi(i)];
-                    const double2 u1 = cmul(twf(twq, 2 * i), z[zi(i + Q)]);
-                    const double2 u2 = cmul(twf(twq, 4 * i), z[zi(i + 2 * Q)]);
-                    const double2 u3 = cmul(twf(twq, 6 * i), z[zi(i + 3 * Q)]);
-                    const double2 a0 = cadd(u0, u2), a1 = csub(u0, u2), a2 = cadd(u1, u3), a3 = mul_mi(csub(u1, u3));
-                    o[r][0] = cadd(a0, a2);
-                    o[r][1] = cadd(a1, a3);
-                    o[r][2] = csub(a0, a2);
-                    o[r][3] = csub(a1, a3);
+                    radix4(z[zi(i)], cmul(twf(twq, 2 * i), z[zi(i + Q)]), cmul(twf(twq, 4 * i), z[zi(i + 2 * Q)]),
+                           cmul(twf(twq, 6 * i), z[zi(i + 3 * Q)]), o[r]);
                 }
                 bar();
 #pragma unroll
@@ -700,7 +662,7 @@ __global__ void __launch_bounds__(kChromaWG) chroma_frames4096_kernel(ChromaArgs
             bar();
             CH_STAMP(3);
         }
-        if (g.chroma_out) project_normalize<kChromaFR / 2>(g, spec, SSTRIDE, red, frame0, nf, team, 2, tid, bar);
+        if (g.chroma_out) project_normalize<proj_frames(k4096)>(g, spec, SSTRIDE, red, frame0, nf, team, 2, tid, bar);
         CH_STAMP(4);
     }
 #ifdef RTS_CHROMA_STAMPS
@@ -710,18 +672,18 @@ __global__ void __launch_bounds__(kChromaWG) chroma_frames4096_kernel(ChromaArgs
 }
 
 __global__ void __launch_bounds__(kChromaNT) chroma_project_kernel(ChromaArgs g) {
-    extern __shared__ __align__(16) unsigned char ch_smem[];
     const int nb = g.L / 2 + 1;
-    const int sstride = nb + 1;
-    double *spec = reinterpret_cast<double *>(ch_smem);   // [kChromaFR][sstride]
-    double *red = spec + (size_t)kChromaFR * sstride;      // [12][256] + [192]
+    const Lds lds = lds_layout(kProject, g.L);
+    const int sstride = lds.sstride;
+    double *spec = reinterpret_cast<double *>(ch_smem);     // [kChromaFR][sstride]: no FFT buffer, no twiddles
+    double *red = spec + (size_t)lds.frames * sstride;      // reduction scratch
     const int tid = threadIdx.x;
     for (int frame0 = blockIdx.x * kChromaFR; frame0 < g.n_frames; frame0 += gridDim.x * kChromaFR) {
         const int nf = (g.n_frames - frame0 < kChromaFR) ? g.n_frames - frame0 : kChromaFR;
         for (int f = 0; f < nf; f++)
             for (int k = tid; k < nb; k += kChromaNT) spec[(size_t)f * sstride + k] = g.spec_in[(size_t)(frame0 + f) * nb + k];
         __syncthreads();
-        project_normalize<kChromaFR>(g, spec, sstride, red, frame0, nf, 0, 1, tid, [] { __syncthreads(); });
+        project_normalize<proj_frames(kProject)>(g, spec, sstride, red, frame0, nf, 0, 1, tid, [] { __syncthreads(); });
     }
 }
 
@@ -741,18 +703,55 @@ __global__ void chroma_diff_kernel(const void *in, void *out, long long n_out, i
     }
 }
 
+// One kernel as a plan launches it.  Frames per group and the grid: chroma_plan.h.
+struct ChromaKernel {
+    const void *fn;
+    int block;    // threads per workgroup
+    size_t smem;  // dynamic LDS
+};
+
 }  // namespace rts
 
 struct rts_chroma {
-    int L, hop, logL2;
+    int L, hop;
     double *window;    // device [L]
     double2 *twiddle;  // device [L/2]
-    double *fb;        // device [12][L/2+1]
-    double *fbt;       // device [L/2+1][12]
-    size_t smem_frames, smem_frames4096, smem_frames_big, smem_project;
+    double *fbt;       // device [L/2+1][12]: the filterbank, bin-major
+    rts::ChromaKernel kern[rts::chroma_plan::kKernels][2];  // [kernel][float64 samples], fixed at create
     int device;  // the HIP device the plan's tables live on
     int cus;     // its compute units
 };
+
+namespace rts {
+
+// The argument fields every launch of plan `h` shares; the caller adds its inputs and sizes.
+static ChromaArgs chroma_args(const rts_chroma *h, int normalize, void *chroma_out_dev, int out_dtype) {
+    ChromaArgs g;
+    memset(&g, 0, sizeof(g));
+    g.window = h->window;
+    g.twiddle = h->twiddle;
+    g.fbt = h->fbt;
+    g.chroma_out = chroma_out_dev;
+    g.L = h->L;
+    g.hop = h->hop;
+    g.normalize = normalize;
+    g.out_f64 = out_dtype == RTS_F64;
+    return g;
+}
+
+// The one launch: kernel `k` of the plan's table for `n_frames` frames (of the longest stream when B > 0, a batched
+// launch with gridDim.y = B).
+static int chroma_launch(const rts_chroma *h, Kernel k, int sample_dtype, int n_frames, int B, ChromaArgs g, void *stream) {
+    if (int rc = check_device(h->device, "plan"); rc != RTS_OK) return rc;
+    const ChromaKernel &kn = h->kern[k][sample_dtype == RTS_F64];
+    void *params[] = {&g};
+    (void)hipLaunchKernel(kn.fn, dim3(grid_x(k, n_frames, h->cus, B > 0), B > 0 ? B : 1), dim3(kn.block), params, kn.smem,
+                          (hipStream_t)stream);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+
+}  // namespace rts
 
 static hipError_t upload_transposed(double *dst_dev, const double *fb_host, int nb) {
     double *t = (double *)malloc(sizeof(double) * rts::kCh * nb);
@@ -805,10 +804,8 @@ int rts_chroma_create(int fft_len, int hop, const double *window_host, const dou
     hipError_t e;
     if ((e = hipMalloc((void **)&h->window, sizeof(double) * L)) != hipSuccess ||
         (e = hipMalloc((void **)&h->twiddle, sizeof(double2) * N2)) != hipSuccess ||
-        (e = hipMalloc((void **)&h->fb, sizeof(double) * kCh * nb)) != hipSuccess ||
         (e = hipMemcpy(h->window, win, sizeof(double) * L, hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipMemcpy(h->twiddle, tw, sizeof(double2) * N2, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(h->fb, fb_host, sizeof(double) * kCh * nb, hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipMalloc((void **)&h->fbt, sizeof(double) * kCh * nb)) != hipSuccess ||
         (e = upload_transposed(h->fbt, fb_host, nb)) != hipSuccess) {
         free(win);
@@ -818,32 +815,19 @@ int rts_chroma_create(int fft_len, int hop, const double *window_host, const dou
     }
     free(win);
     free(tw);
-    h->smem_frames = sizeof(double2) * (2 * (size_t)N2 + N2 / 2) + sizeof(double) * (size_t)kChromaFR * (N2 + 2) +
-                     ((2 * N2 >= 3264) ? 0 : sizeof(double) * 2 * 3264) + 64;
-    h->smem_project = sizeof(double) * ((size_t)kChromaFR * (nb + 1) + 3264) + 64;
-    h->smem_frames_big = sizeof(double2) * (size_t)N2 + sizeof(double) * (size_t)kBigFR * (N2 + 2) + 64;
-    // per plan, i.e. on the device that is current now (the attribute is per device)
-    h->smem_frames4096 = sizeof(double2) * (2 * (size_t)c4k::ZSLOTS + c4k::NQ) + sizeof(double) * (size_t)kChromaFR * c4k::SSTRIDE + 64;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chroma_frames4096_kernel<float>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chroma_frames4096_kernel<double>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chroma_frames_kernel<float>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chroma_frames_kernel<double>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chroma_frames_big_kernel<float>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chroma_frames_big_kernel<double>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chroma_project_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const void *const fns[kKernels][2] = {
+        {(const void *)&chroma_frames_kernel<float>, (const void *)&chroma_frames_kernel<double>},
+        {(const void *)&chroma_frames4096_kernel<float>, (const void *)&chroma_frames4096_kernel<double>},
+        {(const void *)&chroma_frames_big_kernel<float>, (const void *)&chroma_frames_big_kernel<double>},
+        // no sample type: both columns hold the one kernel, and rts_chroma_project launches column RTS_F32
+        {(const void *)&chroma_project_kernel, (const void *)&chroma_project_kernel}};
+    // The LDS limit is an attribute of the function on the device that is current now, shared by every plan there:
+    // raised to the whole 160 KB, not to this plan's size.
+    for (int k = 0; k < kKernels && e == hipSuccess; k++)
+        for (int f64 = 0; f64 < 2 && e == hipSuccess; f64++) {
+            h->kern[k][f64] = ChromaKernel{fns[k][f64], teams((Kernel)k) * kChromaNT, lds_layout((Kernel)k, L).bytes()};
+            e = hipFuncSetAttribute(fns[k][f64], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        }
     if (e != hipSuccess) {
         rts_chroma_destroy(h);
         return set_error(RTS_ERR_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
@@ -863,7 +847,6 @@ int rts_chroma_destroy(rts_chroma *h) {
     if (!h) return RTS_OK;
     if (h->window) (void)hipFree(h->window);
     if (h->twiddle) (void)hipFree(h->twiddle);
-    if (h->fb) (void)hipFree(h->fb);
     if (h->fbt) (void)hipFree(h->fbt);
     free(h);
     return RTS_OK;
@@ -885,49 +868,13 @@ int rts_chroma_frames(rts_chroma *h, const void *samples_dev, int sample_dtype, 
         return set_error(RTS_ERR_INVALID, "n_frames=%d exceeds the %lld full frames in %lld samples", n_frames,
                          rts_chroma_num_frames(n_samples, h->L, h->hop, pad_left), n_samples);
     if (n_frames == 0) return RTS_OK;
-    if (int rc = rts::check_device(h->device, "plan"); rc != RTS_OK) return rc;
-    ChromaArgs g;
-    memset(&g, 0, sizeof(g));
+    ChromaArgs g = chroma_args(h, normalize, chroma_out_dev, out_dtype);
     g.samples = samples_dev;
-    g.window = h->window;
-    g.twiddle = h->twiddle;
-    g.fb = h->fb;
-    g.fbt = h->fbt;
-    g.chroma_out = chroma_out_dev;
     g.stft_out = reinterpret_cast<double2 *>(stft_out_dev);
     g.n_samples = n_samples;
     g.frame_offset = -(long long)pad_left;
-    g.L = h->L;
-    g.hop = h->hop;
     g.n_frames = n_frames;
-    g.normalize = normalize;
-    g.samples_f64 = sample_dtype == RTS_F64;
-    g.out_f64 = out_dtype == RTS_F64;
-    const int groups = (n_frames + kChromaFR - 1) / kChromaFR;
-    // one workgroup per CU (155 KB of LDS each) walking its share of the frame groups: 41.7 M frames/s against 40.7 M
-    // with four short-lived workgroups per CU (each one loads the twiddle table and its window registers first)
-    const int grid = groups < h->cus ? groups : h->cus;
-    // fft_len 4096 with 32-bit sample indices: the specialised kernel; anything else: the generic one
-    const bool fast = (h->L == 4096) && (n_samples + 2LL * h->L + (long long)n_frames * h->hop < 0x7fffffffLL);
-    if (fast) {
-        if (g.samples_f64)
-            hipLaunchKernelGGL(chroma_frames4096_kernel<double>, dim3(grid), dim3(kChromaWG), h->smem_frames4096, (hipStream_t)stream, g);
-        else
-            hipLaunchKernelGGL(chroma_frames4096_kernel<float>, dim3(grid), dim3(kChromaWG), h->smem_frames4096, (hipStream_t)stream, g);
-    } else if (h->L > 4096) {
-        const int groups_big = (n_frames + kBigFR - 1) / kBigFR;
-        const int grid_big = groups_big < 4 * h->cus ? groups_big : 4 * h->cus;
-        if (g.samples_f64)
-            hipLaunchKernelGGL(chroma_frames_big_kernel<double>, dim3(grid_big), dim3(kChromaNT), h->smem_frames_big, (hipStream_t)stream, g);
-        else
-            hipLaunchKernelGGL(chroma_frames_big_kernel<float>, dim3(grid_big), dim3(kChromaNT), h->smem_frames_big, (hipStream_t)stream, g);
-    } else if (g.samples_f64) {
-        hipLaunchKernelGGL(chroma_frames_kernel<double>, dim3(grid), dim3(kChromaWG), h->smem_frames, (hipStream_t)stream, g);
-    } else {
-        hipLaunchKernelGGL(chroma_frames_kernel<float>, dim3(grid), dim3(kChromaWG), h->smem_frames, (hipStream_t)stream, g);
-    }
-    RTS_HIP(hipGetLastError());
-    return RTS_OK;
+    return chroma_launch(h, flavour(h->L, h->hop, n_samples, n_frames), sample_dtype, n_frames, 0, g, stream);
 }
 
 int rts_chroma_frames_batch(rts_chroma *h, const void *samples_dev, int sample_dtype, long long sample_stride,
@@ -942,47 +889,14 @@ int rts_chroma_frames_batch(rts_chroma *h, const void *samples_dev, int sample_d
         return set_error(RTS_ERR_INVALID, "bad dtype");
     if (B < 1 || n_frames_max < 0 || pad_left < 0 || sample_stride < 0) return set_error(RTS_ERR_INVALID, "bad size");
     if (n_frames_max == 0) return RTS_OK;
-    if (int rc = rts::check_device(h->device, "plan"); rc != RTS_OK) return rc;
-    ChromaArgs g;
-    memset(&g, 0, sizeof(g));
+    ChromaArgs g = chroma_args(h, normalize, chroma_out_dev, out_dtype);
     g.samples = samples_dev;
-    g.window = h->window;
-    g.twiddle = h->twiddle;
-    g.fb = h->fb;
-    g.fbt = h->fbt;
-    g.chroma_out = chroma_out_dev;
     g.frame_offset = -(long long)pad_left;
-    g.L = h->L;
-    g.hop = h->hop;
-    g.normalize = normalize;
-    g.samples_f64 = sample_dtype == RTS_F64;
-    g.out_f64 = out_dtype == RTS_F64;
     g.n_samples_b = n_samples_dev;
     g.n_frames_b = n_frames_dev;
     g.sample_stride = sample_stride;
     g.out_frames_stride = n_frames_max;
-    const int groups_b = (n_frames_max + kChromaFR - 1) / kChromaFR;
-    const int gx = groups_b < 64 ? groups_b : 64;
-    const bool fast = (h->L == 4096) && (sample_stride + 2LL * h->L + (long long)n_frames_max * h->hop < 0x7fffffffLL);
-    if (fast) {
-        if (g.samples_f64)
-            hipLaunchKernelGGL(chroma_frames4096_kernel<double>, dim3(gx, B), dim3(kChromaWG), h->smem_frames4096, (hipStream_t)stream, g);
-        else
-            hipLaunchKernelGGL(chroma_frames4096_kernel<float>, dim3(gx, B), dim3(kChromaWG), h->smem_frames4096, (hipStream_t)stream, g);
-    } else if (h->L > 4096) {
-        const int groups_big = (n_frames_max + kBigFR - 1) / kBigFR;
-        const int gx_big = groups_big < 64 ? groups_big : 64;
-        if (g.samples_f64)
-            hipLaunchKernelGGL(chroma_frames_big_kernel<double>, dim3(gx_big, B), dim3(kChromaNT), h->smem_frames_big, (hipStream_t)stream, g);
-        else
-            hipLaunchKernelGGL(chroma_frames_big_kernel<float>, dim3(gx_big, B), dim3(kChromaNT), h->smem_frames_big, (hipStream_t)stream, g);
-    } else if (g.samples_f64) {
-        hipLaunchKernelGGL(chroma_frames_kernel<double>, dim3(gx, B), dim3(kChromaWG), h->smem_frames, (hipStream_t)stream, g);
-    } else {
-        hipLaunchKernelGGL(chroma_frames_kernel<float>, dim3(gx, B), dim3(kChromaWG), h->smem_frames, (hipStream_t)stream, g);
-    }
-    RTS_HIP(hipGetLastError());
-    return RTS_OK;
+    return chroma_launch(h, flavour(h->L, h->hop, sample_stride, n_frames_max), sample_dtype, n_frames_max, B, g, stream);
 }
 
 int rts_chroma_project(rts_chroma *h, const double *spec_dev, int n_frames, int normalize, void *chroma_out_dev,
@@ -993,21 +907,10 @@ int rts_chroma_project(rts_chroma *h, const double *spec_dev, int n_frames, int 
     if (!dtype_ok(out_dtype)) return set_error(RTS_ERR_INVALID, "bad dtype");
     if (n_frames < 0) return set_error(RTS_ERR_INVALID, "negative size");
     if (n_frames == 0) return RTS_OK;
-    ChromaArgs g;
-    memset(&g, 0, sizeof(g));
-    g.fb = h->fb;
-    g.fbt = h->fbt;
+    ChromaArgs g = chroma_args(h, normalize, chroma_out_dev, out_dtype);
     g.spec_in = spec_dev;
-    g.chroma_out = chroma_out_dev;
-    g.L = h->L;
     g.n_frames = n_frames;
-    g.normalize = normalize;
-    g.out_f64 = out_dtype == RTS_F64;
-    const int groups_p = (n_frames + kChromaFR - 1) / kChromaFR;
-    const int grid = groups_p < 1024 ? groups_p : 1024;
-    hipLaunchKernelGGL(chroma_project_kernel, dim3(grid), dim3(kChromaNT), h->smem_project, (hipStream_t)stream, g);
-    RTS_HIP(hipGetLastError());
-    return RTS_OK;
+    return chroma_launch(h, kProject, RTS_F32, n_frames, 0, g, stream);
 }
 
 #ifdef RTS_CHROMA_STAMPS

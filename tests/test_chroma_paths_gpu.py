@@ -162,6 +162,8 @@ LOOP_CASES = [  # L, hop, float64 samples, frames in the last group
     (1024, 256, False, 1),
     (64, 16, False, 3),
     (8192, 1024, False, 1),
+    (512, 128, False, 2),    # the shortest length whose reduction scratch lives in the team's FFT buffer ...
+    (256, 64, True, 3),      # ... and the longest that keeps it behind the spectra (chroma_plan.h, Lds::red_in_z)
 ]
 
 
@@ -532,7 +534,7 @@ def test_fft4096_beyond_32bit_indices_runs_the_generic_kernel(mods):
     try:
         n_frames = plan.num_frames(n, pad)
         assert n_frames == 1025
-        assert n + 2 * L + n_frames * hop >= 0x7fffffff          # chroma.hip: not `fast`
+        assert n + 2 * L + n_frames * hop >= 0x7fffffff          # chroma_plan.h, flavour(): not the 4096 kernel
         assert (n_frames + FR - 1) // FR == 257                  # more groups than CUs on a 256-CU part
         x = torch.empty(n, dtype=torch.float32, device=plan.device)
         gen = torch.Generator(device=plan.device)

@@ -7,8 +7,11 @@
 For every kernel (a FUNC symbol with a `<name>.kd` descriptor) it compares the instruction bytes and the per-kernel
 metadata of the code object's note (register counts, LDS, scratch, kernarg size, arguments).  Addresses and the order of
 the kernels in the object may differ: a kernel's branches are relative to itself.  Prints one line per kernel that
-differs and a verdict; exit status 0 = identical.
+differs and a verdict; exit status 0 = identical.  Where the code differs at equal length, the line also says whether
+the two disassemblies hold the same multiset of instruction lines, i.e. whether the kernels differ in order only.
 """
+import collections
+import re
 import struct
 import subprocess
 import sys
@@ -16,6 +19,20 @@ import sys
 import yaml
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"  # where tools/check_lds_waits.py finds its llvm-objdump
+OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+
+
+def instruction_lines(path):
+    """{kernel name: Counter of its disassembled instruction lines, addresses and comments stripped}."""
+    text = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", path], check=True, capture_output=True, text=True).stdout
+    out, cur = {}, None
+    for line in text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:", line)
+        if m:
+            cur = out.setdefault(m.group(1), collections.Counter())
+        elif cur is not None and line.strip():
+            cur[re.sub(r"\s*//.*", "", line).strip()] += 1
+    return out
 
 
 def kernels(path):
@@ -48,7 +65,7 @@ def main():
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-    bad = 0
+    bad, lines = 0, None
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
             print("only in %s: %s" % (sys.argv[2] if name in b else sys.argv[1], name))
@@ -58,6 +75,10 @@ def main():
         what = []
         if code_a != code_b:
             what.append("code (%d / %d bytes)" % (len(code_a), len(code_b)))
+            if len(code_a) == len(code_b):
+                lines = lines or (instruction_lines(sys.argv[1]), instruction_lines(sys.argv[2]))
+                what.append("same instruction lines, order differs" if lines[0][name] == lines[1][name]
+                            else "instruction lines differ")
         what += ["%s %r / %r" % (key, meta_a.get(key), meta_b.get(key)) for key in sorted(set(meta_a) | set(meta_b))
                  if key != ".args" and meta_a.get(key) != meta_b.get(key)]
         if meta_a.get(".args") != meta_b.get(".args"):
