@@ -276,6 +276,21 @@ int rts_otw_set_waves(rts_otw *h, int waves);
 /* Average device time of the last kernel launches is measured by the caller with HIP events on
  * `stream`; this returns the kernel's name as it appears in rocprofv3 traces. */
 const char *rts_otw_kernel_name(const rts_otw *h);
+/* Which instantiation of that kernel a launch of this handle gets: chosen at create from the band width, RTS_OTW_SPEC,
+ * the feature dtypes and the batch size relative to the device's compute units.  `live_dtype`: the dtype
+ * of the live input of the launch asked about -- rts_otw_run's own; RTS_F64 for rts_otw_insert, rts_otw_push and every
+ * rts_live_* session, whose frames are read from the handle's float64 history.
+ *   out[0]: the LDS window in cells (64 ... 2048);  out[1]: where the kernel keeps the frames it reads more than once,
+ *   RTS_OTW_RING_*;  out[2]: 1 the pipelined kernel, 0 the plain one (RTS_OTW_SPEC=0, or a dense mirror is attached);
+ *   out[3]: 1 if a launch that can bring a fresh stream at least c frames runs otw_bandfill_kernel first (rts_otw_read_fill
+ *   says which streams then took it), 0 if every launch runs the step loop alone.
+ * Host-side only: no GPU call, nothing is enqueued or synchronised.  RTS_ERR_INVALID: NULL argument, bad live_dtype.
+ * RTS_ERR_UNSUPPORTED where the launch itself is refused (RTS_OTW_SPEC=0 at c > 500 without a dense mirror). */
+#define RTS_OTW_RING_FLOAT 0     /* float32 frames in an LDS ring */
+#define RTS_OTW_RING_DOUBLE 1    /* float64 frames in an LDS ring */
+#define RTS_OTW_RING_NONE 2      /* no ring: frames come from global memory */
+#define RTS_OTW_RING_NONE_LEAN 3 /* the same, the residency-oriented flavour of batches of RTS_OTW_TP_FROM streams per CU */
+int rts_otw_read_kernel(const rts_otw *h, int live_dtype, int32_t out[4]);
 
 /* ------------------------------------------------------------------------------------------
  * Offline DTW, batched over B independent (a, b) pairs.

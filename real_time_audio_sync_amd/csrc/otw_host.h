@@ -5,8 +5,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "otw_device.h"
 #include "otw_fill.h"  // launch() enqueues otw_bandfill_kernel in front of the step kernel
+#include "otw_plan.h"  // which instantiation a launch gets and whether the band fill runs: host-only, tested on the CPU
 
 namespace rts {
 
@@ -197,7 +200,19 @@ __global__ void __launch_bounds__(256) otw_path_cost_kernel(PathCostArgs a) {
 struct OtwKernel {
     const void *fn;
     size_t smem;  // dynamic LDS
+    int pipelined, ring;  // what the instantiation is (set_kernel, from its template arguments): rts_otw_read_kernel
 };
+
+static_assert(otw_plan::kRingFloat == RTS_OTW_RING_FLOAT && otw_plan::kRingDouble == RTS_OTW_RING_DOUBLE &&
+                  otw_plan::kRingNone == RTS_OTW_RING_NONE && otw_plan::kRingNoneLean == RTS_OTW_RING_NONE_LEAN,
+              "otw_plan.h numbers the ring kinds as include/rtsync.h does");
+template <typename RT>
+constexpr int ring_kind() {
+    if constexpr (std::is_same<RT, float>::value) return otw_plan::kRingFloat;
+    else if constexpr (std::is_same<RT, double>::value) return otw_plan::kRingDouble;
+    else if constexpr (std::is_same<RT, LiveFromGlobal>::value) return otw_plan::kRingNone;
+    else return otw_plan::kRingNoneLean;
+}
 
 }  // namespace rts
 
@@ -243,47 +258,45 @@ template <int W, int DENSE, typename RT, bool SPEC>
 static int set_kernel(OtwKernel *k) {
     k->fn = reinterpret_cast<const void *>(&otw_advance_kernel<W, DENSE, RT, SPEC>);
     k->smem = otw_lds_bytes<W, RT, SPEC>();
+    k->pipelined = SPEC;
+    k->ring = ring_kind<RT>();
     RTS_HIP(hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k->smem));
     return RTS_OK;
 }
 
+// The instantiation of a table entry without mirror (otw_plan::entry).  The wide windows have one, the pipelined kernel
+// without ring; an else branch, so that none of the ring kernels is instantiated for them.
+template <int W>
+static int set_entry(const otw_plan::Entry &e, OtwKernel *k) {
+    if constexpr (W >= otw_plan::kWideWindow) {
+        return set_kernel<W, 0, LiveFromGlobal, true>(k);
+    } else {
+        if (!e.pipelined) return e.ring == otw_plan::kRingFloat ? set_kernel<W, 0, float, false>(k) : set_kernel<W, 0, double, false>(k);
+        switch (e.ring) {
+            case otw_plan::kRingNoneLean: return set_kernel<W, 0, LiveFromGlobalLean, true>(k);
+            case otw_plan::kRingFloat: return set_kernel<W, 0, float, true>(k);
+            case otw_plan::kRingDouble: return set_kernel<W, 0, double, true>(k);
+            default: return set_kernel<W, 0, LiveFromGlobal, true>(k);
+        }
+    }
+}
+
 // The handle's kernels, chosen once at create: everything the choice depends on is fixed then, except whether a launch
 // writes a dense mirror and whether its live input is float64 (rts_otw_run's dtype; the history is always float64).
-// The dense mirror is a separate instantiation so that the default kernel carries none of its code.
+// The dense mirror (otw_eran.py:23,27) is a separate instantiation so that the default kernel carries none of its code;
+// it runs the plain role-specialised kernel (otw_plan::mirror_entry).
 template <int W>
 static int resolve_kernels(rts_otw *h) {
-    const int B = h->B;
-    if constexpr (W >= 1024) {
-        // no ring fits beside a 1024-cell window's bands: every frame is read from global memory.  The dense mirror
-        // (otw_eran.py:23,27) runs the plain role-specialised kernel that way
-        if (int rc = set_kernel<W, kMirrorDense, LiveFromGlobal, false>(&h->k_dense); rc != RTS_OK) return rc;
-        if (int rc = set_kernel<W, kMirrorTrace, LiveFromGlobal, false>(&h->k_trace); rc != RTS_OK) return rc;
-        if (!h->spec) return RTS_OK;  // RTS_OTW_SPEC=0: no plain entry, launch() refuses
-        if (int rc = set_kernel<W, 0, LiveFromGlobal, true>(&h->k_plain[0]); rc != RTS_OK) return rc;
-        h->k_plain[1] = h->k_plain[0];
-        return RTS_OK;
-    } else {  // (an else branch, so that none of the ring kernels below is instantiated for the wide windows)
-        if (int rc = set_kernel<W, kMirrorDense, double, false>(&h->k_dense); rc != RTS_OK) return rc;
-        if (int rc = set_kernel<W, kMirrorTrace, double, false>(&h->k_trace); rc != RTS_OK) return rc;
-        for (int live_f64 = 0; live_f64 < 2; live_f64++) {
-            OtwKernel *k = &h->k_plain[live_f64];
-            // float32 rings only when both inputs are float32: every value then widens back exactly
-            const bool f32 = h->ref_dtype != RTS_F64 && !live_f64;
-            int rc;
-            if (h->spec) {
-                // two streams per CU or more: the 73-register flavour, three workgroups per CU
-                if (B >= h->tp_from * h->cus && B > 0) rc = set_kernel<W, 0, LiveFromGlobalLean, true>(k);
-                else if (f32) rc = set_kernel<W, 0, float, true>(k);
-                // float64 features: the ring (one workgroup per CU at W = 512) while every stream has a CU to itself
-                // (B = 64: 4.67 vs 4.93 ms), no ring and up to four workgroups per CU beyond
-                else rc = (B <= h->cus) ? set_kernel<W, 0, double, true>(k) : set_kernel<W, 0, LiveFromGlobal, true>(k);
-            } else {
-                rc = f32 ? set_kernel<W, 0, float, false>(k) : set_kernel<W, 0, double, false>(k);
-            }
-            if (rc != RTS_OK) return rc;
-        }
-        return RTS_OK;
+    using MirrorRT = std::conditional_t<otw_plan::mirror_entry(W).ring == otw_plan::kRingNone, LiveFromGlobal, double>;
+    static_assert(!otw_plan::mirror_entry(W).pipelined, "the pipelined kernel writes no dense mirror");
+    if (int rc = set_kernel<W, kMirrorDense, MirrorRT, false>(&h->k_dense); rc != RTS_OK) return rc;
+    if (int rc = set_kernel<W, kMirrorTrace, MirrorRT, false>(&h->k_trace); rc != RTS_OK) return rc;
+    for (int live_f64 = 0; live_f64 < 2; live_f64++) {
+        const otw_plan::Entry e = otw_plan::entry(W, h->spec, h->tp_from, h->cus, h->B, h->ref_dtype == RTS_F64, live_f64 != 0);
+        if (!e.ok) continue;  // RTS_OTW_SPEC=0 at a wide window: no plain entry, launch() refuses
+        if (int rc = set_entry<W>(e, &h->k_plain[live_f64]); rc != RTS_OK) return rc;
     }
+    return RTS_OK;
 }
 
 static int resolve_kernels(rts_otw *h) {
@@ -298,12 +311,16 @@ static int resolve_kernels(rts_otw *h) {
     return set_error(RTS_ERR_UNSUPPORTED, "no kernel for window %d", h->W);
 }
 
+static int no_kernel(const rts_otw *h) {
+    return set_error(RTS_ERR_UNSUPPORTED, "band widths above 500 (c=%d) run only on the pipelined 8-wave kernel", h->c);
+}
+
 // max_new: the largest number of new frames the call can bring to any stream (a host-side hint).  Only a launch that can
 // bring a fresh stream its first c frames pays for the band-fill kernel; which streams it fills is decided on the device
 // (otw_fill_eligible), every other stream is left to the step loop untouched.
 static int launch(rts_otw *h, const OtwArgs &args, hipStream_t s, int max_new) {
     if ((uintptr_t)args.live & 15) return set_error(RTS_ERR_INVALID, "live features must be 16-byte aligned");
-    const bool fill = h->fill && max_new >= h->c && h->c >= 2 && h->W <= 512 && !args.dense_acc && !args.trace_cells;
+    const bool fill = otw_plan::fill_gate(h->fill, max_new, h->c, h->W, args.dense_acc || args.trace_cells);
     if (args.state == h->state) h->fill_last = fill;  // (the dense and trace replays run on scratch state and never fill)
     if (fill) {
         const dim3 block(otw_fill_threads(h->c));
@@ -311,7 +328,7 @@ static int launch(rts_otw *h, const OtwArgs &args, hipStream_t s, int max_new) {
         RTS_HIP(hipGetLastError());
     }
     const OtwKernel &k = args.trace_cells ? h->k_trace : args.dense_acc ? h->k_dense : h->k_plain[args.live_f64 != 0];
-    if (!k.fn) return set_error(RTS_ERR_UNSUPPORTED, "band widths above 500 (c=%d) run only on the pipelined 8-wave kernel", h->c);
+    if (!k.fn) return no_kernel(h);
     void *params[] = {const_cast<OtwArgs *>(&args)};
     RTS_HIP(hipLaunchKernel(k.fn, dim3(h->B), dim3(512), params, k.smem, s));
     return RTS_OK;
@@ -457,7 +474,7 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
     if (N < 1 || B < 1) return set_error(RTS_ERR_INVALID, "N and B must be >= 1 (got N=%d B=%d)", N, B);
     if (!dtype_ok(ref_dtype)) return set_error(RTS_ERR_INVALID, "bad ref_dtype %d", ref_dtype);
     if (c < 1) return set_error(RTS_ERR_INVALID, "c must be >= 1 (got %d)", c);
-    if (c > 2036)
+    if (c > otw_plan::kMaxC)
         return set_error(RTS_ERR_UNSUPPORTED, "band width c=%d exceeds the 2036 cells the LDS-resident kernel holds", c);
     if (max_run_count < 1) return set_error(RTS_ERR_INVALID, "max_run_count must be >= 1");
     if (variant < RTS_VARIANT_OTW || variant > RTS_VARIANT_LIVENOTE_V2)
@@ -477,8 +494,7 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
     h->max_run_count = max_run_count;
     h->variant = variant;
     h->cost_kind = cost_kind;
-    h->W = 64;
-    while (h->W < c + 12) h->W *= 2;
+    h->W = otw_plan::window(c);
     const OtwKnobs knobs = otw_knobs();
     h->spec = knobs.spec;
     h->tp_from = knobs.tp_from;
@@ -653,6 +669,19 @@ int rts_otw_set_waves(rts_otw *h, int waves) {
 }
 
 const char *rts_otw_kernel_name(const rts_otw *) { return "otw_advance_kernel"; }
+
+int rts_otw_read_kernel(const rts_otw *h, int live_dtype, int32_t out[4]) {
+    using namespace rts;
+    if (!h || !out) return set_error(RTS_ERR_INVALID, "NULL argument");
+    if (!dtype_ok(live_dtype)) return set_error(RTS_ERR_INVALID, "bad live_dtype %d", live_dtype);
+    const OtwKernel &k = h->dense_acc ? h->k_dense : h->k_plain[live_dtype == RTS_F64];
+    if (!k.fn) return no_kernel(h);
+    out[0] = h->W;
+    out[1] = k.ring;
+    out[2] = k.pipelined;
+    out[3] = otw_plan::fill_gate(h->fill, h->c, h->c, h->W, h->dense_acc != nullptr);
+    return RTS_OK;
+}
 
 int rts_otw_run(rts_otw *h, const void *live_dev, int live_dtype, int T_max, const int32_t *live_len_dev,
                 int mode, void *stream) {

@@ -288,3 +288,13 @@ class BatchedOTW(_BatchedHandle):
     @property
     def kernel_name(self):
         return nat.lib.rts_otw_kernel_name(self._h).decode()
+
+    def kernel(self, live_dtype=None):
+        """What a launch with live input of ``live_dtype`` runs (rts_otw_read_kernel; no GPU call): ``dict(window, ring,
+        pipelined, fill)`` with ``ring`` one of 'float', 'double', 'none', 'none-lean'.  ``None``: float64, the handle's
+        own history, which ``insert`` and ``push`` read whatever dtype their frames come in; for ``run`` pass the live
+        tensor's dtype."""
+        out = (ctypes.c_int32 * 4)()
+        code = nat.F64 if live_dtype is None else _np_dtype_code(live_dtype)
+        nat.check(nat.lib.rts_otw_read_kernel(self._h, code, out))
+        return dict(window=int(out[0]), ring=nat.OTW_RINGS[out[1]], pipelined=bool(out[2]), fill=bool(out[3]))

@@ -15,7 +15,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(n_trials=120, seed=7, verbose=True):
+CS = [53, 60, 64, 100, 116, 117, 130, 200, 244, 245, 300, 400, 500, 500, 501, 640, 1012, 1013, 1500, 2036]
+
+
+def run(n_trials=120, seed=7, verbose=True, pad_to=None, max_c=None, f64_only=False, expect=None):
+    """``pad_to``: tile each trial's streams up to that batch size (stream b carries the trial's stream b % batch; the
+    oracle still runs once per distinct stream, all pad_to streams are compared).  ``max_c`` / ``f64_only`` restrict the
+    band widths drawn from and the feature dtype; ``expect``: what ``BatchedOTW.kernel`` must report for every trial's
+    launch (a dict, e.g. dict(ring="none", pipelined=True)).  Returns the number of streams compared."""
     import torch
     import oracle
     from real_time_audio_sync_amd import otw_batch as ob, synth
@@ -24,14 +31,14 @@ def run(n_trials=120, seed=7, verbose=True):
     t0 = time.time()
     checked = 0
     for trial in range(n_trials):
-        c = int(rs.choice([53, 60, 64, 100, 116, 117, 130, 200, 244, 245, 300, 400, 500, 500, 501, 640, 1012, 1013, 1500, 2036]))
+        c = int(rs.choice([v for v in CS if max_c is None or v <= max_c]))
         n_ref = int(rs.choice([c // 2 + 3, c + 1, c + 40, 2 * c, 3 * c]))
         n_ref = min(n_ref, 1400 if c <= 1012 else 2600)
         mrc = int(rs.choice([1, 2, 3, 5]))
         variant = str(rs.choice(["otw", "otw", "livenote", "livenote_v2"]))
         euclid = bool(variant == "livenote_v2" and rs.rand() < 0.4)
         mode = "set_live" if rs.rand() < 0.25 else "insert"
-        f32 = bool(rs.rand() < 0.5) and not euclid
+        f32 = bool(rs.rand() < 0.5) and not euclid and not f64_only
         batch = int(rs.choice([1, 2, 4]))
         if rs.rand() < 0.15:
             ref, base_live = synth.synth_tie(n_ref, seed=seed * 1000 + trial)
@@ -57,9 +64,14 @@ def run(n_trials=120, seed=7, verbose=True):
             lives.append(lv)
         refx = synth._as_f32_values(np.abs(ref - 0.2)) if euclid else ref
         tdt = torch.float32 if f32 else torch.float64
-        eng = ob.BatchedOTW(refx, c, mrc, batch=batch, variant=variant, euclid=euclid, dtype=tdt)
-        lvd, lnd = eng.pack(lives, dtype=tdt)
+        B = batch if pad_to is None else max(int(pad_to), batch)
+        eng = ob.BatchedOTW(refx, c, mrc, batch=B, variant=variant, euclid=euclid, dtype=tdt)
+        if expect is not None:
+            got = eng.kernel(tdt)
+            assert all(got[k] == v for k, v in expect.items()), ("kernel", got, expect, trial, c, B)
+        lvd, lnd = eng.pack([lives[b % batch] for b in range(B)], dtype=tdt)
         eng.run(lvd, lnd, mode=mode)
+        states = eng.states() if B > batch else None
         for b, lv in enumerate(lives):
             o = oracle.OtwOracle(refx, c, mrc, vmap[variant], oracle.COST_EUCLID if euclid else oracle.COST_DOT)
             if mode == "set_live":
@@ -79,6 +91,13 @@ def run(n_trials=120, seed=7, verbose=True):
                 orb, ocb = o.bands()
                 assert np.array_equal(rb, orb, equal_nan=True) and np.array_equal(cb, ocb, equal_nan=True), ("bands", tag)
             checked += 1
+            # the copies of this stream further up the batch: the same path, state words and bands as the one just compared
+            for q in range(b + batch, B, batch):
+                assert np.array_equal(eng.path(q), o.path), ("path", tag, q)
+                assert np.array_equal(states[q][:14], states[b][:14]), ("state", tag, q)
+                if mode == "insert":
+                    assert all(np.array_equal(x, y, equal_nan=True) for x, y in zip(eng.bands(q), (orb, ocb))), ("bands", tag, q)
+                checked += 1
         eng.close()
         if verbose and trial % 100 == 99:
             print("trial %d, %d streams checked, %.0f s" % (trial + 1, checked, time.time() - t0), flush=True)

@@ -60,6 +60,7 @@ int main(void) {
     EXPECT(rts_otw_set_dense(NULL, NULL, NULL, NULL), RTS_ERR_INVALID);
     EXPECT(rts_otw_replay_dense(NULL, NULL, RTS_F64, 0, NULL, band, band, NULL), RTS_ERR_INVALID);
     EXPECT(rts_otw_set_waves(NULL, 8), RTS_ERR_INVALID);
+    EXPECT(rts_otw_read_kernel(NULL, RTS_F64, st), RTS_ERR_INVALID);
 
     /* ---- DTW ---- */
     size_t bytes = 0;
