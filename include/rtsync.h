@@ -770,6 +770,98 @@ int rts_live_columns_view(rts_live *h, double **cols_dev, int *cols_cap, int *co
 /* Samples pending per stream after everything submitted so far (the host-side mirror; exact). */
 int rts_live_pending(rts_live *h, long long *pending_host /* [B] */);
 
+/* ------------------------------------------------------------------------------------------
+ * Beats and labels: ground-truth tables on the device, the live beat words, the batched accuracy metric.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct rts_annot rts_annot;
+
+/* What the reference does with an alignment once it has one:
+ *   livenote_live.py:197-202  after every insert: (beat, label) = get_beat_and_label(ln.path[-1][1], ...) (:211-227);
+ *                             `if beat: self.beat = beat`, `if mus_label: self.mus_label = mus_label` -- both sticky
+ *   tests.py:59-137           test_simple.get_error: get_beat (:112-128) of every path point of a recording pair, the
+ *                             squared beat error and the percentages of points off by more than 1 / 3 / 5 / 10 beats / seconds
+ * The table of a piece: n >= 1 rows (time_s double, beat int32) of its ground-truth CSV (tests.py:45-57), optionally one
+ * flag per row: the row's label is a non-empty string (the label strings stay with the caller).  P tables lie back to back
+ * in one pool of n_rows rows, piece p being rows [first[p], first[p] + len[p]).
+ *
+ * Lookup of frame f >= 0 in a table (float64, the operations of get_beat in their order):
+ *   time = (double)f * frame_seconds                 (frame_seconds: 2048 / 22050. in the reference, computed by the caller)
+ *   i = the first row with time <= times[i]          (the reference's linear search for the first closed interval that holds
+ *                                                     the time finds the same row, the times being non-decreasing)
+ *   no such row:                 no beat (NaN), seg = -1
+ *   i == 0 and times[0] == 0:    beat = beats[0]
+ *   otherwise:                   beat = beats[i] - (times[i] - time) / (times[i] - start), start = 0.0 for i == 0, else times[i-1]
+ *   seg = 0 for i == 0, else i - 1                   (the label index of livenote_live.py:221, :225)
+ *
+ * rts_annot_create copies the tables to the current device, to which the handle then belongs, and returns when they are
+ * there; label_ok_host may be NULL (no flags: every row counts as labelled).
+ *   RTS_ERR_INVALID: NULL out or table pointer, frame_seconds not finite and > 0, n_rows outside [1, 2^31), P < 1, and per
+ *   piece in order, the message naming the piece and the row: len < 1, rows outside the pool, a time that is not finite, a
+ *   time below the one before it, a negative beat. */
+int rts_annot_create(int P, long long n_rows, const long long *first_host /* [P] */, const int32_t *len_host /* [P] */,
+                     const double *times_host /* [n_rows] */, const int32_t *beats_host /* [n_rows] */,
+                     const uint8_t *label_ok_host /* [n_rows] or NULL */, double frame_seconds, rts_annot **out);
+int rts_annot_destroy(rts_annot *h);
+
+/* The lookup for B streams of up to n_max frames each: entry (b, k), k < n_dev[b] (n_dev NULL: n_max; larger values are
+ * clamped to n_max), is frame frames_dev[b][k] + frame0_dev[b] (frame0_dev NULL: 0) looked up in piece piece_dev[b]; beat_dev
+ * [B][n_max] gets the beat, seg_dev (may be NULL) the label index.  A negative frames_dev entry or a piece outside [0, P)
+ * gives NaN / -1.  Entries behind n_dev[b] are not written.  Asynchronous on `stream`; allocates nothing, does not
+ * synchronise, writes only beat_dev and seg_dev.  n_max == 0 enqueues nothing.
+ *   RTS_ERR_INVALID: NULL handle, frames_dev, piece_dev or beat_dev, B outside [1, 65535], n_max < 0, another device current. */
+int rts_annot_beats(rts_annot *h, const int32_t *frames_dev /* [B][n_max] */, int n_max, const int32_t *n_dev /* [B] or NULL */,
+                    const int32_t *piece_dev /* [B] */, const int32_t *frame0_dev /* [B] or NULL */, int B,
+                    double *beat_dev /* [B][n_max] */, int32_t *seg_dev /* [B][n_max] or NULL */, void *stream);
+
+/* The metric of tests.py:59-137 (AlignmentError.stats in evaluate.py) for B paths in one launch.  path_dev / path_len_dev
+ * are laid out like the outputs of rts_dtw_paths and rts_otw_read_path: column 0 the live side (a), column 1 the reference
+ * side (b).  For the points (l, r) of pair b in order: l_beat from the table of piece0_dev[b], r_beat from that of
+ * piece1_dev[b]; a point is skipped when either beat is none or equal to 0.0 (`if l_beat and r_beat`); diff = |l_beat -
+ * r_beat|; sq_err_dev[b] is the sum of diff * diff in path order, one float64 addition after the other, bit for bit the
+ * Python loop's; seconds_off = |get_time(r_beat) - get_time(l_beat)| with get_time(x) read off the table of piece0 (the
+ * live side, for both beats: tests.py:130-137): whole = (int)x toward zero, sec = times[whole], and if whole + 1 < n, sec +=
+ * (x mod 1) * (times[whole + 1] - times[whole]), x mod 1 taking the sign of the divisor like Python's %.
+ * counts_dev[b] = { count of points that passed the skip rule, points with diff > 1, 3, 5, 10, points with seconds_off > 1,
+ * 3, 5, 10, index_errors }.  Deviation from the reference: a point one of whose `whole` is < 0 or >= n is counted in
+ * index_errors and in nothing else, the sum included (the reference raises IndexError for >= n and wraps round through
+ * Python's negative indexing at a beat of exactly -1.0).
+ * One workgroup per pair loops over the path; path_len <= 0 (the -1 fault marker of rts_dtw_paths included) gives zeros,
+ * larger than P_max is clamped to it.  A piece outside [0, P) has no beats.  Asynchronous, allocates nothing, does not
+ * synchronise, writes only sq_err_dev and counts_dev.
+ *   RTS_ERR_INVALID: NULL handle or table pointer, path_dev NULL with P_max > 0, P_max < 0, B < 1, another device current. */
+#define RTS_ANNOT_COUNTS 10
+int rts_annot_path_error(rts_annot *h, const int32_t *path_dev /* [B][P_max][2] */, int P_max,
+                         const int32_t *path_len_dev /* [B] */, const int32_t *piece0_dev /* [B] */,
+                         const int32_t *piece1_dev /* [B] */, int B, double *sq_err_dev /* [B] */,
+                         int32_t *counts_dev /* [B][RTS_ANNOT_COUNTS] */, void *stream);
+
+/* Beat and label of every microphone without a read-back: the last step of livenote_live.py's loop (:197-202).
+ * rts_live_annotate(h, annot, mask, piece, frame0): annot NULL switches annotations off (the other arguments are ignored and
+ * the words stay as they are).  Otherwise `annot` -- held by reference, it must outlive the handle or the next
+ * rts_live_annotate -- becomes the handle's tables, and every stream with mask_host[b] != 0 gets piece_host[b] (in [0, P)) and
+ * frame0_host[b] (>= 0; frame0_host NULL: 0), the frame of its piece at which its reference range starts: after a restart
+ * onto a range that starts inside a piece the path's indices are relative to the range.  A stream that was never selected has
+ * no piece.  The host tables are consumed when the call returns; the change is ordered on `stream` behind the feeds already
+ * submitted, like rts_live_restart.  Allowed at any time.  The first call with tables allocates a fourth host-mapped block
+ * (NaN / -1 / -1 for every stream) and two [B] device tables.
+ * With annotations on, every rts_live_submit enqueues ONE more launch, after the tracker push (and the watch launch) and
+ * before the publication of the status words, in a feed without columns too.  Per stream it takes the reference index of
+ * the last stored point of the tracker's path, as rts_otw_read_path / rts_wtw_read_path would return it (ln.path[-1][1]),
+ * looks frame0 + that index up in the stream's piece and updates the block:
+ *   beat[b]       changes iff the new beat is not none and != 0.0      (`if beat:`)
+ *   label[b]      the label index seg; changes iff seg >= 0 and the flag of row seg is set (no flags: always)   (`if mus_label:`)
+ *   ref_frame[b]  the frame of the piece just looked up, or -1 while the stream has no path point.
+ * rts_live_restart republishes NaN / -1 / -1 for the selected streams, rts_live_reset for all; both keep pieces and offsets.
+ * Either tracker, either feature kind, with the gate and on resampling handles.  With annotations off, or never switched
+ * on, a feed enqueues exactly what it enqueues without this function.
+ * rts_live_beats: the non-blocking look, like rts_live_confidence and with the same guarantee: when *feeds_done >= k, every
+ * word read reflects a feed >= k.  Any output pointer may be NULL.
+ *   RTS_ERR_INVALID: NULL handle; with tables: NULL mask_host or piece_host, a selected stream's piece outside [0, P) or
+ *   negative frame0, tables of another device, a failed handle; rts_live_beats before the first rts_live_annotate with tables. */
+int rts_live_annotate(rts_live *h, rts_annot *annot, const uint8_t *mask_host /* [B] */, const int32_t *piece_host /* [B] */,
+                      const int32_t *frame0_host /* [B] or NULL */, void *stream);
+int rts_live_beats(rts_live *h, double *beat /* [B] */, int32_t *label /* [B] */, int32_t *ref_frame /* [B] */, int *feeds_done);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,14 @@ _decl("rts_live_confidence", _i32, [_vp, _vp, _vp, _pi32])
 _decl("rts_live_gate", _i32, [_vp, ctypes.c_double, _i32])
 _decl("rts_live_levels", _i32, [_vp, _vp, _vp, _vp, _vp, _pi32])
 _decl("rts_live_gate_columns", _i32, [_vp, _i32, _vp, _i32, _pi32, _vp])
+_decl("rts_live_annotate", _i32, [_vp, _vp, _vp, _vp, _vp, _vp])
+_decl("rts_live_beats", _i32, [_vp, _vp, _vp, _vp, _pi32])
+
+ANNOT_COUNTS = 10  # RTS_ANNOT_COUNTS: count, off_beats[4], off_secs[4], index_errors
+_decl("rts_annot_create", _i32, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.POINTER(_vp)])
+_decl("rts_annot_destroy", _i32, [_vp])
+_decl("rts_annot_beats", _i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp])
+_decl("rts_annot_path_error", _i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp])
 
 
 def check(rc):

@@ -1,0 +1,175 @@
+"""Beats and labels on the device: the ground-truth tables of a repertoire (``AnnotationTables``), the lookup of the
+reference's ``get_beat`` / ``get_beat_and_label`` for whole batches of frames, and its accuracy metric
+(tests.py:59-137, ``evaluate.AlignmentError.stats``) for a whole corpus of paths in one launch.
+
+``evaluate.py`` stays the host form and the definition: every number here equals its number bit for bit, the squared beat
+error included (one float64 addition after the other, in path order).  ``LiveSession.annotate`` binds tables to a live
+session; the device then publishes beat and bar label of every microphone with each feed (csrc/annot.hip)."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _native as nat
+from . import evaluate
+
+THRESHOLDS = evaluate.AlignmentError.THRESHOLDS
+
+
+def _table(t):
+    """(times float64, beats int32, labels list | None) of a CSV path or a (times, beats[, labels]) tuple."""
+    if isinstance(t, str):
+        t = evaluate.read_annotations(t)
+    times = np.asarray(t[0], dtype=np.float64).reshape(-1)
+    beats = np.asarray(t[1]).reshape(-1)
+    if len(beats) and not np.array_equal(beats, beats.astype(np.int32)):
+        raise ValueError("beats must be integers that fit int32")
+    labels = t[2] if len(t) > 2 else None
+    if len(times) != len(beats) or (labels is not None and len(labels) != len(times)):
+        raise ValueError("times, beats and labels of a table must have one length")
+    return times, beats.astype(np.int32), (None if labels is None else [str(s) for s in labels])
+
+
+class AnnotationTables(object):
+    def __init__(self, tables, frame_seconds=evaluate.FRAME_SECONDS, device="cuda:0"):
+        """``tables``: one entry per piece, each a ground-truth CSV path (``time_seconds,beat[,label]``) or a tuple
+        ``(times, beats[, labels])``.  Times must be finite and non-decreasing, beats >= 0, every table needs a row
+        (rts_annot_create refuses anything else, naming piece and row).  ``labels[piece]`` holds the label strings of a
+        piece (None for a piece without a label column); only "is the label non-empty" goes to the device.
+        ``frame_seconds``: seconds per chroma frame, hop_size / fs."""
+        self.device = self.dev = torch.device(device)
+        if self.device.index is None:
+            self.device = self.dev = torch.device(self.device.type, torch.cuda.current_device())
+        parsed = [_table(t) for t in tables]
+        self.P = len(parsed)
+        self.times = [p[0] for p in parsed]
+        self.beat_rows = [p[1] for p in parsed]
+        self.labels = [p[2] for p in parsed]
+        self.frame_seconds = float(frame_seconds)
+        lens = np.array([len(t) for t in self.times], dtype=np.int32)
+        first = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)]).astype(np.int64) if self.P else np.zeros(0, np.int64)
+        times = np.ascontiguousarray(np.concatenate(self.times)) if self.P else np.zeros(0)
+        beats = np.ascontiguousarray(np.concatenate(self.beat_rows)) if self.P else np.zeros(0, np.int32)
+        flags = None
+        if any(l is not None for l in self.labels):   # a piece without a label column: every row counts as labelled
+            flags = np.ascontiguousarray(np.concatenate(
+                [np.ones(n, np.uint8) if l is None else np.array([1 if s else 0 for s in l], dtype=np.uint8).reshape(-1)
+                 for n, l in zip(lens, self.labels)]))
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib.rts_annot_create(self.P, len(times), first.ctypes.data, lens.ctypes.data, times.ctypes.data,
+                                               beats.ctypes.data, flags.ctypes.data if flags is not None else None,
+                                               self.frame_seconds, ctypes.byref(h)))
+        self._h = h
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _i32(self, v, n, what):
+        t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.int32).reshape(-1))
+        t = t.to(device=self.device, dtype=torch.int32).contiguous()
+        if t.numel() != n:
+            raise ValueError("%s: %d entries for %d streams / pairs" % (what, t.numel(), n))
+        return t
+
+    # ---- lookup -----------------------------------------------------------------------------------------------
+    @nat.on_device
+    def beats(self, frames, pieces, frame0=None, n=None):
+        """``get_beat`` of many frames.  ``frames``: a list of B integer arrays (one per stream, any lengths), or an
+        int32 device tensor [B][n_max] with ``n`` (valid entries per stream; None = all).  ``pieces``: the table of
+        every stream; ``frame0``: added to every frame of the stream (where its reference range starts inside its
+        piece).  A negative frame or a piece that does not exist has no beat.
+
+        List form: synchronises and returns a list of ``(beat float64 (NaN = none), seg int32 (-1 = none))`` arrays.
+        Tensor form: asynchronous; returns device tensors ``(beat [B][n_max], seg [B][n_max])`` whose entries behind
+        ``n[b]`` are not written."""
+        as_list = not torch.is_tensor(frames)
+        if as_list:
+            rows = [np.asarray(f, dtype=np.int32).reshape(-1) for f in frames]
+            B, n_max = len(rows), max([len(r) for r in rows] + [0])
+            host = np.zeros((B, max(n_max, 1)), dtype=np.int32)
+            for b, r in enumerate(rows):
+                host[b, :len(r)] = r
+            frames = torch.from_numpy(host).to(self.device)
+            n = [len(r) for r in rows]
+        frames = frames.to(device=self.device, dtype=torch.int32).contiguous()
+        B, n_max = int(frames.shape[0]), int(frames.shape[1])
+        pieces = self._i32(pieces, B, "pieces")
+        frame0 = self._i32(frame0, B, "frame0") if frame0 is not None else None
+        n = self._i32(n, B, "n") if n is not None else None
+        beat = torch.empty((B, n_max), dtype=torch.float64, device=self.device)
+        seg = torch.empty((B, n_max), dtype=torch.int32, device=self.device)
+        nat.check(nat.lib.rts_annot_beats(self._h, frames.data_ptr(), n_max, n.data_ptr() if n is not None else None,
+                                          pieces.data_ptr(), frame0.data_ptr() if frame0 is not None else None, B,
+                                          beat.data_ptr(), seg.data_ptr(), self._stream()))
+        if not as_list:
+            return beat, seg
+        beat, seg = beat.cpu().numpy(), seg.cpu().numpy()
+        return [(beat[b, :len(r)].copy(), seg[b, :len(r)].copy()) for b, r in enumerate(rows)]
+
+    # ---- metric -----------------------------------------------------------------------------------------------
+    @nat.on_device
+    def path_error_counts(self, path, path_len, pieces0, pieces1):
+        """The raw metric (rts_annot_path_error): device tensors ``path`` int32 [B][P_max][2] and ``path_len`` int32 [B]
+        (the layout of ``dtw.dtw_paths``: column 0 the live side, column 1 the reference side) -> device tensors
+        ``(squared_beat_error float64 [B], counts int32 [B][10])``, counts being count, points off by more than 1, 3,
+        5, 10 beats, by more than 1, 3, 5, 10 seconds, index errors.  Asynchronous."""
+        path = path.to(device=self.device, dtype=torch.int32).contiguous()
+        B, P_max = int(path.shape[0]), int(path.shape[1])
+        path_len = self._i32(path_len, B, "path_len")
+        pieces0, pieces1 = self._i32(pieces0, B, "pieces0"), self._i32(pieces1, B, "pieces1")
+        sq = torch.empty((B,), dtype=torch.float64, device=self.device)
+        counts = torch.empty((B, nat.ANNOT_COUNTS), dtype=torch.int32, device=self.device)
+        nat.check(nat.lib.rts_annot_path_error(self._h, path.data_ptr() if P_max else None, P_max, path_len.data_ptr(),
+                                               pieces0.data_ptr(), pieces1.data_ptr(), B, sq.data_ptr(), counts.data_ptr(),
+                                               self._stream()))
+        return sq, counts
+
+    def path_errors(self, paths, pieces0, pieces1):
+        """``evaluate.AlignmentError(ref_csv, live_csv, path).stats()`` of many recording pairs in one launch.
+        ``paths``: a list of (P_k, 2) integer arrays of path points (live frame, reference frame), or the device triple
+        ``(path, path_len, total)`` that ``dtw.dtw_paths`` returns (a pair, or ``dtw_subseq_paths``' longer tuple, does
+        as well: the first two entries are used).  ``pieces0[k]`` is the table of pair k's live side (column 0),
+        ``pieces1[k]`` that of its reference side.
+
+        Returns one dict per pair, shaped like ``stats()`` and equal to it (``count``, ``squared_beat_error``,
+        ``pct_off_beats``, ``pct_off_seconds``), or None for a pair none of whose points counted (where ``stats()``
+        raises ZeroDivisionError).  Raises IndexError, naming the pairs, when the integer part of a beat is no row of the
+        live side's table (``get_time``'s list index, tests.py:130-134).  Synchronises."""
+        if isinstance(paths, tuple) and len(paths) >= 2 and torch.is_tensor(paths[0]):
+            path, plen = paths[0], paths[1]
+        else:
+            arrs = [np.asarray(p, dtype=np.int32).reshape(-1, 2) for p in paths]
+            host = np.zeros((len(arrs), max([len(a) for a in arrs] + [1]), 2), dtype=np.int32)
+            for k, a in enumerate(arrs):
+                host[k, :len(a)] = a
+            path = torch.from_numpy(host).to(self.device)
+            plen = torch.tensor([len(a) for a in arrs], dtype=torch.int32, device=self.device)
+        sq, counts = self.path_error_counts(path, plen, pieces0, pieces1)
+        sq, counts = sq.cpu().numpy(), counts.cpu().numpy()
+        bad = [k for k in range(len(sq)) if counts[k, 9] > 0]
+        if bad:
+            raise IndexError("pair%s %s: the integer part of a beat is no row of the live side's table (%s path points)"
+                             % ("s" if len(bad) > 1 else "", ", ".join(str(k) for k in bad),
+                                ", ".join(str(int(counts[k, 9])) for k in bad)))
+        out = []
+        for k in range(len(sq)):
+            count = int(counts[k, 0])
+            if count == 0:
+                out.append(None)
+                continue
+            out.append(dict(count=count, squared_beat_error=float(sq[k]),
+                            pct_off_beats={t: float(v) / count * 100 for t, v in zip(THRESHOLDS, counts[k, 1:5].tolist())},
+                            pct_off_seconds={t: float(v) / count * 100 for t, v in zip(THRESHOLDS, counts[k, 5:9].tolist())}))
+        return out
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                torch.cuda.synchronize(self.device)
+            except Exception:
+                pass
+            nat.destroy_on(self.device, nat.lib.rts_annot_destroy, h)
+
+    __del__ = close

@@ -89,7 +89,31 @@ __attribute__((visibility("hidden"))) int resample_live_restart_enqueue(const rt
                                                                         int B, float *tail, long long *tot,
                                                                         hipStream_t s);
 
-#define RTS_HIP(call)                                                                         \
+// The annotation tables as the live handle uses them (csrc/annot.hip).  annot_select_enqueue: piece and frame offset of the
+// selected streams into two [B] device tables, the values travelling by value like a restart's selection.
+// annot_live_enqueue: the one launch a feed adds with annotations on -- per stream the reference index of the last stored
+// point of the tracker's path ([B][path_cap][2], its count in word st_n_path of the stream's state), offset by frame0 and
+// looked up in the stream's piece, into three host-mapped tables (sticky: see include/rtsync.h, rts_live_annotate).
+struct AnnotLive {
+    const int32_t *state;  // the tracker's state words, state_len per stream
+    int state_len, st_n_path;
+    const int32_t *path;
+    int path_cap;
+    const int32_t *piece, *frame0;  // [B] device
+    double *beat;                   // [B] host-mapped
+    int32_t *label, *ref_frame;     // [B] host-mapped
+    int B;
+};
+__attribute__((visibility("hidden"))) int annot_pieces(const rts_annot *a);
+__attribute__((visibility("hidden"))) int annot_device(const rts_annot *a);
+__attribute__((visibility("hidden"))) int annot_select_enqueue(int B, const uint8_t *mask_host, const int32_t *piece_host,
+                                                               const int32_t *frame0_host, int32_t *piece_dev,
+                                                               int32_t *frame0_dev, hipStream_t s);
+__attribute__((visibility("hidden"))) int annot_live_enqueue(const rts_annot *a, const AnnotLive &g, hipStream_t s);
+// The path buffer of a WTW handle, [B][*path_cap][2] (rts_otw_device_views is the OTW counterpart).
+__attribute__((visibility("hidden"))) void wtw_path_view(const rts_wtw *h, const int32_t **path, int *path_cap);
+
+#define RTS_HIP(call)                                                                        \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
         if (e_ != hipSuccess)                                                                 \

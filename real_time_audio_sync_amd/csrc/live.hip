@@ -31,6 +31,8 @@
 //   rts_otw_push | rts_wtw_push   the columns into the alignment state (insert semantics, column by column)
 //   rts_otw_path_cost     only after rts_live_watch(K > 0): the tracker's mean cell cost over its last K path points into a
 //                         second host-mapped block -- rts_live_confidence reads it like rts_live_poll reads the status words
+//   annot_live_kernel     only after rts_live_annotate with tables (csrc/annot.hip): beat and label of the reference frame of
+//                         every tracker's last path point into a fourth host-mapped block -- rts_live_beats reads it
 //   live_compact_kernel   drop hop * n_frames consumed samples per stream (data = data[2048:], livenote_live.py:208),
 //                         and publish {status, live position, ref position, feed number} of every stream into
 //                         host-mapped memory -- rts_live_poll reads those words without touching the stream.
@@ -73,6 +75,9 @@ struct LiveArgs {
     // rts_live_watch (NULL until its first call): host-mapped confidence words, republished by live_restart_kernel
     double *conf_mean;           // [B]
     int32_t *conf_n;             // [B]
+    // rts_live_annotate (NULL until its first call with tables): host-mapped beat words, republished by live_restart_kernel
+    double *ann_beat;            // [B]
+    int32_t *ann_label, *ann_ref;  // [B]
 };
 
 __device__ __forceinline__ void live_publish(const LiveArgs &g, int b) {
@@ -195,6 +200,11 @@ __global__ void live_restart_kernel(RestartSel sel, LiveArgs g, GateArgs t) {
         g.conf_n[b] = 0;
         g.conf_mean[b] = __longlong_as_double(0x7ff8000000000000LL);
     }
+    if (g.ann_beat) {  // nothing looked up yet
+        g.ann_beat[b] = __longlong_as_double(0x7ff8000000000000LL);
+        g.ann_label[b] = -1;
+        g.ann_ref[b] = -1;
+    }
     if (t.q) live_gate_restart(t, b);
     __threadfence_system();
 }
@@ -243,6 +253,12 @@ struct rts_live {
     int gate_on;
     rts::GateArgs gate;
     unsigned char *gate_host;
+    // rts_live_annotate: the tables in use (NULL = off), what its launch takes (the tracker's path and the two [B] device
+    // tables, from the first call with tables) and the fourth host-mapped block, double beat[B] then int32 label[B], ref_frame[B]
+    rts_annot *annot;
+    rts::AnnotLive ann;
+    int32_t *ann_tables;  // piece[B] then frame0[B] on the device
+    unsigned char *ann_host;
 };
 
 namespace rts {
@@ -271,6 +287,20 @@ static void live_conf_clear(rts_live *h) {
 static int live_watch_launch(rts_live *h, void *stream) {
     if (h->watch_k < 1) return RTS_OK;
     return rts_otw_path_cost(h->otw, h->watch_k, h->args.conf_mean, h->args.conf_n, nullptr, stream);
+}
+
+static void live_annot_clear(rts_live *h) {
+    double *beat = reinterpret_cast<double *>(h->ann_host);
+    int32_t *words = reinterpret_cast<int32_t *>(beat + h->geo.B);
+    for (int b = 0; b < h->geo.B; b++) beat[b] = __builtin_nan("");
+    for (int b = 0; b < 2 * h->geo.B; b++) words[b] = -1;
+}
+
+// With annotations on, one more launch per feed behind the watch launch and before live_compact_kernel, like the watch
+// launch and for the same reason: the compaction writes the feed number last.
+static int live_annot_launch(rts_live *h, hipStream_t s) {
+    if (!h->annot) return RTS_OK;
+    return annot_live_enqueue(h->annot, h->ann, s);
 }
 
 static void live_gate_clear(rts_live *h) {
@@ -310,7 +340,8 @@ static int live_refuse(const rts_live *h, LiveRefusal why, const FeedPlan &p, co
 // n_max is 0, rts_wtw_push after its entry check, which wtw.py:76-77 runs on every insert(), new column or not; in diff
 // mode the tracker is pushed only when some stream hands it a column (n_max_diff > 0; the rows still lie n_max apart);
 // the watch launch follows rts_live_watch, the two gate launches rts_live_gate: with the gate on the push takes the gated
-// buffer and its counts, and nothing else moves.  The compaction and the publication end every feed.
+// buffer and its counts, and nothing else moves; the beat launch follows rts_live_annotate.  The compaction and the
+// publication end every feed.
 static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, void *stream) {
     const int B = h->geo.B;
     hipStream_t s = (hipStream_t)stream;
@@ -358,6 +389,7 @@ static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, 
         rc != RTS_OK)
         return rc;
     if (int rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
+    if (int rc = live_annot_launch(h, s); rc != RTS_OK) return rc;
     hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -412,12 +444,13 @@ int rts_live_destroy(rts_live *h) {
     void *dev[] = {h->args.buf,   h->args.pending,   h->args.n_samples, h->args.n_frames, h->args.cols,    h->args.dcols,
                    h->args.carry, h->args.has_carry, h->args.n_cols,    h->rs_stage, h->rs_tail, h->rs_tot,
                    h->gate.lev,   h->gate.gcols,     h->gate.n_gated,   h->gate.q,   h->gate.prev, h->gate.seen,
-                   h->gate.passed, h->gate.ord};
+                   h->gate.passed, h->gate.ord, h->ann_tables};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     if (h->pub_host) (void)hipHostFree(h->pub_host);
     if (h->conf_host) (void)hipHostFree(h->conf_host);
     if (h->gate_host) (void)hipHostFree(h->gate_host);
+    if (h->ann_host) (void)hipHostFree(h->ann_host);
     free(h);  // the mirrors with it
     return RTS_OK;
 }
@@ -568,6 +601,7 @@ int rts_live_reset(rts_live *h, void *stream) {
     memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * nB);
     if (h->conf_host) live_conf_clear(h);
     if (h->gate_host) live_gate_clear(h);
+    if (h->ann_host) live_annot_clear(h);
     memset(h->used, 0, sizeof(h->used));
     h->slot = -1;
     h->feeds = 0;
@@ -713,6 +747,90 @@ int rts_live_confidence(rts_live *h, double *mean_cost, int32_t *n_points, int *
     const int fd = live_read_published(h, [=](int b) {
         if (mean_cost) mean_cost[b] = mean[b];
         if (n_points) n_points[b] = n[b];
+    });
+    if (feeds_done) *feeds_done = fd;
+    return RTS_OK;
+}
+
+int rts_live_annotate(rts_live *h, rts_annot *annot, const uint8_t *mask_host, const int32_t *piece_host,
+                      const int32_t *frame0_host, void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!annot) {  // off: the words stay as they are
+        h->annot = nullptr;
+        return RTS_OK;
+    }
+    if (int rc = live_usable(h); rc != RTS_OK) return rc;
+    if (!mask_host || !piece_host) return set_error(RTS_ERR_INVALID, "mask_host and piece_host must be given with tables");
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    if (annot_device(annot) != h->device)
+        return set_error(RTS_ERR_INVALID, "the tables live on device %d, the handle on device %d", annot_device(annot), h->device);
+    const int B = h->geo.B, P = annot_pieces(annot);
+    for (int b = 0; b < B; b++) {
+        if (!mask_host[b]) continue;
+        if (piece_host[b] < 0 || piece_host[b] >= P)
+            return set_error(RTS_ERR_INVALID, "stream %d: piece %d outside [0, %d)", b, piece_host[b], P);
+        if (frame0_host && frame0_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: negative frame0 %d", b, frame0_host[b]);
+    }
+    if (!h->ann_host) {
+        const size_t nB = (size_t)B;
+        int32_t *tables = nullptr;
+        unsigned char *host = nullptr;
+        void *dev = nullptr;
+        hipError_t e = hipMalloc((void **)&tables, sizeof(int32_t) * 2 * nB);
+        if (e == hipSuccess) e = hipMemset(tables, 0xff, sizeof(int32_t) * nB);  // no piece
+        if (e == hipSuccess) e = hipMemset(tables + nB, 0, sizeof(int32_t) * nB);
+        if (e == hipSuccess)
+            e = hipHostMalloc((void **)&host, (sizeof(double) + 2 * sizeof(int32_t)) * nB, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&dev, host, 0);
+        if (e != hipSuccess) {
+            if (tables) (void)hipFree(tables);
+            if (host) (void)hipHostFree(host);
+            return set_error(RTS_ERR_HIP, "rts_live_annotate: %s", hipGetErrorString(e));
+        }
+        AnnotLive a = {};
+        a.state = h->args.state;
+        a.state_len = h->args.state_len;
+        a.st_n_path = h->otw ? RTS_ST_N_PATH : RTS_WTW_ST_N_PATH;
+        if (h->otw) {
+            int32_t *path = nullptr;
+            (void)rts_otw_device_views(h->otw, &path, &a.path_cap, nullptr);
+            a.path = path;
+        } else {
+            wtw_path_view(h->wtw, &a.path, &a.path_cap);
+        }
+        a.piece = tables;
+        a.frame0 = tables + nB;
+        a.beat = reinterpret_cast<double *>(dev);
+        a.label = reinterpret_cast<int32_t *>(a.beat + nB);
+        a.ref_frame = a.label + nB;
+        a.B = B;
+        h->ann = a;
+        h->ann_tables = tables;
+        h->ann_host = host;
+        h->args.ann_beat = a.beat;
+        h->args.ann_label = a.label;
+        h->args.ann_ref = a.ref_frame;
+        live_annot_clear(h);
+    }
+    if (int rc = annot_select_enqueue(B, mask_host, piece_host, frame0_host, h->ann_tables, h->ann_tables + B, (hipStream_t)stream);
+        rc != RTS_OK)
+        return rc;
+    h->annot = annot;
+    return RTS_OK;
+}
+
+int rts_live_beats(rts_live *h, double *beat, int32_t *label, int32_t *ref_frame, int *feeds_done) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!h->ann_host) return set_error(RTS_ERR_INVALID, "rts_live_beats before any rts_live_annotate with tables");
+    const volatile double *bt = reinterpret_cast<const volatile double *>(h->ann_host);
+    const volatile int32_t *w = reinterpret_cast<const volatile int32_t *>(h->ann_host + sizeof(double) * (size_t)h->geo.B);
+    const int B = h->geo.B;
+    const int fd = live_read_published(h, [=](int b) {
+        if (beat) beat[b] = bt[b];
+        if (label) label[b] = w[b];
+        if (ref_frame) ref_frame[b] = w[B + b];
     });
     if (feeds_done) *feeds_done = fd;
     return RTS_OK;

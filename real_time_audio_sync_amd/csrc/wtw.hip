@@ -908,6 +908,10 @@ static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win
 
 int wtw_batch(const rts_wtw *h) { return h->B; }
 int wtw_history(const rts_wtw *h) { return h->args.live_stride; }
+void wtw_path_view(const rts_wtw *h, const int32_t **path, int *path_cap) {
+    *path = h->args.path;
+    *path_cap = h->args.path_cap;
+}
 
 }  // namespace rts
 

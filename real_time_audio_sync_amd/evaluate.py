@@ -22,6 +22,20 @@ def read_ground_truth(csv_path):
     return times, beats
 
 
+def read_annotations(csv_path):
+    """-> (times [s], beats [int], labels [str] | None) from a Songs/**.csv file: ``read_ground_truth`` plus the third
+    column, the bar labels the live program shows (livenote_live.py:101-112).  None when the file has two columns only
+    (Songs/bach/*.csv); a row without a third field in a file that has them reads ''."""
+    times, beats, labels, any_label = [], [], [], False
+    with open(csv_path) as fh:
+        for row in csv.reader(fh):
+            times.append(float(row[0]))
+            beats.append(int(row[1]))
+            labels.append(row[2] if len(row) > 2 else "")
+            any_label = any_label or len(row) > 2
+    return times, beats, (labels if any_label else None)
+
+
 def get_beat(sample, gt_times, gt_beats, frame_seconds=FRAME_SECONDS):
     """Fractional beat of chroma frame ``sample``: linear interpolation between annotated beat times,
     the stretch before the first annotation being interpolated from time zero; None past the last

@@ -120,6 +120,8 @@ class LiveSession(object):
         self.fs = int(fs)
         self._gated = False                                  # gate() has made the handle's gate buffers
         self._direct = np.zeros(self.B, dtype=np.int64)      # frames reacquire() pushed into the tracker since a restart
+        self._annot = None                                   # the AnnotationTables annotate() bound, while they are on
+        self._annot_of = self._annot_piece = self._last_tables = None   # pool frame -> table; table of each stream; for label_text
 
     # ---- feeding ----------------------------------------------------------------------------------------------
     def _stream(self):
@@ -247,6 +249,85 @@ class LiveSession(object):
             self.otw._version += 1
         eng._restarted(first, lens, pieces)
         self._direct[mask != 0] = 0
+        if self._annot is not None and pieces:   # new piece / offset: the beats stay in the piece's own time
+            self._annotate_streams(sorted(pieces))
+
+    # ---- beats and labels -------------------------------------------------------------------------------------
+    def _annotate_streams(self, streams):
+        """rts_live_annotate for the listed streams, piece and frame offset taken from what the tracker follows now."""
+        eng = self.otw or self.wtw
+        mask, piece, frame0 = np.zeros(self.B, np.uint8), np.zeros(self.B, np.int32), np.zeros(self.B, np.int32)
+        for b in streams:
+            mask[b] = 1
+            if self._conv is not None:
+                f, n = eng._piece[b]
+                if f not in self._annot_of:
+                    raise ValueError("stream %d follows a reference that piece_of gives no table for" % b)
+                piece[b], frame0[b] = self._annot_of[f], n - int(eng.ref_lens[b])
+        nat.check(nat.lib.rts_live_annotate(self._h, self._annot._h, mask.ctypes.data, piece.ctypes.data,
+                                            frame0.ctypes.data, self._stream()))
+        self._annot_piece[mask != 0] = piece[mask != 0]
+
+    @nat.on_device
+    def annotate(self, tables, piece_of=None):
+        """Beat and bar label of every microphone with each feed, without a read-back (rts_live_annotate): the last step of
+        the reference's loop, ``get_beat_and_label(ln.path[-1][1])`` after every insert (livenote_live.py:197-202).
+        ``tables``: an ``annotate.AnnotationTables`` of this device; it must stay open while it is in use here.
+        ``piece_of``: with per-stream references, a list of ``(reference, table index)`` pairs, ``reference`` being an
+        object given at create (``ref_chroma`` list / ``extra_refs``, matched by identity like ``restart`` does); every
+        reference a stream follows needs an entry.  A single-reference session uses table 0.  ``restart`` with ``refs`` /
+        ``offsets`` and ``reacquire`` re-issue the call for their streams with the new piece and the offset as the
+        piece's frame at which the range starts, so beats stay in the piece's own time after "follow from bar 50".
+        With annotations on, each feed enqueues one more small launch; ``beats()`` reads its words.  ``annotate(None)``
+        switches annotations off: the words stay as they are.  Allowed at any time; ordered behind the feeds already
+        submitted."""
+        if tables is None:
+            nat.check(nat.lib.rts_live_annotate(self._h, None, None, None, None, self._stream()))
+            self._annot = None
+            return
+        of = {}
+        if self._conv is not None:
+            eng = self.otw or self.wtw
+            for r, idx in (piece_of or ()):
+                if id(r) not in self._conv:
+                    raise ValueError("piece_of names a reference that was not given at create (ref_chroma list / extra_refs)")
+                if not 0 <= int(idx) < tables.P:
+                    raise ValueError("piece_of: table %d outside [0, %d)" % (int(idx), tables.P))
+                of[eng._pool[id(self._conv[id(r)][1])][1]] = int(idx)
+        elif piece_of is not None:
+            raise ValueError("piece_of needs per-stream references (a list as ref_chroma)")
+        prev = self._annot, self._annot_of
+        self._annot, self._annot_of, self._last_tables = tables, of, tables
+        if self._annot_piece is None:
+            self._annot_piece = np.full(self.B, -1, dtype=np.int32)
+            self._beat = np.zeros(self.B, dtype=np.float64)
+            self._beat_words = np.zeros((2, self.B), dtype=np.int32)
+        try:
+            self._annotate_streams(range(self.B))
+        except Exception:
+            self._annot, self._annot_of = prev
+            raise
+
+    def beats(self):
+        """Non-blocking: {'beat' float64 [B] (NaN: none yet), 'label' int32 [B] (index into the piece's labels, -1: none
+        yet), 'label_text' list (the label string, None where there is none or the piece has no label column),
+        'ref_frame' int32 [B] (the frame of the piece looked up last, -1 while the stream has no path point),
+        'feeds_done'} as last published by the device.  Beat and label are sticky like the reference's display: a feed
+        changes the beat only to a beat that is neither none nor 0.0, and the label only to a non-empty one.  Needs
+        ``annotate(tables)`` first."""
+        done = ctypes.c_int()
+        have = self._annot_piece is not None
+        nat.check(nat.lib.rts_live_beats(self._h, self._beat.ctypes.data if have else None,
+                                         self._beat_words[0].ctypes.data if have else None,
+                                         self._beat_words[1].ctypes.data if have else None, ctypes.byref(done)))
+        label = self._beat_words[0].copy()
+        tab = self._last_tables
+        text = []
+        for b in range(self.B):
+            names = tab.labels[self._annot_piece[b]] if tab is not None and self._annot_piece[b] >= 0 else None
+            text.append(names[label[b]] if names is not None and 0 <= label[b] < len(names) else None)
+        return dict(beat=self._beat.copy(), label=label, label_text=text, ref_frame=self._beat_words[1].copy(),
+                    feeds_done=done.value)
 
     def locate(self, queries, q_len=None, euclid=None):
         """Where in the repertoire is each microphone?  ``BatchedOTW.locate`` / ``BatchedWTW.locate`` of the bound
