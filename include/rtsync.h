@@ -862,6 +862,78 @@ int rts_live_annotate(rts_live *h, rts_annot *annot, const uint8_t *mask_host /*
                       const int32_t *frame0_host /* [B] or NULL */, void *stream);
 int rts_live_beats(rts_live *h, double *beat /* [B] */, int32_t *label /* [B] */, int32_t *ref_frame /* [B] */, int *feeds_done);
 
+/* ------------------------------------------------------------------------------------------
+ * Tempo: the slope of a path over a trailing window, for offline paths, trackers and live feeds.
+ * ------------------------------------------------------------------------------------------ */
+/* The engine says where a performer is; this says how fast.  The reference's live loop prints the wall-clock frame next to
+ * ln.path[-1] after every insert (livenote_live.py:203-206) and leaves the comparison to the operator.
+ *
+ * A path is n_pts stored points (x_k, y_k) = (live, reference) of int32.  The window at point i with length K is the points
+ * p0 = max(0, i - K + 1) .. i, n = i - p0 + 1 of them.  A point is bad when x is outside [0, x_limit) or y outside
+ * [0, y_limit); a window that contains a bad point has slope = pos = NaN.  Otherwise, all sums exact integers:
+ *   Sx = sum x, Sy = sum y, Sxx = sum x^2, Sxy = sum x y over the window
+ *   den = n Sxx - Sx^2, num = n Sxy - Sx Sy            (translation invariant)
+ *   slope = den > 0 ? (double)num / (double)den : NaN    (two int64 -> float64 conversions, round to nearest even, one
+ *                                                         division; den == 0: n < 2, or the live index never moves)
+ *   Sx' = Sx - n x_i, Sy' = Sy - n y_i                   (relative to the newest point)
+ *   pos = ((double)y_i + ((double)Sy' - slope * (double)Sx') / (double)n) + slope * ahead
+ * every operation rounded on its own, in this order: the regression line read at the newest live frame plus `ahead` frames.
+ * NaN is the canonical quiet NaN 0x7ff8000000000000.  The windows are trailing, so entry i of a curve is what a live
+ * tracker would have published when point i was its newest.  2 <= K <= 1024; `ahead` finite.
+ * The results are exact while num and den fit in int64; K^2 * x_limit * y_limit >= 2^63 is refused (RTS_ERR_UNSUPPORTED) on
+ * the host, from the limits alone.
+ *
+ * rts_path_tempo: the curve of B paths laid out like the outputs of rts_dtw_paths and rts_otw_read_path.  slope_dev[b][i]
+ * and pos_dev[b][i] (pos_dev may be NULL) for i < len_dev[b]; entries behind are not written; len <= 0 (the -1 fault marker
+ * of rts_dtw_paths included) writes nothing, len > P_max is clamped.  One workgroup per path.  Asynchronous on `stream`;
+ * allocates nothing, does not synchronise, writes only the two outputs.  P_max == 0 enqueues nothing.
+ *   RTS_ERR_INVALID: NULL len_dev or slope_dev, path_dev NULL with P_max > 0, P_max < 0, B < 1, K outside [2, 1024], `ahead`
+ *   not finite, a limit < 1. */
+int rts_path_tempo(const int32_t *path_dev /* [B][P_max][2] */, int P_max, const int32_t *len_dev /* [B] */, int B, int K,
+                   double ahead, long long x_limit, long long y_limit, double *slope_dev /* [B][P_max] */,
+                   double *pos_dev /* [B][P_max] or NULL */, void *stream);
+
+/* The window over the last n = min(K, stored points) points of every stream's own path, as rts_otw_read_path /
+ * rts_wtw_read_path would return it (the stored count clamped to the path's capacity): slope_dev[b], pos_dev[b] (may be
+ * NULL) and n_dev[b], the window length used -- 0 for a fresh or just-restarted stream, whose outputs are NaN.  Limits:
+ * x_limit = 2 N_b, y_limit = N_b, N_b the length of the stream's own reference (per-stream references included); for WTW
+ * that is the stream's live capacity 2 M_b and its reference length M_b.  Reads the handle only; one launch, asynchronous.
+ *   RTS_ERR_INVALID: NULL handle, slope_dev or n_dev, K outside [2, 1024], `ahead` not finite, another device current.
+ *   RTS_ERR_UNSUPPORTED: the overflow rule with the handle's longest reference. */
+int rts_otw_tempo(rts_otw *h, int K, double ahead, double *slope_dev /* [B] */, double *pos_dev /* [B] or NULL */,
+                  int32_t *n_dev /* [B] */, void *stream);
+int rts_wtw_tempo(rts_wtw *h, int K, double ahead, double *slope_dev /* [B] */, double *pos_dev /* [B] or NULL */,
+                  int32_t *n_dev /* [B] */, void *stream);
+
+/* Slope to beats per minute through the annotation tables, conventions as rts_annot_beats: entry (b, k), k < n_dev[b], is
+ * frame frames_dev[b][k] + frame0_dev[b] of piece piece_dev[b] with slope slope_dev[b][k] (reference frames per live frame).
+ * With i, start, times[i] what the lookup of that frame uses: bpm = (slope * 60.0) / (times[i] - start), one beat per table
+ * segment like get_beat.  NaN: no row, i == 0 and times[0] == 0, times[i] == start, a NaN slope, a negative frames_dev entry,
+ * a piece outside [0, P).  Entries behind n_dev[b] are not written.  Asynchronous, allocates nothing, writes only bpm_dev.
+ *   RTS_ERR_INVALID: NULL handle, frames_dev, slope_dev, piece_dev or bpm_dev, B outside [1, 65535], n_max < 0, another
+ *   device current. */
+int rts_annot_bpm(rts_annot *h, const int32_t *frames_dev /* [B][n_max] */, const double *slope_dev /* [B][n_max] */, int n_max,
+                  const int32_t *n_dev /* [B] or NULL */, const int32_t *piece_dev /* [B] */,
+                  const int32_t *frame0_dev /* [B] or NULL */, int B, double *bpm_dev /* [B][n_max] */, void *stream);
+
+/* Tempo of every microphone without a read-back.  rts_live_follow_tempo(h, K, ahead): K = 0 switches it off (the words stay
+ * as they are), 2 <= K <= 1024 on.  The first call with K > 0 allocates a fifth host-mapped block, double slope[B], pos[B],
+ * bpm[B] then int32 n[B], NaN / NaN / NaN / 0 for every stream.  With it on, every rts_live_submit enqueues ONE more launch,
+ * after the tracker push, the watch launch and the beat launch and before the publication of the status words, in a feed
+ * without columns too: rts_otw_tempo / rts_wtw_tempo of the bound tracker into that block, and bpm[b] by the rule of
+ * rts_annot_bpm from the stream's piece and frame0 as rts_live_annotate set them, at frame0 + the last stored point's
+ * reference index -- the frame rts_live_beats reports; NaN while annotations are off or the stream has no piece.  With the
+ * gate on (rts_live_gate) live indices count the columns the tracker received, so the slope is in reference frames per
+ * column handed on; rts_live_gate_columns maps them back.  rts_live_restart republishes NaN / NaN / NaN / 0 for the selected
+ * streams, rts_live_reset for all.  A handle that never calls it enqueues exactly what it enqueues without this function.
+ * rts_live_tempo: the non-blocking look, like rts_live_confidence and with the same guarantee: when *feeds_done >= k, every
+ * word read reflects a feed >= k.  Any output pointer may be NULL.
+ *   RTS_ERR_INVALID: NULL handle, a failed handle, K outside {0} and [2, 1024], `ahead` not finite, another device current;
+ *   rts_live_tempo before the first rts_live_follow_tempo(K > 0).  RTS_ERR_UNSUPPORTED: the overflow rule. */
+int rts_live_follow_tempo(rts_live *h, int K, double ahead);
+int rts_live_tempo(rts_live *h, double *slope /* [B] */, double *pos /* [B] */, double *bpm /* [B] */, int32_t *n /* [B] */,
+                   int *feeds_done);
+
 #ifdef __cplusplus
 }
 #endif

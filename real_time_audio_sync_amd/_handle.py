@@ -59,6 +59,22 @@ class _BatchedHandle:
         return out
 
     @nat.on_device
+    def tempo(self, K=64, ahead=0.0):
+        """How fast is every stream going (rts_otw_tempo / rts_wtw_tempo)?  The least-squares line through the last
+        ``n = min(K, path points)`` points of every stream's own path: numpy ``(slope float64 [B], pos float64 [B], n int32
+        [B])``.  ``slope`` is reference frames per live frame (1.0: the reference's tempo); ``pos`` the line read at the
+        newest live frame plus ``ahead`` frames, in reference frames.  NaN for a stream with fewer than two points, one
+        whose live index did not move inside the window, and one with a point outside its reference.  ``2 <= K <= 1024``.
+        The definition (exact integer sums, one rounding per float64 operation) is include/rtsync.h's; ``tempo.path_tempo``
+        gives the whole curve of a path, whose entry i is this call's answer when point i was the newest.  Synchronises."""
+        slope = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        pos = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        n = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        nat.check(self._fn("tempo")(self._h, int(K), float(ahead), slope.data_ptr(), pos.data_ptr(), n.data_ptr(),
+                                    self._stream()))
+        return slope.cpu().numpy(), pos.cpu().numpy(), n.cpu().numpy()
+
+    @nat.on_device
     def restart(self, streams, refs=None, offsets=None):
         """Put the listed streams back to the start while the others keep running (the subclasses document ``refs`` and
         ``offsets``)."""

@@ -153,6 +153,14 @@ _decl("rts_annot_destroy", _i32, [_vp])
 _decl("rts_annot_beats", _i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp])
 _decl("rts_annot_path_error", _i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp])
 
+TEMPO_MIN_K, TEMPO_MAX_K = 2, 1024  # kTempoMinK, kTempoMaxK (csrc/tempo_plan.h)
+_decl("rts_path_tempo", _i32, [_vp, _i32, _vp, _i32, _i32, ctypes.c_double, _i64, _i64, _vp, _vp, _vp])
+_decl("rts_otw_tempo", _i32, [_vp, _i32, ctypes.c_double, _vp, _vp, _vp, _vp])
+_decl("rts_wtw_tempo", _i32, [_vp, _i32, ctypes.c_double, _vp, _vp, _vp, _vp])
+_decl("rts_annot_bpm", _i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp])
+_decl("rts_live_follow_tempo", _i32, [_vp, _i32, ctypes.c_double])
+_decl("rts_live_tempo", _i32, [_vp, _vp, _vp, _vp, _vp, _pi32])
+
 
 def check(rc):
     if rc != 0:

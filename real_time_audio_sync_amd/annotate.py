@@ -107,6 +107,44 @@ class AnnotationTables(object):
         beat, seg = beat.cpu().numpy(), seg.cpu().numpy()
         return [(beat[b, :len(r)].copy(), seg[b, :len(r)].copy()) for b, r in enumerate(rows)]
 
+    @nat.on_device
+    def bpm(self, frames, slopes, pieces, frame0=None, n=None):
+        """Slopes of a path (reference frames per live frame: ``tempo.path_tempo``, ``BatchedOTW.tempo``) in beats per
+        minute (rts_annot_bpm): ``(slope * 60.0) / (times[i] - start)`` with ``i`` and ``start`` what ``beats()`` uses for
+        the same frame, one beat per table segment.  NaN where the frame has no row, the row has no width, or the slope is
+        NaN.  ``frames`` / ``slopes``: lists of B arrays of equal lengths per stream (synchronises, returns a list of
+        float64 arrays), or device tensors int32 / float64 [B][n_max] with ``n`` (asynchronous, returns a device tensor
+        whose entries behind ``n[b]`` are not written).  ``pieces`` / ``frame0`` as for ``beats()``."""
+        as_list = not torch.is_tensor(frames)
+        if as_list:
+            rows = [np.asarray(f, dtype=np.int32).reshape(-1) for f in frames]
+            srows = [np.asarray(s, dtype=np.float64).reshape(-1) for s in slopes]
+            if len(rows) != len(srows) or any(len(r) != len(s) for r, s in zip(rows, srows)):
+                raise ValueError("frames and slopes must have the same lengths")
+            B, n_max = len(rows), max([len(r) for r in rows] + [0])
+            host, shost = np.zeros((B, max(n_max, 1)), dtype=np.int32), np.zeros((B, max(n_max, 1)), dtype=np.float64)
+            for b, (r, s) in enumerate(zip(rows, srows)):
+                host[b, :len(r)] = r
+                shost[b, :len(s)] = s
+            frames, slopes = torch.from_numpy(host).to(self.device), torch.from_numpy(shost).to(self.device)
+            n = [len(r) for r in rows]
+        frames = frames.to(device=self.device, dtype=torch.int32).contiguous()
+        slopes = slopes.to(device=self.device, dtype=torch.float64).contiguous()
+        if tuple(frames.shape) != tuple(slopes.shape) or frames.dim() != 2:
+            raise ValueError("frames and slopes must both be [B][n_max]")
+        B, n_max = int(frames.shape[0]), int(frames.shape[1])
+        pieces = self._i32(pieces, B, "pieces")
+        frame0 = self._i32(frame0, B, "frame0") if frame0 is not None else None
+        n = self._i32(n, B, "n") if n is not None else None
+        out = torch.empty((B, n_max), dtype=torch.float64, device=self.device)
+        nat.check(nat.lib.rts_annot_bpm(self._h, frames.data_ptr(), slopes.data_ptr(), n_max,
+                                        n.data_ptr() if n is not None else None, pieces.data_ptr(),
+                                        frame0.data_ptr() if frame0 is not None else None, B, out.data_ptr(), self._stream()))
+        if not as_list:
+            return out
+        out = out.cpu().numpy()
+        return [out[b, :len(r)].copy() for b, r in enumerate(rows)]
+
     # ---- metric -----------------------------------------------------------------------------------------------
     @nat.on_device
     def path_error_counts(self, path, path_len, pieces0, pieces1):

@@ -18,59 +18,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "annot_device.h"
 #include "annot_plan.h"
 #include "common.h"
 
 namespace rts {
-
-struct AnnotTables {
-    const double *times;      // [n_rows]
-    const int32_t *beats;     // [n_rows]
-    const uint8_t *label_ok;  // [n_rows] the row's label is a non-empty string; NULL: no flags were given
-    const long long *first;   // [P]
-    const int32_t *len;       // [P]
-    int P;
-    double frame_seconds;
-};
-
-struct AnnotPiece {
-    const double *times;
-    const int32_t *beats;
-    int n;  // 0: no such piece
-};
-
-__device__ __forceinline__ AnnotPiece annot_piece(const AnnotTables &t, int piece) {
-    AnnotPiece p = {nullptr, nullptr, 0};
-    if (piece < 0 || piece >= t.P) return p;
-    const long long first = t.first[piece];
-    p.times = t.times + first;
-    p.beats = t.beats + first;
-    p.n = t.len[piece];
-    return p;
-}
-
-__device__ __forceinline__ double annot_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// -> the beat (NaN: none) and *seg
-__device__ __forceinline__ double annot_lookup(const AnnotPiece &p, long long frame, double frame_seconds, int *seg) {
-    *seg = -1;
-    if (p.n < 1 || frame < 0) return annot_nan();
-    const double time = (double)frame * frame_seconds;
-    int lo = 0, hi = p.n;  // the first i in [0, n] with time <= times[i]; n: none
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (time <= p.times[mid]) hi = mid;
-        else lo = mid + 1;
-    }
-    if (lo >= p.n) return annot_nan();
-    const int i = lo;
-    const double end = p.times[i];
-    const double beat = (double)p.beats[i];
-    *seg = i == 0 ? 0 : i - 1;
-    if (i == 0 && end == 0.0) return beat - 0.0;
-    const double start = i == 0 ? 0.0 : p.times[i - 1];
-    return beat - (end - time) / (end - start);
-}
 
 // grid (ceil(n_max / 256), B): one lane per entry.
 __global__ void __launch_bounds__(kAnnotThreads)
@@ -218,6 +170,7 @@ namespace rts {
 
 int annot_pieces(const rts_annot *a) { return a->t.P; }
 int annot_device(const rts_annot *a) { return a->device; }
+const AnnotTables *annot_tables(const rts_annot *a) { return &a->t; }
 
 int annot_select_enqueue(int B, const uint8_t *mask_host, const int32_t *piece_host, const int32_t *frame0_host,
                          int32_t *piece_dev, int32_t *frame0_dev, hipStream_t s) {

@@ -113,6 +113,36 @@ __attribute__((visibility("hidden"))) int annot_live_enqueue(const rts_annot *a,
 // The path buffer of a WTW handle, [B][*path_cap][2] (rts_otw_device_views is the OTW counterpart).
 __attribute__((visibility("hidden"))) void wtw_path_view(const rts_wtw *h, const int32_t **path, int *path_cap);
 
+// The tail kernel of csrc/tempo.hip as the trackers and the live handle launch it: the regression window over the last
+// min(K, stored) points of every stream's own path (rts_otw_tempo in include/rtsync.h has the definition).  otw_tempo_view /
+// wtw_tempo_view fill in what describes the handle -- state, path, and the reference lengths the limits x_limit = 2 N_b,
+// y_limit = N_b come from -- and return the handle's longest reference; the caller adds K, ahead and the outputs.
+// bpm != NULL (the live handle): beats per minute through the tables `annot` at frame0[b] + the last point's reference
+// index in piece[b]; NaN where annot, piece or frame0 is NULL.  The stores end with a system-scope fence: the live handle's
+// outputs are host-mapped.
+struct AnnotTables;
+struct TempoTail {
+    const int32_t *state;  // the tracker's state words, state_len per stream
+    int state_len, st_n_path;
+    const int32_t *path;  // [B][path_cap][2]
+    int path_cap;
+    const int32_t *ref_len;  // [B] per-stream reference lengths, NULL: N for every stream
+    int N;
+    int K;
+    double ahead;
+    double *slope, *pos, *bpm;  // [B]; pos and bpm may be NULL
+    int32_t *n_out;             // [B]
+    const int32_t *piece, *frame0;  // [B] device, for bpm
+    int B;
+};
+__attribute__((visibility("hidden"))) int otw_tempo_view(const rts_otw *h, TempoTail *t);
+__attribute__((visibility("hidden"))) int wtw_tempo_view(const rts_wtw *h, TempoTail *t);
+// The checks rts_otw_tempo / rts_wtw_tempo / rts_live_follow_tempo share: K, ahead and, with the handle's longest
+// reference N_max, the overflow rule.  RTS_OK or the error, the message set.
+__attribute__((visibility("hidden"))) int tempo_tail_check(int K, double ahead, int N_max);
+__attribute__((visibility("hidden"))) int tempo_tail_enqueue(const TempoTail &t, const rts_annot *annot, hipStream_t s);
+__attribute__((visibility("hidden"))) const AnnotTables *annot_tables(const rts_annot *a);
+
 #define RTS_HIP(call)                                                                        \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \

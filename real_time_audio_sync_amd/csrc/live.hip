@@ -33,6 +33,8 @@
 //                         second host-mapped block -- rts_live_confidence reads it like rts_live_poll reads the status words
 //   annot_live_kernel     only after rts_live_annotate with tables (csrc/annot.hip): beat and label of the reference frame of
 //                         every tracker's last path point into a fourth host-mapped block -- rts_live_beats reads it
+//   tempo_tail_kernel     only after rts_live_follow_tempo(K > 0) (csrc/tempo.hip): slope, position and beats per minute of the
+//                         last K points of every tracker's path into a fifth host-mapped block -- rts_live_tempo reads it
 //   live_compact_kernel   drop hop * n_frames consumed samples per stream (data = data[2048:], livenote_live.py:208),
 //                         and publish {status, live position, ref position, feed number} of every stream into
 //                         host-mapped memory -- rts_live_poll reads those words without touching the stream.
@@ -78,6 +80,9 @@ struct LiveArgs {
     // rts_live_annotate (NULL until its first call with tables): host-mapped beat words, republished by live_restart_kernel
     double *ann_beat;            // [B]
     int32_t *ann_label, *ann_ref;  // [B]
+    // rts_live_follow_tempo (NULL until its first call with K > 0): host-mapped tempo words, republished by live_restart_kernel
+    double *tempo_words;         // slope[B], pos[B], bpm[B]
+    int32_t *tempo_n;            // [B]
 };
 
 __device__ __forceinline__ void live_publish(const LiveArgs &g, int b) {
@@ -205,6 +210,10 @@ __global__ void live_restart_kernel(RestartSel sel, LiveArgs g, GateArgs t) {
         g.ann_label[b] = -1;
         g.ann_ref[b] = -1;
     }
+    if (g.tempo_words) {  // no window yet
+        for (int q = 0; q < 3; q++) g.tempo_words[(size_t)q * g.B + b] = __longlong_as_double(0x7ff8000000000000LL);
+        g.tempo_n[b] = 0;
+    }
     if (t.q) live_gate_restart(t, b);
     __threadfence_system();
 }
@@ -259,6 +268,11 @@ struct rts_live {
     rts::AnnotLive ann;
     int32_t *ann_tables;  // piece[B] then frame0[B] on the device
     unsigned char *ann_host;
+    // rts_live_follow_tempo: K points per stream (0 = off), what its launch takes (the tracker's view and the outputs, from
+    // the first call with K > 0) and the fifth host-mapped block, double slope[B], pos[B], bpm[B] then int32 n[B]
+    int tempo_k;
+    rts::TempoTail tempo;
+    unsigned char *tempo_host;
 };
 
 namespace rts {
@@ -303,6 +317,22 @@ static int live_annot_launch(rts_live *h, hipStream_t s) {
     return annot_live_enqueue(h->annot, h->ann, s);
 }
 
+static void live_tempo_clear(rts_live *h) {
+    double *words = reinterpret_cast<double *>(h->tempo_host);
+    for (int b = 0; b < 3 * h->geo.B; b++) words[b] = __builtin_nan("");
+    memset(words + 3 * (size_t)h->geo.B, 0, sizeof(int32_t) * (size_t)h->geo.B);
+}
+
+// With tempo on, one more launch per feed behind the beat launch and before live_compact_kernel, for the same reason.
+// Beats per minute need what rts_live_annotate set up: the tables while they are on, piece and offset of every stream.
+static int live_tempo_launch(rts_live *h, hipStream_t s) {
+    if (h->tempo_k < 1) return RTS_OK;
+    TempoTail t = h->tempo;
+    t.piece = h->ann_tables;
+    t.frame0 = h->ann_tables ? h->ann_tables + h->geo.B : nullptr;
+    return tempo_tail_enqueue(t, h->annot, s);
+}
+
 static void live_gate_clear(rts_live *h) {
     double *level = reinterpret_cast<double *>(h->gate_host);
     for (int b = 0; b < h->geo.B; b++) level[b] = __builtin_nan("");
@@ -340,8 +370,8 @@ static int live_refuse(const rts_live *h, LiveRefusal why, const FeedPlan &p, co
 // n_max is 0, rts_wtw_push after its entry check, which wtw.py:76-77 runs on every insert(), new column or not; in diff
 // mode the tracker is pushed only when some stream hands it a column (n_max_diff > 0; the rows still lie n_max apart);
 // the watch launch follows rts_live_watch, the two gate launches rts_live_gate: with the gate on the push takes the gated
-// buffer and its counts, and nothing else moves; the beat launch follows rts_live_annotate.  The compaction and the
-// publication end every feed.
+// buffer and its counts, and nothing else moves; the beat launch follows rts_live_annotate, the tempo launch
+// rts_live_follow_tempo.  The compaction and the publication end every feed.
 static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, void *stream) {
     const int B = h->geo.B;
     hipStream_t s = (hipStream_t)stream;
@@ -390,6 +420,7 @@ static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, 
         return rc;
     if (int rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
     if (int rc = live_annot_launch(h, s); rc != RTS_OK) return rc;
+    if (int rc = live_tempo_launch(h, s); rc != RTS_OK) return rc;
     hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -451,6 +482,7 @@ int rts_live_destroy(rts_live *h) {
     if (h->conf_host) (void)hipHostFree(h->conf_host);
     if (h->gate_host) (void)hipHostFree(h->gate_host);
     if (h->ann_host) (void)hipHostFree(h->ann_host);
+    if (h->tempo_host) (void)hipHostFree(h->tempo_host);
     free(h);  // the mirrors with it
     return RTS_OK;
 }
@@ -602,6 +634,7 @@ int rts_live_reset(rts_live *h, void *stream) {
     if (h->conf_host) live_conf_clear(h);
     if (h->gate_host) live_gate_clear(h);
     if (h->ann_host) live_annot_clear(h);
+    if (h->tempo_host) live_tempo_clear(h);
     memset(h->used, 0, sizeof(h->used));
     h->slot = -1;
     h->feeds = 0;
@@ -831,6 +864,59 @@ int rts_live_beats(rts_live *h, double *beat, int32_t *label, int32_t *ref_frame
         if (beat) beat[b] = bt[b];
         if (label) label[b] = w[b];
         if (ref_frame) ref_frame[b] = w[B + b];
+    });
+    if (feeds_done) *feeds_done = fd;
+    return RTS_OK;
+}
+
+int rts_live_follow_tempo(rts_live *h, int K, double ahead) {
+    using namespace rts;
+    if (int rc = live_usable(h); rc != RTS_OK) return rc;
+    if (K == 0) {  // off: the words stay as they are
+        h->tempo_k = 0;
+        return RTS_OK;
+    }
+    TempoTail t = {};
+    const int N_max = h->otw ? otw_tempo_view(h->otw, &t) : wtw_tempo_view(h->wtw, &t);
+    if (int rc = tempo_tail_check(K, ahead, N_max); rc != RTS_OK) return rc;
+    if (!h->tempo_host) {
+        if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+        const size_t nB = (size_t)h->geo.B;
+        RTS_HIP(hipHostMalloc((void **)&h->tempo_host, (3 * sizeof(double) + sizeof(int32_t)) * nB,
+                              hipHostMallocMapped | hipHostMallocCoherent));
+        void *dev = nullptr;
+        if (hipError_t e = hipHostGetDevicePointer(&dev, h->tempo_host, 0); e != hipSuccess) {
+            (void)hipHostFree(h->tempo_host);
+            h->tempo_host = nullptr;
+            return set_error(RTS_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
+        }
+        h->args.tempo_words = reinterpret_cast<double *>(dev);
+        h->args.tempo_n = reinterpret_cast<int32_t *>(h->args.tempo_words + 3 * nB);
+        live_tempo_clear(h);
+    }
+    t.slope = h->args.tempo_words;
+    t.pos = t.slope + h->geo.B;
+    t.bpm = t.pos + h->geo.B;
+    t.n_out = h->args.tempo_n;
+    t.K = K;
+    t.ahead = ahead;
+    h->tempo = t;
+    h->tempo_k = K;
+    return RTS_OK;
+}
+
+int rts_live_tempo(rts_live *h, double *slope, double *pos, double *bpm, int32_t *n, int *feeds_done) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!h->tempo_host) return set_error(RTS_ERR_INVALID, "rts_live_tempo before any rts_live_follow_tempo(K > 0)");
+    const int B = h->geo.B;
+    const volatile double *w = reinterpret_cast<const volatile double *>(h->tempo_host);
+    const volatile int32_t *cnt = reinterpret_cast<const volatile int32_t *>(h->tempo_host + 3 * sizeof(double) * (size_t)B);
+    const int fd = live_read_published(h, [=](int b) {
+        if (slope) slope[b] = w[b];
+        if (pos) pos[b] = w[B + b];
+        if (bpm) bpm[b] = w[2 * B + b];
+        if (n) n[b] = cnt[b];
     });
     if (feeds_done) *feeds_done = fd;
     return RTS_OK;

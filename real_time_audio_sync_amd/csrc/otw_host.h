@@ -539,6 +539,17 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
 
 int otw_batch(const rts_otw *h) { return h->B; }
 int otw_history(const rts_otw *h) { return h->hist_stride; }
+int otw_tempo_view(const rts_otw *h, TempoTail *t) {
+    t->state = h->state;
+    t->state_len = RTS_STATE_LEN;
+    t->st_n_path = RTS_ST_N_PATH;
+    t->path = h->path;
+    t->path_cap = h->path_cap;
+    t->ref_len = h->refs.len;
+    t->N = h->N;
+    t->B = h->B;
+    return h->N;
+}
 
 }  // namespace rts
 
@@ -786,6 +797,23 @@ int rts_otw_path_cost(rts_otw *h, int K, double *mean_dev, int32_t *n_dev, doubl
     hipLaunchKernelGGL(otw_path_cost_kernel, dim3(h->B), dim3(64 * ((K + 63) / 64)), 0, (hipStream_t)stream, a);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
+}
+
+int rts_otw_tempo(rts_otw *h, int K, double ahead, double *slope_dev, double *pos_dev, int32_t *n_dev, void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!slope_dev) return set_error(RTS_ERR_INVALID, "slope_dev is NULL");
+    if (!n_dev) return set_error(RTS_ERR_INVALID, "n_dev is NULL");
+    if (int rc = tempo_tail_check(K, ahead, h->N); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    TempoTail t = {};
+    otw_tempo_view(h, &t);
+    t.K = K;
+    t.ahead = ahead;
+    t.slope = slope_dev;
+    t.pos = pos_dev;
+    t.n_out = n_dev;
+    return tempo_tail_enqueue(t, nullptr, (hipStream_t)stream);
 }
 
 int rts_otw_read_states(rts_otw *h, int32_t *states, void *stream) {

@@ -908,6 +908,17 @@ static int wtw_create(const double *chroma_ref_dev, int F, int M, int B, int win
 
 int wtw_batch(const rts_wtw *h) { return h->B; }
 int wtw_history(const rts_wtw *h) { return h->args.live_stride; }
+int wtw_tempo_view(const rts_wtw *h, TempoTail *t) {
+    t->state = h->args.state;
+    t->state_len = RTS_WTW_STATE_LEN;
+    t->st_n_path = RTS_WTW_ST_N_PATH;
+    t->path = h->args.path;
+    t->path_cap = h->args.path_cap;
+    t->ref_len = h->args.ref_len;
+    t->N = h->args.M;
+    t->B = h->B;
+    return h->args.M;
+}
 void wtw_path_view(const rts_wtw *h, const int32_t **path, int *path_cap) {
     *path = h->args.path;
     *path_cap = h->args.path_cap;
@@ -1002,6 +1013,23 @@ int rts_wtw_recent(rts_wtw *h, int M_max, double *out_dev, int32_t *len_dev, con
                        h->args.live_stride, h->args.M, h->args.ref_len, M_max, out_dev, len_dev, mask_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
+}
+
+int rts_wtw_tempo(rts_wtw *h, int K, double ahead, double *slope_dev, double *pos_dev, int32_t *n_dev, void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!slope_dev) return set_error(RTS_ERR_INVALID, "slope_dev is NULL");
+    if (!n_dev) return set_error(RTS_ERR_INVALID, "n_dev is NULL");
+    if (int rc = tempo_tail_check(K, ahead, h->args.M); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    TempoTail t = {};
+    wtw_tempo_view(h, &t);
+    t.K = K;
+    t.ahead = ahead;
+    t.slope = slope_dev;
+    t.pos = pos_dev;
+    t.n_out = n_dev;
+    return tempo_tail_enqueue(t, nullptr, (hipStream_t)stream);
 }
 
 int rts_wtw_push(rts_wtw *h, const void *cols_dev, int cols_dtype, int n_max, const int32_t *n_new_dev, int precheck,

@@ -438,6 +438,31 @@ class LiveSession(object):
                                               self._conf_n.ctypes.data if mean is not None else None, ctypes.byref(done)))
         return dict(mean=self._conf_mean.copy(), n=self._conf_n.copy(), feeds_done=done.value)
 
+    @nat.on_device
+    def follow_tempo(self, K, ahead=0.0):
+        """Tempo of every microphone with every feed (rts_live_follow_tempo): K = 2..1024 path points per stream, 0 = off
+        (the default).  With it on, each feed enqueues one more small launch, ``tempo(K, ahead)`` of the bound tracker
+        (OTW or WTW) published into host-mapped memory together with beats per minute through the tables of
+        ``annotate``; ``tempo()`` reads it.  With the gate on, live indices count the columns the tracker received, so the
+        slope is per column handed on; ``frame_columns`` maps them back."""
+        nat.check(nat.lib.rts_live_follow_tempo(self._h, int(K), float(ahead)))
+        if int(K) > 0 and getattr(self, "_tempo_words", None) is None:
+            self._tempo_words = np.zeros((3, self.B), dtype=np.float64)
+            self._tempo_n = np.zeros(self.B, dtype=np.int32)
+
+    def tempo(self):
+        """Non-blocking: {'slope' float64 [B], 'pos' float64 [B], 'bpm' float64 [B], 'n' int32 [B], 'feeds_done'} as last
+        published by the device: slope (reference frames per live frame) and position of the regression line through the
+        last ``n`` path points of every stream -- ``BatchedOTW.tempo`` / ``BatchedWTW.tempo`` as of feed ``feeds_done`` or
+        later; NaN with n = 0 for a stream without a path point or just restarted.  ``bpm``: the slope in beats per
+        minute at the frame ``beats()`` reports (``AnnotationTables.bpm``), NaN while annotations are off or the stream
+        has no piece.  Needs ``follow_tempo(K)`` first."""
+        done = ctypes.c_int()
+        w = getattr(self, "_tempo_words", None)
+        nat.check(nat.lib.rts_live_tempo(self._h, *([w[q].ctypes.data for q in range(3)] if w is not None else [None] * 3),
+                                         self._tempo_n.ctypes.data if w is not None else None, ctypes.byref(done)))
+        return dict(slope=w[0].copy(), pos=w[1].copy(), bpm=w[2].copy(), n=self._tempo_n.copy(), feeds_done=done.value)
+
     def backward(self, streams=None):
         """The backward path of every stream (or the listed ones) through the bound OTW tracker
         (``BatchedOTW.backward``): ``(paths, totals, ends)`` for everything the microphones' columns have brought the
