@@ -934,6 +934,61 @@ int rts_live_follow_tempo(rts_live *h, int K, double ahead);
 int rts_live_tempo(rts_live *h, double *slope /* [B] */, double *pos /* [B] */, double *bpm /* [B] */, int32_t *n /* [B] */,
                    int *feeds_done);
 
+/* ------------------------------------------------------------------------------------------
+ * Tuning: the offset of a source from A4 = 440 Hz, estimated on the device from its STFT.
+ * ------------------------------------------------------------------------------------------ */
+/* The chroma filterbank handed to rts_chroma_create is built for one A4; the reference builds it for 440 Hz and leaves the
+ * rest open (chroma.py:24, "# TODO: check additions (tuning, normalization, etc.)").  A source that is off by a quarter tone
+ * smears every partial over two chroma bins.  This estimates the offset without taking the STFT to the host: a histogram of
+ * the spectral peaks' distances from the nearest equal-tempered pitch, R bins to the semitone, and a pick from it.  The
+ * filterbank for the offset found is the caller's to build (filters.chroma_filterbank(a440=filters.tuning_a440(cents))).
+ *
+ * Input: the complex STFT rts_chroma_frames writes into stft_out_dev, [n_frames][fft_len/2+1] pairs of doubles (re, im).
+ * Every float64 operation below is rounded on its own, in the order written; sqrt and / are the correctly rounded ones.
+ * Per frame m:
+ *   P[k] = re*re + im*im                for every bin (two products, one sum)
+ *   Pmax = max_k P[k],  lim = thr_pow * Pmax
+ *   bin k in [k_lo, k_hi] is a peak when P[k] > P[k-1] and P[k] >= P[k+1] and P[k] >= lim   (an all-zero frame has none)
+ * and for a peak:
+ *   a = sqrt(P[k-1]), b = sqrt(P[k]), c = sqrt(P[k+1])
+ *   avg = 0.5*(c - a),  sh = (2.0*b - c) - a,  d = sh > 0 ? avg/sh : 0.0
+ *   f = ((double)k + d) * bin_hz
+ *   n = the largest index with E[n] <= f in the handle's ascending edge table E[0 .. n_edges)      (binary search)
+ *   dropped when there is no such n or n >= n_edges - 1; otherwise hist[seg[m]][n mod R] += 1.
+ * NaN input leaves the counts undefined; every index stays bounded.  The table is the host's (filters.tuning_edges):
+ * E[n] = 440 * 2^((s_lo - 0.5 + n/R)/12), so histogram bin i holds offsets in [-50 + 100 i/R, -50 + 100 (i+1)/R) cents and
+ * the device takes no logarithm -- which is what lets the histogram equal a serial restatement bit for bit.
+ *
+ * rts_tuning_create validates on the host, before any device call:
+ *   RTS_ERR_UNSUPPORTED: fft_len not a power of two in [64, 8192]; R > 1024.
+ *   RTS_ERR_INVALID: not 1 <= k_lo <= k_hi <= fft_len/2 - 1; R < 1; n_edges < 2; NULL edges_host or out; an edge that is
+ *   not finite, positive and above the one before it; thr_pow outside [0, 1]; bin_hz not finite and > 0.
+ * The handle belongs to the device that is current at create; rts_tuning_destroy(NULL) is RTS_OK.
+ *
+ * rts_tuning_accumulate ADDS the counts of n_frames frames to hist_dev [S][R] uint64 and never clears it: frame m goes to
+ * row seg_dev[m] (int32; a value outside [0, S) drops the frame), every frame to row 0 when seg_dev is NULL.  Counts are
+ * integers, so calls over any split of the frames give the same histogram.  One launch of persistent workgroups, each
+ * owning a contiguous range of frames and adding to hist_dev only when its segment changes and at its end.  Asynchronous
+ * on `stream`; allocates nothing, does not synchronise, writes only hist_dev.  n_frames == 0 enqueues nothing.
+ *   RTS_ERR_INVALID: NULL handle; n_frames < 0; S < 1; with n_frames > 0: NULL stft_dev or hist_dev, stft_dev not 16-byte
+ *   aligned, another device current.
+ *
+ * rts_tuning_pick: per row s of hist_dev, N = sum hist[s]; N == 0 gives cents 0.0 and n 0.  Otherwise, all integers,
+ *   score[i] = sum_{d=-W..W} (W + 1 - |d|) * hist[s][(i + d) mod R]       (circular: -50 and +49 cents are neighbours)
+ *   i* = the first maximum of score
+ *   cents_dev[s] = ((double)i* + 0.5) * 100.0 / (double)R - 50.0,  n_dev[s] = N.
+ * One workgroup per row; asynchronous, allocates nothing, writes only the two outputs.
+ *   RTS_ERR_INVALID: NULL handle, hist_dev, cents_dev or n_dev; S < 1; W < 0 or 2 W + 1 > R; another device current. */
+typedef struct rts_tuning rts_tuning;
+int rts_tuning_create(int fft_len, int k_lo, int k_hi, int R, int n_edges, const double *edges_host /* [n_edges] */,
+                      double bin_hz, double thr_pow, rts_tuning **out);
+int rts_tuning_destroy(rts_tuning *p);
+int rts_tuning_accumulate(rts_tuning *p, const double *stft_dev /* [n_frames][fft_len/2+1][2] */, long long n_frames,
+                          const int32_t *seg_dev /* [n_frames] or NULL */, int S, unsigned long long *hist_dev /* [S][R] */,
+                          void *stream);
+int rts_tuning_pick(rts_tuning *p, const unsigned long long *hist_dev /* [S][R] */, int S, int W, double *cents_dev /* [S] */,
+                    long long *n_dev /* [S] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,12 @@ _decl("rts_annot_bpm", _i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp
 _decl("rts_live_follow_tempo", _i32, [_vp, _i32, ctypes.c_double])
 _decl("rts_live_tempo", _i32, [_vp, _vp, _vp, _vp, _vp, _pi32])
 
+TUNING_MAX_R = 1024  # kTuningMaxR (csrc/tuning_plan.h)
+_decl("rts_tuning_create", _i32, [_i32, _i32, _i32, _i32, _i32, _vp, ctypes.c_double, ctypes.c_double, ctypes.POINTER(_vp)])
+_decl("rts_tuning_destroy", _i32, [_vp])
+_decl("rts_tuning_accumulate", _i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp])
+_decl("rts_tuning_pick", _i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp])
+
 
 def check(rc):
     if rc != 0:

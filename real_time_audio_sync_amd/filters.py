@@ -28,6 +28,28 @@ def chroma_filterbank(sr=22050, n_fft=4096, n_chroma=12, a440=440.0, ctroct=5.0,
     return np.ascontiguousarray(w[:, : n_fft // 2 + 1], dtype=np.float64)
 
 
+def tuning_a440(cents):
+    """The A4 of a source that lies ``cents`` from 440 Hz: what ``chroma_filterbank(a440=...)`` takes."""
+    return 440.0 * 2.0 ** (float(cents) / 1200.0)
+
+
+def tuning_edges(fs, n_fft, f_min=150.0, f_max=4000.0, R=100):
+    """(k_lo, k_hi, E) for the tuning estimator (rts_tuning_create): the FFT bins whose peaks count, those with centres in
+    [f_min, f_max], and the ascending float64 edge table E[n] = 440 * 2^((s_lo - 0.5 + n/R)/12), n = 0 .. (s_hi - s_lo) * R,
+    that cuts every semitone from s_lo to s_hi (relative to A4 = 440) into R parts starting half a semitone below the
+    pitch.  A frequency between E[n] and E[n+1] lies in histogram bin n mod R, which holds the offsets
+    [-50 + 100 i/R, -50 + 100 (i+1)/R) cents from the nearest equal-tempered pitch.  The table covers every frequency an
+    interpolated peak of a bin in [k_lo, k_hi] can have, (k_lo - 0.5) to (k_hi + 0.5) bins, with a semitone to spare."""
+    fs, n_fft, R = float(fs), int(n_fft), int(R)
+    k_lo = max(1, int(math.ceil(f_min * n_fft / fs)))
+    k_hi = min(n_fft // 2 - 1, int(math.floor(f_max * n_fft / fs)))
+    s_lo = int(math.floor(12.0 * math.log2((k_lo - 0.5) * fs / n_fft / 440.0) + 0.5)) - 1
+    s_hi = int(math.ceil(12.0 * math.log2((k_hi + 0.5) * fs / n_fft / 440.0) + 0.5)) + 1
+    n = np.arange((s_hi - s_lo) * R + 1, dtype=np.float64)
+    E = 440.0 * np.exp2((s_lo - 0.5 + n / R) / 12.0)
+    return k_lo, k_hi, np.ascontiguousarray(E, dtype=np.float64)
+
+
 def hann_window(n):
     """The symmetric window the reference multiplies every frame by (np.hanning, chroma.py:39,:62)."""
     return np.hanning(n).astype(np.float64)

@@ -36,7 +36,7 @@ class _DeviceView(object):
 class LiveSession(object):
     def __init__(self, ref_chroma, batch, c=500, max_run_count=3, variant="otw", fft_len=4096, hop_size=2048,
                  fs=22050, max_pending=1 << 16, device="cuda:0", wtw_params=None, extra_refs=(), features="chroma",
-                 euclid=False, fs_in=None):
+                 euclid=False, fs_in=None, tuning=None):
         """``ref_chroma``: (12, N) reference chroma (e.g. chroma.wav_to_chroma(ref_path)), or a list of ``batch`` such
         arrays, one per stream (one piece per microphone; a list entry that repeats is uploaded once).  With
         ``wtw_params`` ({'dtw_win_size', 'dtw_hop_size'} in samples, like wtw.py:29-30) the streams are followed by
@@ -55,7 +55,12 @@ class LiveSession(object):
         ``fs_in``: the microphones' own sample rate.  None or ``fs`` gives the ordinary session.  Anything else puts the
         device resampler (chroma.ResamplePlan) in front of the chain: ``feed``, ``feed_block`` and ``staging`` then take
         samples at ``fs_in``, ``max_pending`` and ``pending()`` stay in samples at ``fs``, and a stream that has been
-        fed n samples has handed ``resampler.avail(n)`` samples on, the same ones however the input was cut."""
+        fed n samples has handed ``resampler.avail(n)`` samples on, the same ones however the input was cut.
+
+        ``tuning``: the microphones' offset from A4 = 440 Hz in cents (``chroma.estimate_tuning_batch`` of a sound
+        check finds it), handed to the session's ``ChromaPlan``; None is the 440 Hz filterbank.  One offset per
+        session -- the chroma kernels share one filterbank among the streams of a pass -- reported as
+        ``session.tuning``.  It changes the table the plan uploads and nothing a feed enqueues."""
         if features not in _FEATURES:
             raise ValueError("features must be 'chroma' or 'chroma_diff', not %r" % (features,))
         if features == "chroma_diff" and wtw_params is not None:
@@ -64,7 +69,8 @@ class LiveSession(object):
         if euclid and wtw_params is not None:
             raise ValueError("euclid selects the OTW family's cost; WTW has its own (wtw_params)")
         self.features = features
-        self.plan = ChromaPlan(fft_len, hop_size, fs, device)
+        self.plan = ChromaPlan(fft_len, hop_size, fs, device, tuning=tuning)
+        self.tuning = self.plan.tuning
         self.dev = self.device = self.plan.device
         self.B, self.L, self.H = int(batch), int(fft_len), int(hop_size)
         self.cap = int(max_pending)

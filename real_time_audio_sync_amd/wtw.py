@@ -105,9 +105,14 @@ class BatchedWTW(_BatchedHandle):
 
 class WTW():
     """``WTW(ref_recording, {'fft_len','hop_size','dtw_win_size','dtw_hop_size'}, debug_params)``;
-    ``insert(list_of_float_samples)`` returns None or "stop"; ``.path`` is a list of (live, ref)."""
+    ``insert(list_of_float_samples)`` returns None or "stop"; ``.path`` is a list of (live, ref).
 
-    def __init__(self, ref_recording, params, debug_params, device="cuda:0", resample=False):
+    ``tuning``: None, or the offset from A4 = 440 Hz in cents the chroma filterbank is built for
+    (``chroma.estimate_tuning``).  The one plan serves the reference file and the inserted buffers, so both get the
+    same offset; a reference with an offset of its own is made with ``chroma.wav_to_chroma(tuning=...)`` and followed
+    with ``BatchedWTW``."""
+
+    def __init__(self, ref_recording, params, debug_params, device="cuda:0", resample=False, tuning=None):
         # reference audio, fs = 22050 (wtw.py:23-24); resample=True: a file at another rate is resampled on the device,
         # where librosa.load resamples silently (wtw.py:23)
         if resample:
@@ -118,23 +123,24 @@ class WTW():
         else:
             self.ref, self.fs = filters.load_wav(ref_recording)
         assert (self.fs == 22050)
-        self._init_from_samples(self.ref, params, debug_params, device)
+        self._init_from_samples(self.ref, params, debug_params, device, tuning)
 
     @classmethod
-    def from_samples(cls, ref_samples, params, debug_params=None, fs=22050, device="cuda:0"):
+    def from_samples(cls, ref_samples, params, debug_params=None, fs=22050, device="cuda:0", tuning=None):
         """Same object from already-loaded mono samples (what librosa.load would have returned)."""
         self = cls.__new__(cls)
         self.ref, self.fs = np.asarray(ref_samples), fs
-        self._init_from_samples(self.ref, params, debug_params or {}, device)
+        self._init_from_samples(self.ref, params, debug_params or {}, device, tuning)
         return self
 
-    def _init_from_samples(self, ref, params, debug_params, device):
+    def _init_from_samples(self, ref, params, debug_params, device, tuning=None):
         self.fft_len = params['fft_len']
         self.hop_size = params['hop_size']
         self.dtw_win_size = params['dtw_win_size']
         self.dtw_hop_size = params['dtw_hop_size']
         self.chroma_info = debug_params.get('chroma', False) if isinstance(debug_params, dict) else False
-        self._plan = ChromaPlan(self.fft_len, self.hop_size, self.fs, device)
+        self._plan = ChromaPlan(self.fft_len, self.hop_size, self.fs, device, tuning=tuning)
+        self.tuning = self._plan.tuning
         self.chromafb = self._plan.chromafb
         dev = self._plan.device
         ref_dev = torch.from_numpy(np.ascontiguousarray(ref)).to(dev)
