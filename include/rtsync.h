@@ -267,7 +267,8 @@ int rts_otw_backward(rts_otw *h, const void *live_dev, int live_dtype, int T_max
 /* Device time of the handle's last rts_otw_backward, split into its two parts (HIP events the call records on its
  * stream): the trace replay and the backtrace.  Waits for that call to finish. */
 int rts_otw_backward_times(rts_otw *h, float *replay_ms, float *backtrace_ms);
-/* Formerly a tuning knob (waves per stream workgroup); every kernel now runs 8 waves.  8 is accepted and changes
+/* Formerly a tuning knob (waves per stream workgroup); the library now chooses the count itself (8 everywhere but for
+ * the wide forms, rts_otw_read_kernel_waves).  8 is accepted and changes
  * nothing, the retired counts 1, 2 and 4 return RTS_ERR_UNSUPPORTED, anything else RTS_ERR_INVALID.
  * Without a dense mirror the library runs its pipelined kernel (the next step's strips are computed
  * beside this step's control work); the environment variable RTS_OTW_SPEC=0, read by rts_otw_create, selects
@@ -291,6 +292,13 @@ const char *rts_otw_kernel_name(const rts_otw *h);
 #define RTS_OTW_RING_NONE 2      /* no ring: frames come from global memory */
 #define RTS_OTW_RING_NONE_LEAN 3 /* the same, the residency-oriented flavour of batches of RTS_OTW_TP_FROM streams per CU */
 int rts_otw_read_kernel(const rts_otw *h, int live_dtype, int32_t out[4]);
+/* The waves per stream of that instantiation: 8, or 12 / 16 for the wide forms of the pipelined kernel with a ring at band
+ * widths 245..500, which a handle takes when every stream has a compute unit to itself (B <= CUs) and which
+ * spend the further waves on the cost strips.  Results do not depend on it.  The environment variable RTS_OTW_WAVES=8, 12
+ * or 16, read by rts_otw_create, fixes the count wherever the kernel has such a form (A/B measurements, tests); any other
+ * value makes rts_otw_create return RTS_ERR_INVALID.  Same arguments, same errors as rts_otw_read_kernel, whose four
+ * words stay as they are. */
+int rts_otw_read_kernel_waves(const rts_otw *h, int live_dtype, int32_t *waves);
 
 /* ------------------------------------------------------------------------------------------
  * Offline DTW, batched over B independent (a, b) pairs.

@@ -82,6 +82,7 @@ _decl("rts_otw_backward", _i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, 
 _decl("rts_otw_backward_times", _i32, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)])
 _decl("rts_otw_kernel_name", ctypes.c_char_p, [_vp])
 _decl("rts_otw_read_kernel", _i32, [_vp, _i32, _vp])
+_decl("rts_otw_read_kernel_waves", _i32, [_vp, _i32, _vp])
 OTW_RINGS = ("float", "double", "none", "none-lean")  # RTS_OTW_RING_*
 _decl("rts_dtw_workspace_bytes", _i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_size_t)])
 _decl("rts_dtw", _i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -4,7 +4,7 @@
 // livenote_v2.py:43-236 (restated on the CPU, for tests only, in oracle/rtsync_oracle.c).
 //
 // Design:
-//   * one workgroup (8 waves) per live stream; the whole per-stream state lives in LDS for the
+//   * one workgroup (8 waves; 12 where a CU holds one stream, otw_plan::threads) per live stream; the whole per-stream state lives in LDS for the
 //     duration of a launch: the two live accumulated-cost bands (row t over columns [j-c, j] and
 //     column j over rows [t-c, t]), ring windows of the last W live (and, plain kernel, reference)
 //     chroma frames, and the cost strips the helper waves prepare ahead of time;
@@ -851,7 +851,10 @@ __device__ __forceinline__ void otw_finish(OtwLds<W, RT> &S, OtwCtl &k, const Ot
 // column (jn+2) if j advanced.  The cells by which the *kept* rows / columns must grow are exactly the last cells of
 // those new strips, so the thread that computes one stores it twice.  None of it is read before the next step, so all
 // of this is off the critical path.
-template <int W, typename RT>
+// ONE: one cell in flight per thread instead of two -- the throughput flavour (registers for residency), and the wide
+// workgroups, whose hn helper threads are at least as many as a strip has cells (c + 2 <= W - 10 <= hn): a second cell
+// would be a duplicate of the first by construction, so the loop body runs at most once per thread.
+template <int W, typename RT, bool ONE>
 __device__ __forceinline__ void otw_cost_row(OtwLds<W, RT> &S, const OtwEnv &e, int r, int k_lo, int k_hi, int dual_lo,
                                              int hidx, int hn) {
     if (r >= e.live_len || r >= e.live_cap) return;  // never consumed
@@ -866,7 +869,7 @@ __device__ __forceinline__ void otw_cost_row(OtwLds<W, RT> &S, const OtwEnv &e, 
 #pragma unroll
         for (int f = 0; f < kF; f++) lf[f] = (double)S.livew[f][r & (W - 1)];
     }
-    if constexpr (kThroughput<RT>) {  // one cell in flight: registers for residency
+    if constexpr (ONE) {
         for (int ka = k_lo + hidx; ka <= k_hi; ka += hn) {
             double ra[kF];
             otw_ref_frame(e, ka, ra);
@@ -891,7 +894,7 @@ __device__ __forceinline__ void otw_cost_row(OtwLds<W, RT> &S, const OtwEnv &e, 
         }
     }
 }
-template <int W, typename RT>
+template <int W, typename RT, bool ONE>
 __device__ __forceinline__ void otw_cost_col(OtwLds<W, RT> &S, const OtwEnv &e, int q, int r_lo, int r_hi, int dual_lo,
                                              int hidx, int hn) {
     if (q >= e.N) return;
@@ -902,10 +905,15 @@ __device__ __forceinline__ void otw_cost_col(OtwLds<W, RT> &S, const OtwEnv &e, 
     double *Dcol = S.Dc[q & 1];
     double rf[kF];
     otw_ref_frame(e, q, rf);
-    if constexpr (kThroughput<RT>) {
+    if constexpr (ONE) {
         for (int ra_ = r_lo + hidx; ra_ <= r_hi; ra_ += hn) {
             double la[kF];
-            otw_live_frame(e, ra_, la);
+            if constexpr (!kHasLiveRing<RT>) {
+                otw_live_frame(e, ra_, la);
+            } else {
+#pragma unroll
+                for (int f = 0; f < kF; f++) la[f] = (double)S.livew[f][ra_ & (W - 1)];
+            }
             const double da = cell_cost(la, rf, e.euclid);
             Dcol[swz<W>(ra_)] = da;
             if (ra_ >= dual_lo) S.Dr[ra_ & 1][swz<W>(q)] = da;
@@ -937,27 +945,27 @@ __device__ __forceinline__ void otw_cost_col(OtwLds<W, RT> &S, const OtwEnv &e, 
 }
 
 // Establish the invariant for (t, j) from nothing (launch prologue, all threads).
-template <int W, typename RT>
+template <int W, typename RT, bool ONE>
 __device__ __forceinline__ void otw_costs_prime(OtwLds<W, RT> &S, const OtwEnv &e, int t, int j, int hidx, int hn) {
     const int c = e.c;
     const int none = 0x7fffffff;
-    otw_cost_row<W, RT>(S, e, t + 1, j - c + 1, j + 2, none, hidx, hn);
-    otw_cost_row<W, RT>(S, e, t + 2, j - c + 1, j + 2, none, hidx, hn);
-    otw_cost_col<W, RT>(S, e, j + 1, t - c + 1, t + 2, none, hidx, hn);
-    otw_cost_col<W, RT>(S, e, j + 2, t - c + 1, t + 2, none, hidx, hn);
+    otw_cost_row<W, RT, ONE>(S, e, t + 1, j - c + 1, j + 2, none, hidx, hn);
+    otw_cost_row<W, RT, ONE>(S, e, t + 2, j - c + 1, j + 2, none, hidx, hn);
+    otw_cost_col<W, RT, ONE>(S, e, j + 1, t - c + 1, t + 2, none, hidx, hn);
+    otw_cost_col<W, RT, ONE>(S, e, j + 2, t - c + 1, t + 2, none, hidx, hn);
 }
 
 // Restore the invariant for (pt, jn) after the move the plan describes (helper waves).  A Both step computes its new
 // row first and its new column second; the one cell they share, (pt+2, jn+2), comes out identical from both.
-template <int W, typename RT>
+template <int W, typename RT, bool ONE>
 __device__ __forceinline__ void otw_costs_advance(OtwLds<W, RT> &S, const OtwEnv &e, int pt, int jn, bool do_row,
                                                   bool do_col, int hidx, int hn) {
     const int c = e.c;
     // new row pt+2: its cells in columns jn+1, jn+2 are what the two column buffers lack (row pt+2); in a Both step
     // column jn+2 is new as well and covers that cell itself
-    if (do_row) otw_cost_row<W, RT>(S, e, pt + 2, jn - c + 1, jn + 2, jn + 1, hidx, hn);
+    if (do_row) otw_cost_row<W, RT, ONE>(S, e, pt + 2, jn - c + 1, jn + 2, jn + 1, hidx, hn);
     // new column jn+2: its cells in rows pt+1, pt+2 are what the two row buffers lack (column jn+2)
-    if (do_col) otw_cost_col<W, RT>(S, e, jn + 2, pt - c + 1, pt + 2, pt + 1, hidx, hn);
+    if (do_col) otw_cost_col<W, RT, ONE>(S, e, jn + 2, pt - c + 1, pt + 2, pt + 1, hidx, hn);
 }
 
 // A speculative strip (during the step that leaves the state at (pt, jn)): the strip the next Row-only step (row
@@ -1195,17 +1203,23 @@ __device__ __forceinline__ OtwSettled otw_settle_hit(double *R, double *C, const
 // the launch ends.  __syncthreads() would also drain those stores (a full release: vmcnt(0)) once per step.
 #define RTS_STEP_BARRIER() ::rts::lds_barrier()
 
-template <int W, int DENSE, typename RT, bool SPEC>
+// NT: threads of the workgroup, 512 (eight waves) everywhere but the wide forms of the pipelined W = 512 ring kernels
+// (768 / 1024: otw_plan::threads), which give the waves a CU has to spare when it holds one stream to the cost strips.
+template <int W, int DENSE, typename RT, bool SPEC, int NT>
 // (the throughput flavour exists for its residency -- three workgroups of eight waves per CU, i.e. at most 80 VGPRs: said to
 // the compiler here, because the ILP-first scheduling this file is built with otherwise spends 87)
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(kThroughput<RT> ? 6 : 1)))
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kThroughput<RT> ? 6 : 1)))
 otw_advance_kernel(OtwArgs a) {
     static_assert(!SPEC || !DENSE, "the pipelined kernel writes no dense mirror");
-    constexpr int NT = 512;  // eight waves
+    static_assert(NT == 512 || (SPEC && W == 512 && kHasLiveRing<RT> && (NT == 768 || NT == 1024)),
+                  "wide workgroups: the pipelined W = 512 ring kernels only");
     // Waves >= HW0 pre-compute the next step's cell costs while waves 0/1 run the chains (pipelined kernel:
     // wave 2 runs the speculative column strip).
     constexpr int HW0 = SPEC ? 3 : 2;
     constexpr int NHELP = NT - 64 * HW0;
+    // one cost cell in flight per thread: the throughput flavour, and helpers that outnumber a strip's cells (otw_cost_row)
+    constexpr bool kOneCell = kThroughput<RT> || NT > 512;
+    static_assert(NT == 512 || NHELP >= W - 10, "a wide form's helpers cover a strip (c + 2 <= W - 10 cells) in one pass");
     RTS_STAMP_LOCALS();  // diagnostic builds only (otw_stamps.h), like every RTS_STAMP* / RTS_LW_* / RTS_W0_* below
     extern __shared__ __align__(16) unsigned char smem_raw[];
     OtwLds<W, RT> &S = *reinterpret_cast<OtwLds<W, RT> *>(smem_raw);
@@ -1403,7 +1417,7 @@ otw_advance_kernel(OtwArgs a) {
     pl.t = pl.j0 = 0;
     pl.flags = kPlanExit;
     if constexpr (SPEC) {
-        otw_costs_prime<W, RT>(S, e, S.t, S.j, tid, NT);
+        otw_costs_prime<W, RT, kOneCell>(S, e, S.t, S.j, tid, NT);
         if (wave == 0) {
             k.cA = rfl(S.R[swz<W>(k.j)]);
             k.cU = (k.t > 0) ? rfl(S.C[swz<W>(k.t - 1)]) : inf;
@@ -1442,7 +1456,7 @@ otw_advance_kernel(OtwArgs a) {
                     if (wave == HW0) otw_refill<W, RT>(S, k, e, pt + 3, 0, false);  // the reference has no ring here
                 if (!(pflags & kPlanHit)) RTS_STEP_BARRIER();  // this step's chains have read their cost buffers
                 if (!(pflags & kPlanStop))
-                    otw_costs_advance<W, RT>(S, e, pt, j0 + (do_col ? 1 : 0), do_row, do_col, tid - 64 * HW0, NHELP);
+                    otw_costs_advance<W, RT, kOneCell>(S, e, pt, j0 + (do_col ? 1 : 0), do_row, do_col, tid - 64 * HW0, NHELP);
                 RTS_LW_END(RTS_STEP_KIND(praw, pflags));
                 RTS_STEP_BARRIER();
                 sp ^= 1;

@@ -27,7 +27,7 @@ struct OtwArgs {
     int path_cap, live_cap;   // live_cap = 2N (otw_eran.py:14); the history stride is live_stride
     int ref_f64, live_f64;
     int clamp_len;            // run mode: never read past live_stride frames
-    long long *debug;         // diagnostic builds only (-DRTS_OTW_STAMPS): [B][16] cycle sums (level 2: [B][64])
+    long long *debug;         // diagnostic builds only (-DRTS_OTW_STAMPS): [B][16] cycle sums (level 2: [B][128])
     int spec;                 // 1: the pipelined kernel was selected (host-side choice; the kernel does not read it)
     double *dense_acc;        // optional [B][2N][N]: the reference's dense acc_cost (otw_eran.py:27), NULL = off
     double *dense_cost;       // optional [B][2N][N]: the reference's dense cost (otw_eran.py:23)

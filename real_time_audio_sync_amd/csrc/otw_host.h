@@ -17,7 +17,7 @@ namespace rts {
 // dynamic LDS an instantiation needs.
 struct LiveFromGlobal;
 struct LiveFromGlobalLean;
-template <int W, int DENSE, typename RT, bool SPEC>
+template <int W, int DENSE, typename RT, bool SPEC, int NT>
 __global__ void otw_advance_kernel(OtwArgs a);
 template <int W, typename RT, bool SPEC>
 constexpr size_t otw_lds_bytes();
@@ -195,12 +195,13 @@ __global__ void __launch_bounds__(256) otw_path_cost_kernel(PathCostArgs a) {
 }
 
 // One otw_advance_kernel instantiation as the handle launches it: eight waves -- wave 0: control (+ chains of steps that
-// are not hits), waves 1/2: chains, 3..7: cost strips, ring refill -- per stream.  fn == NULL: the handle has no kernel
-// for that kind of launch, which is refused.
+// are not hits), waves 1/2: chains, 3..7: cost strips, ring refill -- per stream; the wide forms (otw_plan::threads) have
+// 12 or 16, all the further ones cost strips.  fn == NULL: the handle has no kernel for that kind of launch, which is
+// refused.
 struct OtwKernel {
     const void *fn;
     size_t smem;  // dynamic LDS
-    int pipelined, ring;  // what the instantiation is (set_kernel, from its template arguments): rts_otw_read_kernel
+    int pipelined, ring, threads;  // what the instantiation is (set_kernel, from its template arguments): rts_otw_read_kernel
 };
 
 static_assert(otw_plan::kRingFloat == RTS_OTW_RING_FLOAT && otw_plan::kRingDouble == RTS_OTW_RING_DOUBLE &&
@@ -236,6 +237,7 @@ struct rts_otw {
     int device;         // the HIP device the handle's buffers live on (one handle = one device)
     int cus;            // its compute units
     int tp_from;        // batches of at least tp_from streams per CU take the residency-oriented kernel flavour
+    int waves;          // RTS_OTW_WAVES: 0 = auto, or 8 / 12 / 16 waves per stream where the kernel has that form (otw_plan::threads)
     int fill;           // RTS_OTW_FILL: 1 = a launch that can bring c frames to a fresh stream runs otw_bandfill_kernel first
     int fill_last;      // the handle's last launch enqueued it (host-side: which kernels ran is decided per call)
     int32_t *fill_took; // [B]: 1 where the stream's band was filled by that kernel (written by it, for every stream)
@@ -254,12 +256,13 @@ namespace rts {
 
 // Resolves one entry of the handle's kernel table.  The dynamic-LDS limit is a per-device function attribute: raised
 // here, at create, on the handle's device (a handle lives on one device).
-template <int W, int DENSE, typename RT, bool SPEC>
+template <int W, int DENSE, typename RT, bool SPEC, int NT = 512>
 static int set_kernel(OtwKernel *k) {
-    k->fn = reinterpret_cast<const void *>(&otw_advance_kernel<W, DENSE, RT, SPEC>);
+    k->fn = reinterpret_cast<const void *>(&otw_advance_kernel<W, DENSE, RT, SPEC, NT>);
     k->smem = otw_lds_bytes<W, RT, SPEC>();
     k->pipelined = SPEC;
     k->ring = ring_kind<RT>();
+    k->threads = NT;
     RTS_HIP(hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k->smem));
     return RTS_OK;
 }
@@ -267,7 +270,14 @@ static int set_kernel(OtwKernel *k) {
 // The instantiation of a table entry without mirror (otw_plan::entry).  The wide windows have one, the pipelined kernel
 // without ring; an else branch, so that none of the ring kernels is instantiated for them.
 template <int W>
-static int set_entry(const otw_plan::Entry &e, OtwKernel *k) {
+static int set_entry(const otw_plan::Entry &e, int threads, OtwKernel *k) {
+    if constexpr (W == 512) {  // the wide forms (otw_plan::threads): the pipelined ring kernels of this window alone
+        if (threads != 512) {
+            const bool f = e.ring == otw_plan::kRingFloat;
+            if (threads == 768) return f ? set_kernel<W, 0, float, true, 768>(k) : set_kernel<W, 0, double, true, 768>(k);
+            return f ? set_kernel<W, 0, float, true, 1024>(k) : set_kernel<W, 0, double, true, 1024>(k);
+        }
+    }
     if constexpr (W >= otw_plan::kWideWindow) {
         return set_kernel<W, 0, LiveFromGlobal, true>(k);
     } else {
@@ -294,7 +304,8 @@ static int resolve_kernels(rts_otw *h) {
     for (int live_f64 = 0; live_f64 < 2; live_f64++) {
         const otw_plan::Entry e = otw_plan::entry(W, h->spec, h->tp_from, h->cus, h->B, h->ref_dtype == RTS_F64, live_f64 != 0);
         if (!e.ok) continue;  // RTS_OTW_SPEC=0 at a wide window: no plain entry, launch() refuses
-        if (int rc = set_entry<W>(e, &h->k_plain[live_f64]); rc != RTS_OK) return rc;
+        const int threads = otw_plan::threads(W, e, h->B, h->cus, h->waves);  // (h->waves was checked at create)
+        if (int rc = set_entry<W>(e, threads, &h->k_plain[live_f64]); rc != RTS_OK) return rc;
     }
     return RTS_OK;
 }
@@ -330,7 +341,7 @@ static int launch(rts_otw *h, const OtwArgs &args, hipStream_t s, int max_new) {
     const OtwKernel &k = args.trace_cells ? h->k_trace : args.dense_acc ? h->k_dense : h->k_plain[args.live_f64 != 0];
     if (!k.fn) return no_kernel(h);
     void *params[] = {const_cast<OtwArgs *>(&args)};
-    RTS_HIP(hipLaunchKernel(k.fn, dim3(h->B), dim3(512), params, k.smem, s));
+    RTS_HIP(hipLaunchKernel(k.fn, dim3(h->B), dim3(k.threads), params, k.smem, s));
     return RTS_OK;
 }
 
@@ -457,12 +468,20 @@ static void fill_dense(const rts_otw *h, double *acc, double *cost, const Restar
 // least RTS_OTW_TP_FROM streams per CU take the residency-oriented flavour (tests: 0 selects it at any batch size).
 // Results are identical.
 // RTS_OTW_FILL=0 leaves the band fill of fresh streams to the step loop (otw_bandfill_kernel is never enqueued).
+// RTS_OTW_WAVES=8 / 12 / 16 fixes the waves per stream of the kernels that have a wide form (otw_plan::threads; A/B runs,
+// tests); unset or empty: chosen from the batch size.  Anything else is refused by rts_otw_create.
 struct OtwKnobs {
-    int spec, tp_from, fill;
+    int spec, tp_from, fill, waves;
 };
 static OtwKnobs otw_knobs() {
     const char *sp = getenv("RTS_OTW_SPEC"), *tp = getenv("RTS_OTW_TP_FROM"), *fl = getenv("RTS_OTW_FILL");
-    return {sp ? (atoi(sp) != 0) : 1, tp ? atoi(tp) : 2, fl ? (atoi(fl) != 0) : 1};
+    const char *wv = getenv("RTS_OTW_WAVES");
+    int waves = 0;
+    if (wv && *wv) {
+        waves = atoi(wv);
+        if (waves == 0) waves = -1;  // "0", "auto", "x": not a wave count
+    }
+    return {sp ? (atoi(sp) != 0) : 1, tp ? atoi(tp) : 2, fl ? (atoi(fl) != 0) : 1, waves};
 }
 
 // The constructor behind rts_otw_create (first_host == NULL: one reference of N frames) and rts_otw_create_refs (N =
@@ -483,6 +502,10 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
         return set_error(RTS_ERR_INVALID, "bad cost_kind %d", cost_kind);
     if ((long long)N * 3 + 8 > 0x3fffffffLL) return set_error(RTS_ERR_INVALID, "N too large");
 
+    const OtwKnobs knobs = otw_knobs();
+    if (!otw_plan::waves_ok(knobs.waves))
+        return set_error(RTS_ERR_INVALID, "RTS_OTW_WAVES must be 8, 12 or 16 (got \"%s\")", getenv("RTS_OTW_WAVES"));
+
     rts_otw *h = (rts_otw *)calloc(1, sizeof(rts_otw));
     if (!h) return set_error(RTS_ERR_INVALID, "out of host memory");
     h->ref = ref_dev;
@@ -495,8 +518,8 @@ static int otw_create(const void *ref_dev, int ref_dtype, int F, int N, int B, i
     h->variant = variant;
     h->cost_kind = cost_kind;
     h->W = otw_plan::window(c);
-    const OtwKnobs knobs = otw_knobs();
     h->spec = knobs.spec;
+    h->waves = knobs.waves;
     h->tp_from = knobs.tp_from;
     h->fill = knobs.fill;
     h->hist_stride = 2 * N;
@@ -691,6 +714,16 @@ int rts_otw_read_kernel(const rts_otw *h, int live_dtype, int32_t out[4]) {
     out[1] = k.ring;
     out[2] = k.pipelined;
     out[3] = otw_plan::fill_gate(h->fill, h->c, h->c, h->W, h->dense_acc != nullptr);
+    return RTS_OK;
+}
+
+int rts_otw_read_kernel_waves(const rts_otw *h, int live_dtype, int32_t *waves) {
+    using namespace rts;
+    if (!h || !waves) return set_error(RTS_ERR_INVALID, "NULL argument");
+    if (!dtype_ok(live_dtype)) return set_error(RTS_ERR_INVALID, "bad live_dtype %d", live_dtype);
+    const OtwKernel &k = h->dense_acc ? h->k_dense : h->k_plain[live_dtype == RTS_F64];
+    if (!k.fn) return no_kernel(h);
+    *waves = k.threads / 64;
     return RTS_OK;
 }
 

@@ -51,6 +51,25 @@ inline Entry entry(int W, int spec, int tp_from, int cus, int B, bool ref_f64, b
     return Entry{1, 1, B <= cus ? kRingDouble : kRingNone};
 }
 
+// Threads per workgroup of an entry's kernel: 512 (eight waves) but for the wide forms of the pipelined W = 512 ring
+// kernels, which exist for the batches that leave every stream a CU of its own.  The 512-thread kernel is sized for two
+// workgroups per CU; alone on a CU it leaves half of every SIMD's wave slots empty, and the wide forms fill them with
+// helper waves (cost strips): 768 threads = 12 waves, 9 of them helpers, 1024 = 16 waves, 13 helpers.
+//   `waves`: RTS_OTW_WAVES, read at create.  0 (unset): kWideWaves where B <= cus, else 8 -- a float32 handle with
+//   cus < B < tp_from * cus shares a CU between two workgroups and keeps 512 threads.  8 / 12 / 16: that width at any B
+//   (A/B runs, tests).  Anything else: -1, rts_otw_create refuses.
+//   Every other kernel -- plain, none, none-lean, W != 512, the dense mirror -- has the 512-thread form alone, whatever
+//   `waves` says: its residency or its tests depend on it.
+constexpr int kWideWaves = 12;  // what `auto` takes where B <= cus: the measured winner over 8 and 16 (profiles/otw_wide_summary.md)
+inline bool waves_ok(int waves) { return waves == 0 || waves == 8 || waves == 12 || waves == 16; }
+inline int threads(int W, const Entry &e, int B, int cus, int waves) {
+    if (!waves_ok(waves)) return -1;
+    const bool has_wide = e.ok && e.pipelined && W == 512 && (e.ring == kRingFloat || e.ring == kRingDouble);
+    if (!has_wide) return 512;
+    if (waves == 0) waves = (B <= cus) ? kWideWaves : 8;
+    return 64 * waves;
+}
+
 // The entry of a launch that writes the dense mirror or the backward trace: the plain kernel at every window, whatever
 // RTS_OTW_SPEC, with the double ring where one fits.
 constexpr Entry mirror_entry(int W) { return Entry{1, 0, W >= kWideWindow ? kRingNone : kRingDouble}; }

@@ -6,9 +6,9 @@
 //     5 plan); 6 / 14 = their counts.  The plain kernel's wave 0 uses 0, 3, 5 and 8 for its four phases.
 //   -DRTS_OTW_STAMPS=2: only the work / end-of-step wait split of the pipelined kernel, two stamps per step, by step
 //     kind: 0 Row-only / Column-only hit, 1 Both hit while the band fills (planned as a hit), 2 Both hit with a full band
-//     (planned "hit if", resolved to a hit), 3 every other step.  [B][64]: 16 words per step kind -- 0 wave-0 work, 1 its
-//     end-of-step wait, 2 steps, 3..9 own work of waves 1..7; words 10, 11 of kind 0: the extra carry rounds of waves 1, 2
-//     (all steps).
+//     (planned "hit if", resolved to a hit), 3 every other step.  [B][128]: 32 words per step kind -- 0 wave-0 work, 1 its
+//     end-of-step wait, 2 steps, 3..17 own work of waves 1..15 (as many as the instantiation has: NT / 64 - 1; the rest
+//     stay 0); words 18, 19 of kind 0: the extra carry rounds of waves 1, 2 (all steps).
 // These are macros because they name the kernel's locals (RTS_STAMP_LOCALS declares them; tid, lane, wave, a, e and the
 // plan constants are the kernel's own), and the sums are separate scalars: an indexed array would go to scratch.
 // RTS_W0_STEP_END contains the step's barrier (RTS_STEP_BARRIER, otw.hip) in every build.
@@ -65,13 +65,13 @@
     long long lb_k0 = 0, lb_k1 = 0, lb_k2 = 0, lb_k3 = 0; /* wave 0: end-of-step barrier wait */                        \
     long long ln_k0 = 0, ln_k1 = 0, ln_k2 = 0, ln_k3 = 0; /* wave 0: steps */                                           \
     long long l_last = 0;                                                                                               \
-    long long lo_k0 = 0, lo_k1 = 0, lo_k2 = 0, lo_t0 = 0; /* waves 1..7: own work in hit steps */                       \
+    long long lo_k0 = 0, lo_k1 = 0, lo_k2 = 0, lo_t0 = 0; /* waves 1..15: own work in hit steps */                      \
     long long lo_rounds = 0                               /* waves 1, 2: extra carry rounds of their speculative chains */
 #define RTS_ROUNDS_ACC (&lo_rounds)
 // the step kind from the plan flags as published (raw) and as resolved by otw_resolve_plan (res)
 #define RTS_STEP_KIND(raw, res)                                                                          \
     (!((res) & kPlanHit) ? 3 : (((res) & (kPlanRow | kPlanCol)) != (kPlanRow | kPlanCol)) ? 0 : ((raw) & kPlanHitIf) ? 2 : 1)
-// waves 1..7: the wave's own work in a step, from the plan read to the end-of-step barrier
+// waves 1..NT/64-1: the wave's own work in a step, from the plan read to the end-of-step barrier
 #define RTS_LW_BEGIN() do { lo_t0 = (long long)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); } while (0)
 #define RTS_LW_END(kind)                                                  \
     do {                                                                  \
@@ -105,13 +105,13 @@
 #define RTS_STAMP_WRITE_BACK()                                                                                          \
     do {                                                                                                                \
         if (a.debug) {                                                                                                  \
-            long long *dbg = a.debug + (size_t)e.b * 64;                                                                \
+            long long *dbg = a.debug + (size_t)e.b * 128;                                                               \
             if (tid == 0) {                                                                                             \
-                dbg[0] = lw_k0, dbg[1] = lb_k0, dbg[2] = ln_k0, dbg[16] = lw_k1, dbg[17] = lb_k1, dbg[18] = ln_k1;      \
-                dbg[32] = lw_k2, dbg[33] = lb_k2, dbg[34] = ln_k2, dbg[48] = lw_k3, dbg[49] = lb_k3, dbg[50] = ln_k3;   \
+                dbg[0] = lw_k0, dbg[1] = lb_k0, dbg[2] = ln_k0, dbg[32] = lw_k1, dbg[33] = lb_k1, dbg[34] = ln_k1;      \
+                dbg[64] = lw_k2, dbg[65] = lb_k2, dbg[66] = ln_k2, dbg[96] = lw_k3, dbg[97] = lb_k3, dbg[98] = ln_k3;   \
             }                                                                                                           \
-            if (lane == 0 && wave >= 1 && wave <= 7) dbg[2 + wave] = lo_k0, dbg[18 + wave] = lo_k1, dbg[34 + wave] = lo_k2; \
-            if (lane == 0 && wave >= 1 && wave <= 2) dbg[9 + wave] = lo_rounds;                                         \
+            if (lane == 0 && wave >= 1 && wave <= 15) dbg[2 + wave] = lo_k0, dbg[34 + wave] = lo_k1, dbg[66 + wave] = lo_k2; \
+            if (lane == 0 && wave >= 1 && wave <= 2) dbg[17 + wave] = lo_rounds;                                        \
         }                                                                                                               \
     } while (0)
 
@@ -142,7 +142,7 @@ int rts_otw_set_debug(rts_otw *h, long long *debug_dev) {
 }
 /* What this library was built with, so that the caller sizes the buffer by the library and not by its own settings. */
 int rts_otw_stamp_level(void) { return RTS_OTW_STAMPS; }
-int rts_otw_debug_words(void) { return (RTS_OTW_STAMPS == 2) ? 64 : 16; }
+int rts_otw_debug_words(void) { return (RTS_OTW_STAMPS == 2) ? 128 : 16; }
 
 }  // extern "C"
 #endif

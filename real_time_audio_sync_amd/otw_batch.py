@@ -289,12 +289,18 @@ class BatchedOTW(_BatchedHandle):
     def kernel_name(self):
         return nat.lib.rts_otw_kernel_name(self._h).decode()
 
-    def kernel(self, live_dtype=None):
+    def kernel(self, live_dtype=None, with_waves=False):
         """What a launch with live input of ``live_dtype`` runs (rts_otw_read_kernel; no GPU call): ``dict(window, ring,
         pipelined, fill)`` with ``ring`` one of 'float', 'double', 'none', 'none-lean'.  ``None``: float64, the handle's
         own history, which ``insert`` and ``push`` read whatever dtype their frames come in; for ``run`` pass the live
-        tensor's dtype."""
+        tensor's dtype.  ``with_waves``: also ``waves``, the waves per stream of that kernel (rts_otw_read_kernel_waves:
+        8, or 12 / 16 for the wide forms a handle takes at ``batch <= CUs``; ``RTS_OTW_WAVES`` fixes it at create)."""
         out = (ctypes.c_int32 * 4)()
         code = nat.F64 if live_dtype is None else _np_dtype_code(live_dtype)
         nat.check(nat.lib.rts_otw_read_kernel(self._h, code, out))
-        return dict(window=int(out[0]), ring=nat.OTW_RINGS[out[1]], pipelined=bool(out[2]), fill=bool(out[3]))
+        info = dict(window=int(out[0]), ring=nat.OTW_RINGS[out[1]], pipelined=bool(out[2]), fill=bool(out[3]))
+        if with_waves:
+            waves = ctypes.c_int32()
+            nat.check(nat.lib.rts_otw_read_kernel_waves(self._h, code, ctypes.byref(waves)))
+            info["waves"] = int(waves.value)
+        return info

@@ -2,7 +2,7 @@
 """Diagnostic (not shipped): build librtsync with -DRTS_OTW_STAMPS into tools/_diag/ and print
 the share of wave-0 cycles each phase of otw_advance_kernel takes on the bench workload.
 
-    RTS_DIAG_LEVEL=1|2 python tools/otw_phase_profile.py [--build]
+    RTS_DIAG_LEVEL=1|2 [RTS_OTW_WAVES=8|12|16] python tools/otw_phase_profile.py [--build]
 
 RTS_DIAG_LIB=<path> runs a
 diagnostic library built earlier.  The stamp level and the size of the debug buffer are the library's own
@@ -16,15 +16,21 @@ DEFAULT_SO = os.path.join(DIAG, "librtsync_diag.so")
 
 
 def build():
+    """otw.hip with the stamps, linked with the package's own objects of every other source (the tracker's ABI reaches into
+    tempo.hip and from there on, so the library is only whole with all of them)."""
+    from real_time_audio_sync_amd import _build
+    _build.build()
+    if not os.path.isdir(_build.OBJ_DIR):   # the library was there already, its objects were not
+        _build.build(force=True)
     os.makedirs(DIAG, exist_ok=True)
     so = DEFAULT_SO
-    src = [os.path.join(ROOT, "real_time_audio_sync_amd", "csrc", f) for f in ("common.cpp", "otw.hip")]
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
-           "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-amdgpu-sched-strategy=max-ilp",  # as _build.PER_SOURCE_FLAGS["otw.hip"]
-           "-DRTS_OTW_STAMPS=%s" % os.environ.get("RTS_DIAG_LEVEL", "1"), "-o", so]
-    for s in src:
-        cmd += ["-x", "hip", s]
-    subprocess.check_call(cmd)
+    obj = os.path.join(DIAG, "otw.hip.o")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc] + _build.HIPCC_FLAGS + _build.PER_SOURCE_FLAGS["otw.hip"] +
+                          ["-DRTS_OTW_STAMPS=%s" % os.environ.get("RTS_DIAG_LEVEL", "1"), "-c", "-x", "hip",
+                           os.path.join(_build.CSRC, "otw.hip"), "-o", obj])
+    others = [os.path.join(_build.OBJ_DIR, os.path.basename(f) + ".o") for f in _build.sources() if os.path.basename(f) != "otw.hip"]
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj] + others)
     return so
 
 
@@ -72,23 +78,27 @@ def main():
         d = dbg.cpu().numpy().astype(np.float64)
         frames = st[:, 8].sum()
         if LEVEL2:
-            # [B][64]: 16 words per step kind (0 wave-0 work, 1 its end-of-step wait, 2 steps, 3..9 own work of waves 1..7)
+            # [B][128]: 32 words per step kind (0 wave-0 work, 1 its end-of-step wait, 2 steps, 3..17 own work of waves
+            # 1..15: those past the kernel's own count stay 0 and are not printed)
             kinds = ("single hits (Row-only / Column-only)", "Both hits while the band fills", "Both hits with a full band (\"hit if\")")
-            tot = d.reshape(B, 4, 16).sum(axis=0)
+            assert words == 128, "a level-2 library of another stamp layout (otw_stamps.h)"
+            tot = d.reshape(B, 4, 32).sum(axis=0)
+            nh = max((i for i in range(13) if tot[:3, 5 + i].any()), default=4) + 1  # helper waves that stamped: 5, 9 or 13
+            hl = "helper waves 3-%d" % (2 + nh)
             hits = tot[:3].sum(axis=0)
             n = max(hits[2], 1)
             print("hit steps: %d  wave-0 work %.0f cycles, end-of-step barrier wait %.0f cycles" % (hits[2], hits[0] / n, hits[1] / n))
             n3 = max(tot[3, 2], 1)
             print("other steps: %d  wave-0 work %.0f cycles, end-of-step barrier wait %.0f cycles" % (tot[3, 2], tot[3, 0] / n3, tot[3, 1] / n3))
-            print("hit steps, own work: wave 1 (row speculation) %.0f, wave 2 (column speculation) %.0f, helper waves 3-7: %s"
-                  % (hits[3] / n, hits[4] / n, ", ".join("%.0f" % (hits[5 + i] / n) for i in range(5))))
+            print("hit steps, own work: wave 1 (row speculation) %.0f, wave 2 (column speculation) %.0f, %s: %s"
+                  % (hits[3] / n, hits[4] / n, hl, ", ".join("%.0f" % (hits[5 + i] / n) for i in range(nh))))
             for kd, label in enumerate(kinds):
                 nk = max(tot[kd, 2], 1)
-                print("%s: %d  wave-0 work %.0f + wait %.0f, wave 1 %.0f, wave 2 %.0f, helper waves 3-7: %s"
-                      % (label, tot[kd, 2], tot[kd, 0] / nk, tot[kd, 1] / nk, tot[kd, 3] / nk, tot[kd, 4] / nk,
-                         ", ".join("%.0f" % (tot[kd, 5 + i] / nk) for i in range(5))))
+                print("%s: %d  wave-0 work %.0f + wait %.0f, wave 1 %.0f, wave 2 %.0f, %s: %s"
+                      % (label, tot[kd, 2], tot[kd, 0] / nk, tot[kd, 1] / nk, tot[kd, 3] / nk, tot[kd, 4] / nk, hl,
+                         ", ".join("%.0f" % (tot[kd, 5 + i] / nk) for i in range(nh))))
             steps = max(tot[:, 2].sum(), 1)
-            print("extra carry rounds per speculative chain: row %.2f, column %.2f" % (tot[0, 10] / steps, tot[0, 11] / steps))
+            print("extra carry rounds per speculative chain: row %.2f, column %.2f" % (tot[0, 18] / steps, tot[0, 19] / steps))
             return
         nm = ["barrier-2 wait", "phase A (chain / install) | hit: step entry", "barrier-1 wait", "settle", "decide", "plan + refill"]
         for base, label in ((0, "hit steps"), (8, "other steps")):
