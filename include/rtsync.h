@@ -440,6 +440,40 @@ int rts_locate(const void *queries_dev, int q_dtype, int M_max, const int32_t *q
                const int32_t *piece_len_dev, int P, int cost_kind, double *cost_dev, int32_t *end_dev,
                int32_t *start_dev, double *row_dev, int32_t *rowstart_dev, void *stream);
 
+/* Ranked non-overlapping matches per (stream, piece): music repeats, and an excerpt of a repeated section matches every
+ * pass equally well, of which rts_locate reports the earliest only.  For one query, one piece of N columns, its last
+ * row D = D[M-1][:] and its starts S = S[M-1][:] exactly as rts_locate defines them:
+ *   rank r = 0, 1, ..., K-1: among the columns j with D[j] finite that are not suppressed, the first minimum of D[j]
+ *          (strict <, columns ascending): end_r = j, cost_r = D[j], start_r = S[j].  Column j is suppressed when its own
+ *          match range [S[j], j] intersects the range of an earlier rank: S[j] <= end_q && j >= start_q for some q < r.
+ *   The list ends at the first rank where no column is left or where cost_r > max_cost (+inf: no cut-off).
+ * Rank 0 is rts_locate's (cost, end, start) bit for bit; costs are non-decreasing in rank, ranges pairwise disjoint; with
+ * M = 1 the ranks are the K cheapest columns in stable order.
+ *   queries_dev ... cost_kind: rts_locate's arguments, unchanged.
+ *   cost_dev double[B][P][K], end_dev / start_dev int32[B][P][K], n_dev int32[B][P]: n = ranks written; slots from n on
+ *          hold +inf, -1, -1.  A piece with len < 1 or outside the pool gives n = 0 and empty slots for every stream; so
+ *          does a stream with q_len <= 0 for every piece.
+ *   Overlapping pieces: rts_locate's row holds "the value of one of them" in shared cells, so a valid piece whose pool
+ *          range intersects the range of another valid piece (identical ranges included) gets n = -1: slot 0 holds
+ *          rts_locate's own answer for it, the other slots are empty.  (q_len <= 0 comes first: n = 0.)  The flag is
+ *          decided on the device, by one workgroup that tests every piece against the table: P * P / 1024 tests per
+ *          thread, meant for a repertoire's few hundred pieces.
+ *   ws_dev: rts_locate_matches_workspace_bytes(B, n_pool_frames) bytes of the caller's device memory, any alignment.  It
+ *          holds the rows and the starts: 256 + (8 B n_pool_frames rounded up to 256) + (4 B n_pool_frames rounded up to
+ *          256) bytes.  It needs no initialisation and no result depends on what it held before.
+ * Three launches on `stream`: the kernel of rts_locate with both row outputs in the workspace, the overlap flags, the
+ * ranks (one workgroup per (piece, stream): K rounds of a first-minimum reduction over the piece's row).
+ * Limits and errors as rts_locate, and: 1 <= K <= 32 (K < 1 RTS_ERR_INVALID, K > 32 RTS_ERR_UNSUPPORTED); a NaN max_cost,
+ * n_dev or ws_dev NULL, ws_bytes too small, n_pool_frames > 2^40: RTS_ERR_INVALID naming the argument.  All checks come
+ * before the first HIP call.
+ * Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable). */
+int rts_locate_matches_workspace_bytes(int B, long long n_pool_frames, size_t *bytes);
+int rts_locate_matches(const void *queries_dev, int q_dtype, int M_max, const int32_t *q_len_dev, int B,
+                       const void *pool_dev, int pool_dtype, int F, long long n_pool_frames,
+                       const long long *piece_first_dev, const int32_t *piece_len_dev, int P, int cost_kind, int K,
+                       double max_cost, double *cost_dev, int32_t *end_dev, int32_t *start_dev, int32_t *n_dev,
+                       void *ws_dev, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Chroma front end: frame -> window -> rFFT -> power -> 12-bin filterbank -> L2 normalise.
  * ------------------------------------------------------------------------------------------ */

@@ -14,6 +14,9 @@ def __getattr__(name):
     if name == "locate_batch":
         from .locate import locate_batch
         return locate_batch
+    if name == "locate_matches":
+        from .locate import locate_matches
+        return locate_matches
     if name == "locate":
         import importlib
         return importlib.import_module(".locate", __name__)

@@ -84,7 +84,7 @@ class _BatchedHandle:
         self._restarted(first, lens, pieces)
 
     @nat.on_device
-    def locate(self, queries, q_len=None, euclid=None):
+    def locate(self, queries, q_len=None, euclid=None, matches=1):
         """Where in the repertoire is each microphone?  ``queries``: the last frames every stream heard -- a device
         tensor [B][M_max][12] (frame-major like ``push`` takes them), or a list of B arrays (12, M_b) in the
         reference's layout; at most 256 frames.  ``q_len``: valid frames per stream for the tensor form (list of ints
@@ -94,8 +94,13 @@ class _BatchedHandle:
         Returns, per stream, a list of ``(ref_object, start, end, cost)`` for every distinct piece uploaded at create
         (``refs`` + ``extra_refs``), cheapest first, ties in upload order: the excerpt matches frames start..end of
         that piece.  ``restart([b], refs=[ref_object], offsets=[start])`` puts the stream there.  Features must be
-        finite (``locate.locate_batch``).  Synchronises."""
-        from .locate import locate_batch
+        finite (``locate.locate_batch``).  Synchronises.
+
+        ``matches=K`` (2..32): up to K ranked, non-overlapping matches per piece instead of the first minimum alone
+        (``locate.locate_matches``) -- an excerpt of a repeated section is found in every pass of the repeat.  Every
+        stream's list then holds an entry for every rank of every piece, cheapest first, ties in upload order, then in
+        rank order.  ``matches=1`` is the call above, unchanged."""
+        from .locate import locate_batch, locate_matches
         if self._pool is None:
             raise ValueError("locate needs a handle made by with_references")
         if not torch.is_tensor(queries):
@@ -118,6 +123,17 @@ class _BatchedHandle:
                                   torch.tensor([n for _, _, n in pieces], dtype=torch.int32, device=self.device))
         if euclid is None:
             euclid = bool(getattr(self, "euclid", False))
+        if int(matches) != 1:
+            cost, end, start, n = (t.cpu().numpy() for t in locate_matches(queries, q_len, self.ref, *self._piece_tables,
+                                                                           int(matches), euclid=euclid))
+            out = []
+            for b in range(self.B):
+                # n = -1 (pieces that share pool frames; with_references never builds such a pool): slot 0 alone
+                ranks = [(p, r) for p in range(len(pieces)) for r in range(max(int(n[b, p]), -int(n[b, p])))
+                         if np.isfinite(cost[b, p, r]) and end[b, p, r] >= 0]
+                ranks.sort(key=lambda pr: (cost[b, pr[0], pr[1]], pr[0], pr[1]))
+                out.append([(pieces[p][0], int(start[b, p, r]), int(end[b, p, r]), float(cost[b, p, r])) for p, r in ranks])
+            return out
         cost, end, start = (t.cpu().numpy() for t in
                             locate_batch(queries, q_len, self.ref, *self._piece_tables, euclid=euclid))
         out = []
@@ -145,27 +161,42 @@ class _BatchedHandle:
                                      mask.data_ptr() if mask is not None else None, self._stream()))
         return frames, lens
 
-    def locate_recent(self, M=128, streams=None, euclid=None):
+    def locate_recent(self, M=128, streams=None, euclid=None, matches=1):
         """``locate`` on what the streams heard last: ``recent(M, streams)`` handed to ``locate``.  Same return value;
         streams not listed get ``[]``."""
         frames, lens = self.recent(M, streams)
-        return self.locate(frames, lens, euclid)
+        return self.locate(frames, lens, euclid, matches)
 
-    def reacquire(self, streams, M=128):
+    def reacquire(self, streams, M=128, matches=1, choose=None):
         """This microphone is lost: put it where it really is.  For the listed streams: take the last ``M`` frames each
         heard (``recent``, before anything is cleared), ``locate`` them in the repertoire, ``restart`` every stream
         that got an answer onto the cheapest ``(piece, start)``, and ``push`` its excerpt into the restarted tracker, so
         that it re-follows those frames from ``start`` and stands at "now" instead of M frames behind.  One restart
         and one push in all; the other streams receive no frame and no restart.  Returns ``{b: (piece, start, end,
         cost) | None}`` (None: nothing heard yet, nothing changed).  Whether a stream is lost is the caller's decision:
-        compare ``path_cost`` with ``cost / (M + end - start + 1)`` of a ``locate_recent``.  Synchronises (locate)."""
-        return self._reacquire(streams, M, self.restart)
+        compare ``path_cost`` with ``cost / (M + end - start + 1)`` of a ``locate_recent``.  Synchronises (locate).
 
-    def _reacquire(self, streams, M, restart):
+        A piece that repeats a section holds several equally good matches, and the cheapest entry is the earliest of
+        them.  ``matches=K`` searches with ``locate(..., matches=K)``; ``choose(b, candidates) -> index | None`` picks the
+        candidate stream b is restarted on (``candidates``: its list, a ``locate.Candidates`` whose ``M`` is the number
+        of frames the excerpt has; None: leave this stream alone, it is reported as None).  Without ``choose`` the first
+        candidate is taken; ``locate.nearest_to`` builds one that prefers the pass nearest to where the stream was."""
+        return self._reacquire(streams, M, self.restart, matches, choose)
+
+    def _reacquire(self, streams, M, restart, matches=1, choose=None):
         streams = list(dict.fromkeys(int(b) for b in streams))
         frames, lens = self.recent(M, streams)
-        found = self.locate(frames, lens)
-        out = {b: (found[b][0] if found[b] else None) for b in streams}
+        found = self.locate(frames, lens, None, matches)
+        if choose is None:
+            out = {b: (found[b][0] if found[b] else None) for b in streams}
+        else:
+            from .locate import Candidates
+            heard, out = lens.cpu().numpy(), {}
+            for b in streams:
+                cand = Candidates(found[b])
+                cand.M = int(heard[b])
+                k = choose(b, cand) if cand else None
+                out[b] = cand[int(k)] if k is not None else None
         moved = [b for b in streams if out[b] is not None]
         if moved:
             restart(moved, refs=[out[b][0] for b in moved], offsets=[out[b][1] for b in moved])

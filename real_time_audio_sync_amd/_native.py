@@ -95,7 +95,10 @@ _decl("rts_dtw_subseq_paths", _i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp,
                                      _vp, _vp, _vp, ctypes.c_size_t, _vp])
 _decl("rts_locate", _i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                            _vp, _vp])
-
+LOCATE_MAX_K = 32  # kLocMaxK (csrc/locate.hip)
+_decl("rts_locate_matches_workspace_bytes", _i32, [_i32, _i64, ctypes.POINTER(ctypes.c_size_t)])
+_decl("rts_locate_matches", _i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _i32,
+                                   ctypes.c_double, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp])
 
 _decl("rts_chroma_num_frames", _i64, [_i64, _i32, _i32, _i32])
 _decl("rts_chroma_create", _i32, [_i32, _i32, _vp, _vp, ctypes.POINTER(_vp)])

@@ -261,13 +261,173 @@ __global__ void __launch_bounds__(kLocMaxM) locate_kernel(LocArgs g) {
 
 }  // namespace rts
 
-extern "C" {
+namespace rts {
 
-int rts_locate(const void *queries_dev, int q_dtype, int M_max, const int32_t *q_len_dev, int B, const void *pool_dev,
-               int pool_dtype, int F, long long n_pool_frames, const long long *piece_first_dev,
-               const int32_t *piece_len_dev, int P, int cost_kind, double *cost_dev, int32_t *end_dev,
-               int32_t *start_dev, double *row_dev, int32_t *rowstart_dev, void *stream) {
-    using namespace rts;
+constexpr int kLocMaxK = 32;            // ranks per (stream, piece) of rts_locate_matches
+constexpr int kLocMatchThreads = 256;   // locate_matches_kernel: four waves scan one row
+constexpr int kLocOverlapThreads = 1024;
+
+struct LocMatchArgs {
+    const int32_t *q_len;      // [B] or NULL
+    const long long *first;    // [P]
+    const int32_t *len;        // [P]
+    const double *row;         // [B][n_pool]: D[M-1][:] of every valid piece at its pool position
+    const int32_t *rowstart;   // [B][n_pool]: S[M-1][:]
+    double *cost;              // [B][P][K]
+    int32_t *end, *start;      // [B][P][K]
+    int32_t *n;                // [B][P]
+    long long n_pool;
+    double max_cost;
+    int M_max, P, K;
+};
+
+__device__ __forceinline__ bool loc_piece_valid(long long first, int N, long long n_pool) {
+    return N >= 1 && first >= 0 && first <= n_pool - N;
+}
+
+// One workgroup, behind locate_kernel and in front of locate_matches_kernel.
+// 1. n[b][p] = -1 for a valid piece whose pool range intersects that of another valid piece (its cells of the row hold
+//    "the value of one of them"), 0 otherwise: every thread tests its pieces against the whole table.
+// 2. locate_kernel left its own (cost, end, start) packed [B][P] at the front of the [B][P][K] outputs; those of the
+//    flagged pieces move to their slot 0, at K (b P + p).  Index i moves up to K i >= i, so chunks of the packed
+//    array are taken from the top down, each read into registers before any of it is written: a store can only land
+//    on packed entries of this chunk or of one already moved.  Entries of pieces without a flag are not moved at
+//    all: locate_matches_kernel finds rank 0 again in the row, bit for bit.
+__global__ void __launch_bounds__(kLocOverlapThreads) locate_overlap_kernel(LocMatchArgs g, int B) {
+    for (int p = threadIdx.x; p < g.P; p += kLocOverlapThreads) {
+        const long long f = g.first[p];
+        const int N = g.len[p];
+        int flag = 0;
+        if (loc_piece_valid(f, N, g.n_pool)) {
+            for (int q = 0; q < g.P; q++) {
+                const long long fq = g.first[q];
+                const int Nq = g.len[q];
+                if (q != p && loc_piece_valid(fq, Nq, g.n_pool) && fq < f + N && f < fq + Nq) flag = -1;
+            }
+        }
+        for (int b = 0; b < B; b++) g.n[(size_t)b * g.P + p] = flag;
+    }
+    __syncthreads();
+    if (g.K == 1) return;  // slot 0 is the packed entry itself
+    const long long total = (long long)B * g.P;
+    for (long long c0 = (total - 1) / kLocOverlapThreads * kLocOverlapThreads; c0 >= 0; c0 -= kLocOverlapThreads) {
+        const long long i = c0 + threadIdx.x;
+        const bool mv = i < total && g.n[i] < 0;
+        double c = 0.0;
+        int e = 0, s = 0;
+        if (mv) {
+            c = g.cost[i];
+            e = g.end[i];
+            s = g.start[i];
+        }
+        __syncthreads();
+        if (mv) {
+            g.cost[i * g.K] = c;
+            g.end[i * g.K] = e;
+            g.start[i * g.K] = s;
+        }
+    }
+}
+
+// Ranked non-overlapping matches of one (piece, stream) from its last row: K rounds of a first-minimum reduction.  A
+// round: every lane scans columns tid, tid + 256, ... (coalesced; the row stays in L2 between
+// rounds) and keeps its first minimum among the finite columns whose own range [S[j], j] meets no range taken so far --
+// the interval test against the <= K ranges in LDS, run (with the load of S[j]) only for a column that would improve the
+// lane's minimum; the (value, column) pairs are combined over their total order by a butterfly in the wave and through
+// LDS across the four waves; thread 0 appends the winner.  Nothing is written but the outputs.
+__global__ void __launch_bounds__(kLocMatchThreads) locate_matches_kernel(LocMatchArgs g) {
+    constexpr int kWaves = kLocMatchThreads / 64;
+    __shared__ double wv[kWaves];
+    __shared__ int wc[kWaves];
+    __shared__ int rs[kLocMaxK], re[kLocMaxK];  // ranges taken: start, end
+    __shared__ int more;
+    const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const size_t out = (size_t)b * g.P + p;
+    const int K = g.K;
+
+    int M = g.q_len ? g.q_len[b] : g.M_max;
+    M = M < g.M_max ? M : g.M_max;
+    const long long first = g.first[p];
+    const int N = g.len[p];
+    const bool nothing = M < 1 || !loc_piece_valid(first, N, g.n_pool);  // locate_kernel's own test
+    if (nothing || g.n[out] < 0) {  // uniform: the whole workgroup leaves before its first barrier
+        // nothing to match: n = 0, every slot empty.  Overlapping piece: n = -1 and slot 0 are already in place.
+        for (int k = tid + (nothing ? 0 : 1); k < K; k += kLocMatchThreads) {
+            g.cost[out * K + k] = INFINITY;
+            g.end[out * K + k] = -1;
+            g.start[out * K + k] = -1;
+        }
+        if (nothing && tid == 0) g.n[out] = 0;
+        return;
+    }
+
+    const double *D = g.row + (size_t)b * (size_t)g.n_pool + (size_t)first;
+    const int32_t *S = g.rowstart + (size_t)b * (size_t)g.n_pool + (size_t)first;
+    int n = 0;
+    for (int r = 0; r < K; r++) {
+        double v = INFINITY;  // a lane without a column never wins
+        int c = 0x7fffffff;
+        for (int j = tid; j < N; j += kLocMatchThreads) {
+            const double d = D[j];
+            if (d < v && d > -INFINITY) {  // strict: the lane's first minimum stays; NaN and +-inf never enter
+                const int s = S[j];
+                bool taken = false;
+                for (int q = 0; q < r; q++) taken |= (s <= re[q]) & (j >= rs[q]);
+                if (!taken) {
+                    v = d;
+                    c = j;
+                }
+            }
+        }
+        for (int d = 32; d >= 1; d >>= 1) {
+            const double ov = __shfl_xor(v, d);
+            const int oc = __shfl_xor(c, d);
+            if (ov < v || (ov == v && oc < c)) {
+                v = ov;
+                c = oc;
+            }
+        }
+        if (lane == 0) {
+            wv[wave] = v;
+            wc[wave] = c;
+        }
+        lds_barrier();
+        if (tid == 0) {
+#pragma unroll
+            for (int w = 1; w < kWaves; w++) {
+                if (wv[w] < v || (wv[w] == v && wc[w] < c)) {
+                    v = wv[w];
+                    c = wc[w];
+                }
+            }
+            const bool hit = c < N && !(v > g.max_cost);
+            if (hit) {
+                const int s = S[c];
+                rs[r] = s;
+                re[r] = c;
+                g.cost[out * K + r] = v;
+                g.end[out * K + r] = c;
+                g.start[out * K + r] = s;
+            }
+            more = hit;
+        }
+        lds_barrier();
+        if (!more) break;  // uniform
+        n = r + 1;
+    }
+    for (int k = n + tid; k < K; k += kLocMatchThreads) {
+        g.cost[out * K + k] = INFINITY;
+        g.end[out * K + k] = -1;
+        g.start[out * K + k] = -1;
+    }
+    if (tid == 0) g.n[out] = n;
+}
+
+// The argument checks rts_locate and rts_locate_matches share (all of them before the first HIP call).
+static int loc_check(const void *queries_dev, int q_dtype, int M_max, int B, const void *pool_dev, int pool_dtype, int F,
+                     long long n_pool_frames, const long long *piece_first_dev, const int32_t *piece_len_dev, int P,
+                     int cost_kind, const double *cost_dev, const int32_t *end_dev, const int32_t *start_dev) {
     if (!queries_dev) return set_error(RTS_ERR_INVALID, "queries_dev is NULL");
     if (!pool_dev) return set_error(RTS_ERR_INVALID, "pool_dev is NULL");
     if (!piece_first_dev) return set_error(RTS_ERR_INVALID, "piece_first_dev is NULL");
@@ -286,6 +446,45 @@ int rts_locate(const void *queries_dev, int q_dtype, int M_max, const int32_t *q
     if (!dtype_ok(pool_dtype)) return set_error(RTS_ERR_INVALID, "bad pool_dtype %d", pool_dtype);
     if (cost_kind != RTS_COST_DOT && cost_kind != RTS_COST_EUCLID)
         return set_error(RTS_ERR_INVALID, "bad cost_kind %d", cost_kind);
+    return RTS_OK;
+}
+
+static void loc_launch(const LocArgs &g, int B, int pool_dtype, int cost_kind, hipStream_t s) {
+    const int S = sdp::n_strips(g.M_max);
+    const bool y64 = pool_dtype == RTS_F64, euclid = cost_kind == RTS_COST_EUCLID;
+    const dim3 grid(g.P, B), block(64 * S);
+    const size_t smem = loc_lds_bytes(S, y64);
+    if (y64 && euclid)
+        hipLaunchKernelGGL((locate_kernel<true, true>), grid, block, smem, s, g);
+    else if (y64)
+        hipLaunchKernelGGL((locate_kernel<true, false>), grid, block, smem, s, g);
+    else if (euclid)
+        hipLaunchKernelGGL((locate_kernel<false, true>), grid, block, smem, s, g);
+    else
+        hipLaunchKernelGGL((locate_kernel<false, false>), grid, block, smem, s, g);
+}
+
+constexpr size_t kLocWsAlign = 256;
+inline size_t loc_ws_round(size_t n) { return (n + kLocWsAlign - 1) / kLocWsAlign * kLocWsAlign; }
+// ws_dev rounded up to 256 | rows double [B][n_pool], rounded up to 256 | starts int32 [B][n_pool], rounded up to 256
+inline size_t loc_ws_bytes(int B, long long n_pool) {
+    const size_t cells = (size_t)B * (size_t)n_pool;
+    return kLocWsAlign + loc_ws_round(cells * sizeof(double)) + loc_ws_round(cells * sizeof(int32_t));
+}
+constexpr long long kLocMaxPool = 1LL << 40;  // keeps B * n_pool_frames * 12 far inside size_t
+
+}  // namespace rts
+
+extern "C" {
+
+int rts_locate(const void *queries_dev, int q_dtype, int M_max, const int32_t *q_len_dev, int B, const void *pool_dev,
+               int pool_dtype, int F, long long n_pool_frames, const long long *piece_first_dev,
+               const int32_t *piece_len_dev, int P, int cost_kind, double *cost_dev, int32_t *end_dev,
+               int32_t *start_dev, double *row_dev, int32_t *rowstart_dev, void *stream) {
+    using namespace rts;
+    const int rc = loc_check(queries_dev, q_dtype, M_max, B, pool_dev, pool_dtype, F, n_pool_frames, piece_first_dev,
+                             piece_len_dev, P, cost_kind, cost_dev, end_dev, start_dev);
+    if (rc != RTS_OK) return rc;
     LocArgs g;
     g.q = queries_dev;
     g.q_len = q_len_dev;
@@ -301,19 +500,81 @@ int rts_locate(const void *queries_dev, int q_dtype, int M_max, const int32_t *q
     g.M_max = M_max;
     g.P = P;
     g.q_f64 = q_dtype == RTS_F64;
-    const int S = sdp::n_strips(M_max);
-    const bool y64 = pool_dtype == RTS_F64, euclid = cost_kind == RTS_COST_EUCLID;
-    const dim3 grid(P, B), block(64 * S);
-    const size_t smem = loc_lds_bytes(S, y64);
+    loc_launch(g, B, pool_dtype, cost_kind, (hipStream_t)stream);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+
+int rts_locate_matches_workspace_bytes(int B, long long n_pool_frames, size_t *bytes) {
+    using namespace rts;
+    if (!bytes) return set_error(RTS_ERR_INVALID, "bytes is NULL");
+    if (B < 1 || B > 65535) return set_error(RTS_ERR_INVALID, "B must be in [1, 65535] (got %d)", B);
+    if (n_pool_frames < 1 || n_pool_frames > kLocMaxPool)
+        return set_error(RTS_ERR_INVALID, "n_pool_frames must be in [1, 2^40] (got %lld)", n_pool_frames);
+    *bytes = loc_ws_bytes(B, n_pool_frames);
+    return RTS_OK;
+}
+
+int rts_locate_matches(const void *queries_dev, int q_dtype, int M_max, const int32_t *q_len_dev, int B,
+                       const void *pool_dev, int pool_dtype, int F, long long n_pool_frames,
+                       const long long *piece_first_dev, const int32_t *piece_len_dev, int P, int cost_kind, int K,
+                       double max_cost, double *cost_dev, int32_t *end_dev, int32_t *start_dev, int32_t *n_dev,
+                       void *ws_dev, size_t ws_bytes, void *stream) {
+    using namespace rts;
+    const int rc = loc_check(queries_dev, q_dtype, M_max, B, pool_dev, pool_dtype, F, n_pool_frames, piece_first_dev,
+                             piece_len_dev, P, cost_kind, cost_dev, end_dev, start_dev);
+    if (rc != RTS_OK) return rc;
+    if (!n_dev) return set_error(RTS_ERR_INVALID, "n_dev is NULL");
+    if (!ws_dev) return set_error(RTS_ERR_INVALID, "ws_dev is NULL");
+    if (K < 1) return set_error(RTS_ERR_INVALID, "K must be >= 1 (got %d)", K);
+    if (K > kLocMaxK) return set_error(RTS_ERR_UNSUPPORTED, "K must be <= %d ranks (got %d)", kLocMaxK, K);
+    if (max_cost != max_cost) return set_error(RTS_ERR_INVALID, "max_cost is NaN");
+    if (n_pool_frames > kLocMaxPool)
+        return set_error(RTS_ERR_INVALID, "n_pool_frames must be <= 2^40 (got %lld)", n_pool_frames);
+    const size_t need = loc_ws_bytes(B, n_pool_frames);
+    if (ws_bytes < need) return set_error(RTS_ERR_INVALID, "ws_bytes is %zu, %zu are needed", ws_bytes, need);
+    const size_t cells = (size_t)B * (size_t)n_pool_frames;
+    unsigned char *base = reinterpret_cast<unsigned char *>(loc_ws_round(reinterpret_cast<uintptr_t>(ws_dev)));
+    double *row = reinterpret_cast<double *>(base);
+    int32_t *rowstart = reinterpret_cast<int32_t *>(base + loc_ws_round(cells * sizeof(double)));
     hipStream_t s = (hipStream_t)stream;
-    if (y64 && euclid)
-        hipLaunchKernelGGL((locate_kernel<true, true>), grid, block, smem, s, g);
-    else if (y64)
-        hipLaunchKernelGGL((locate_kernel<true, false>), grid, block, smem, s, g);
-    else if (euclid)
-        hipLaunchKernelGGL((locate_kernel<false, true>), grid, block, smem, s, g);
-    else
-        hipLaunchKernelGGL((locate_kernel<false, false>), grid, block, smem, s, g);
+    // 1. the locate kernel as it is: rows into the workspace, its own answers packed [B][P] at the front of the outputs
+    LocArgs g;
+    g.q = queries_dev;
+    g.q_len = q_len_dev;
+    g.pool = pool_dev;
+    g.first = piece_first_dev;
+    g.len = piece_len_dev;
+    g.cost = cost_dev;
+    g.end = end_dev;
+    g.start = start_dev;
+    g.row = row;
+    g.rowstart = rowstart;
+    g.n_pool = n_pool_frames;
+    g.M_max = M_max;
+    g.P = P;
+    g.q_f64 = q_dtype == RTS_F64;
+    loc_launch(g, B, pool_dtype, cost_kind, s);
+    RTS_HIP(hipGetLastError());
+    // 2. overlap flags (and slot 0 of the flagged pieces), 3. the ranks
+    LocMatchArgs m;
+    m.q_len = q_len_dev;
+    m.first = piece_first_dev;
+    m.len = piece_len_dev;
+    m.row = row;
+    m.rowstart = rowstart;
+    m.cost = cost_dev;
+    m.end = end_dev;
+    m.start = start_dev;
+    m.n = n_dev;
+    m.n_pool = n_pool_frames;
+    m.max_cost = max_cost;
+    m.M_max = M_max;
+    m.P = P;
+    m.K = K;
+    hipLaunchKernelGGL(locate_overlap_kernel, dim3(1), dim3(kLocOverlapThreads), 0, s, m, B);
+    RTS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(locate_matches_kernel, dim3(P, B), dim3(kLocMatchThreads), 0, s, m);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }

@@ -335,13 +335,13 @@ class LiveSession(object):
         return dict(beat=self._beat.copy(), label=label, label_text=text, ref_frame=self._beat_words[1].copy(),
                     feeds_done=done.value)
 
-    def locate(self, queries, q_len=None, euclid=None):
+    def locate(self, queries, q_len=None, euclid=None, matches=1):
         """Where in the repertoire is each microphone?  ``BatchedOTW.locate`` / ``BatchedWTW.locate`` of the bound
         tracker (needs per-stream references: a list as ``ref_chroma``), with the pieces named by the objects given at
         create, so that every entry ``(ref, start, end, cost)`` goes straight into ``restart([b], refs=[ref],
         offsets=[start])``.  The session keeps no history of columns: ``queries`` are what the caller collected from
-        ``last_columns()``."""
-        found = (self.otw or self.wtw).locate(queries, q_len, euclid)
+        ``last_columns()``.  ``matches=K``: up to K ranked non-overlapping matches per piece, as there."""
+        found = (self.otw or self.wtw).locate(queries, q_len, euclid, matches)
         given = {id(conv): obj for obj, conv in self._conv.values()}
         return [[(given[id(r)], s, e, c) for r, s, e, c in entries] for entries in found]
 
@@ -350,26 +350,32 @@ class LiveSession(object):
         given = {id(conv): obj for obj, conv in self._conv.values()}
         return (given[id(entry[0])],) + tuple(entry[1:])
 
-    def locate_recent(self, M=128, streams=None, euclid=None):
+    def locate_recent(self, M=128, streams=None, euclid=None, matches=1):
         """``locate`` on the last ``M`` columns every stream (or the listed ones) handed to its tracker, taken from the
         tracker's own history on the device (``recent`` of the bound tracker): no column is collected on the host.  Same
         return value as ``locate``; streams not listed get ``[]``."""
         if self._conv is None:
             raise ValueError("locate needs per-stream references (a list as ref_chroma)")
-        found = (self.otw or self.wtw).locate_recent(M, streams, euclid)
+        found = (self.otw or self.wtw).locate_recent(M, streams, euclid, matches)
         return [[self._given(e) for e in entries] for entries in found]
 
-    def reacquire(self, streams, M=128):
+    def reacquire(self, streams, M=128, matches=1, choose=None):
         """This microphone is lost: put it where it really is (``BatchedOTW.reacquire`` / ``BatchedWTW.reacquire`` of the
         bound tracker, the pieces named by the objects given at create).  The restart goes through ``restart``: the
         listed streams' pending samples -- and with ``features='chroma_diff'`` their carried chroma column -- are
         dropped as documented there; the excerpt is then pushed into the bound tracker directly, so the position words
         ``poll()`` shows for these streams are those of a fresh stream until the next feed publishes the caught-up
-        ones, and ``confidence()`` reads n = 0 until then.  Returns ``{b: (ref, start, end, cost) | None}``."""
+        ones, and ``confidence()`` reads n = 0 until then.  Returns ``{b: (ref, start, end, cost) | None}``.
+        ``matches`` / ``choose`` as ``BatchedOTW.reacquire``; ``choose`` sees the pieces as the objects given at create
+        (``where`` of ``locate.nearest_to`` names them so)."""
         if self._conv is None:
             raise ValueError("reacquire needs per-stream references (a list as ref_chroma)")
         eng = self.otw or self.wtw
-        out = eng._reacquire(streams, M, self._restart_known)
+        def chosen(b, cand):   # the caller's choose on the caller's names for the pieces
+            named = type(cand)(self._given(e) for e in cand)
+            named.M = cand.M
+            return choose(b, named)
+        out = eng._reacquire(streams, M, self._restart_known, matches, chosen if choose is not None else None)
         if self._gated:   # frame_columns: the excerpt's frames come first in the restarted streams' trackers
             for b, e in out.items():
                 if e is not None:
