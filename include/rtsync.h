@@ -1031,6 +1031,112 @@ int rts_tuning_accumulate(rts_tuning *p, const double *stft_dev /* [n_frames][ff
 int rts_tuning_pick(rts_tuning *p, const unsigned long long *hist_dev /* [S][R] */, int S, int W, double *cents_dev /* [S] */,
                     long long *n_dev /* [S] */, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ensemble following: one microphone against several recordings of its piece, fused in beats.
+ * ------------------------------------------------------------------------------------------ */
+/* Every answer of a stream depends on its one recording resembling tonight's performance.  The reference ships two or three
+ * performances of almost every piece, each with its own beat table, and its harness compares performances in beats, the
+ * scale the recordings share (tests.py:59-137).  Here a microphone is followed against all recordings of its piece at once
+ * (one stream each, a "group"), the group's position is the median beat of its members, and a member that loses its place is
+ * outvoted, marked, and can be restarted where the others are (Arzt and Widmer, "Real-time music tracking using multiple
+ * performances as a reference", ISMIR 2015).
+ *
+ * Every float64 operation below is rounded on its own, in the order written.  NaN is the canonical quiet NaN
+ * 0x7ff8000000000000.
+ *
+ * Inverse lookup, beat x -> frame of piece p with rows (times[i], beats[i]), n of them (rts_annot_frames).  A piece is
+ * invertible when its beats are strictly increasing; rts_annot_create decides that once per piece.
+ *   x is NaN, p outside [0, P), p not invertible:                                   frame = -1
+ *   i = the first row with x <= (double)beats[i] (bisection); none:                   frame = -1
+ *   x < (double)beats[i] - 1.0:                                                       frame = -1   (a gap of the table, or
+ *                                                         before the stretch get_beat interpolates from time zero)
+ *   end = times[i], start = i == 0 ? 0.0 : times[i-1]
+ *   time = end - ((double)beats[i] - x) * (end - start)
+ *   f = floor(time / frame_seconds + 0.5);  f < 0: frame = 0;  f > INT32_MAX: frame = -1;  else frame = f
+ * With floor(. + 0.5) the round trip frame -> get_beat -> frame is the identity on every frame that has a beat, in the
+ * reference's 22 tables (Songs/) as in the two under tests/golden/.  rts_annot_frames has the geometry and conventions of
+ * rts_annot_beats: entry (b, k), k < n_dev[b] (NULL: n_max; clamped to n_max), is beats_dev[b][k] in piece piece_dev[b];
+ * entries behind n_dev[b] are not written.  Asynchronous, allocates nothing, writes only frame_dev.  n_max == 0 enqueues
+ * nothing.
+ *   RTS_ERR_INVALID: NULL handle, beats_dev, piece_dev or frame_dev, B outside [1, 65535], n_max < 0, another device current.
+ *
+ * Member beat.  Member b is stream b of a tracker with piece[b] and frame0[b] as rts_live_annotate takes them: the lookup of
+ * rts_annot_beats of frame0[b] + y_last, y_last the reference index of the last stored path point (ln.path[-1][1],
+ * livenote_live.py:197).  NaN while the stream has no path point, y_last < 0, or the stream has no piece.  Not sticky; a
+ * beat of 0.0 is a position, only NaN is "none".
+ *
+ * Fusion step, once per group and step.  A group has 1 to 64 members in ascending stream order; parameters max_dev (beats,
+ * > 0, +inf allowed) and patience in [1, 65535]; every member carries strikes and out, 0 when fresh.
+ *   1. valid_i: beta_i is not NaN.
+ *   2. in_i = valid_i && !out_i; when no member is in: in_i = valid_i (everyone valid is heard again).
+ *   3. n_in == 0: consensus = spread = NaN, every dev_i = NaN, strikes and out unchanged; the step ends.
+ *   4. v = the in-set sorted ascending by (value, member index), `<` on float64 (-0.0 and 0.0 tie, the index decides):
+ *      consensus = n odd ? v[(n-1)/2] : (v[n/2-1] + v[n/2]) * 0.5;  spread = v[n-1] - v[0].
+ *   5. every valid member: dev_i = beta_i - consensus; fabs(dev_i) > max_dev ? strikes_i = min(strikes_i + 1, patience)
+ *      : strikes_i = 0;  out_i = strikes_i >= patience.  An invalid member: dev_i = NaN, strikes and out unchanged.
+ * Published per group: consensus, spread, n_in, n_valid; per stream: dev, strikes, out.  A stream in no group reads NaN / 0 / 0.
+ *
+ * rts_ensemble_create: group_host[b] in [-1, n_groups) is stream b's group (-1: none).  Builds the CSR tables and the [B]
+ * strikes / out state (zero) on the current device, to which the handle then belongs.
+ *   RTS_ERR_INVALID, the message naming the argument: NULL out or group_host, B < 1, n_groups outside [1, B], max_dev NaN or
+ *   <= 0, patience outside [1, 65535], an entry outside [-1, n_groups), a group without a member or with more than 64.
+ * rts_ensemble_reset clears strikes and out of the streams with mask_host[b] != 0 (NULL: all), ordered on `stream`; the
+ * mask travels by value and is consumed when the call returns.
+ *
+ * rts_otw_consensus / rts_wtw_consensus: one fusion step over every group from the tracker's paths as they stand, one
+ * launch of one wave per group (ranks by counting across the wave, no LDS, no atomics).  group_dev = consensus[n_groups] then
+ * spread[n_groups]; group_n_dev = n_in[n_groups] then n_valid[n_groups]; dev_dev[B]; member_dev = strikes[B] then out[B].
+ * frame0_dev NULL: 0.  Advances the ensemble's state and writes the five outputs, nothing else; asynchronous, allocates
+ * nothing.
+ *   RTS_ERR_INVALID: a NULL handle, tables or output; B of the ensemble != B of the tracker; a handle on another device.
+ *
+ * rts_path_consensus, the offline curve over live frames t = 0 .. T-1 of B paths laid out like the outputs of rts_dtw_paths
+ * (len <= 0 gives an empty path, len > P_max is clamped; the live index must not decrease along a path): at frame t member
+ * b stands at the y of its last point k with x_k <= t (none, or y < 0: invalid at t); beta by the member-beat rule; the
+ * fusion step runs with state that is zero at t = 0 and carries from t to t + 1 -- private state: the handle's own is
+ * neither read nor written, only its groups and parameters are used.  With max_dev = +inf this is the plain median per
+ * frame.  consensus_dev[g][t]; spread_dev, n_in_dev (same shape) and out_dev[b][t], out of stream b after step t (0 for a
+ * stream in no group), may be NULL.  One wave per group, a cursor per lane: O(len + T) per member.  T == 0 enqueues nothing.
+ *   RTS_ERR_INVALID: a NULL handle, tables, len_dev, piece_dev or consensus_dev; path_dev NULL with P_max > 0; P_max < 0;
+ *   T < 0; a handle on another device.
+ *
+ * Live.  rts_live_follow_consensus(h, e): e NULL switches it off (the words stay as they are).  Otherwise `e` -- held by
+ * reference like the tables of rts_live_annotate -- becomes the handle's ensemble; the first call allocates a sixth
+ * host-mapped block.  With it on, every rts_live_submit enqueues ONE more launch, after the beat and tempo launches and
+ * before the publication of the status words, in a feed without columns too: the fusion step of rts_otw_consensus /
+ * rts_wtw_consensus with piece and frame0 as rts_live_annotate set them.  While annotations are switched off the launch is
+ * skipped and the words stay.  rts_live_restart clears strikes and out of the selected streams and republishes NaN / 0 / 0
+ * for them; rts_live_reset does so for all and publishes NaN / NaN / 0 / 0 per group.  A handle that never calls it enqueues
+ * exactly what it enqueues without this function.
+ * rts_live_consensus: the non-blocking look, like rts_live_confidence and with the same guarantee: when *feeds_done >= k,
+ * every word read reflects a feed >= k.  Group outputs have n_groups entries of the ensemble bound last.  Any output pointer
+ * may be NULL.
+ *   RTS_ERR_INVALID: NULL handle, a failed handle, B of the ensemble != B of the handle, an ensemble of another device,
+ *   rts_live_follow_consensus before any rts_live_annotate with tables; rts_live_consensus before the first
+ *   rts_live_follow_consensus with an ensemble. */
+typedef struct rts_ensemble rts_ensemble;
+int rts_ensemble_create(int B, const int32_t *group_host /* [B] */, int n_groups, double max_dev, int patience, rts_ensemble **out);
+int rts_ensemble_destroy(rts_ensemble *h);
+int rts_ensemble_reset(rts_ensemble *h, const uint8_t *mask_host /* [B], NULL: all */, void *stream);
+int rts_annot_frames(rts_annot *h, const double *beats_dev /* [B][n_max] */, int n_max, const int32_t *n_dev /* [B] or NULL */,
+                     const int32_t *piece_dev /* [B] */, int B, int32_t *frame_dev /* [B][n_max] */, void *stream);
+int rts_otw_consensus(rts_otw *h, rts_ensemble *e, rts_annot *a, const int32_t *piece_dev /* [B] */,
+                      const int32_t *frame0_dev /* [B] or NULL */, double *group_dev /* [2][n_groups] */,
+                      int32_t *group_n_dev /* [2][n_groups] */, double *dev_dev /* [B] */, int32_t *member_dev /* [2][B] */,
+                      void *stream);
+int rts_wtw_consensus(rts_wtw *h, rts_ensemble *e, rts_annot *a, const int32_t *piece_dev /* [B] */,
+                      const int32_t *frame0_dev /* [B] or NULL */, double *group_dev /* [2][n_groups] */,
+                      int32_t *group_n_dev /* [2][n_groups] */, double *dev_dev /* [B] */, int32_t *member_dev /* [2][B] */,
+                      void *stream);
+int rts_path_consensus(rts_ensemble *e, rts_annot *a, const int32_t *path_dev /* [B][P_max][2] */, int P_max,
+                       const int32_t *len_dev /* [B] */, const int32_t *piece_dev /* [B] */,
+                       const int32_t *frame0_dev /* [B] or NULL */, int T, double *consensus_dev /* [n_groups][T] */,
+                       double *spread_dev /* [n_groups][T] or NULL */, int32_t *n_in_dev /* [n_groups][T] or NULL */,
+                       int32_t *out_dev /* [B][T] or NULL */, void *stream);
+int rts_live_follow_consensus(rts_live *h, rts_ensemble *e /* NULL: off */);
+int rts_live_consensus(rts_live *h, double *consensus, double *spread, int32_t *n_in, int32_t *n_valid /* [n_groups] */,
+                       double *dev, int32_t *strikes, int32_t *out /* [B] */, int *feeds_done);
+
 #ifdef __cplusplus
 }
 #endif

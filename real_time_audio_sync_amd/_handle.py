@@ -75,6 +75,19 @@ class _BatchedHandle:
         return slope.cpu().numpy(), pos.cpu().numpy(), n.cpu().numpy()
 
     @nat.on_device
+    def consensus(self, ens, tables, pieces, frame0=None):
+        """Where is every group of streams, in beats (rts_otw_consensus / rts_wtw_consensus)?  One fusion step of
+        ``ens`` (an ``ensemble.Ensemble`` of this handle's B streams) from the paths as they stand: every member's beat is
+        the lookup, in ``tables`` (an ``AnnotationTables``), of ``frame0[b]`` + the reference index of its last path point
+        in table ``pieces[b]``; the group's consensus is the median of the members that are in.  ``pieces`` / ``frame0``:
+        lists or int32 device tensors of B entries, like ``AnnotationTables.beats`` takes them.  Advances the strikes and
+        out that ``ens`` carries.  Returns numpy ``dict(consensus, spread float64 [n_groups], n_in, n_valid int32
+        [n_groups], dev float64 [B], strikes, out int32 [B])``; NaN / 0 / 0 for a stream in no group.  The definition is
+        include/rtsync.h's (rts_ensemble_create).  Synchronises."""
+        from .ensemble import tracker_consensus
+        return tracker_consensus(self, self._fn("consensus"), ens, tables, pieces, frame0)
+
+    @nat.on_device
     def restart(self, streams, refs=None, offsets=None):
         """Put the listed streams back to the start while the others keep running (the subclasses document ``refs`` and
         ``offsets``)."""

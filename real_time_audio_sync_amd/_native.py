@@ -171,6 +171,17 @@ _decl("rts_tuning_destroy", _i32, [_vp])
 _decl("rts_tuning_accumulate", _i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp])
 _decl("rts_tuning_pick", _i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp])
 
+ENSEMBLE_MAX_MEMBERS, ENSEMBLE_MAX_PATIENCE = 64, 65535  # kEnsembleMaxMembers, kEnsembleMaxPatience (csrc/ensemble_plan.h)
+_decl("rts_ensemble_create", _i32, [_i32, _vp, _i32, ctypes.c_double, _i32, ctypes.POINTER(_vp)])
+_decl("rts_ensemble_destroy", _i32, [_vp])
+_decl("rts_ensemble_reset", _i32, [_vp, _vp, _vp])
+_decl("rts_annot_frames", _i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp])
+_decl("rts_otw_consensus", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+_decl("rts_wtw_consensus", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+_decl("rts_path_consensus", _i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp])
+_decl("rts_live_follow_consensus", _i32, [_vp, _vp])
+_decl("rts_live_consensus", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi32])
+
 
 def check(rc):
     if rc != 0:

@@ -108,6 +108,37 @@ class AnnotationTables(object):
         return [(beat[b, :len(r)].copy(), seg[b, :len(r)].copy()) for b, r in enumerate(rows)]
 
     @nat.on_device
+    def frames(self, beats, pieces, n=None):
+        """The way back, beat -> frame of a piece (rts_annot_frames; ``ensemble.frames_of_beat`` is the host form): the
+        frame whose ``beats()`` lookup is nearest to the beat, -1 where there is none -- a NaN beat, a piece that does not
+        exist or whose beats are not strictly increasing, a beat behind the table's last, in a gap of it, or more than
+        one beat before its first row.  ``beats``: a list of B float arrays (one per stream, any lengths), or a float64
+        device tensor [B][n_max] with ``n`` (valid entries per stream; None = all).  ``pieces``: the table of every stream.
+
+        List form: synchronises and returns a list of int32 arrays.  Tensor form: asynchronous; returns an int32 device
+        tensor [B][n_max] whose entries behind ``n[b]`` are not written."""
+        as_list = not torch.is_tensor(beats)
+        if as_list:
+            rows = [np.asarray(x, dtype=np.float64).reshape(-1) for x in beats]
+            B, n_max = len(rows), max([len(r) for r in rows] + [0])
+            host = np.zeros((B, max(n_max, 1)), dtype=np.float64)
+            for b, r in enumerate(rows):
+                host[b, :len(r)] = r
+            beats = torch.from_numpy(host).to(self.device)
+            n = [len(r) for r in rows]
+        beats = beats.to(device=self.device, dtype=torch.float64).contiguous()
+        B, n_max = int(beats.shape[0]), int(beats.shape[1])
+        pieces = self._i32(pieces, B, "pieces")
+        n = self._i32(n, B, "n") if n is not None else None
+        out = torch.empty((B, n_max), dtype=torch.int32, device=self.device)
+        nat.check(nat.lib.rts_annot_frames(self._h, beats.data_ptr(), n_max, n.data_ptr() if n is not None else None,
+                                           pieces.data_ptr(), B, out.data_ptr(), self._stream()))
+        if not as_list:
+            return out
+        out = out.cpu().numpy()
+        return [out[b, :len(r)].copy() for b, r in enumerate(rows)]
+
+    @nat.on_device
     def bpm(self, frames, slopes, pieces, frame0=None, n=None):
         """Slopes of a path (reference frames per live frame: ``tempo.path_tempo``, ``BatchedOTW.tempo``) in beats per
         minute (rts_annot_bpm): ``(slope * 60.0) / (times[i] - start)`` with ``i`` and ``start`` what ``beats()`` uses for

@@ -4,6 +4,7 @@
 //                                                                                            per feed of a live handle)
 //   tests.py:112-128                     get_beat of every path point                      -> rts_annot_beats
 //   tests.py:59-137                      test_simple.get_error: the accuracy metric        -> rts_annot_path_error
+//   the way back, beat -> frame of a piece (annot_frame_of in csrc/annot_device.h)         -> rts_annot_frames
 // The definition is include/rtsync.h's; the checks of the tables and the launch geometry are csrc/annot_plan.h's.
 //
 // Lookup of frame f in a table of n rows (annot_lookup): time = (double)f * frame_seconds, i = the first row with time <=
@@ -40,6 +41,19 @@ annot_beats_kernel(AnnotTables t, const int32_t *frames, int n_max, const int32_
     const double beat = annot_lookup(annot_piece(t, piece_dev[b]), frame, t.frame_seconds, &seg);
     beat_out[e] = beat;
     if (seg_out) seg_out[e] = seg;
+}
+
+// grid (ceil(n_max / 256), B): one lane per entry, the other way round: beat -> frame of the stream's piece.
+__global__ void __launch_bounds__(kAnnotThreads)
+annot_frames_kernel(AnnotTables t, const double *beats, int n_max, const int32_t *n_dev, const int32_t *piece_dev,
+                    int32_t *frame_out) {
+    const int b = blockIdx.y;
+    const int k = blockIdx.x * kAnnotThreads + threadIdx.x;
+    int n = n_dev ? n_dev[b] : n_max;
+    if (n > n_max) n = n_max;
+    if (k >= n) return;
+    const size_t e = (size_t)b * n_max + k;
+    frame_out[e] = annot_frame_of(t, piece_dev[b], beats[e]);
 }
 
 // AlignmentError.get_time (tests.py:130-134) on the live table: *bad when the beat's integer part is no row of it
@@ -226,10 +240,16 @@ int rts_annot_create(int P, long long n_rows, const long long *first_host, const
     }
     rts_annot *h = (rts_annot *)calloc(1, sizeof(rts_annot));
     if (!h) return set_error(RTS_ERR_INVALID, "out of host memory");
-    // one block: times, first (8-byte values), beats, len, flags
+    // one block: times, first (8-byte values), beats, len, the pieces' invertible flags, the rows' label flags
     const size_t nr = (size_t)n_rows, np = (size_t)P;
     const size_t o_first = sizeof(double) * nr, o_beats = o_first + sizeof(long long) * np, o_len = o_beats + sizeof(int32_t) * nr,
-                 o_flags = o_len + sizeof(int32_t) * np, bytes = o_flags + (label_ok_host ? nr : 0);
+                 o_inv = o_len + sizeof(int32_t) * np, o_flags = o_inv + np, bytes = o_flags + (label_ok_host ? nr : 0);
+    uint8_t *inv = (uint8_t *)malloc(np);
+    if (!inv) {
+        free(h);
+        return set_error(RTS_ERR_INVALID, "out of host memory");
+    }
+    for (int p = 0; p < P; p++) inv[p] = annot_invertible(beats_host + first_host[p], len_host[p]) ? 1 : 0;
     hipError_t e = hipGetDevice(&h->device);
     if (e == hipSuccess) e = hipMalloc(&h->block, bytes);
     unsigned char *d = static_cast<unsigned char *>(h->block);
@@ -237,7 +257,9 @@ int rts_annot_create(int P, long long n_rows, const long long *first_host, const
     if (e == hipSuccess) e = hipMemcpy(d + o_first, first_host, sizeof(long long) * np, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d + o_beats, beats_host, sizeof(int32_t) * nr, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d + o_len, len_host, sizeof(int32_t) * np, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + o_inv, inv, np, hipMemcpyHostToDevice);
     if (e == hipSuccess && label_ok_host) e = hipMemcpy(d + o_flags, label_ok_host, nr, hipMemcpyHostToDevice);
+    free(inv);
     if (e != hipSuccess) {
         rts_annot_destroy(h);
         return set_error(RTS_ERR_HIP, "rts_annot_create: %s", hipGetErrorString(e));
@@ -246,6 +268,7 @@ int rts_annot_create(int P, long long n_rows, const long long *first_host, const
     h->t.first = reinterpret_cast<const long long *>(d + o_first);
     h->t.beats = reinterpret_cast<const int32_t *>(d + o_beats);
     h->t.len = reinterpret_cast<const int32_t *>(d + o_len);
+    h->t.invertible = d + o_inv;
     h->t.label_ok = label_ok_host ? d + o_flags : nullptr;
     h->t.P = P;
     h->t.frame_seconds = frame_seconds;
@@ -266,6 +289,22 @@ int rts_annot_beats(rts_annot *h, const int32_t *frames_dev, int n_max, const in
     const AnnotGrid g = annot_beats_grid(B, n_max);
     hipLaunchKernelGGL(annot_beats_kernel, dim3(g.x, g.y), dim3(kAnnotThreads), 0, (hipStream_t)stream, h->t, frames_dev, n_max,
                        n_dev, piece_dev, frame0_dev, beat_dev, seg_dev);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+
+int rts_annot_frames(rts_annot *h, const double *beats_dev, int n_max, const int32_t *n_dev, const int32_t *piece_dev, int B,
+                     int32_t *frame_dev, void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!beats_dev || !piece_dev || !frame_dev) return set_error(RTS_ERR_INVALID, "beats_dev, piece_dev and frame_dev must be given");
+    if (B < 1 || B > 65535) return set_error(RTS_ERR_INVALID, "B must be in [1, 65535] (got %d)", B);
+    if (n_max < 0) return set_error(RTS_ERR_INVALID, "n_max must be >= 0");
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    if (n_max == 0) return RTS_OK;
+    const AnnotGrid g = annot_beats_grid(B, n_max);
+    hipLaunchKernelGGL(annot_frames_kernel, dim3(g.x, g.y), dim3(kAnnotThreads), 0, (hipStream_t)stream, h->t, beats_dev, n_max,
+                       n_dev, piece_dev, frame_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }

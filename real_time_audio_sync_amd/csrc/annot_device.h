@@ -12,6 +12,7 @@ struct AnnotTables {
     const uint8_t *label_ok;  // [n_rows] the row's label is a non-empty string; NULL: no flags were given
     const long long *first;   // [P]
     const int32_t *len;       // [P]
+    const uint8_t *invertible;  // [P] the piece's beats are strictly increasing (annot_invertible, csrc/annot_plan.h)
     int P;
     double frame_seconds;
 };
@@ -58,6 +59,29 @@ __device__ __forceinline__ double annot_lookup(const AnnotPiece &p, long long fr
     if (i == 0 && end == 0.0) return beat - 0.0;
     const double start = i == 0 ? 0.0 : p.times[i - 1];
     return beat - (end - time) / (end - start);
+}
+
+// The inverse lookup, beat x -> frame of piece `piece` (include/rtsync.h, rts_annot_frames): -1 where there is none.
+__device__ __forceinline__ int32_t annot_frame_of(const AnnotTables &t, int piece, double x) {
+    if (!(x == x) || piece < 0 || piece >= t.P || !t.invertible[piece]) return -1;
+    const AnnotPiece p = annot_piece(t, piece);
+    int lo = 0, hi = p.n;  // the first i with x <= (double)beats[i]
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (x <= (double)p.beats[mid]) hi = mid;
+        else lo = mid + 1;
+    }
+    const int i = lo;
+    if (i >= p.n) return -1;
+    const double beat = (double)p.beats[i];
+    if (x < beat - 1.0) return -1;  // a gap of the table, or before the stretch get_beat interpolates from time zero
+    const double end = p.times[i];
+    const double start = i == 0 ? 0.0 : p.times[i - 1];
+    const double time = end - (beat - x) * (end - start);
+    const double f = floor(time / t.frame_seconds + 0.5);
+    if (!(f >= 0.0)) return f == f ? 0 : -1;
+    if (f > 2147483647.0) return -1;
+    return (int32_t)f;
 }
 
 }  // namespace rts

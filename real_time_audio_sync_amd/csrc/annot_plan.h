@@ -54,6 +54,14 @@ inline AnnotRefusal annot_check(int P, long long n_rows, const long long *first,
     return kAnnotOk;
 }
 
+// A piece is invertible -- rts_annot_frames maps a beat back to a frame of it -- when its beats are strictly increasing.
+// Decided once per piece at rts_annot_create, on tables that passed annot_check.
+inline bool annot_invertible(const int32_t *beats, int32_t n) {
+    for (int32_t i = 1; i < n; i++)
+        if (beats[i] <= beats[i - 1]) return false;
+    return n >= 1;
+}
+
 // The message of a refusal, naming piece and row.
 inline void annot_message(char *buf, size_t size, AnnotRefusal why, const AnnotFault &w, long long n_rows) {
     switch (why) {

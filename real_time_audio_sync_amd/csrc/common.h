@@ -143,7 +143,27 @@ __attribute__((visibility("hidden"))) int tempo_tail_check(int K, double ahead, 
 __attribute__((visibility("hidden"))) int tempo_tail_enqueue(const TempoTail &t, const rts_annot *annot, hipStream_t s);
 __attribute__((visibility("hidden"))) const AnnotTables *annot_tables(const rts_annot *a);
 
-#define RTS_HIP(call)                                                                        \
+// The fusion kernel of csrc/ensemble.hip as rts_otw_consensus / rts_wtw_consensus and the live handle launch it: one
+// fusion step (include/rtsync.h, rts_ensemble_create) over every group of `e`, the member beats taken from the tracker that
+// `view` describes (otw_tempo_view / wtw_tempo_view: state, path, B) at frame0[b] + the last stored point's reference index
+// in piece[b] of `annot`.  Advances e's strikes / out.  The stores end with a system-scope fence: the live handle's outputs
+// are host-mapped.
+struct EnsembleOut {
+    double *consensus, *spread;  // [n_groups]
+    int32_t *n_in, *n_valid;     // [n_groups]
+    double *dev;                 // [B]
+    int32_t *strikes, *out;      // [B]
+};
+__attribute__((visibility("hidden"))) int ensemble_batch(const rts_ensemble *e);
+__attribute__((visibility("hidden"))) int ensemble_groups(const rts_ensemble *e);
+__attribute__((visibility("hidden"))) int ensemble_device(const rts_ensemble *e);
+// the handle's carried state on the device, strikes[B] then out[B] (live_restart_kernel clears the selected streams')
+__attribute__((visibility("hidden"))) int32_t *ensemble_state(const rts_ensemble *e);
+__attribute__((visibility("hidden"))) int ensemble_fuse_enqueue(rts_ensemble *e, const rts_annot *annot, const TempoTail &view,
+                                                                const int32_t *piece, const int32_t *frame0,
+                                                                const EnsembleOut &o, hipStream_t s);
+
+#define RTS_HIP(call)                                                                       \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
         if (e_ != hipSuccess)                                                                 \

@@ -35,6 +35,9 @@
 //                         every tracker's last path point into a fourth host-mapped block -- rts_live_beats reads it
 //   tempo_tail_kernel     only after rts_live_follow_tempo(K > 0) (csrc/tempo.hip): slope, position and beats per minute of the
 //                         last K points of every tracker's path into a fifth host-mapped block -- rts_live_tempo reads it
+//   ensemble_fuse_kernel  only after rts_live_follow_consensus with an ensemble and while annotations are on (csrc/ensemble.hip):
+//                         the median beat of every group of streams, each member's deviation, strikes and out into a sixth
+//                         host-mapped block -- rts_live_consensus reads it
 //   live_compact_kernel   drop hop * n_frames consumed samples per stream (data = data[2048:], livenote_live.py:208),
 //                         and publish {status, live position, ref position, feed number} of every stream into
 //                         host-mapped memory -- rts_live_poll reads those words without touching the stream.
@@ -83,6 +86,11 @@ struct LiveArgs {
     // rts_live_follow_tempo (NULL until its first call with K > 0): host-mapped tempo words, republished by live_restart_kernel
     double *tempo_words;         // slope[B], pos[B], bpm[B]
     int32_t *tempo_n;            // [B]
+    // rts_live_follow_consensus (NULL until its first call with an ensemble): the host-mapped per-stream words, republished
+    // by live_restart_kernel, and the bound ensemble's carried state on the device (NULL while consensus is off)
+    double *ens_dev;             // [B]
+    int32_t *ens_member;         // strikes[B], out[B]
+    int32_t *ens_state;          // strikes[B], out[B] of the ensemble handle
 };
 
 __device__ __forceinline__ void live_publish(const LiveArgs &g, int b) {
@@ -214,6 +222,11 @@ __global__ void live_restart_kernel(RestartSel sel, LiveArgs g, GateArgs t) {
         for (int q = 0; q < 3; q++) g.tempo_words[(size_t)q * g.B + b] = __longlong_as_double(0x7ff8000000000000LL);
         g.tempo_n[b] = 0;
     }
+    if (g.ens_state) g.ens_state[b] = g.ens_state[g.B + b] = 0;  // a fresh member: no strikes, heard again
+    if (g.ens_dev) {
+        g.ens_dev[b] = __longlong_as_double(0x7ff8000000000000LL);
+        g.ens_member[b] = g.ens_member[g.B + b] = 0;
+    }
     if (t.q) live_gate_restart(t, b);
     __threadfence_system();
 }
@@ -273,6 +286,13 @@ struct rts_live {
     int tempo_k;
     rts::TempoTail tempo;
     unsigned char *tempo_host;
+    // rts_live_follow_consensus: the ensemble in use (NULL = off), the groups of the one bound last, and the sixth
+    // host-mapped block, sized for B groups: double consensus[B], spread[B], dev[B] then int32 n_in[B], n_valid[B],
+    // strikes[B], out[B] (the group words use the first n_groups entries of theirs)
+    rts_ensemble *ens;
+    int ens_groups;
+    unsigned char *ens_host;
+    rts::EnsembleOut ens_out;  // the block as the device sees it
 };
 
 namespace rts {
@@ -333,6 +353,21 @@ static int live_tempo_launch(rts_live *h, hipStream_t s) {
     return tempo_tail_enqueue(t, h->annot, s);
 }
 
+static void live_ens_clear(rts_live *h) {
+    double *words = reinterpret_cast<double *>(h->ens_host);
+    for (int b = 0; b < 3 * h->geo.B; b++) words[b] = __builtin_nan("");
+    memset(words + 3 * (size_t)h->geo.B, 0, sizeof(int32_t) * 4 * (size_t)h->geo.B);
+}
+
+// With consensus on, one more launch per feed behind the beat and tempo launches and before live_compact_kernel, for the
+// same reason.  The member beat needs what rts_live_annotate set up: while annotations are off the launch is skipped.
+static int live_ens_launch(rts_live *h, hipStream_t s) {
+    if (!h->ens || !h->annot) return RTS_OK;
+    TempoTail view = {};
+    (void)(h->otw ? otw_tempo_view(h->otw, &view) : wtw_tempo_view(h->wtw, &view));
+    return ensemble_fuse_enqueue(h->ens, h->annot, view, h->ann_tables, h->ann_tables + h->geo.B, h->ens_out, s);
+}
+
 static void live_gate_clear(rts_live *h) {
     double *level = reinterpret_cast<double *>(h->gate_host);
     for (int b = 0; b < h->geo.B; b++) level[b] = __builtin_nan("");
@@ -371,7 +406,7 @@ static int live_refuse(const rts_live *h, LiveRefusal why, const FeedPlan &p, co
 // mode the tracker is pushed only when some stream hands it a column (n_max_diff > 0; the rows still lie n_max apart);
 // the watch launch follows rts_live_watch, the two gate launches rts_live_gate: with the gate on the push takes the gated
 // buffer and its counts, and nothing else moves; the beat launch follows rts_live_annotate, the tempo launch
-// rts_live_follow_tempo.  The compaction and the publication end every feed.
+// rts_live_follow_tempo, the consensus launch rts_live_follow_consensus.  The compaction and the publication end every feed.
 static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, void *stream) {
     const int B = h->geo.B;
     hipStream_t s = (hipStream_t)stream;
@@ -421,6 +456,7 @@ static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, 
     if (int rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
     if (int rc = live_annot_launch(h, s); rc != RTS_OK) return rc;
     if (int rc = live_tempo_launch(h, s); rc != RTS_OK) return rc;
+    if (int rc = live_ens_launch(h, s); rc != RTS_OK) return rc;
     hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -483,6 +519,7 @@ int rts_live_destroy(rts_live *h) {
     if (h->gate_host) (void)hipHostFree(h->gate_host);
     if (h->ann_host) (void)hipHostFree(h->ann_host);
     if (h->tempo_host) (void)hipHostFree(h->tempo_host);
+    if (h->ens_host) (void)hipHostFree(h->ens_host);
     free(h);  // the mirrors with it
     return RTS_OK;
 }
@@ -635,6 +672,10 @@ int rts_live_reset(rts_live *h, void *stream) {
     if (h->gate_host) live_gate_clear(h);
     if (h->ann_host) live_annot_clear(h);
     if (h->tempo_host) live_tempo_clear(h);
+    if (h->ens) {
+        if (int rc = rts_ensemble_reset(h->ens, nullptr, stream); rc != RTS_OK) return rc;
+    }
+    if (h->ens_host) live_ens_clear(h);
     memset(h->used, 0, sizeof(h->used));
     h->slot = -1;
     h->feeds = 0;
@@ -917,6 +958,71 @@ int rts_live_tempo(rts_live *h, double *slope, double *pos, double *bpm, int32_t
         if (pos) pos[b] = w[B + b];
         if (bpm) bpm[b] = w[2 * B + b];
         if (n) n[b] = cnt[b];
+    });
+    if (feeds_done) *feeds_done = fd;
+    return RTS_OK;
+}
+
+int rts_live_follow_consensus(rts_live *h, rts_ensemble *e) {
+    using namespace rts;
+    if (int rc = live_usable(h); rc != RTS_OK) return rc;
+    if (!e) {  // off: the words stay as they are
+        h->ens = nullptr;
+        h->args.ens_state = nullptr;
+        return RTS_OK;
+    }
+    if (!h->ann_host)
+        return set_error(RTS_ERR_INVALID, "rts_live_follow_consensus before any rts_live_annotate with tables: the member beat "
+                                          "needs every stream's piece and frame0");
+    if (ensemble_batch(e) != h->geo.B)
+        return set_error(RTS_ERR_INVALID, "the ensemble e was created for B = %d streams, the handle has %d", ensemble_batch(e),
+                         h->geo.B);
+    if (ensemble_device(e) != h->device)
+        return set_error(RTS_ERR_INVALID, "the ensemble e lives on device %d, the handle on device %d", ensemble_device(e),
+                         h->device);
+    if (!h->ens_host) {
+        if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+        const size_t nB = (size_t)h->geo.B;
+        RTS_HIP(hipHostMalloc((void **)&h->ens_host, (3 * sizeof(double) + 4 * sizeof(int32_t)) * nB,
+                              hipHostMallocMapped | hipHostMallocCoherent));
+        void *dev = nullptr;
+        if (hipError_t er = hipHostGetDevicePointer(&dev, h->ens_host, 0); er != hipSuccess) {
+            (void)hipHostFree(h->ens_host);
+            h->ens_host = nullptr;
+            return set_error(RTS_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(er));
+        }
+        double *w = reinterpret_cast<double *>(dev);
+        int32_t *n = reinterpret_cast<int32_t *>(w + 3 * nB);
+        const EnsembleOut o = {w, w + nB, n, n + nB, w + 2 * nB, n + 2 * nB, n + 3 * nB};
+        h->ens_out = o;
+        h->args.ens_dev = o.dev;
+        h->args.ens_member = o.strikes;
+        live_ens_clear(h);
+    }
+    h->ens = e;
+    h->ens_groups = ensemble_groups(e);
+    h->args.ens_state = ensemble_state(e);
+    return RTS_OK;
+}
+
+int rts_live_consensus(rts_live *h, double *consensus, double *spread, int32_t *n_in, int32_t *n_valid, double *dev,
+                       int32_t *strikes, int32_t *out, int *feeds_done) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!h->ens_host) return set_error(RTS_ERR_INVALID, "rts_live_consensus before any rts_live_follow_consensus with an ensemble");
+    const int B = h->geo.B, G = h->ens_groups;
+    const volatile double *w = reinterpret_cast<const volatile double *>(h->ens_host);
+    const volatile int32_t *n = reinterpret_cast<const volatile int32_t *>(h->ens_host + 3 * sizeof(double) * (size_t)B);
+    const int fd = live_read_published(h, [=](int b) {
+        if (b < G) {  // the group words ride under the sequence words of the first G streams: every stream's is written last
+            if (consensus) consensus[b] = w[b];
+            if (spread) spread[b] = w[B + b];
+            if (n_in) n_in[b] = n[b];
+            if (n_valid) n_valid[b] = n[B + b];
+        }
+        if (dev) dev[b] = w[2 * B + b];
+        if (strikes) strikes[b] = n[2 * B + b];
+        if (out) out[b] = n[3 * B + b];
     });
     if (feeds_done) *feeds_done = fd;
     return RTS_OK;

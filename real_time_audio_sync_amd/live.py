@@ -475,6 +475,43 @@ class LiveSession(object):
                                          self._tempo_n.ctypes.data if w is not None else None, ctypes.byref(done)))
         return dict(slope=w[0].copy(), pos=w[1].copy(), bpm=w[2].copy(), n=self._tempo_n.copy(), feeds_done=done.value)
 
+    @nat.on_device
+    def follow_consensus(self, groups, max_dev=2.0, patience=4):
+        """Several streams vote on where a microphone is (rts_live_follow_consensus): ``groups[b]`` is the group of stream
+        b (-1: none), 1 to 64 streams each -- the trackers that follow one microphone against different recordings of its
+        piece (``ensemble.EnsembleSession`` sets this up).  With it on, each feed enqueues one more small launch: the
+        median beat of every group, every member's distance from it, and ``out`` for a member that lay more than
+        ``max_dev`` beats away ``patience`` feeds in a row (it is left out of the median until one feed back within it);
+        ``consensus()`` reads the words.  Needs ``annotate(tables)`` first, and does nothing while annotations are off.
+        ``groups`` may be an ``ensemble.Ensemble`` of this device; ``None`` switches consensus off (the words stay).
+        ``restart`` clears the listed streams' strikes, ``reset`` everyone's."""
+        from .ensemble import Ensemble
+        if groups is None:
+            nat.check(nat.lib.rts_live_follow_consensus(self._h, None))
+            return
+        ens = groups if isinstance(groups, Ensemble) else Ensemble(groups, max_dev, patience, device=self.dev)
+        nat.check(nat.lib.rts_live_follow_consensus(self._h, ens._h))
+        if getattr(self, "_ens", None) is not None and self._ens is not ens:
+            self.sync()                                   # feeds in flight still vote with the ensemble bound before
+        self._ens = ens                                   # held by reference on the device side: keep it alive
+        self._ens_f = np.zeros((3, self.B), dtype=np.float64)
+        self._ens_i = np.zeros((4, self.B), dtype=np.int32)
+
+    def consensus(self):
+        """Non-blocking: {'consensus', 'spread' float64 [n_groups], 'n_in', 'n_valid' int32 [n_groups], 'dev' float64 [B],
+        'strikes', 'out' int32 [B], 'feeds_done'} as last published by the device: the groups' median beat (NaN: no member
+        has a beat) and the range of the members that voted, how many voted and how many have a beat at all; per stream
+        its beat minus the consensus (NaN: no beat, or in no group), its strikes and whether it is out.  Unlike ``beats()``
+        nothing here is sticky.  Needs ``follow_consensus`` first."""
+        done = ctypes.c_int()
+        f, i = getattr(self, "_ens_f", None), getattr(self, "_ens_i", None)
+        ptr = lambda a, q: a[q].ctypes.data if a is not None else None   # noqa: E731
+        nat.check(nat.lib.rts_live_consensus(self._h, ptr(f, 0), ptr(f, 1), ptr(i, 0), ptr(i, 1), ptr(f, 2), ptr(i, 2), ptr(i, 3),
+                                             ctypes.byref(done)))
+        G = self._ens.n_groups
+        return dict(consensus=f[0, :G].copy(), spread=f[1, :G].copy(), n_in=i[0, :G].copy(), n_valid=i[1, :G].copy(),
+                    dev=f[2].copy(), strikes=i[2].copy(), out=i[3].copy(), feeds_done=done.value)
+
     def backward(self, streams=None):
         """The backward path of every stream (or the listed ones) through the bound OTW tracker
         (``BatchedOTW.backward``): ``(paths, totals, ends)`` for everything the microphones' columns have brought the
