@@ -301,6 +301,87 @@ int rts_otw_read_kernel(const rts_otw *h, int live_dtype, int32_t out[4]);
 int rts_otw_read_kernel_waves(const rts_otw *h, int live_dtype, int32_t *waves);
 
 /* ------------------------------------------------------------------------------------------
+ * Snapshots: single streams move from one handle to another.
+ * ------------------------------------------------------------------------------------------ */
+
+/* What an export knows on the host about the records it wrote, filled synchronously from the exporting handle's own
+ * parameters (nothing is read back), and what an import holds against its target before anything is enqueued.  Fields
+ * of another kind than `kind` are 0; a live session's desc (RTS_SNAPSHOT_LIVE) carries the fields of its bound tracker
+ * too and names it in `tracker`. */
+#define RTS_SNAPSHOT_VERSION 1
+#define RTS_SNAPSHOT_OTW 1
+#define RTS_SNAPSHOT_WTW 2
+#define RTS_SNAPSHOT_LIVE 3
+typedef struct rts_snapshot_desc {
+    int32_t kind, version;  /* RTS_SNAPSHOT_*, RTS_SNAPSHOT_VERSION */
+    int32_t n;              /* records in the blob */
+    int32_t ref_dtype;      /* RTS_F32 / RTS_F64 of the exporting handle's reference: the cost of a cell depends on it */
+    long long rec_stride;   /* bytes from one record to the next */
+    int32_t F, c, max_run_count, variant, cost_kind;        /* RTS_SNAPSHOT_OTW */
+    int32_t window, hop, keep_last_d;                       /* RTS_SNAPSHOT_WTW */
+    int32_t fft_len, live_hop, feature_kind, max_pending;   /* RTS_SNAPSHOT_LIVE */
+    int32_t tracker;        /* RTS_SNAPSHOT_LIVE: RTS_SNAPSHOT_OTW / _WTW of the bound tracker, whose fields are filled too; else 0 */
+} rts_snapshot_desc;
+
+/* Why the device refused a record (status_dev of rts_otw_import); 0 = imported. */
+#define RTS_SNAP_BAD_MAGIC 1   /* not a record (or not written yet) */
+#define RTS_SNAP_BAD_VERSION 2
+#define RTS_SNAP_BAD_KIND 3
+#define RTS_SNAP_BAD_RANGE 4   /* the record's N_b differs from the length of the slot's reference range */
+#define RTS_SNAP_BAD_HISTORY 5 /* more history frames than the slot's buffer holds */
+#define RTS_SNAP_BAD_PATH 6    /* more path pairs than the slot's buffer holds, or a path the exporter had truncated */
+#define RTS_SNAP_BAD_LAYOUT 7  /* counts, section offsets, band width / window or used_bytes disagree with each other or with rec_stride */
+
+/* Bytes a record of this handle can take: the stride rts_otw_export needs (a multiple of 16).  A record is
+ *   64 bytes of int32 header words (magic, version, kind, N_b, M_b = 0, valid history frames, valid path pairs, the raw
+ *     history count, c, the byte offsets of the four sections, used_bytes, the n_path word, one zero word),
+ *   the 16 state words, the two persisted bands (2 (c + 1) doubles), the path pairs and the history frames (96 bytes each),
+ * every section starting on a multiple of 16 bytes, packed by the VALID counts: used_bytes is a function of (c, history
+ * frames, path pairs) alone, and the stride is used_bytes at 2 N_max frames and 3 N_max + 8 pairs.  RTS_ERR_UNSUPPORTED
+ * where that reaches 2^31 bytes. */
+int rts_otw_snapshot_bytes(const rts_otw *h, size_t *bytes);
+
+/* Writes one self-contained record per selected stream into caller-owned device memory: record i, at blob_dev +
+ * i * rec_stride, is stream idx_host[i].  A record is a function of the stream's state alone: it holds no slot index and
+ * no pointer, and every byte behind used_bytes up to rec_stride is written as zero, so two exports of an unchanged
+ * stream give the same rec_stride bytes whatever the blob held before.  Carried is exactly what rts_otw_restart resets
+ * (state words, persisted bands, path, insert history and its count, the length of the reference range); everything
+ * else is rebuilt by every launch.  The reference has nothing comparable (its objects live and die with the process).
+ *   idx_host: int32[n] in HOST memory, consumed when the call returns (the selection travels by value, 128 streams per
+ * launch, like a restart's).  blob_dev: 16-byte aligned, n * rec_stride bytes; rec_stride a multiple of 16 and at least
+ * rts_otw_snapshot_bytes.  desc_out: filled on the host from the handle's parameters.  The handle is only read.
+ * Asynchronous on `stream`, in stream order; no allocation, no synchronisation (graph-capturable).
+ *   RTS_ERR_INVALID, naming the argument, with nothing enqueued: NULL handle, idx_host, blob_dev or desc_out, n < 0, an
+ * index outside [0, B), a repeated index, a misaligned blob, a stride too small or no multiple of 16, wrong current
+ * device.  RTS_ERR_UNSUPPORTED: a handle that has consumed an rts_otw_run since its last reset (those frames are the
+ * caller's memory, as for rts_otw_recent), and a handle with the dense mirror attached.  n = 0 is RTS_OK. */
+int rts_otw_export(rts_otw *h, const int32_t *idx_host /* [n] */, int n, void *blob_dev, long long rec_stride,
+                   rts_snapshot_desc *desc_out, void *stream);
+
+/* Reads record i into slot slot_host[i]: from here on that slot behaves exactly like the exported stream would have,
+ * bit for bit -- rts_otw_insert / rts_otw_push continue it, rts_otw_recent, rts_otw_path_cost, rts_otw_tempo,
+ * rts_otw_backward and rts_otw_replay_dense answer as for a stream that was restarted and then fed the same frames.
+ * The target may differ in B, N_max, slot layout and kernel flavour (RTS_OTW_SPEC, RTS_OTW_TP_FROM, RTS_OTW_WAVES);
+ * F, c, max_run_count, variant, cost kind and the reference's dtype must be the exporter's: `desc` is held against the
+ * handle before anything is enqueued.  That the slot follows the same recording is the caller's business (the Python
+ * layer offers a digest); the device checks its length.
+ *   first_host / len_host: both NULL keeps every slot's reference range; both given (rts_otw_create_refs handles
+ * only): int64[n] / int32[n] host tables, entry i the range slot_host[i] moves to, checked as in rts_otw_restart.
+ *   status_dev: int32[n] device memory; entry i is 0 or the RTS_SNAP_* reason for which record i was refused.  The
+ * decision is taken from the record's header and the slot's range length alone; a refused slot keeps everything it owns
+ * (its range too).  Slots that are not selected are never written.
+ *   Asynchronous on `stream`.  The first import into a handle without history allocates it, as the first rts_otw_insert
+ * does; no other allocation, no synchronisation.
+ *   RTS_ERR_INVALID, with nothing enqueued and nothing changed: NULL handle, slot_host, blob_dev, desc or status_dev,
+ * n != desc->n, a slot outside [0, B), a repeated slot, a misaligned blob, rec_stride != desc->rec_stride, a desc field
+ * that differs from the handle (the message names the field), a bad range (the message names the stream), wrong current
+ * device.  RTS_ERR_UNSUPPORTED: a handle with the dense mirror attached. */
+int rts_otw_import(rts_otw *h, const int32_t *slot_host /* [n] */, int n, const void *blob_dev, long long rec_stride,
+                   const rts_snapshot_desc *desc, const long long *first_host /* [n] or NULL */,
+                   const int32_t *len_host /* [n] or NULL */, int32_t *status_dev /* [n] */, void *stream);
+/* The WTW counterparts are declared with the WTW handle below (rts_wtw_export / rts_wtw_import). */
+
+/* ------------------------------------------------------------------------------------------
  * Offline DTW, batched over B independent (a, b) pairs.
  * ------------------------------------------------------------------------------------------ */
 
@@ -632,6 +713,26 @@ int rts_wtw_read_last_d(rts_wtw *h, int b, double *d_host, void *stream);
 /* Device views: live chroma history [B][2M][F] float64 and (if kept) the last window's D [B][W][W]. */
 int rts_wtw_device_views(rts_wtw *h, double **live_chroma_dev, int *live_capacity, double **last_d_dev);
 
+/* Snapshots of single WTW streams: rts_otw_snapshot_bytes / rts_otw_export / rts_otw_import for this tracker, with the
+ * same arguments, the same refusals and the same per-record status words.  A record is the 64-byte header (kind
+ * RTS_SNAPSHOT_WTW, M_b in the word after N_b, which is 0), the eight state words, the last window's D (W * W doubles) on
+ * a keep_last_d handle once a window has run, the path pairs and the live chroma columns up to the appended count
+ * (capped at 2 M_b) -- what rts_wtw_restart resets, plus D.  The appended count is carried capped at 2 M_b + 1: past
+ * 2 M_b the tracker only ever asks whether a column was dropped, and how far the count ran depends on the exporter's
+ * history stride.  Nothing of the strip-DP pipeline's control or ticket words is carried: no window is pending between
+ * two pushes, the control step rewrites every word it later reads, and a handle that runs the window kernel has none;
+ * an import zeroes them like a restart, so a stream may move between a window-kernel handle and a strip-DP handle
+ * (RTS_WTW_WIN=0).  An import writes the count into both of the handle's count arrays, and the slot's history behind
+ * the record's columns reads zero again (wtw.py:55).  The desc must agree in window, hop and keep_last_d; the stride is
+ * the record at 2 M_max columns and the handle's path capacity.  Calls are in stream order between two rts_wtw_push;
+ * an export in the middle of a partly filled window carries the columns that wait for it. */
+int rts_wtw_snapshot_bytes(const rts_wtw *h, size_t *bytes);
+int rts_wtw_export(rts_wtw *h, const int32_t *idx_host /* [n] */, int n, void *blob_dev, long long rec_stride,
+                   rts_snapshot_desc *desc_out, void *stream);
+int rts_wtw_import(rts_wtw *h, const int32_t *slot_host /* [n] */, int n, const void *blob_dev, long long rec_stride,
+                   const rts_snapshot_desc *desc, const long long *first_host /* [n] or NULL */,
+                   const int32_t *len_host /* [n] or NULL */, int32_t *status_dev /* [n] */, void *stream);
+
 /* Device view of the state vectors, [B][RTS_WTW_STATE_LEN] int32 (zero-copy consumers; rts_live_* publishes from it). */
 int rts_wtw_state_view(rts_wtw *h, int32_t **state_dev);
 
@@ -811,6 +912,37 @@ int rts_live_gate_columns(rts_live *h, int b, int32_t *ordinals_host, int cap, i
 int rts_live_columns_view(rts_live *h, double **cols_dev, int *cols_cap, int *cols_stride, int32_t **n_cols_dev);
 /* Samples pending per stream after everything submitted so far (the host-side mirror; exact). */
 int rts_live_pending(rts_live *h, long long *pending_host /* [B] */);
+
+/* Snapshots of single streams of a live session in chroma or chroma-difference mode, over OTW or WTW.
+ * A record is the bound tracker's record in front, written and read through rts_otw_export / rts_otw_import (or the
+ * WTW pair) with all their rules, and at the END of the stride the live tail: four int32 words (pending count, carry
+ * flag, a magic word, max_pending), max_pending float32 samples (zeros behind the count) padded to 16 bytes, and the 12
+ * doubles of the carried chroma column of difference features (zeros without a carry and in chroma mode).
+ * rts_live_snapshot_bytes = the tracker's + 16 + 4 max_pending rounded up to 16 + 96.
+ *   rts_live_export: asynchronous on `stream`, behind the feeds already submitted; reads the session only and does not
+ * allocate.  idx_host, blob_dev, rec_stride, desc_out as for rts_otw_export.  mirror_out: int32[n][2] HOST memory, filled
+ * synchronously from the session's host mirror with each stream's pending count and carry flag (no read-back): hand them
+ * to the import.
+ *   rts_live_import: the one synchronous call here.  `desc` is held against the session (fft_len, live_hop,
+ * feature_kind, max_pending, tracker; then the tracker's own fields) and the mirror words against max_pending before
+ * anything is enqueued.  Then the tracker's import is asked without writing: it fills status_dev, the call waits for it,
+ * and if any record was refused it returns RTS_ERR_INVALID naming that stream, with nothing changed -- neither the
+ * tracker's slots nor pending buffers, carry, mirror or published words.  Otherwise the tracker's import and the live
+ * tail are enqueued, the mirror entries of those slots are set, and the call returns when they have run.  The slots'
+ * words are published like after rts_live_restart: status and positions from the imported tracker state, confidence,
+ * beat and tempo words empty until the next feed, consensus strikes 0, the feed number untouched.  first_host / len_host
+ * as for rts_otw_import.  Unselected streams are never written.
+ *   RTS_ERR_UNSUPPORTED from both: a session with a resampler (its tail and totals are not carried) or with the level
+ * gate on (nor are its queue, ordinals and counters); the tracker's own refusals (after rts_otw_run, dense mirror).
+ * RTS_ERR_INVALID: NULL arguments, a failed handle, wrong current device, a desc mismatch (naming the field), mirror words
+ * outside [0, max_pending] / {0, 1}, and everything rts_otw_export / rts_otw_import refuse. */
+int rts_live_snapshot_bytes(const rts_live *h, size_t *bytes);
+int rts_live_export(rts_live *h, const int32_t *idx_host /* [n] */, int n, void *blob_dev, long long rec_stride,
+                    rts_snapshot_desc *desc_out, int32_t *mirror_out /* [n][2], host */, void *stream);
+int rts_live_import(rts_live *h, const int32_t *slot_host /* [n] */, int n, const void *blob_dev, long long rec_stride,
+                    const rts_snapshot_desc *desc, const int32_t *mirror_host /* [n][2] */,
+                    const long long *first_host /* [n] or NULL */, const int32_t *len_host /* [n] or NULL */,
+                    int32_t *status_dev /* [n] */, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Beats and labels: ground-truth tables on the device, the live beat words, the batched accuracy metric.

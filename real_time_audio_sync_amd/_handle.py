@@ -217,6 +217,38 @@ class _BatchedHandle:
             self.push(frames, lens * keep.to(torch.int32))
         return out
 
+    # ---- snapshots -----------------------------------------------------------------------------
+    def _range_of(self, b):
+        """(first pool frame, frames) of the range stream b follows, and (frames of its piece, offset inside it)."""
+        if self._pool is None:
+            n = int(self.ref.shape[0])
+            return 0, n, n, 0
+        f, n = self._piece[b]
+        rl = int(self.ref_lens[b])
+        return f + n - rl, rl, n, n - rl
+
+    @nat.on_device
+    def export_streams(self, streams, verify=False, blob=None):
+        """The carried state of the listed streams as a ``snapshot.Snapshot`` (rts_otw_export / rts_wtw_export): record
+        i is ``streams[i]``.  Asynchronous on the current stream; the handle is only read.  ``verify``: also record a
+        digest of every stream's reference range (synchronises), which ``import_streams`` holds against the slot it is
+        given.  ``blob``: a uint8 device tensor [n][>= rts_*_snapshot_bytes] to write into instead of a new one.
+        BatchedOTW: not after ``run`` (those frames are the caller's) and not with the dense mirror attached."""
+        from .snapshot import export_streams
+        return export_streams(self, streams, verify, blob)
+
+    @nat.on_device
+    def import_streams(self, snap, slots, refs=None, offsets=None, verify=True, status=None):
+        """Record i of ``snap`` into slot ``slots[i]`` (rts_otw_import / rts_wtw_import): from here on the slot is that
+        stream, bit for bit, whatever this handle's batch size, longest reference, slot layout or kernel flavour; the
+        tracker's own parameters must be the exporter's.  ``refs`` / ``offsets``: one entry per slot, as in ``restart``
+        -- the range the slot moves to (handles made by ``with_references``); without them every slot keeps its range,
+        whose length must be the record's.  ``verify``: compare the digests of a snapshot exported with ``verify``.
+        Reads the per-stream status back and raises ``RtsyncError`` naming the first stream that refused its record and
+        why; such a slot is unchanged, the others are imported.  Synchronises."""
+        from .snapshot import import_streams
+        return import_streams(self, snap, slots, refs, offsets, verify, status)
+
     def _init_refs(self, pool, first, lens):
         self._pool = pool
         self._piece = None if pool is None else [(int(f), int(n)) for f, n in zip(first, lens)]

@@ -84,6 +84,23 @@ _decl("rts_otw_kernel_name", ctypes.c_char_p, [_vp])
 _decl("rts_otw_read_kernel", _i32, [_vp, _i32, _vp])
 _decl("rts_otw_read_kernel_waves", _i32, [_vp, _i32, _vp])
 OTW_RINGS = ("float", "double", "none", "none-lean")  # RTS_OTW_RING_*
+
+
+class SnapshotDesc(ctypes.Structure):
+    """rts_snapshot_desc."""
+    _fields_ = ([("kind", ctypes.c_int32), ("version", ctypes.c_int32), ("n", ctypes.c_int32), ("ref_dtype", ctypes.c_int32),
+                 ("rec_stride", ctypes.c_longlong)]
+                + [(k, ctypes.c_int32) for k in ("F", "c", "max_run_count", "variant", "cost_kind", "window", "hop",
+                                                 "keep_last_d", "fft_len", "live_hop", "feature_kind", "max_pending", "tracker")])
+
+
+SNAPSHOT_VERSION, SNAPSHOT_OTW, SNAPSHOT_WTW, SNAPSHOT_LIVE = 1, 1, 2, 3
+SNAP_REASONS = {1: "not a snapshot record (bad magic)", 2: "another format version", 3: "a record of another kind",
+                4: "the record's reference length differs from the slot's range", 5: "more history than the slot holds",
+                6: "a longer path than the slot holds", 7: "an inconsistent record layout"}  # RTS_SNAP_BAD_*
+_decl("rts_otw_snapshot_bytes", _i32, [_vp, ctypes.POINTER(ctypes.c_size_t)])
+_decl("rts_otw_export", _i32, [_vp, _vp, _i32, _vp, _i64, ctypes.POINTER(SnapshotDesc), _vp])
+_decl("rts_otw_import", _i32, [_vp, _vp, _i32, _vp, _i64, ctypes.POINTER(SnapshotDesc), _vp, _vp, _vp, _vp])
 _decl("rts_dtw_workspace_bytes", _i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_size_t)])
 _decl("rts_dtw", _i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                         ctypes.c_size_t, _vp])
@@ -129,6 +146,9 @@ _decl("rts_wtw_read_path", _i32, [_vp, _i32, _vp, _i32, _pi32, _vp])
 _decl("rts_wtw_read_last_d", _i32, [_vp, _i32, _vp, _vp])
 _decl("rts_wtw_device_views", _i32, [_vp, ctypes.POINTER(_vp), _pi32, ctypes.POINTER(_vp)])
 _decl("rts_wtw_state_view", _i32, [_vp, ctypes.POINTER(_vp)])
+_decl("rts_wtw_snapshot_bytes", _i32, [_vp, ctypes.POINTER(ctypes.c_size_t)])
+_decl("rts_wtw_export", _i32, [_vp, _vp, _i32, _vp, _i64, ctypes.POINTER(SnapshotDesc), _vp])
+_decl("rts_wtw_import", _i32, [_vp, _vp, _i32, _vp, _i64, ctypes.POINTER(SnapshotDesc), _vp, _vp, _vp, _vp])
 WTW_STATE_LEN = 8
 
 _decl("rts_live_create", _i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_vp)])
@@ -143,6 +163,9 @@ _decl("rts_live_submit", _i32, [_vp, _i32, _vp])
 _decl("rts_live_feed", _i32, [_vp, _vp, _i32, _vp, _vp])
 _decl("rts_live_poll", _i32, [_vp, _vp, _vp, _pi32, _pi32])
 _decl("rts_live_pending", _i32, [_vp, _vp])
+_decl("rts_live_snapshot_bytes", _i32, [_vp, ctypes.POINTER(ctypes.c_size_t)])
+_decl("rts_live_export", _i32, [_vp, _vp, _i32, _vp, _i64, ctypes.POINTER(SnapshotDesc), _vp, _vp])
+_decl("rts_live_import", _i32, [_vp, _vp, _i32, _vp, _i64, ctypes.POINTER(SnapshotDesc), _vp, _vp, _vp, _vp, _vp])
 _decl("rts_live_watch", _i32, [_vp, _i32])
 _decl("rts_live_confidence", _i32, [_vp, _vp, _vp, _pi32])
 _decl("rts_live_gate", _i32, [_vp, ctypes.c_double, _i32])

@@ -163,6 +163,18 @@ __attribute__((visibility("hidden"))) int ensemble_fuse_enqueue(rts_ensemble *e,
                                                                 const int32_t *piece, const int32_t *frame0,
                                                                 const EnsembleOut &o, hipStream_t s);
 
+// rts_otw_import / rts_wtw_import with `dry` != 0: every check is made and status_dev is written, nothing else -- neither
+// on the device nor in the handle.  rts_live_import asks this way first, so that a refused record leaves the session as
+// it was.  dry == 0 is the public call.
+__attribute__((visibility("hidden"))) int otw_import_records(rts_otw *h, const int32_t *slot_host, int n, const void *blob_dev,
+                                                             long long rec_stride, const rts_snapshot_desc *desc,
+                                                             const long long *first_host, const int32_t *len_host,
+                                                             int32_t *status_dev, void *stream, int dry);
+__attribute__((visibility("hidden"))) int wtw_import_records(rts_wtw *h, const int32_t *slot_host, int n, const void *blob_dev,
+                                                             long long rec_stride, const rts_snapshot_desc *desc,
+                                                             const long long *first_host, const int32_t *len_host,
+                                                             int32_t *status_dev, void *stream, int dry);
+
 #define RTS_HIP(call)                                                                       \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \

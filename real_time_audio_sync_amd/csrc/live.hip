@@ -1132,3 +1132,5 @@ int rts_live_pending(rts_live *h, long long *pending_host /* [B] */) {
 }
 
 }  // extern "C"
+
+#include "snapshot_live.h"  // rts_live_export / rts_live_import: single streams move between sessions

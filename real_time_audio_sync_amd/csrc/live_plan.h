@@ -86,4 +86,14 @@ inline void live_mirror_commit(const LiveGeom &g, const LiveMirror &cur, const L
     if (g.rs_L) memcpy(cur.rs_tot, next.rs_tot, sizeof(long long) * 2 * (size_t)g.B);
 }
 
+// rts_live_import: the mirror entries of the slots that took a record, from the two words per stream an export handed
+// out (pending samples, carry flag).  The one other writer of the mirror beside live_mirror_commit; entries of streams
+// that are not listed, and the resampler's totals, are not touched.
+inline void live_mirror_import(const LiveGeom &g, const LiveMirror &cur, int n, const int32_t *slots, const int32_t *words) {
+    for (int i = 0; i < n; i++) {
+        cur.pending[slots[i]] = words[2 * i];
+        if (g.diff) cur.has_carry[slots[i]] = words[2 * i + 1] != 0;
+    }
+}
+
 }  // namespace rts

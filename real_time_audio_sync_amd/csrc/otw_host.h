@@ -10,6 +10,7 @@
 #include "otw_device.h"
 #include "otw_fill.h"  // launch() enqueues otw_bandfill_kernel in front of the step kernel
 #include "otw_plan.h"  // which instantiation a launch gets and whether the band fill runs: host-only, tested on the CPU
+#include "snapshot.h"  // rts_otw_export / rts_otw_import: the record kernels both trackers share
 
 namespace rts {
 
@@ -574,6 +575,68 @@ int otw_tempo_view(const rts_otw *h, TempoTail *t) {
     return h->N;
 }
 
+// ---- snapshots (include/rtsync.h; csrc/snapshot.h has the kernels) ----------------------------------------------------
+// The handle as the record kernels see it: exactly what otw_restart_kernel resets.
+static SnapView otw_snap_view(const rts_otw *h, const void *blob, long long rec_stride, int32_t *status) {
+    SnapView v;
+    memset(&v, 0, sizeof(v));
+    v.kind = RTS_SNAPSHOT_OTW;
+    v.state = h->state;
+    v.state_words = RTS_STATE_LEN;
+    v.st_n_path = RTS_ST_N_PATH;
+    v.mid = reinterpret_cast<unsigned long long *>(h->bands);
+    v.mid_stride = 2LL * (h->c + 1);
+    v.param = h->c;
+    v.mid_gate = -1;
+    v.path = h->path;
+    v.path_cap = h->path_cap;
+    v.hist = h->hist;
+    v.hist_stride = h->hist_stride;
+    v.count = h->hist_len;
+    v.ref_first = h->refs.first;
+    v.ref_len = h->refs.len;
+    v.len_default = h->N;
+    v.blob = static_cast<unsigned char *>(const_cast<void *>(blob));
+    v.rec_stride = rec_stride;
+    v.status = status;
+    return v;
+}
+
+static void otw_snap_desc(const rts_otw *h, int n, long long rec_stride, rts_snapshot_desc *d) {
+    memset(d, 0, sizeof(*d));
+    d->kind = RTS_SNAPSHOT_OTW;
+    d->version = RTS_SNAPSHOT_VERSION;
+    d->n = n;
+    d->ref_dtype = h->ref_dtype;
+    d->rec_stride = rec_stride;
+    d->F = h->F;
+    d->c = h->c;
+    d->max_run_count = h->max_run_count;
+    d->variant = h->variant;
+    d->cost_kind = h->cost_kind;
+}
+
+int otw_import_records(rts_otw *h, const int32_t *slot_host, int n, const void *blob_dev, long long rec_stride,
+                       const rts_snapshot_desc *desc, const long long *first_host, const int32_t *len_host,
+                       int32_t *status_dev, void *stream, int dry) {
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!desc) return set_error(RTS_ERR_INVALID, "desc is NULL");
+    if (!status_dev) return set_error(RTS_ERR_INVALID, "status_dev is NULL");
+    if (int rc = snap_check_sel(h->B, slot_host, n, "slot_host", blob_dev, rec_stride); rc != RTS_OK) return rc;
+    rts_snapshot_desc mine;
+    otw_snap_desc(h, n, rec_stride, &mine);
+    if (int rc = snap_check_import(*desc, mine, slot_host, first_host, len_host, h->refs, h->N, "N_max"); rc != RTS_OK) return rc;
+    if (h->dense_acc) return set_error(RTS_ERR_UNSUPPORTED, "rts_otw_import: the dense mirror is attached, and a record does not carry it");
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    if (n == 0) return RTS_OK;
+    if (!dry) {
+        if (int rc = begin_append(h); rc != RTS_OK) return rc;  // the slots now hold frames of the handle's own history
+    }
+    SnapView v = otw_snap_view(h, blob_dev, rec_stride, status_dev);
+    v.dry = dry;
+    return snap_enqueue(true, v, slot_host, n, first_host, len_host, (hipStream_t)stream);
+}
+
 }  // namespace rts
 
 extern "C" {
@@ -847,6 +910,35 @@ int rts_otw_tempo(rts_otw *h, int K, double ahead, double *slope_dev, double *po
     t.pos = pos_dev;
     t.n_out = n_dev;
     return tempo_tail_enqueue(t, nullptr, (hipStream_t)stream);
+}
+
+int rts_otw_snapshot_bytes(const rts_otw *h, size_t *bytes) {
+    using namespace rts;
+    if (!h || !bytes) return set_error(RTS_ERR_INVALID, "NULL argument");
+    const long long need = snap::otw_rec_stride(h->N, h->c);
+    if (int rc = snap_stride_check(need, -1, "N_max", h->N); rc != RTS_OK) return rc;
+    *bytes = (size_t)need;
+    return RTS_OK;
+}
+
+int rts_otw_export(rts_otw *h, const int32_t *idx_host, int n, void *blob_dev, long long rec_stride,
+                   rts_snapshot_desc *desc_out, void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!desc_out) return set_error(RTS_ERR_INVALID, "desc_out is NULL");
+    if (int rc = snap_check_sel(h->B, idx_host, n, "idx_host", blob_dev, rec_stride); rc != RTS_OK) return rc;
+    if (int rc = snap_stride_check(snap::otw_rec_stride(h->N, h->c), rec_stride, "N_max", h->N); rc != RTS_OK) return rc;
+    if (int rc = refuse_run_frames(h, "rts_otw_export"); rc != RTS_OK) return rc;
+    if (h->dense_acc) return set_error(RTS_ERR_UNSUPPORTED, "rts_otw_export: the dense mirror is attached, and a record does not carry it");
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    otw_snap_desc(h, n, rec_stride, desc_out);
+    return snap_enqueue(false, otw_snap_view(h, blob_dev, rec_stride, nullptr), idx_host, n, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int rts_otw_import(rts_otw *h, const int32_t *slot_host, int n, const void *blob_dev, long long rec_stride,
+                   const rts_snapshot_desc *desc, const long long *first_host, const int32_t *len_host,
+                   int32_t *status_dev, void *stream) {
+    return rts::otw_import_records(h, slot_host, n, blob_dev, rec_stride, desc, first_host, len_host, status_dev, stream, 0);
 }
 
 int rts_otw_read_states(rts_otw *h, int32_t *states, void *stream) {

@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "sdp.h"
+#include "snapshot.h"  // rts_wtw_export / rts_wtw_import: the record kernels both trackers share
 
 namespace rts {
 
@@ -1136,4 +1137,100 @@ int rts_wtw_device_views(rts_wtw *h, double **live_chroma_dev, int *live_capacit
     return RTS_OK;
 }
 
+// ---- snapshots (include/rtsync.h; csrc/snapshot.h has the kernels) ----------------------------------------------------
+// The handle as the record kernels see it: what wtw_restart_kernel resets, and D where the handle keeps it.  `appended`
+// is the count array the host has current at this call; an import writes the other one too.
+static rts::SnapView wtw_snap_view(const rts_wtw *h, const void *blob, long long rec_stride, int32_t *status) {
+    const rts::WtwArgs &g = h->args;
+    rts::SnapView v;
+    memset(&v, 0, sizeof(v));
+    v.kind = RTS_SNAPSHOT_WTW;
+    v.state = g.state;
+    v.state_words = RTS_WTW_STATE_LEN;
+    v.st_n_path = RTS_WTW_ST_N_PATH;
+    v.mid = reinterpret_cast<unsigned long long *>(g.dlast);
+    v.mid_stride = (long long)g.W * g.W;
+    v.param = g.dlast ? g.W : 0;
+    v.mid_gate = 5;  // n_windows: D is whatever hipMalloc left there until the first window has run
+    v.path = g.path;
+    v.path_cap = g.path_cap;
+    v.hist = g.live;
+    v.hist_stride = g.live_stride;
+    v.count = g.appended;
+    v.count2 = g.appended_next;
+    v.ref_first = h->refs.first;
+    v.ref_len = h->refs.len;
+    v.len_default = g.M;
+    v.ctl = g.ctl;
+    v.ticket = g.ticket;
+    v.zero_hist = 1;
+    v.blob = static_cast<unsigned char *>(const_cast<void *>(blob));
+    v.rec_stride = rec_stride;
+    v.status = status;
+    return v;
+}
+
+static void wtw_snap_desc(const rts_wtw *h, int n, long long rec_stride, rts_snapshot_desc *d) {
+    memset(d, 0, sizeof(*d));
+    d->kind = RTS_SNAPSHOT_WTW;
+    d->version = RTS_SNAPSHOT_VERSION;
+    d->n = n;
+    d->ref_dtype = RTS_F64;
+    d->rec_stride = rec_stride;
+    d->F = rts::kWF;
+    d->window = h->args.W;
+    d->hop = h->args.hopf;
+    d->keep_last_d = h->args.dlast != nullptr;
+}
+
+static long long wtw_snap_need(const rts_wtw *h) {
+    return rts::snap::wtw_rec_stride(h->args.M, h->args.W, h->args.dlast != nullptr, h->args.path_cap);
+}
+
+int rts_wtw_snapshot_bytes(const rts_wtw *h, size_t *bytes) {
+    using namespace rts;
+    if (!h || !bytes) return set_error(RTS_ERR_INVALID, "NULL argument");
+    if (int rc = snap_stride_check(wtw_snap_need(h), -1, "M_max", h->args.M); rc != RTS_OK) return rc;
+    *bytes = (size_t)wtw_snap_need(h);
+    return RTS_OK;
+}
+
+int rts_wtw_export(rts_wtw *h, const int32_t *idx_host, int n, void *blob_dev, long long rec_stride,
+                   rts_snapshot_desc *desc_out, void *stream) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!desc_out) return set_error(RTS_ERR_INVALID, "desc_out is NULL");
+    if (int rc = snap_check_sel(h->B, idx_host, n, "idx_host", blob_dev, rec_stride); rc != RTS_OK) return rc;
+    if (int rc = snap_stride_check(wtw_snap_need(h), rec_stride, "M_max", h->args.M); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    wtw_snap_desc(h, n, rec_stride, desc_out);
+    return snap_enqueue(false, wtw_snap_view(h, blob_dev, rec_stride, nullptr), idx_host, n, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int rts_wtw_import(rts_wtw *h, const int32_t *slot_host, int n, const void *blob_dev, long long rec_stride,
+                   const rts_snapshot_desc *desc, const long long *first_host, const int32_t *len_host,
+                   int32_t *status_dev, void *stream) {
+    return rts::wtw_import_records(h, slot_host, n, blob_dev, rec_stride, desc, first_host, len_host, status_dev, stream, 0);
+}
+
 }  // extern "C"
+
+namespace rts {
+
+int wtw_import_records(rts_wtw *h, const int32_t *slot_host, int n, const void *blob_dev, long long rec_stride,
+                       const rts_snapshot_desc *desc, const long long *first_host, const int32_t *len_host,
+                       int32_t *status_dev, void *stream, int dry) {
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!desc) return set_error(RTS_ERR_INVALID, "desc is NULL");
+    if (!status_dev) return set_error(RTS_ERR_INVALID, "status_dev is NULL");
+    if (int rc = snap_check_sel(h->B, slot_host, n, "slot_host", blob_dev, rec_stride); rc != RTS_OK) return rc;
+    rts_snapshot_desc mine;
+    wtw_snap_desc(h, n, rec_stride, &mine);
+    if (int rc = snap_check_import(*desc, mine, slot_host, first_host, len_host, h->refs, h->args.M, "M_max"); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    SnapView v = wtw_snap_view(h, blob_dev, rec_stride, status_dev);
+    v.dry = dry;
+    return snap_enqueue(true, v, slot_host, n, first_host, len_host, (hipStream_t)stream);
+}
+
+}  // namespace rts

@@ -258,6 +258,38 @@ class LiveSession(object):
         if self._annot is not None and pieces:   # new piece / offset: the beats stay in the piece's own time
             self._annotate_streams(sorted(pieces))
 
+    # ---- snapshots --------------------------------------------------------------------------------------------
+    @nat.on_device
+    def export_streams(self, streams, verify=False, blob=None):
+        """The carried state of the listed streams as a ``snapshot.Snapshot`` (rts_live_export): the tracker's record, the
+        pending samples and, with ``features='chroma_diff'``, the carried chroma column; ``Snapshot.mirror`` holds the two
+        host mirror words per stream.  Asynchronous, behind the feeds already submitted; the session is only read.  Not
+        for a session that resamples (``fs_in``) or has the gate on."""
+        from .snapshot import export_live
+        return export_live(self, streams, verify, blob)
+
+    @nat.on_device
+    def import_streams(self, snap, slots, refs=None, offsets=None, verify=True, status=None):
+        """Record i of ``snap`` (a live session's snapshot) into slot ``slots[i]`` (rts_live_import): from the next feed on
+        the slot is that stream, bit for bit.  fft_len, hop, features, max_pending and the tracker's parameters must be the
+        exporter's; ``refs`` / ``offsets`` as in ``restart``.  All or nothing: if the device refuses one record the call
+        raises ``RtsyncError`` naming the stream, and ``pending()``, ``poll()`` and the tracker are what they were.
+        ``poll()`` shows the imported positions at once; confidence, beat and tempo words read empty until the next feed.
+        Synchronises."""
+        from .snapshot import import_streams
+        if refs is not None:
+            if self._conv is None or any(id(r) not in self._conv for r in refs):
+                raise ValueError("a reference to import onto must have been given at create (ref_chroma list / extra_refs)")
+            refs = [self._conv[id(r)][1] for r in refs]
+        eng = self.otw or self.wtw
+        got = import_streams(eng, snap, slots, refs, offsets, verify, status, live=self)
+        if self.otw:
+            self.otw._version += 1
+        self._direct[[int(s) for s in slots]] = 0
+        if self._annot is not None and (refs is not None or offsets is not None):   # the beats stay in the piece's own time
+            self._annotate_streams(sorted(int(s) for s in slots))
+        return got
+
     # ---- beats and labels -------------------------------------------------------------------------------------
     def _annotate_streams(self, streams):
         """rts_live_annotate for the listed streams, piece and frame offset taken from what the tracker follows now."""

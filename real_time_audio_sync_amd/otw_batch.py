@@ -161,6 +161,13 @@ class BatchedOTW(_BatchedHandle):
         super().restart(streams, refs, offsets)
         self._version += 1
 
+    def import_streams(self, snap, slots, refs=None, offsets=None, verify=True, status=None):
+        """``_BatchedHandle.import_streams``; c, max_run_count, variant, cost kind and dtype must be the exporter's, batch
+        size, N_max, slot layout and kernel flavour need not.  Not with the dense mirror attached."""
+        got = super().import_streams(snap, slots, refs, offsets, verify, status)
+        self._version += 1
+        return got
+
     # ---- results ------------------------------------------------------------------------------
     @_on_device
     def path_cost(self, K=64, want_costs=False):
