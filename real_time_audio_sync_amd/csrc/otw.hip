@@ -102,7 +102,7 @@ struct OtwSpecOut {
     int pidx[64];
     double d;    // cost of the strip's last cell (the one the shadow leaves out)
     double d2;   // column speculation only: cost of the corner (t+1, j+1) a Both step would add
-    int k1;      // first band position of the strip
+    int k1;      // (unused: the strip's first band position follows from the plan; kept for the layout)
     int flag;    // column speculation: 1 if dropping the strip's first cell leaves every other cell unchanged
 };
 template <int W>
@@ -624,13 +624,17 @@ __device__ __forceinline__ void otw_refill(OtwLds<W, RT> &S, OtwCtl &k, const Ot
     }
 }
 
+// What wave 0's hit-step loop makes of a plan (pipelined kernel): said by otw_make_plan, which has just tested for it, so
+// that the loop does not decode the flags of a plan its own wave wrote.
+enum { kStepOther = 0, kStepRowHit = 1, kStepColHit = 2, kStepBothHit = 3, kStepBothHitIf = 4 };
 struct OtwPlan {
     int t, j0, flags;
+    int kind;  // kStep*: not published, wave 0's own
 };
 
 template <int W, typename RT>
 __device__ __forceinline__ OtwPlan otw_make_plan(OtwLds<W, RT> &S, OtwCtl &k, const OtwEnv &e, bool spec = false,
-                                                 int slot = 0) {
+                                                 int slot = 0, bool all_lanes = false) {
     int flags = 0, pt = k.t;
     if (k.status != RTS_RUNNING) {
         flags = kPlanExit;
@@ -649,12 +653,14 @@ __device__ __forceinline__ OtwPlan otw_make_plan(OtwLds<W, RT> &S, OtwCtl &k, co
         flags = kPlanRow | ((k.dir != RTS_DIR_ROW) ? kPlanCol : 0);
     }
     if ((flags & kPlanCol) && k.j + 1 >= e.N) flags |= kPlanStop;  // otw_eran.py:67-71
+    int kind = kStepOther;
     if (spec) {
         // the shadow becomes the band: any Row-only / Column-only step, and a Both step while both of its strips
         // still start at 0 like the speculated ones (otw_settle_hit_both)
         const bool both = flags == (kPlanRow | kPlanCol);
         const bool both_ok = both && k.t <= e.c - 2 && k.j <= e.c - 2;
         if (k.spec_valid && (flags == kPlanRow || flags == kPlanCol || both_ok)) {
+            kind = both ? kStepBothHit : (flags == kPlanRow) ? kStepRowHit : kStepColHit;
             flags |= kPlanHit;
             if (flags & kPlanRow) k.ri ^= 1;
             if (flags & kPlanCol) k.ci ^= 1;
@@ -662,10 +668,11 @@ __device__ __forceinline__ OtwPlan otw_make_plan(OtwLds<W, RT> &S, OtwCtl &k, co
             // a Both step later on: still the two speculated strips, if the column strip survives losing its first
             // cell (otw_resolve_plan); needs two cells per lane in the chain (W >= 128) and two cells in the strip
             flags |= kPlanHitIf;
+            kind = kStepBothHitIf;
         }
         flags |= (k.ri ? kPlanRi : 0) | (k.ci ? kPlanCi : 0);
     }
-    if (e.lane == 0) {
+    if (all_lanes || e.lane == 0) {  // all_lanes: the same words from every lane (wave 0's hit-step loop says why)
         S.plan_t[slot] = pt;
         S.plan_j0[slot] = k.j;
         S.plan_flags[slot] = flags;
@@ -686,6 +693,7 @@ __device__ __forceinline__ OtwPlan otw_make_plan(OtwLds<W, RT> &S, OtwCtl &k, co
     p.t = pt;
     p.j0 = k.j;
     p.flags = flags;
+    p.kind = kind;
     return p;
 }
 
@@ -986,8 +994,7 @@ __device__ __forceinline__ void otw_spec_strip(const double *Dv, const double *b
                                            fm, fi, nullptr, nullptr, 0, rounds_acc, prev0_sentinel, sentinel, &alt_ok);
     out->pmin[lane] = fm;
     out->pidx[lane] = fi;
-    if (lane == 0) {
-        out->k1 = k1;
+    if (lane == 0) {  // (the strip's first position is not exported: wave 0 has it from the plan, max(0, pos - c + 1))
         out->d = d_last;
         out->d2 = d_next;
         out->flag = alt_ok;
@@ -1004,8 +1011,11 @@ __device__ __forceinline__ void otw_spec_argmin(double lm, int ml, int k1, doubl
     const unsigned long long mask = __ballot(lm == g);
     const bool some = (g < INFINITY) && (mask != 0);
     const int first = (int)__builtin_ctzll(mask | (1ull << 63));  // lanes hold increasing positions
+    // (read on every path: behind the `some` test the compiler sinks the caller's load of `ml` into the branch, i.e. behind
+    // the first wait -- one more LDS round trip per step)
+    const int ml_first = __builtin_amdgcn_readlane(ml, first);
     g_out = g;
-    idx_out = some ? k1 + L * first + __builtin_amdgcn_readlane(ml, first) : 0x7fffffff;
+    idx_out = some ? k1 + L * first + ml_first : 0x7fffffff;
 }
 
 // otw_spec_argmin of the row and of the column shadow strip at once (a Both step as a hit): the same reductions, run side by side.
@@ -1018,10 +1028,11 @@ __device__ __forceinline__ void otw_spec_argmin2(double rlm, int rml, int rk1, d
     const unsigned long long rmask = __ballot(rlm == rg), cmask = __ballot(clm == cg);
     const bool rsome = (rg < INFINITY) && (rmask != 0), csome = (cg < INFINITY) && (cmask != 0);
     const int rfirst = (int)__builtin_ctzll(rmask | (1ull << 63)), cfirst = (int)__builtin_ctzll(cmask | (1ull << 63));
+    const int rml_first = __builtin_amdgcn_readlane(rml, rfirst), cml_first = __builtin_amdgcn_readlane(cml, cfirst);
     rg_out = rg;
     cg_out = cg;
-    ridx_out = rsome ? rk1 + L * rfirst + __builtin_amdgcn_readlane(rml, rfirst) : 0x7fffffff;
-    cidx_out = csome ? ck1 + L * cfirst + __builtin_amdgcn_readlane(cml, cfirst) : 0x7fffffff;
+    ridx_out = rsome ? rk1 + L * rfirst + rml_first : 0x7fffffff;
+    cidx_out = csome ? ck1 + L * cfirst + cml_first : 0x7fffffff;
 }
 
 // The last cell of a shadow strip, in the chain's own order: min(min(side + d, diag + 2d), previous cell + d).  `side`
@@ -1063,12 +1074,13 @@ __device__ __forceinline__ OtwSettled otw_settle_hit_both(double *R, double *C, 
     const int k1r_ = (j0 - c + 1 > 0) ? j0 - c + 1 : 0, k1c_ = (pt - c + 1 > 0) ? pt - c + 1 : 0;
     const double pra_raw = R[swz<W>(j0 - (j0 - k1r_ > 0 ? 1 : 0))], prb_raw = C[swz<W>(t0 - (t0 - k1c_ > 0 ? 1 : 0))];
     const double d1_raw = exr->d, d2_raw = exc->d, d3_raw = exc->d2, rlm = exr->pmin[lane], clm = exc->pmin[lane];
-    const int rml = exr->pidx[lane], cml = exc->pidx[lane], rk1 = exr->k1, ck1 = exc->k1;
+    const int rml = exr->pidx[lane], cml = exc->pidx[lane];
     const double d1 = rfl(d1_raw), d2 = rfl(d2_raw), d3 = rfl(d3_raw);
     double rmin, cmin;
     int ridx, cidx;
-    otw_spec_argmin<W>(rlm, rml, __builtin_amdgcn_readfirstlane(rk1), rmin, ridx);
-    otw_spec_argmin<W>(clm, cml, __builtin_amdgcn_readfirstlane(ck1), cmin, cidx);
+    // the speculated strips start where the plan says: row strip [k1r, j0-1], column strip [max(0, t0-c+1), pt-2]
+    otw_spec_argmin<W>(rlm, rml, k1r_, rmin, ridx);
+    otw_spec_argmin<W>(clm, cml, (t0 - c + 1 > 0) ? t0 - c + 1 : 0, cmin, cidx);
     rmin = rfl(rmin), cmin = rfl(cmin);
     ridx = __builtin_amdgcn_readfirstlane(ridx), cidx = __builtin_amdgcn_readfirstlane(cidx);
     const double pra = rfl(pra_raw), prb = rfl(prb_raw);
@@ -1157,11 +1169,11 @@ __device__ __forceinline__ OtwSettled otw_settle_hit(double *R, double *C, const
     // the LDS reads of the step, independent of each other: one round trip
     const double prev_raw = band[swz<W>(pos - (n > 0 ? 1 : 0))];
     const double d_raw = ex->d, lm = ex->pmin[lane];
-    const int ml = ex->pidx[lane], sk1 = ex->k1;
+    const int ml = ex->pidx[lane];
     const double d = rfl(d_raw);
     double smin_v;
     int sidx_v;
-    otw_spec_argmin<W>(lm, ml, __builtin_amdgcn_readfirstlane(sk1), smin_v, sidx_v);
+    otw_spec_argmin<W>(lm, ml, k1, smin_v, sidx_v);  // the shadow strip starts at the step's own k1
     const double smin = rfl(smin_v);
     const int sidx = __builtin_amdgcn_readfirstlane(sidx_v);
     const double prev_s = rfl(prev_raw);  // unconditional: keeps the read in the round trip above (see otw_settle_hit_both)
@@ -1416,6 +1428,7 @@ otw_advance_kernel(OtwArgs a) {
     OtwPlan pl;  // pipelined kernel, wave 0: the plan it published, kept in registers
     pl.t = pl.j0 = 0;
     pl.flags = kPlanExit;
+    pl.kind = kStepOther;
     if constexpr (SPEC) {
         otw_costs_prime<W, RT, kOneCell>(S, e, S.t, S.j, tid, NT);
         if (wave == 0) {
@@ -1545,6 +1558,12 @@ otw_advance_kernel(OtwArgs a) {
             // hit, or whose decide() would have to reduce a band (a kept minimum that slid out of its window; a Both step's
             // speculated argmin outside the step's window): the general loop runs that step and comes back.  W = 512 only,
             // and not the throughput flavour (its point is its register budget).
+            // How it is written follows from the generated code (profiles/otw_w0_loop_summary.md).  Its stores -- band cells,
+            // path point, next plan -- come from every lane, the same value to the same address, not from lane 0: a
+            // divergent branch inside the loop makes the compiler structurize the whole loop, exits included, with exec
+            // masks and guard flags (and, in the deferred policies, the plan on the vector unit).  The step kind comes
+            // with the plan (OtwPlan::kind), the speculated strip's first position from the plan's own arithmetic, and
+            // decide() / the next plan follow each kind's settle in a copy of their own (decide_plan) instead of joining.
             int2 *const path_row = reinterpret_cast<int2 *>(e.path) + (size_t)e.b * e.path_cap;
             const auto hit_steps = [&](auto v2_c, auto defer_c) __attribute__((always_inline)) {
                 constexpr bool V2 = decltype(v2_c)::value, DEFER = decltype(defer_c)::value;
@@ -1558,17 +1577,76 @@ otw_advance_kernel(OtwArgs a) {
                 for (;;) {
                     const int pt = __builtin_amdgcn_readfirstlane(pl.t), j0 = __builtin_amdgcn_readfirstlane(pl.j0);
                     const int fl = __builtin_amdgcn_readfirstlane(pl.flags);
-                    const int kind = fl & (kPlanHit | kPlanRow | kPlanCol | kPlanStop | kPlanExit | kPlanHitIf);
-                    const bool is_row = kind == (kPlanHit | kPlanRow);
+                    // the step kind as otw_make_plan found it (the flags still say which buffers hold the bands)
+                    const int kind = __builtin_amdgcn_readfirstlane(pl.kind);
+                    if (kind == kStepOther) return;
+                    const bool is_row = kind == kStepRowHit;
                     // a Both step whose strips are the two shadows: planned as a hit (the band is still filling), or "hit
                     // if the column speculation allows" (full band; otw_resolve_plan)
-                    const bool hit_if = kind == (kPlanHitIf | kPlanRow | kPlanCol);
-                    const bool is_both = hit_if || kind == (kPlanHit | kPlanRow | kPlanCol);
-                    if (!is_row && !is_both && kind != (kPlanHit | kPlanCol)) return;
-                    const int jn = is_row ? j0 : j0 + 1;
-                    double rmin, cmin, cl;
-                    int ridx, cidx;
+                    const bool hit_if = kind == kStepBothHitIf;
+                    const bool is_both = kind >= kStepBothHit;
+                    // decide (otw_decide) and the next plan, expanded behind each kind's settle: in front of a common tail
+                    // the compiler carried the values of both settles through blocks of register copies, every step
+                    const auto decide_plan = [&](double rmin, double cmin, int ridx, int cidx, double cl, int jn, int flip,
+                                                 int stamp_kind) __attribute__((always_inline)) {
+                        // a "hit if" step that was resolved to a hit (flip = 1): both shadows have become bands
+                        k.ri ^= flip;
+                        k.ci ^= flip;
+                        // both bands gain `cl` at their top index (it wins only if strictly smaller)
+                        const bool r_new = cl < rmin, c_new = cl < cmin;
+                        rmin = r_new ? cl : rmin;
+                        ridx = r_new ? jn : ridx;
+                        cmin = c_new ? cl : cmin;
+                        cidx = c_new ? pt : cidx;
+                        k.rb_min = rmin;
+                        k.rb_idx = ridx;
+                        k.cb_min = cmin;
+                        k.cb_idx = cidx;
+                        const bool rlt = rmin < cmin;
+                        const int x = rlt ? pt : cidx, y = rlt ? ridx : jn;
+                        bool append = true;
+                        if constexpr (V2) {  // livenote_v2.py:198
+                            const int xs = __builtin_amdgcn_readfirstlane(x), ys = __builtin_amdgcn_readfirstlane(y);
+                            append = (k.n_path == 0) || (xs > k.last_x && ys >= k.last_y);
+                            if (append) {
+                                k.last_x = xs;
+                                k.last_y = ys;
+                            }
+                        }
+                        if (append) {
+                            if (k.n_path < e.path_cap) {
+                                path_row[k.n_path] = make_int2(x, y);
+                            } else {
+                                k.truncated = 1;
+                            }
+                            k.n_path += 1;
+                        }
+                        int nd = __builtin_amdgcn_readfirstlane((x < pt) ? RTS_DIR_COLUMN : (y < jn) ? RTS_DIR_ROW : RTS_DIR_BOTH);
+                        if (pt < c)
+                            nd = RTS_DIR_BOTH;
+                        else if (k.run_count >= e.max_run_count)
+                            nd = (k.prev == RTS_DIR_ROW) ? RTS_DIR_COLUMN : RTS_DIR_ROW;
+                        if constexpr (DEFER) {
+                            k.pend_dir = nd;
+                        } else {
+                            k.run_count = (nd == k.prev) ? k.run_count + 1 : 1;
+                            if (nd != RTS_DIR_BOTH) k.prev = nd;
+                        }
+                        k.dir = nd;
+                        k.pending_col = (nd == RTS_DIR_COLUMN);
+                        k.t = pt;
+                        k.j = jn;
+                        RTS_STAMP(4);
+                        k.spec_valid = 1;
+                        pl = otw_make_plan<W, RT>(S, k, e, true, sp ^ 1, true);
+                        RTS_STAMP(5);
+                        RTS_W0_STEP_END(stamp_kind);
+                        sp ^= 1;
+                    };
                     if (is_both) {
+                        const int jn = j0 + 1;
+                        double rmin, cmin, cl;
+                        int ridx, cidx;
                         // settle (otw_settle_hit_both): the two strips' last cells a = (pt, j0) and b = (pt-1, jn) and the
                         // corner (pt, jn).  Nothing is written -- no LDS word, no control state -- before the step is known
                         // to be a hit whose two argmins lie inside the step's windows; otherwise the general loop runs it
@@ -1615,7 +1693,7 @@ otw_advance_kernel(OtwArgs a) {
                             }
                         }
                         cl = cl_both;
-                        if (lane == 0) {
+                        {  // (every lane stores: see above the loop)
                             R[swz<W>(j0)] = av;
                             C[swz<W>(t0)] = bv;
                             R[swz<W>(jn)] = cl;
@@ -1634,7 +1712,9 @@ otw_advance_kernel(OtwArgs a) {
                         k.cL = av;
                         k.cA = cl;
                         RTS_STAMP(3);
+                        decide_plan(rmin, cmin, ridx, cidx, cl, jn, hit_if ? 1 : 0, hit_if ? 2 : 1);
                     } else {
+                        const int jn = is_row ? j0 : j0 + 1;
                         // the band this step does not recompute keeps its minimum only while that stays inside the window
                         const int keep_lo = is_row ? pt - c + 1 : jn - c + 1;
                         const int keep_idx = __builtin_amdgcn_readfirstlane(is_row ? k.cb_idx : k.rb_idx);
@@ -1659,14 +1739,14 @@ otw_advance_kernel(OtwArgs a) {
                         }
                         const double prev_raw = band[swz<W>(pos - (n > 0 ? 1 : 0))];
                         const double d = ex->d, lm = ex->pmin[lane];
-                        const int ml = ex->pidx[lane], sk1 = ex->k1;
-                        double smin;
+                        const int ml = ex->pidx[lane];
+                        double smin, cl;
                         int sidx;
-                        otw_spec_argmin<W>(lm, ml, __builtin_amdgcn_readfirstlane(sk1), smin, sidx);
+                        otw_spec_argmin<W>(lm, ml, k1, smin, sidx);  // the shadow strip starts at the step's own k1
                         const double prev = (n > 0) ? prev_raw : ((k1 > 0) ? sentinel : inf);
                         const double diag = (pos > 0) ? (is_row ? k.cL : k.cU) + 2 * d : inf;
                         cl = vmin(vmin(k.cA + d, diag), prev + d);
-                        if (lane == 0) {
+                        {
                             band[swz<W>(pos)] = cl;
                             other[swz<W>(is_row ? pt : jn)] = cl;  // column j0 gains row pt / row pt gains column jn
                         }
@@ -1685,65 +1765,9 @@ otw_advance_kernel(OtwArgs a) {
                         RTS_STAMP(3);
                         // decide (otw_decide): the strip's band brings the speculated argmin, the other band keeps its
                         // minimum
-                        rmin = is_row ? smin : k.rb_min, cmin = is_row ? k.cb_min : smin;
-                        ridx = is_row ? sidx : k.rb_idx, cidx = is_row ? k.cb_idx : sidx;
+                        decide_plan(is_row ? smin : k.rb_min, is_row ? k.cb_min : smin, is_row ? sidx : k.rb_idx,
+                                    is_row ? k.cb_idx : sidx, cl, jn, 0, 0);
                     }
-                    // a "hit if" step that was resolved to a hit: both shadows have become bands.  (Here, on the common path and
-                    // without a branch: k.ri / k.ci live in VGPRs, and a flip inside the Both branch cost three more copies of
-                    // the pair -- six registers, which put the kernel over the 128 that two workgroups per CU allow.)
-                    const int flip = (is_both && hit_if) ? 1 : 0;
-                    k.ri ^= flip;
-                    k.ci ^= flip;
-                    // both bands gain `cl` at their top index (it wins only if strictly smaller)
-                    const bool r_new = cl < rmin, c_new = cl < cmin;
-                    rmin = r_new ? cl : rmin;
-                    ridx = r_new ? jn : ridx;
-                    cmin = c_new ? cl : cmin;
-                    cidx = c_new ? pt : cidx;
-                    k.rb_min = rmin;
-                    k.rb_idx = ridx;
-                    k.cb_min = cmin;
-                    k.cb_idx = cidx;
-                    const bool rlt = rmin < cmin;
-                    const int x = rlt ? pt : cidx, y = rlt ? ridx : jn;
-                    bool append = true;
-                    if constexpr (V2) {  // livenote_v2.py:198
-                        const int xs = __builtin_amdgcn_readfirstlane(x), ys = __builtin_amdgcn_readfirstlane(y);
-                        append = (k.n_path == 0) || (xs > k.last_x && ys >= k.last_y);
-                        if (append) {
-                            k.last_x = xs;
-                            k.last_y = ys;
-                        }
-                    }
-                    if (append) {
-                        if (k.n_path < e.path_cap) {
-                            if (lane == 0) path_row[k.n_path] = make_int2(x, y);
-                        } else {
-                            k.truncated = 1;
-                        }
-                        k.n_path += 1;
-                    }
-                    int nd = __builtin_amdgcn_readfirstlane((x < pt) ? RTS_DIR_COLUMN : (y < jn) ? RTS_DIR_ROW : RTS_DIR_BOTH);
-                    if (pt < c)
-                        nd = RTS_DIR_BOTH;
-                    else if (k.run_count >= e.max_run_count)
-                        nd = (k.prev == RTS_DIR_ROW) ? RTS_DIR_COLUMN : RTS_DIR_ROW;
-                    if constexpr (DEFER) {
-                        k.pend_dir = nd;
-                    } else {
-                        k.run_count = (nd == k.prev) ? k.run_count + 1 : 1;
-                        if (nd != RTS_DIR_BOTH) k.prev = nd;
-                    }
-                    k.dir = nd;
-                    k.pending_col = (nd == RTS_DIR_COLUMN);
-                    k.t = pt;
-                    k.j = jn;
-                    RTS_STAMP(4);
-                    k.spec_valid = 1;
-                    pl = otw_make_plan<W, RT>(S, k, e, true, sp ^ 1);
-                    RTS_STAMP(5);
-                    RTS_W0_STEP_END(is_both ? (hit_if ? 2 : 1) : 0);
-                    sp ^= 1;
                 }
             };
             for (;;) {
