@@ -1269,6 +1269,94 @@ int rts_live_follow_consensus(rts_live *h, rts_ensemble *e /* NULL: off */);
 int rts_live_consensus(rts_live *h, double *consensus, double *spread, int32_t *n_in, int32_t *n_valid /* [n_groups] */,
                        double *dev, int32_t *strikes, int32_t *out /* [B] */, int *feeds_done);
 
+/* ------------------------------------------------------------------------------------------
+ * Render: one recording on another's time axis, along an alignment path.
+ * ------------------------------------------------------------------------------------------ */
+/* The reference stops at the path (its harness takes error statistics of it, tests.py:59-137); nothing in it plays a
+ * recording along one, so no reference interface is replaced here.  This is time-scale modification by waveform-similarity overlap-add (WSOLA; Verhelst and Roelands,
+ * ICASSP 1993) along a piecewise-linear integer time map, defined by this project to the bit like the resampler above.
+ *
+ * Plan.  Frames of N samples (N % 16 == 0, 64 <= N <= 4096) at a hop of H = N / 2, a search tolerance of delta samples
+ * (0 <= delta <= 1024) and a window w[0 .. N) of host doubles (filters.hann_window_periodic(N): w[m] + w[m + H] = 1, so
+ * the identity map gives the input back).  Input samples x[n] are float32, or PCM16 scaled by 1/32768 exactly as
+ * rts_resample_run scales it; x[n] = 0 for n < 0 and for n >= n_in.
+ *
+ * Time map of a stream: A >= 2 anchors (out_pos[s], in_pos[s]), int64 pairs, out_pos[0] = 0, out_pos strictly increasing,
+ * in_pos not decreasing, every segment shorter than 2^31 on both axes and every position below 2^62 in magnitude.  Block k
+ * begins at output position t = k H; with s the last anchor with out_pos[s] <= t, at most A - 2,
+ *   a_k = in_pos[s] + floor((t - out_pos[s]) * (in_pos[s+1] - in_pos[s]) / (out_pos[s+1] - out_pos[s]))
+ * in exact 64-bit integer arithmetic.  (A block that begins at or behind the last anchor continues the last segment; n_out
+ * may then lie at most 2^31 behind out_pos[A-2].)
+ *
+ * Frame positions.  p_0 = a_0.  For k >= 1 the frame is sought near a_k so that it continues the frame before it: with the
+ * target x[p_{k-1} + H + n], n = 0 .. N-1, candidate delta in [-delta, delta] scores
+ *   c(delta) = ((s_0 + s_1) + (s_2 + s_3)) + ((s_4 + s_5) + (s_6 + s_7))
+ *   s_r      = sum over q = 0 .. N/8 - 1, q ascending, from 0.0, of (double)x[a_k + delta + 8 q + r] * (double)x[p_{k-1} + H + 8 q + r]
+ * (the products are exact in float64, every add rounds once).  The winner is the first maximum in the order delta = 0,
+ * -delta, -delta + 1, .., delta: a candidate replaces the best so far only when it is strictly greater, so a NaN score never
+ * wins, a NaN score at 0 keeps 0, and digital silence gives 0.  p_k = a_k + the winner.
+ *
+ * Output, block k, m = 0 .. H-1:
+ *   y[k H + m] = (float)( w[m + H] * (double)x[p_{k-1} + H + m]  +  w[m] * (double)x[p_k + m] )
+ * each product one float64 multiply, one float64 add of the two (the earlier frame's product first, no fused multiply-add),
+ * one rounding to float32.  Block 0 has the single term (float)(w[m] * (double)x[p_0 + m]).  rts_warp_blocks(n_out, N) =
+ * ceil(n_out / H) blocks exist; samples at or behind n_out are not written.
+ *
+ * State of a stream: (k, p_{k-1}), two int64, zeros before the first block.  Nothing else is carried: rendering blocks
+ * [0, k1) and then [k1, K) gives the bits of one run. */
+typedef struct rts_warp rts_warp;
+
+/* per-stream status words: rts_warp_anchors writes the first six (a sum of them), rts_warp_run the last three */
+#define RTS_WARP_PATH_EMPTY 1      /* path_len < 1 */
+#define RTS_WARP_PATH_START 2      /* the path does not begin at u = 0 */
+#define RTS_WARP_PATH_BACKWARD 4   /* u or v steps backwards (or v begins below 0) */
+#define RTS_WARP_PATH_SHORT_OUT 8  /* n_out <= the last u * hop_f */
+#define RTS_WARP_PATH_SHORT_IN 16  /* n_in < the last v * hop_f */
+#define RTS_WARP_PATH_TOO_MANY 32  /* more anchors than A_max */
+#define RTS_WARP_NO_MAP 64         /* n_anchor outside [2, A_max]: rts_warp_anchors refused the path */
+#define RTS_WARP_BAD_MAP 128       /* the anchors break a rule of the time map */
+#define RTS_WARP_BAD_STATE 256     /* n_out < 0 or >= 2^62, k < 0 or > rts_warp_blocks(n_out), |p| >= 2^62 */
+
+/* ceil(n_out / (N / 2)); 0 for n_out <= 0; -1 for an N that rts_warp_create does not take.  Pure host arithmetic. */
+long long rts_warp_blocks(long long n_out, int N);
+/* The plan: the window on the current device, to which the plan then belongs.  window_host: N doubles.
+ * RTS_ERR_INVALID, naming the argument, before any GPU call: NULL out or window_host, N odd or < 2, delta < 0.
+ * RTS_ERR_UNSUPPORTED: N not a multiple of 16 or outside [64, 4096] (48 and 4112 are refused), delta > 1024. */
+int rts_warp_create(int N, int delta, const double *window_host, rts_warp **out);
+int rts_warp_destroy(rts_warp *plan);
+/* Time maps from monotone paths, on the device: path_dev int32 [B][P_max][2] and path_len_dev int32 [B] as rts_dtw_paths
+ * writes them (a length above P_max is clamped to it).  With u = path[t][onto], v = path[t][1 - onto] -- `onto` in {0, 1}
+ * is the column whose time axis the output gets -- every t with t == 0 or u_t != u_{t-1} gives the anchor (u_t * hop_f,
+ * v_t * hop_f), hop_f the samples per feature frame; the closing anchor (n_out_dev[b], n_in_dev[b]) (int64 [B] each, the
+ * output and input sample counts) follows.  anchors_dev int64 [B][A_max][2], n_anchor_dev int32 [B], status_dev int32 [B].
+ * A stream with any of path_len < 1, u_0 != 0, a step backwards in u or v, n_out <= the last u * hop_f, n_in < the last
+ * v * hop_f or more than A_max anchors gets the sum of the RTS_WARP_PATH_* words as its status and n_anchor 0 (its row of
+ * anchors_dev is then undefined within its A_max entries); every other stream status 0.  One workgroup per path: flags, a
+ * workgroup prefix sum, a scatter.  Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable).
+ *   RTS_ERR_INVALID, naming the argument, before any GPU call: a NULL pointer (path_dev may be NULL when P_max == 0),
+ *   P_max < 0, onto outside {0, 1}, hop_f < 1, B outside [1, 65535], A_max < 2. */
+int rts_warp_anchors(const int32_t *path_dev, int P_max, const int32_t *path_len_dev, int onto, int hop_f,
+                     const long long *n_out_dev, const long long *n_in_dev, int B, long long *anchors_dev, int A_max,
+                     int32_t *n_anchor_dev, int32_t *status_dev, void *stream);
+/* Renders up to k_count further blocks of each of B streams, beginning at the stream's own k = state_dev[b][0]:
+ * samples_dev is [B][sample_stride] of sample_dtype (RTS_F32 | RTS_I16) with n_in_dev[b] (int64) samples in stream b,
+ * anchors_dev / n_anchor_dev / A_max as rts_warp_anchors leaves them (or made by the caller), n_out_dev int64 [B].  Block k
+ * is written to out_dev[b][(k - k_start) * H ..], k_start the stream's k when the call began -- relative to the call, so
+ * that a caller streams into a chunk buffer of k_count * H samples per stream however far the stream has come; out_dev
+ * float32 [B][out_stride].  Rows that begin on a 16-byte boundary are written with 16-byte stores.  state_dev int64 [B][2]
+ * moves on to (min(k + k_count, K), p of the last block rendered).  A stream whose n_anchor is outside [2, A_max], whose
+ * anchors break a rule of the map, or whose state is impossible gets RTS_WARP_NO_MAP / RTS_WARP_BAD_MAP /
+ * RTS_WARP_BAD_STATE in status_dev[b]: nothing is written for it and its state stays; every other stream status 0.  One
+ * workgroup per stream walks its blocks in order.  Asynchronous on `stream`; no allocation, no synchronisation
+ * (graph-capturable).
+ *   RTS_ERR_INVALID, naming the argument, before any GPU call: a NULL plan or pointer (out_dev may be NULL when k_count ==
+ *   0), sample_dtype, sample_stride < 0, A_max < 2, k_count < 0, out_stride < 0, B outside [1, 65535], a plan of another
+ *   device. */
+int rts_warp_run(rts_warp *plan, const void *samples_dev, int sample_dtype, long long sample_stride,
+                 const long long *n_in_dev, const long long *anchors_dev, const int32_t *n_anchor_dev, int A_max,
+                 const long long *n_out_dev, long long *state_dev /* [B][2]: k, p_prev */, long long k_count,
+                 float *out_dev, long long out_stride, int32_t *status_dev, int B, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,4 +20,10 @@ def __getattr__(name):
     if name == "locate":
         import importlib
         return importlib.import_module(".locate", __name__)
+    if name == "warp_pairs":
+        from .render import warp_pairs
+        return warp_pairs
+    if name == "render":
+        import importlib
+        return importlib.import_module(".render", __name__)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -205,6 +205,15 @@ _decl("rts_path_consensus", _i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp
 _decl("rts_live_follow_consensus", _i32, [_vp, _vp])
 _decl("rts_live_consensus", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi32])
 
+WARP_MIN_N, WARP_MAX_N, WARP_MAX_DELTA = 64, 4096, 1024  # kWarpMinN, kWarpMaxN, kWarpMaxDelta (csrc/warp_plan.h)
+(WARP_PATH_EMPTY, WARP_PATH_START, WARP_PATH_BACKWARD, WARP_PATH_SHORT_OUT, WARP_PATH_SHORT_IN, WARP_PATH_TOO_MANY,
+ WARP_NO_MAP, WARP_BAD_MAP, WARP_BAD_STATE) = (1 << i for i in range(9))
+_decl("rts_warp_blocks", _i64, [_i64, _i32])
+_decl("rts_warp_create", _i32, [_i32, _i32, _vp, ctypes.POINTER(_vp)])
+_decl("rts_warp_destroy", _i32, [_vp])
+_decl("rts_warp_anchors", _i32, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp])
+_decl("rts_warp_run", _i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp])
+
 
 def check(rc):
     if rc != 0:

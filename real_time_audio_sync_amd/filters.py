@@ -55,6 +55,12 @@ def hann_window(n):
     return np.hanning(n).astype(np.float64)
 
 
+def hann_window_periodic(n):
+    """The periodic Hann window, 0.5 - 0.5 cos(2 pi m / n): its two halves sum to one at a hop of n / 2, which the
+    symmetric form above does not, so overlap-add of unmoved frames gives the input back (render.WarpPlan's default)."""
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(int(n), dtype=np.float64) / int(n))
+
+
 def resample_ratio(fs_in, fs_out=22050):
     """(L, M) with L / M = fs_out / fs_in, reduced by the gcd: 44 100 -> 22 050 is (1, 2), 48 000 -> 22 050 (147, 320)."""
     fs_in, fs_out = int(fs_in), int(fs_out)
