@@ -1357,6 +1357,115 @@ int rts_warp_run(rts_warp *plan, const void *samples_dev, int sample_dtype, long
                  const long long *n_out_dev, long long *state_dev /* [B][2]: k, p_prev */, long long k_count,
                  float *out_dev, long long out_stride, int32_t *status_dev, int B, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Live accompaniment: a track rendered along every tracker, feed by feed.
+ * ------------------------------------------------------------------------------------------ */
+/* Playing a track so that it follows the musician at the microphone is what a score follower is for.  With it on, every
+ * rts_live_submit turns the tail of each armed stream's path into the next anchor of that stream's time map (the steering
+ * law below) and renders the blocks that have become due with rts_warp_run, in the feed's own chain, into host-mapped
+ * memory: nothing is read back and nothing synchronises.  The reference has nothing of the kind; the law is this
+ * project's, to the bit (tests/accomp_model.py restates it).
+ *
+ * Parameters of a session (rts_accomp_params, with the two plans):
+ *   N, H = N / 2    the warp plan's frame and hop; `hop`: the chroma plan's hop, microphone samples per live frame
+ *   hop_track       track samples per reference frame, 1 .. 65536
+ *   K               points of the regression window, 2 .. 1024 (the range of rts_otw_tempo)
+ *   glide  G        samples over which a correction is spread, 0 <= G < 2^31
+ *   lead            signed, |lead| < 2^31: what the output path adds between a sample leaving here and sounding, plus the
+ *                   offset between a live index and the microphone sample its frame is centred on
+ *   rate_min_pm, rate_max_pm   limits of the rate in track samples per 1000 output samples at equal hops,
+ *                   0 <= min <= max <= 4000, max >= 1
+ *   chunk_blocks    the most blocks rendered per feed and stream, >= 1
+ *   A_max           anchors per stream, >= 2
+ * The track pool tracks_dev (RTS_F32 | RTS_I16) is one run of samples that stays the caller's, like references; stream b's
+ * track is its samples [first_b, first_b + len_b), and origin_b -- origin_host[b], or 0 -- is the track sample, counted
+ * from first_b, that belongs to reference frame 0 of the range the stream's tracker follows.  All positions of a stream's
+ * map are pool samples: x[n] = 0 for n >= first_b + len_b and for n < 0, and a frame or a search window that reaches in
+ * front of first_b reads the pool there (leave N + delta samples of silence between tracks that must not meet).
+ *
+ * State of stream b on the device: fed (samples the append has taken since the stream was armed), base (-1: waiting), the
+ * renderer's (k, p_prev), the anchors and their count, n_out.  Arming sets fed = 0, base = -1, the state zero, the one
+ * anchor (0, first_b + origin_b), n_out = 0.
+ *
+ * Steering, once per feed and armed stream, behind the tracker's push; every integer exact int64, every float64
+ * operation rounded on its own:
+ *   1. fed_prev = fed; fed += n_b, the samples the feed's append took for the stream.
+ *   2. base < 0: a tracker that has stored no path point leaves the stream waiting -- status WAIT, no block.  Otherwise
+ *      base = fed_prev: output sample t sounds at microphone sample base + t, the clock starting with the feed that
+ *      produced the first point.
+ *   3. k_due = min((fed - base) / H, k + chunk_blocks), LATE when the min cut it.  k_due == k: no block.  Otherwise, with
+ *      A_max anchors stored: status FULL, no block.
+ *   4. (o0, i0) the last anchor (o0 == k H); o1 = k_due H; Ls = o1 - o0.
+ *   5. lo = (Ls hop_track rate_min_pm) / (hop 1000), hi the same with rate_max_pm, nominal = (Ls hop_track) / hop.
+ *   6. slope and pos of the last n = min(K, stored) points as rts_otw_tempo / rts_wtw_tempo define them with ahead = 0 and
+ *      their limits; x_i the newest point's live index.  A NaN slope or slope <= 0: step_raw = nominal, status FREE.
+ *   7. otherwise x1 = (double)(base + o1 + G + lead) / (double)hop;  y1 = pos + slope * (x1 - (double)x_i);
+ *      tgt_f = floor(y1 * (double)hop_track); not finite or |tgt_f| >= 2^52: FREE as above; else
+ *      d = clamp((int64)tgt_f + first_b + origin_b - i0, 0, 2^31 - 1);  step_raw = (d Ls) / (Ls + G).
+ *   8. step = clamp(step_raw, lo, hi), status LO / HI when it clamped;  i1 = min(i0 + step, max(i0, first_b + len_b)),
+ *      status END when that cut it.
+ *   9. the anchor (o1, i1) is appended and n_out = o1: blocks [k, k_due) lie in the last segment.
+ *  10. published: out_total = o1, in_pos = i1, rate = (double)(i1 - i0) / (double)Ls, blocks = k_due - k, the status.
+ *      A feed without a block publishes out_total and in_pos of the last anchor, the rate published last (NaN before the
+ *      first block), blocks 0; a stream that is not armed 0, 0, NaN, 0 and status 0.
+ * The map keeps every rule of rts_warp_run's time map, and the audio is by definition what rts_warp_run renders for those
+ * anchors, k_count = chunk_blocks, block k at sample (k - k_start) H of the stream's row.
+ *
+ * Delivery.  Feed f (counted from 1, the number rts_live_poll reports) renders into chunk f % 4 of a ring of four
+ * host-mapped chunks [B][chunk_blocks H] float32 (rows begin on 32-byte boundaries) and publishes its words into slot f % 4
+ * of a seventh host-mapped block.  When *feeds_done >= f the chunk and the words of feed f are complete; feed f + 4 writes
+ * over them, so a consumer looks at least once in three feeds (out_total tells it when it did not).  Samples of a row
+ * behind blocks H are left from earlier feeds. */
+typedef struct rts_accomp_params {
+    int32_t hop_track, K;
+    long long glide, lead;
+    int32_t rate_min_pm, rate_max_pm, chunk_blocks, A_max;
+} rts_accomp_params;
+
+#define RTS_ACC_ON 1     /* the stream is armed */
+#define RTS_ACC_WAIT 2   /* its tracker has no path point yet: the clock has not started */
+#define RTS_ACC_FREE 4   /* no usable slope: the segment runs at the nominal rate */
+#define RTS_ACC_LO 8     /* the step was raised to the lower rate limit */
+#define RTS_ACC_HI 16    /* the step was cut to the upper rate limit */
+#define RTS_ACC_END 32   /* the anchor was held at the end of the track */
+#define RTS_ACC_FULL 64  /* A_max anchors are stored: nothing more is rendered */
+#define RTS_ACC_LATE 128 /* more than chunk_blocks blocks were due: the rest follows with the next feeds */
+
+/* Arms the streams with mask_host[b] != 0 (again, when they are armed already: from output sample 0), switching the
+ * accompaniment on; a NULL warp_plan switches it off, and the next time it is switched on every stream starts disarmed.
+ * The streams are armed in the chain of the next rts_live_submit, in front of its steering.  The first call with a plan
+ * allocates the per-stream state, the seventh host-mapped block and the ring; a later call with another plan, pool, dtype
+ * or parameters waits for the device, frees them and starts over with every stream disarmed.  The plan and the pool must
+ * outlive their use here.  rts_live_restart disarms the restarted streams (status 0, nothing rendered until they are
+ * armed again), rts_live_reset all streams; rts_live_export / rts_live_import refuse a session with the accompaniment on,
+ * rts_live_gate(min_level > 0) too.  A session that never calls this allocates none of it and enqueues exactly what it
+ * enqueues without this function; with it on a feed enqueues two more launches.
+ *   RTS_ERR_UNSUPPORTED: a session with the level gate on or with a resampler (live indices are not microphone time there);
+ *   chunk_blocks H >= 2^31 or (chunk_blocks H hop_track rate_max_pm) / (hop 1000) >= 2^31 (a segment of the map could
+ *   reach 2^31); the overflow rule of rts_otw_tempo for K.
+ *   RTS_ERR_INVALID: NULL handle, a failed handle, NULL tracks_dev, mask_host, first_host, len_host or params, track_dtype,
+ *   every parameter limit above, a masked stream with first or len < 0 or a position at or beyond 2^61, more than 65535
+ *   streams, a plan of another device, another device current. */
+int rts_live_accompany(rts_live *h, rts_warp *warp_plan, const void *tracks_dev, int track_dtype /* RTS_F32 | RTS_I16 */,
+                       const uint8_t *mask_host /* [B] */, const long long *first_host /* [B] */,
+                       const long long *len_host /* [B] */, const long long *origin_host /* [B] or NULL */,
+                       const rts_accomp_params *params);
+/* The non-blocking look, like rts_live_tempo and with its guarantee: *feeds_done = f is the newest feed every stream has
+ * published, *chunk_host the chunk of feed f ([B] rows *row_stride samples apart, stream b's audio its first blocks[b] * H
+ * samples) and the [B] words those of feed f.  A stream whose slot holds another feed's words -- the accompaniment was off
+ * in feed f, or four more feeds have been submitted -- reads blocks 0, status 0, rate NaN.  warp_status: what rts_warp_run
+ * left for the stream (RTS_WARP_NO_MAP while it has fewer than two anchors).  Any output pointer may be NULL.
+ *   RTS_ERR_INVALID: NULL handle; before the first rts_live_accompany with a plan. */
+int rts_live_accompaniment(rts_live *h, const float **chunk_host, long long *row_stride, int32_t *blocks /* [B] */,
+                           long long *out_total /* [B] */, long long *in_pos /* [B] */, double *rate /* [B] */,
+                           int32_t *status /* [B] */, int32_t *warp_status /* [B] */, int *feeds_done);
+/* For tests and tools, like rts_otw_read_path: waits for `stream`, then *n = the anchors stream b has stored, the first
+ * min(*n, cap) of them as (out_pos, in_pos) pairs in anchors_host (may be NULL) and the renderer's (k, p_prev) in state
+ * (may be NULL).
+ *   RTS_ERR_INVALID: NULL handle or n, b outside [0, B), cap < 0, before the first rts_live_accompany with a plan, another
+ *   device current. */
+int rts_live_accomp_map(rts_live *h, int b, long long *anchors_host, int cap, int *n, long long state[2], void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,20 @@ _decl("rts_warp_anchors", _i32, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp
 _decl("rts_warp_run", _i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp])
 
 
+class AccompParams(ctypes.Structure):
+    """rts_accomp_params."""
+    _fields_ = [("hop_track", ctypes.c_int32), ("K", ctypes.c_int32), ("glide", ctypes.c_longlong), ("lead", ctypes.c_longlong),
+                ("rate_min_pm", ctypes.c_int32), ("rate_max_pm", ctypes.c_int32), ("chunk_blocks", ctypes.c_int32),
+                ("A_max", ctypes.c_int32)]
+
+
+(ACC_ON, ACC_WAIT, ACC_FREE, ACC_LO, ACC_HI, ACC_END, ACC_FULL, ACC_LATE) = (1 << i for i in range(8))  # RTS_ACC_*
+ACC_SLOTS = 4  # chunks in the ring of rts_live_accompaniment
+_decl("rts_live_accompany", _i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(AccompParams)])
+_decl("rts_live_accompaniment", _i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _pi32])
+_decl("rts_live_accomp_map", _i32, [_vp, _i32, _vp, _i32, _pi32, _vp, _vp])
+
+
 def check(rc):
     if rc != 0:
         raise RtsyncError("rtsync error %d: %s" % (rc, lib.rts_last_error().decode("utf-8", "replace")))

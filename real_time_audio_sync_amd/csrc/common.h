@@ -163,6 +163,38 @@ __attribute__((visibility("hidden"))) int ensemble_fuse_enqueue(rts_ensemble *e,
                                                                 const int32_t *piece, const int32_t *frame0,
                                                                 const EnsembleOut &o, hipStream_t s);
 
+// The live accompaniment as the live handle drives it (csrc/accomp.hip; include/rtsync.h, rts_live_accompany, has the law).
+// accomp_check: every parameter refusal, and the geometry (the plan's hop, the chroma plan's `hop`) on success.
+// accomp_create: the per-stream device state, the seventh host-mapped block and the ring of chunks, every stream disarmed.
+// accomp_arm notes the masked streams, which the next accomp_enqueue arms in its feed's chain; accomp_off drops what was
+// noted and has the next accomp_enqueue disarm every stream first.  accomp_enqueue: the steering launch and one
+// rts_warp_run into slot feed_no % 4 of the ring, `view` as otw_tempo_view / wtw_tempo_view fill it, n_samples / pending the
+// live handle's own [B] words between its append and its compaction.  accomp_look reads slot feed % 4 of both host-mapped
+// blocks; accomp_map synchronises.
+struct Accomp;
+struct AccompGeom;
+__attribute__((visibility("hidden"))) int accomp_check(const rts_accomp_params *q, const rts_warp *plan, int hop, int device,
+                                                       AccompGeom *out);
+__attribute__((visibility("hidden"))) bool accomp_same(const Accomp *a, const AccompGeom &p, const rts_warp *plan,
+                                                       const void *tracks, int dtype);
+__attribute__((visibility("hidden"))) int accomp_create(const AccompGeom &p, rts_warp *plan, const void *tracks, int dtype, int B,
+                                                        int device, Accomp **out);
+__attribute__((visibility("hidden"))) void accomp_destroy(Accomp *a);
+__attribute__((visibility("hidden"))) int accomp_tracks_check(int B, const uint8_t *mask, const long long *first,
+                                                              const long long *len, const long long *origin);
+__attribute__((visibility("hidden"))) void accomp_arm(Accomp *a, const uint8_t *mask, const long long *first, const long long *len,
+                                                      const long long *origin);
+__attribute__((visibility("hidden"))) void accomp_off(Accomp *a);
+__attribute__((visibility("hidden"))) int accomp_restart(Accomp *a, const RestartSel &sel, hipStream_t s);
+__attribute__((visibility("hidden"))) int accomp_reset(Accomp *a, hipStream_t s);
+__attribute__((visibility("hidden"))) int accomp_enqueue(Accomp *a, const TempoTail &view, const int32_t *n_samples,
+                                                         const int32_t *pending, int feed_no, hipStream_t s);
+__attribute__((visibility("hidden"))) void accomp_look(const Accomp *a, int feed, const float **chunk_host, long long *row_stride,
+                                                       int32_t *blocks, long long *out_total, long long *in_pos, double *rate,
+                                                       int32_t *status, int32_t *warp_status);
+__attribute__((visibility("hidden"))) int accomp_map(const Accomp *a, int b, long long *anchors_host, int cap, int *n,
+                                                     long long state[2], hipStream_t s);
+
 // rts_otw_import / rts_wtw_import with `dry` != 0: every check is made and status_dev is written, nothing else -- neither
 // on the device nor in the handle.  rts_live_import asks this way first, so that a refused record leaves the session as
 // it was.  dry == 0 is the public call.

@@ -38,6 +38,10 @@
 //   ensemble_fuse_kernel  only after rts_live_follow_consensus with an ensemble and while annotations are on (csrc/ensemble.hip):
 //                         the median beat of every group of streams, each member's deviation, strikes and out into a sixth
 //                         host-mapped block -- rts_live_consensus reads it
+//   accomp_steer_kernel, rts_warp_run   only after rts_live_accompany with a plan (csrc/accomp.hip): the next anchor of every
+//                         armed stream's time map from the tail of its tracker's path, and the blocks that made due rendered
+//                         into this feed's chunk of a host-mapped ring, their words into a seventh host-mapped block --
+//                         rts_live_accompaniment reads both
 //   live_compact_kernel   drop hop * n_frames consumed samples per stream (data = data[2048:], livenote_live.py:208),
 //                         and publish {status, live position, ref position, feed number} of every stream into
 //                         host-mapped memory -- rts_live_poll reads those words without touching the stream.
@@ -50,6 +54,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "accomp_plan.h"
 #include "common.h"
 #include "live_plan.h"
 
@@ -293,6 +298,10 @@ struct rts_live {
     int ens_groups;
     unsigned char *ens_host;
     rts::EnsembleOut ens_out;  // the block as the device sees it
+    // rts_live_accompany: on / off, and everything it owns (csrc/accomp.hip), made by the first call with a plan: the streams'
+    // steering state on the device, the seventh host-mapped block and the ring of chunks
+    int acc_on;
+    rts::Accomp *acc;
 };
 
 namespace rts {
@@ -368,6 +377,15 @@ static int live_ens_launch(rts_live *h, hipStream_t s) {
     return ensemble_fuse_enqueue(h->ens, h->annot, view, h->ann_tables, h->ann_tables + h->geo.B, h->ens_out, s);
 }
 
+// With accompaniment on, behind the consensus launch and before live_compact_kernel, for the same reason: the steering launch
+// and one rts_warp_run (and, in the first feed after streams were armed, the launch that arms them).
+static int live_accomp_launch(rts_live *h, int feed_no, hipStream_t s) {
+    if (!h->acc_on) return RTS_OK;
+    TempoTail view = {};
+    (void)(h->otw ? otw_tempo_view(h->otw, &view) : wtw_tempo_view(h->wtw, &view));
+    return accomp_enqueue(h->acc, view, h->args.n_samples, h->args.pending, feed_no, s);
+}
+
 static void live_gate_clear(rts_live *h) {
     double *level = reinterpret_cast<double *>(h->gate_host);
     for (int b = 0; b < h->geo.B; b++) level[b] = __builtin_nan("");
@@ -406,7 +424,8 @@ static int live_refuse(const rts_live *h, LiveRefusal why, const FeedPlan &p, co
 // mode the tracker is pushed only when some stream hands it a column (n_max_diff > 0; the rows still lie n_max apart);
 // the watch launch follows rts_live_watch, the two gate launches rts_live_gate: with the gate on the push takes the gated
 // buffer and its counts, and nothing else moves; the beat launch follows rts_live_annotate, the tempo launch
-// rts_live_follow_tempo, the consensus launch rts_live_follow_consensus.  The compaction and the publication end every feed.
+// rts_live_follow_tempo, the consensus launch rts_live_follow_consensus, the steering launch and the rendering
+// rts_live_accompany.  The compaction and the publication end every feed.
 static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, void *stream) {
     const int B = h->geo.B;
     hipStream_t s = (hipStream_t)stream;
@@ -457,6 +476,7 @@ static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, 
     if (int rc = live_annot_launch(h, s); rc != RTS_OK) return rc;
     if (int rc = live_tempo_launch(h, s); rc != RTS_OK) return rc;
     if (int rc = live_ens_launch(h, s); rc != RTS_OK) return rc;
+    if (int rc = live_accomp_launch(h, g.feed_no, s); rc != RTS_OK) return rc;
     hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -520,6 +540,7 @@ int rts_live_destroy(rts_live *h) {
     if (h->ann_host) (void)hipHostFree(h->ann_host);
     if (h->tempo_host) (void)hipHostFree(h->tempo_host);
     if (h->ens_host) (void)hipHostFree(h->ens_host);
+    accomp_destroy(h->acc);
     free(h);  // the mirrors with it
     return RTS_OK;
 }
@@ -676,6 +697,9 @@ int rts_live_reset(rts_live *h, void *stream) {
         if (int rc = rts_ensemble_reset(h->ens, nullptr, stream); rc != RTS_OK) return rc;
     }
     if (h->ens_host) live_ens_clear(h);
+    if (h->acc) {  // every stream disarmed; on / off stays
+        if (int rc = accomp_reset(h->acc, (hipStream_t)stream); rc != RTS_OK) return rc;
+    }
     memset(h->used, 0, sizeof(h->used));
     h->slot = -1;
     h->feeds = 0;
@@ -703,6 +727,9 @@ int rts_live_restart(rts_live *h, const uint8_t *mask_host, const long long *fir
         if (h->rs) {
             if (int rc = resample_live_restart_enqueue(h->rs, sel, h->geo.B, h->rs_tail, h->rs_tot, (hipStream_t)stream); rc != RTS_OK)
                 return rc;
+        }
+        if (h->acc) {  // a restarted stream is disarmed until rts_live_accompany arms it again
+            if (int rc = accomp_restart(h->acc, sel, (hipStream_t)stream); rc != RTS_OK) return rc;
         }
     }
     for (int b = 0; b < h->geo.B; b++)
@@ -1034,6 +1061,8 @@ int rts_live_gate(rts_live *h, double min_level, int hold) {
     if (!(min_level >= 0.0) || min_level > 1.7976931348623157e308)
         return set_error(RTS_ERR_INVALID, "min_level must be a finite mean square >= 0 (0 = gate off)");
     if (hold < 0 || hold > kGateMaxHold) return set_error(RTS_ERR_INVALID, "hold must be in [0, %d] (got %d)", kGateMaxHold, hold);
+    if (min_level > 0.0 && h->acc_on)
+        return set_error(RTS_ERR_UNSUPPORTED, "rts_live_gate with the accompaniment on: with a gate live indices are not microphone time");
     if (h->feeds != 0)
         return set_error(RTS_ERR_INVALID, "rts_live_gate after %d feeds: the gate is set before the first feed after create or "
                                           "rts_live_reset, so that every ordinal counts from a closed stream", h->feeds);
@@ -1129,6 +1158,70 @@ int rts_live_pending(rts_live *h, long long *pending_host /* [B] */) {
     if (!h || !pending_host) return set_error(RTS_ERR_INVALID, "NULL argument");
     memcpy(pending_host, h->cur.pending, sizeof(long long) * (size_t)h->geo.B);
     return RTS_OK;
+}
+
+int rts_live_accompany(rts_live *h, rts_warp *warp_plan, const void *tracks_dev, int track_dtype, const uint8_t *mask_host,
+                       const long long *first_host, const long long *len_host, const long long *origin_host,
+                       const rts_accomp_params *params) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!warp_plan) {  // off: the words and chunks stay as they are
+        h->acc_on = 0;
+        if (h->acc) accomp_off(h->acc);
+        return RTS_OK;
+    }
+    if (int rc = live_usable(h); rc != RTS_OK) return rc;
+    if (h->gate_on)
+        return set_error(RTS_ERR_UNSUPPORTED, "rts_live_accompany with the level gate on: live indices count the columns the "
+                                              "tracker received, not microphone time");
+    if (h->rs)
+        return set_error(RTS_ERR_UNSUPPORTED, "rts_live_accompany on a session that resamples its input: live indices are not "
+                                              "in samples of the microphones' clock");
+    if (!tracks_dev) return set_error(RTS_ERR_INVALID, "tracks_dev is NULL");
+    if (track_dtype != RTS_F32 && track_dtype != RTS_I16) return set_error(RTS_ERR_INVALID, "track_dtype must be RTS_F32 or RTS_I16");
+    if (!mask_host || !first_host || !len_host) return set_error(RTS_ERR_INVALID, "mask_host, first_host and len_host must be given");
+    if (h->geo.B > 65535) return set_error(RTS_ERR_INVALID, "B = %d: the renderer takes at most 65535 streams", h->geo.B);
+    AccompGeom p;
+    if (int rc = accomp_check(params, warp_plan, h->geo.hop, h->device, &p); rc != RTS_OK) return rc;
+    TempoTail view = {};
+    const int N_max = h->otw ? otw_tempo_view(h->otw, &view) : wtw_tempo_view(h->wtw, &view);
+    if (int rc = tempo_tail_check(p.K, 0.0, N_max); rc != RTS_OK) return rc;
+    if (int rc = accomp_tracks_check(h->geo.B, mask_host, first_host, len_host, origin_host); rc != RTS_OK) return rc;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    if (h->acc && !accomp_same(h->acc, p, warp_plan, tracks_dev, track_dtype)) {
+        // another plan, pool or law: everything is rebuilt once the device has finished with what there is
+        h->acc_on = 0;
+        RTS_HIP(hipDeviceSynchronize());
+        accomp_destroy(h->acc);
+        h->acc = nullptr;
+    }
+    if (!h->acc) {
+        if (int rc = accomp_create(p, warp_plan, tracks_dev, track_dtype, h->geo.B, h->device, &h->acc); rc != RTS_OK) return rc;
+    }
+    accomp_arm(h->acc, mask_host, first_host, len_host, origin_host);
+    h->acc_on = 1;
+    return RTS_OK;
+}
+
+int rts_live_accompaniment(rts_live *h, const float **chunk_host, long long *row_stride, int32_t *blocks, long long *out_total,
+                           long long *in_pos, double *rate, int32_t *status, int32_t *warp_status, int *feeds_done) {
+    using namespace rts;
+    if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
+    if (!h->acc) return set_error(RTS_ERR_INVALID, "rts_live_accompaniment before any rts_live_accompany with a plan");
+    const int fd = live_read_published(h, [](int) {});
+    accomp_look(h->acc, fd, chunk_host, row_stride, blocks, out_total, in_pos, rate, status, warp_status);
+    if (feeds_done) *feeds_done = fd;
+    return RTS_OK;
+}
+
+int rts_live_accomp_map(rts_live *h, int b, long long *anchors_host, int cap, int *n, long long state[2], void *stream) {
+    using namespace rts;
+    if (!h || !n) return set_error(RTS_ERR_INVALID, "NULL argument");
+    if (!h->acc) return set_error(RTS_ERR_INVALID, "rts_live_accomp_map before any rts_live_accompany with a plan");
+    if (b < 0 || b >= h->geo.B) return set_error(RTS_ERR_INVALID, "stream %d out of range [0, %d)", b, h->geo.B);
+    if (cap < 0) return set_error(RTS_ERR_INVALID, "cap must be >= 0");
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    return accomp_map(h->acc, b, anchors_host, cap, n, state, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -116,6 +116,8 @@ static int live_snap_usable(const rts_live *h, const char *what) {
         return set_error(RTS_ERR_UNSUPPORTED, "%s: the session resamples its input, and a record does not carry the resampler's tail and totals", what);
     if (h->gate_on)
         return set_error(RTS_ERR_UNSUPPORTED, "%s: the level gate is on, and a record does not carry its queue and counters", what);
+    if (h->acc_on)
+        return set_error(RTS_ERR_UNSUPPORTED, "%s: the accompaniment is on, and a record does not carry a stream's clock, time map and renderer state", what);
     return check_device(h->device, "handle");
 }
 

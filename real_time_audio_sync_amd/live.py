@@ -128,6 +128,11 @@ class LiveSession(object):
         self._direct = np.zeros(self.B, dtype=np.int64)      # frames reacquire() pushed into the tracker since a restart
         self._annot = None                                   # the AnnotationTables annotate() bound, while they are on
         self._annot_of = self._annot_piece = self._last_tables = None   # pool frame -> table; table of each stream; for label_text
+        # accompany(): the warp plan and the uploaded pool of tracks with the key they were made for, the objects given (kept
+        # alive: the pool is recognised by their identity), per stream (first, len, origin) while it is on, the parameters,
+        # and the arrays accompaniment() reads the words into
+        self._acc_plan = self._acc_pool = self._acc_key = self._acc_tracks = self._acc_par = self._acc_words = None
+        self._acc_given = {}
 
     # ---- feeding ----------------------------------------------------------------------------------------------
     def _stream(self):
@@ -257,6 +262,8 @@ class LiveSession(object):
         self._direct[mask != 0] = 0
         if self._annot is not None and pieces:   # new piece / offset: the beats stay in the piece's own time
             self._annotate_streams(sorted(pieces))
+        if self._acc_tracks is not None:   # rts_live_restart disarmed them: the track follows the offset
+            self._accompany_streams([int(b) for b in streams])
 
     # ---- snapshots --------------------------------------------------------------------------------------------
     @nat.on_device
@@ -544,6 +551,132 @@ class LiveSession(object):
         return dict(consensus=f[0, :G].copy(), spread=f[1, :G].copy(), n_in=i[0, :G].copy(), n_valid=i[1, :G].copy(),
                     dev=f[2].copy(), strikes=i[2].copy(), out=i[3].copy(), feeds_done=done.value)
 
+    # ---- accompaniment ----------------------------------------------------------------------------------------
+    @nat.on_device
+    def accompany(self, tracks, origins=None, warp_N=1024, delta=256, hop_track=None, K=64, glide=None, lead=0,
+                  rates=(0.5, 2.0), chunk_seconds=0.25, max_anchors=1 << 14):
+        """Play a track along every microphone (rts_live_accompany; include/rtsync.h has the steering law).  ``tracks``: one
+        array of samples (float32, or int16 PCM) for every stream, or a list with one entry per stream -- an array, or None
+        for a stream that gets no accompaniment; an array that repeats is uploaded once.  ``origins``: per stream, the track
+        sample that belongs to frame 0 of the stream's piece (default 0); a stream that follows its piece from an offset
+        (``restart(offsets=...)``) is armed ``offset * hop_track`` samples further on.  ``hop_track``: track
+        samples per reference frame (default ``hop_size``: the track is the reference's own recording).  ``K``: path points
+        in the regression window.  ``glide``: samples over which a correction is spread (default 0.2 s).  ``lead``: signed
+        samples, what the output path adds between ``accompaniment()`` and the loudspeaker plus the offset between a live
+        index and the microphone sample its frame is centred on.  ``rates``: limits of the playing rate.
+        ``chunk_seconds``: the most audio a feed renders per stream (a multiple of the warp hop ``warp_N // 2``, at least
+        one); it must exceed the length of a feed, or the output falls behind (status ``ACC_LATE``).  ``max_anchors``: one
+        anchor per feed that renders; a stream whose list is full stops (``ACC_FULL``) until it is armed again.
+
+        The tracks are uploaded once per object given and recognised by identity afterwards: hand over a new array to play
+        other audio, one changed in place is not uploaded again.  A stream keeps its track when ``restart(refs=...)`` moves it
+        onto another piece (it is armed again on the same track at the new offset): call ``accompany`` again with that
+        piece's track.  With ``features='chroma_diff'`` a live index lags the microphone by one frame (the tracker's first
+        frame is the stream's second chroma column): add ``hop_size`` to ``lead``.
+
+        Each call arms the listed streams from output sample 0, with the next feed; calling it again with the same
+        arguments re-arms them, with others it waits for the device and rebuilds.  ``accompany(None)`` switches it off.
+        ``restart`` disarms the restarted streams and arms them again at ``origin + offset * hop_track``; ``reset`` disarms
+        everyone.  Not with ``fs_in`` or the gate (live indices are not microphone time there), and ``export_streams`` /
+        ``import_streams`` refuse while it is on.  Two more launches per feed; nothing is read back."""
+        from .render import WarpPlan
+        if tracks is None:
+            nat.check(nat.lib.rts_live_accompany(self._h, None, None, nat.F32, None, None, None, None, None))
+            self._acc_tracks = None
+            return
+        per = list(tracks) if isinstance(tracks, (list, tuple)) else [tracks] * self.B
+        if len(per) != self.B:
+            raise ValueError("%d tracks for %d streams" % (len(per), self.B))
+        uniq, given = {}, {}
+        for t in per:
+            if t is not None:
+                uniq.setdefault(id(t), np.ascontiguousarray(t))
+                given[id(t)] = t
+        if not uniq:
+            raise ValueError("no stream has a track")
+        pcm = all(a.dtype == np.int16 for a in uniq.values())
+        gap = int(warp_N) + int(delta)                   # silence between tracks: a search window never meets a neighbour
+        first, pieces, at = {}, [], 0
+        for key, a in uniq.items():
+            if a.ndim != 1:
+                raise ValueError("a track must be a 1-D array of samples")
+            first[key] = at
+            a = a if pcm or a.dtype != np.int16 else a.astype(np.float32) * np.float32(1.0 / 32768.0)
+            pieces += [a.astype(np.int16 if pcm else np.float32), np.zeros(gap, dtype=np.int16 if pcm else np.float32)]
+            at += len(a) + gap
+        key = (tuple(sorted(first.items())), pcm, int(warp_N), int(delta))
+        if self._acc_key != key or any(self._acc_given.get(k) is not t for k, t in given.items()):   # another pool or plan
+            if self._acc_plan is not None:
+                self.sync()
+                nat.check(nat.lib.rts_live_accompany(self._h, None, None, nat.F32, None, None, None, None, None))
+                torch.cuda.synchronize(self.dev)
+                self._acc_plan.close()
+            self._acc_plan = WarpPlan(warp_N, delta, device=self.dev)
+            self._acc_pool = torch.from_numpy(np.concatenate(pieces)).to(self.dev)
+            self._acc_key, self._acc_given = key, given   # the objects given stay alive, so their ids stay theirs
+        H = self._acc_plan.H
+        org = [0] * self.B if origins is None else [int(o) for o in origins]
+        par = nat.AccompParams(int(self.H if hop_track is None else hop_track), int(K),
+                               int(self.fs // 5 if glide is None else glide), int(lead), int(round(rates[0] * 1000)),
+                               int(round(rates[1] * 1000)), max(1, -(-int(round(chunk_seconds * self.fs)) // H)), int(max_anchors))
+        self._acc_par = par
+        self._acc_tracks = [None if t is None else (first[id(t)], len(uniq[id(t)]), org[b]) for b, t in enumerate(per)]
+        self._accompany_streams([b for b in range(self.B) if per[b] is not None])
+        self._acc_words = dict(blocks=np.zeros(self.B, np.int32), out_total=np.zeros(self.B, np.int64),
+                               in_pos=np.zeros(self.B, np.int64), rate=np.zeros(self.B, np.float64),
+                               status=np.zeros(self.B, np.int32), warp_status=np.zeros(self.B, np.int32))
+
+    def _accompany_streams(self, streams):
+        """rts_live_accompany for the listed streams, each origin moved to the frame of its piece at which the range the
+        stream follows now begins (``restart(offsets=...)``), like ``_annotate_streams`` moves frame0."""
+        eng = self.otw or self.wtw
+        mask, first, lens, org = (np.zeros(self.B, np.uint8), np.zeros(self.B, np.int64), np.zeros(self.B, np.int64),
+                                  np.zeros(self.B, np.int64))
+        for b in streams:
+            if self._acc_tracks[b] is None:
+                continue
+            mask[b] = 1
+            first[b], lens[b], org[b] = self._acc_tracks[b]
+            if self._conv is not None:
+                org[b] += (eng._piece[b][1] - int(eng.ref_lens[b])) * self._acc_par.hop_track
+        if not mask.any():
+            return
+        nat.check(nat.lib.rts_live_accompany(self._h, self._acc_plan._h, self._acc_pool.data_ptr(),
+                                             nat.I16 if self._acc_pool.dtype == torch.int16 else nat.F32, mask.ctypes.data,
+                                             first.ctypes.data, lens.ctypes.data, org.ctypes.data, ctypes.byref(self._acc_par)))
+
+    def accompaniment(self):
+        """Non-blocking: ``(audio, words)`` of the newest feed every stream has published.  ``audio[b]``: a float32 numpy
+        view of stream b's row of that feed's chunk, cut to ``blocks[b] * (warp_N // 2)`` samples -- host-mapped memory the
+        device wrote; copy it before three more feeds are submitted, the fourth writes over it.  ``words``: {'blocks',
+        'out_total' (output samples made since the stream was armed, this chunk included), 'in_pos' (the track sample the
+        map has reached, counted in the pool ``accompany`` uploaded), 'rate', 'status' (a sum of ``_native.ACC_*``),
+        'warp_status', 'feeds_done'}.  A consumer appends ``audio[b]`` whenever ``feeds_done`` has moved on."""
+        w = self._acc_words
+        if w is None:
+            raise nat.RtsyncError("accompaniment() needs accompany(tracks) first")
+        chunk, stride, done = ctypes.c_void_p(), ctypes.c_longlong(), ctypes.c_int()
+        nat.check(nat.lib.rts_live_accompaniment(self._h, ctypes.byref(chunk), ctypes.byref(stride), w["blocks"].ctypes.data,
+                                                 w["out_total"].ctypes.data, w["in_pos"].ctypes.data, w["rate"].ctypes.data,
+                                                 w["status"].ctypes.data, w["warp_status"].ctypes.data, ctypes.byref(done)))
+        ring = np.ctypeslib.as_array(ctypes.cast(chunk.value, ctypes.POINTER(ctypes.c_float)), shape=(self.B, stride.value))
+        H = self._acc_plan.H
+        audio = [ring[b, :int(w["blocks"][b]) * H] for b in range(self.B)]
+        words = dict((k, v.copy()) for k, v in w.items())
+        words["feeds_done"] = done.value
+        return audio, words
+
+    @nat.on_device
+    def accompaniment_map(self, b=0):
+        """(anchors int64 [A][2] as (out_pos, in_pos), (k, p_prev)) of stream b's time map and renderer state
+        (rts_live_accomp_map).  Waits for the feeds in flight: for tests and tools."""
+        n, state = ctypes.c_int(), np.zeros(2, dtype=np.int64)
+        cap = int(self._acc_par.A_max)
+        out = np.zeros((cap, 2), dtype=np.int64)
+        nat.check(nat.lib.rts_live_accomp_map(self._h, int(b), out.ctypes.data, cap, ctypes.byref(n), state.ctypes.data,
+                                              self._stream()))
+        return out[:max(0, min(n.value, cap))].copy(), (int(state[0]), int(state[1]))
+
     def backward(self, streams=None):
         """The backward path of every stream (or the listed ones) through the bound OTW tracker
         (``BatchedOTW.backward``): ``(paths, totals, ends)`` for everything the microphones' columns have brought the
@@ -574,8 +707,9 @@ class LiveSession(object):
             except Exception:
                 pass
             nat.destroy_on(self.dev, nat.lib.rts_live_destroy, h)
+        self._acc_pool = None                                # behind the handle that pointed at them
         for o in (getattr(self, "otw", None), getattr(self, "wtw", None), getattr(self, "plan", None),
-                  getattr(self, "resampler", None)):
+                  getattr(self, "resampler", None), getattr(self, "_acc_plan", None)):
             if o is not None:
                 o.close()
 
