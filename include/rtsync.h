@@ -1466,6 +1466,62 @@ int rts_live_accompaniment(rts_live *h, const float **chunk_host, long long *row
  *   device current. */
 int rts_live_accomp_map(rts_live *h, int b, long long *anchors_host, int cap, int *n, long long state[2], void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The time map of a path: positions of one recording on the other, annotation tables carried over.
+ * ------------------------------------------------------------------------------------------ */
+/* The reference stops at the path here too (tests.py:59-137 takes error statistics of it); reading a time of one
+ * recording and saying where that moment lies on the other is this project's definition, to the bit, like the resampler's
+ * and the renderer's.  tests/pathmap_model.py holds it in plain Python.
+ *
+ * Knots.  A path of P points (p[t][0], p[t][1]), int32, in the layout of rts_dtw_paths; a side `from` in {0, 1} and two
+ * int32 offsets per pair, off[0] added to column 0 and off[1] to column 1 (NULL: zeros; where a restarted stream's or a
+ * subsequence path's own range begins): u_t = p[t][from] + off[from], v_t = p[t][1 - from] + off[1 - from], in 64 bits.
+ * The path is usable when P >= 1, u and v do not decrease in t and no u_t or v_t is below 0; steps larger than 1 are
+ * allowed.  The knots k_0 < k_1 < .. < k_{K-1} are the distinct values of u.  lo_i is v at the first point with u = k_i,
+ * hi_i v at the last, and m_i = (double)(lo_i + hi_i) * 0.5, exact: the middle of the vertical run (rts_warp_anchors keeps
+ * its first-point rule).  m_i does not decrease in i, since lo_{i+1} >= hi_i.
+ *
+ * A position x, float64, in frames (fractions allowed), maps to
+ *   NaN                                                                  if x is NaN, x < k_0 or x > k_{K-1}
+ *                                                                        (compared as doubles, before any conversion)
+ *   m_i                                                                  if x == k_i
+ *   m_i + ((x - k_i) * (m_{i+1} - m_i)) / (double)(k_{i+1} - k_i)        otherwise, i the last knot with k_i <= x
+ * every operation float64 and rounded on its own, no fused multiply-add.  y does not decrease in x (the product of the
+ * largest x - k_i with m_{i+1} - m_i divides exactly), y == x to the bit on the identity path, and y(k_i) == m_i.
+ *
+ * Status of a pair, a sum of: */
+#define RTS_PATHMAP_OK 0
+#define RTS_PATHMAP_EMPTY 1    /* len < 1 (the -1 of rts_dtw_paths' fault contract included); rts_annot_transfer: no such piece */
+#define RTS_PATHMAP_BACKWARD 2 /* a column steps back */
+#define RTS_PATHMAP_NEGATIVE 4 /* an index is below 0 after the offsets */
+/* A pair whose status is not 0 gets NaN in all of its valid entries; its neighbours are unaffected.
+ *
+ * rts_path_map: y_dev[b][e] = the image of x_dev[b][e] for e < n_dev[b] (NULL: n_max; clamped to [0, n_max]); entries
+ * behind it are not written.  path_dev int32 [B][P_max][2], len_dev int32 [B] (a length above P_max is clamped to it),
+ * off_dev int32 [B][2] or NULL, x_dev / y_dev float64 [B][n_max], status_dev int32 [B].  One workgroup of 256 lanes per
+ * pair: it walks the path once and reduces the status, then every lane maps entries with at most three bisections of
+ * column `from`.  Asynchronous on `stream`; no allocation, no synchronisation (graph-capturable); writes y_dev and
+ * status_dev only, and no result depends on what they held.
+ *   RTS_ERR_INVALID, naming the argument, before any GPU call: a NULL pointer (path_dev may be NULL when P_max == 0, x_dev
+ *   and y_dev when n_max == 0), P_max or n_max outside [0, 2^30], `from` outside {0, 1}, B outside [1, 65535]. */
+int rts_path_map(const int32_t *path_dev /* [B][P_max][2] */, int P_max, const int32_t *len_dev /* [B] */,
+                 const int32_t *off_dev /* [B][2] or NULL */, int from, const double *x_dev /* [B][n_max] */, int n_max,
+                 const int32_t *n_dev /* [B] or NULL */, int B, double *y_dev /* [B][n_max] */, int32_t *status_dev /* [B] */,
+                 void *stream);
+/* A table carried along a path: for pair b and row r of table piece_dev[b] of `h`, x = times[r] / frame_seconds (one
+ * division, the handle's own frame_seconds), times_dev[b][r] = y(x) * frame_seconds, or NaN where x has no image or the
+ * path is refused; n_rows_dev[b] = the table's length, entries behind it are not written.  A piece outside [0, P) gives
+ * n_rows 0 and status RTS_PATHMAP_EMPTY (its path is not looked at).  Path, offsets, `from`, status and launch shape as
+ * rts_path_map.  The map does not decrease, so the finite images of a table's times are non-decreasing and finite: with
+ * the beats of the same rows they pass rts_annot_create's rules.
+ *   RTS_ERR_INVALID before any GPU call: a NULL handle or pointer (path_dev may be NULL when P_max == 0), P_max or
+ *   rows_max outside [0, 2^30], `from` outside {0, 1}, B outside [1, 65535], rows_max below the longest table of the handle (piece_dev
+ *   lies on the device, so every table counts as selected), another device current. */
+int rts_annot_transfer(rts_annot *h, const int32_t *path_dev /* [B][P_max][2] */, int P_max, const int32_t *len_dev /* [B] */,
+                       const int32_t *off_dev /* [B][2] or NULL */, int from, const int32_t *piece_dev /* [B] */, int B,
+                       int rows_max, double *times_dev /* [B][rows_max] */, int32_t *n_rows_dev /* [B] */,
+                       int32_t *status_dev /* [B] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

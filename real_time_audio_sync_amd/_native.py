@@ -228,6 +228,12 @@ _decl("rts_live_accompany", _i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, ctyp
 _decl("rts_live_accompaniment", _i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _pi32])
 _decl("rts_live_accomp_map", _i32, [_vp, _i32, _vp, _i32, _pi32, _vp, _vp])
 
+PATHMAP_OK, PATHMAP_EMPTY, PATHMAP_BACKWARD, PATHMAP_NEGATIVE = 0, 1, 2, 4  # RTS_PATHMAP_*
+PATHMAP_REASONS = ((PATHMAP_EMPTY, "no path point"), (PATHMAP_BACKWARD, "a column steps back"),
+                   (PATHMAP_NEGATIVE, "an index below 0 after the offsets"))
+_decl("rts_path_map", _i32, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp])
+_decl("rts_annot_transfer", _i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp])
+
 
 def check(rc):
     if rc != 0:

@@ -4,7 +4,8 @@ reference's ``get_beat`` / ``get_beat_and_label`` for whole batches of frames, a
 
 ``evaluate.py`` stays the host form and the definition: every number here equals its number bit for bit, the squared beat
 error included (one float64 addition after the other, in path order).  ``LiveSession.annotate`` binds tables to a live
-session; the device then publishes beat and bar label of every microphone with each feed (csrc/annot.hip)."""
+session; the device then publishes beat and bar label of every microphone with each feed (csrc/annot.hip).
+``AnnotationTables.transfer`` carries a table along an alignment path onto the other recording (csrc/pathmap.hip)."""
 import ctypes
 
 import numpy as np
@@ -175,6 +176,65 @@ class AnnotationTables(object):
             return out
         out = out.cpu().numpy()
         return [out[b, :len(r)].copy() for b, r in enumerate(rows)]
+
+    # ---- transfer ---------------------------------------------------------------------------------------------
+    @nat.on_device
+    def transfer_times(self, path, path_len, pieces, from_side, offsets=None):
+        """The raw transfer (rts_annot_transfer): device tensors ``path`` int32 [B][P_max][2] and ``path_len`` int32 [B]
+        -> device tensors ``(times float64 [B][rows_max], n_rows int32 [B], status int32 [B])``, rows_max the longest table
+        of the handle; entries behind ``n_rows[b]`` are not written.  Asynchronous."""
+        from . import pathmap
+        path, path_len = pathmap.pack_paths((path, path_len), self.device)
+        B, P_max = int(path.shape[0]), int(path.shape[1])
+        pieces = self._i32(pieces, B, "pieces")
+        off = pathmap.pack_offsets(offsets, B, self.device)
+        rows_max = max([len(t) for t in self.times] + [1])
+        times = torch.empty((B, rows_max), dtype=torch.float64, device=self.device)
+        n_rows = torch.empty((B,), dtype=torch.int32, device=self.device)
+        status = torch.empty((B,), dtype=torch.int32, device=self.device)
+        nat.check(nat.lib.rts_annot_transfer(self._h, path.data_ptr() if P_max else None, P_max, path_len.data_ptr(),
+                                             off.data_ptr() if off is not None else None, int(from_side), pieces.data_ptr(),
+                                             B, rows_max, times.data_ptr(), n_rows.data_ptr(), status.data_ptr(),
+                                             self._stream()))
+        return times, n_rows, status
+
+    def transfer(self, paths, pieces, from_side, offsets=None):
+        """Carry tables along alignment paths: pair k's table ``pieces[k]`` belongs to the recording in column
+        ``from_side`` of ``paths[k]``, and the result is that table on the time axis of the recording in the other column
+        (include/rtsync.h, rts_path_map: the time of every row, in frames, mapped along the path).  ``paths`` as
+        ``path_errors`` takes them; ``offsets``: None or two integers per pair, added to column 0 and column 1 of its path.
+
+        Returns ``(tables, dropped)``: ``tables[k]`` a tuple ``(times, beats, labels)`` ready for ``AnnotationTables([...])``
+        -- the rows with an image, beat numbers and label strings unchanged (labels None for a piece without a label
+        column), times replaced -- and ``dropped[k]`` the indices of the rows that lie before the first or behind the last
+        aligned frame.  The map does not decrease, so a kept table passes rts_annot_create's rules.  Raises ValueError for
+        a refused path, a piece that does not exist or a pair with no row left, naming the pairs.  Synchronises."""
+        from . import pathmap
+        path, plen = pathmap.pack_paths(paths, self.device)
+        if int(path.shape[0]) < 1:
+            return [], []
+        pieces = [int(p) for p in (pieces.tolist() if torch.is_tensor(pieces) else pieces)]
+        missing = [k for k, p in enumerate(pieces) if p < 0 or p >= self.P]
+        if missing:
+            raise ValueError("transfer: pair%s %s: no such piece" % ("s" if len(missing) > 1 else "",
+                                                                     ", ".join(str(k) for k in missing)))
+        times, n_rows, status = self.transfer_times(path, plen, pieces, from_side, offsets)
+        times, n_rows, status = times.cpu().numpy(), n_rows.cpu().numpy(), status.cpu().numpy()
+        bad = pathmap.refusals(status)
+        if bad:
+            raise ValueError("transfer: " + pathmap.refusal_message(bad))
+        tables, dropped = [], []
+        for k, p in enumerate(pieces):
+            new = times[k, :int(n_rows[k])]
+            keep = np.flatnonzero(np.isfinite(new))
+            tables.append((new[keep].copy(), self.beat_rows[p][keep].copy(),
+                           None if self.labels[p] is None else [self.labels[p][r] for r in keep]))
+            dropped.append([int(r) for r in np.flatnonzero(~np.isfinite(new))])
+        empty = [k for k, t in enumerate(tables) if len(t[0]) == 0]
+        if empty:
+            raise ValueError("transfer: pair%s %s: no row of the table lies on the aligned stretch"
+                             % ("s" if len(empty) > 1 else "", ", ".join(str(k) for k in empty)))
+        return tables, dropped
 
     # ---- metric -----------------------------------------------------------------------------------------------
     @nat.on_device

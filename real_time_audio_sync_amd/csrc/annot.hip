@@ -176,6 +176,7 @@ __global__ void __launch_bounds__(kAnnotLiveThreads) annot_live_kernel(AnnotTabl
 struct rts_annot {
     rts::AnnotTables t;  // device pointers
     long long n_rows;
+    int longest;  // rows of the longest table
     int device;
     void *block;  // the one allocation behind them
 };
@@ -184,6 +185,7 @@ namespace rts {
 
 int annot_pieces(const rts_annot *a) { return a->t.P; }
 int annot_device(const rts_annot *a) { return a->device; }
+int annot_longest(const rts_annot *a) { return a->longest; }
 const AnnotTables *annot_tables(const rts_annot *a) { return &a->t; }
 
 int annot_select_enqueue(int B, const uint8_t *mask_host, const int32_t *piece_host, const int32_t *frame0_host,
@@ -273,6 +275,8 @@ int rts_annot_create(int P, long long n_rows, const long long *first_host, const
     h->t.P = P;
     h->t.frame_seconds = frame_seconds;
     h->n_rows = n_rows;
+    for (int p = 0; p < P; p++)
+        if (len_host[p] > h->longest) h->longest = len_host[p];
     *out = h;
     return RTS_OK;
 }

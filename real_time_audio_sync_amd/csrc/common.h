@@ -106,6 +106,7 @@ struct AnnotLive {
 };
 __attribute__((visibility("hidden"))) int annot_pieces(const rts_annot *a);
 __attribute__((visibility("hidden"))) int annot_device(const rts_annot *a);
+__attribute__((visibility("hidden"))) int annot_longest(const rts_annot *a);  // rows of the handle's longest table
 __attribute__((visibility("hidden"))) int annot_select_enqueue(int B, const uint8_t *mask_host, const int32_t *piece_host,
                                                                const int32_t *frame0_host, int32_t *piece_dev,
                                                                int32_t *frame0_dev, hipStream_t s);

@@ -157,6 +157,34 @@ def path_consensus(paths, groups, tables, pieces, T, frame0=None, max_dev=math.i
     return (cons, spread, n_in, out) if outputs else cons
 
 
+def annotate_recordings(recordings, table, annotated=0, device="cuda:0", frame_seconds=None):
+    """One annotated recording of a piece and several that are not -> an ``annotate.AnnotationTables`` with a table for
+    each of them.  ``recordings``: G chroma arrays (12, N_k); ``table``: the ground truth of ``recordings[annotated]``, a
+    CSV path or a ``(times, beats[, labels])`` tuple.  Makes one ``dtw.align_pairs`` call, recording ``annotated`` against
+    each of the others, and one ``AnnotationTables.transfer`` along those paths.  Table ``annotated`` of the result is the
+    one given; the others hold its rows at the times the alignment puts them (rows in front of or behind the aligned
+    stretch are dropped).  ``frame_seconds``: seconds per chroma frame (None: ``evaluate.FRAME_SECONDS``)."""
+    from . import annotate, dtw
+    recordings = list(recordings)
+    G, annotated = len(recordings), int(annotated)
+    if not 0 <= annotated < G:
+        raise ValueError("annotated = %d with %d recordings" % (annotated, G))
+    args = dict(device=device) if frame_seconds is None else dict(device=device, frame_seconds=frame_seconds)
+    own = annotate._table(table)
+    if G == 1:
+        return annotate.AnnotationTables([own], **args)
+    others = [k for k in range(G) if k != annotated]
+    pairs = dtw.align_pairs(np.asarray(recordings[annotated]), [recordings[k] for k in others], device=device)
+    source = annotate.AnnotationTables([own], **args)
+    try:
+        carried, _ = source.transfer([p for p, _ in pairs], [0] * len(others), 0)   # column 0 is the annotated recording
+    finally:
+        source.close()
+    tables = dict(zip(others, carried))
+    tables[annotated] = own
+    return annotate.AnnotationTables([tables[k] for k in range(G)], **args)
+
+
 class EnsembleSession(object):
     """``mics`` microphones, each followed against all ``G = len(recordings)`` recordings of one piece.
 
@@ -182,6 +210,13 @@ class EnsembleSession(object):
         self.live.annotate(tables, piece_of=[(r, k) for k, r in enumerate(self.recordings)])
         self.live.follow_consensus([b // self.G for b in range(self.B)], max_dev, patience)
         self.max_dev, self.patience = float(max_dev), int(patience)
+
+    @classmethod
+    def from_annotated(cls, recordings, table, mics, annotated=0, **kw):
+        """A session from one ground-truth table: ``table`` belongs to ``recordings[annotated]``, the other recordings get
+        theirs from ``annotate_recordings`` (on ``kw['device']``, default "cuda:0").  Everything else as the constructor."""
+        tables = annotate_recordings(recordings, table, annotated, device=kw.get("device", "cuda:0"))
+        return cls(recordings, tables, mics, **kw)
 
     def feed(self, buffers, wait=False):
         """``buffers``: one array of new samples per microphone (None / empty = nothing new), written G times into the
