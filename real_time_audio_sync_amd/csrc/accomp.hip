@@ -338,11 +338,8 @@ int accomp_create(const AccompGeom &p, rts_warp *plan, const void *tracks, int d
     e = accomp_dev_zeroed(e, &a->d.n_anchor, nB);
     e = accomp_dev_zeroed(e, &a->d.armed, nB);
     const size_t ring_bytes = sizeof(float) * kAccSlots * nB * (size_t)a->row;
-    if (e == hipSuccess)
-        e = hipHostMalloc((void **)&a->words_host, kAccSlots * accomp_words_bytes(B), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&a->words_dev, a->words_host, 0);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&a->ring_host, ring_bytes, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&a->ring_dev, a->ring_host, 0);
+    if (e == hipSuccess) e = mapped_alloc(kAccSlots * accomp_words_bytes(B), (void **)&a->words_host, (void **)&a->words_dev);
+    if (e == hipSuccess) e = mapped_alloc(ring_bytes, (void **)&a->ring_host, (void **)&a->ring_dev);
     if (e != hipSuccess) {
         accomp_destroy(a);
         return set_error(RTS_ERR_HIP, "rts_live_accompany: %s", hipGetErrorString(e));

@@ -1,5 +1,5 @@
 // librtsync.so: error reporting, device discovery (rts_last_error, rts_version, rts_device_count) and the host-side rules
-// the tracker handles share (device check, reference ranges and tables, path read-back, restart selection).
+// the handles share (device check, host-mapped blocks, reference ranges and tables, path read-back, restart selection).
 #include "common.h"
 
 #include <string.h>
@@ -26,6 +26,15 @@ int check_device(int handle_device, const char *noun) {
         return set_error(RTS_ERR_INVALID, "%s was created on device %d but device %d is current "
                                           "(one process per GPU, or hipSetDevice before the call)", noun, handle_device, d);
     return RTS_OK;
+}
+
+hipError_t mapped_alloc(size_t bytes, void **host, void **dev) {
+    void *h = nullptr, *d = nullptr;
+    hipError_t e = hipHostMalloc(&h, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess && (e = hipHostGetDevicePointer(&d, h, 0)) != hipSuccess) (void)hipHostFree(h);
+    *host = e == hipSuccess ? h : nullptr;
+    *dev = e == hipSuccess ? d : nullptr;
+    return e;
 }
 
 int ref_ranges_check(int B, const uint8_t *mask_host, const long long *first_host, const int32_t *len_host,

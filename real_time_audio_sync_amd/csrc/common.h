@@ -24,6 +24,10 @@ __attribute__((visibility("hidden"))) int wtw_history(const rts_wtw *h);
 // driving it with another device current would launch against foreign buffers.
 __attribute__((visibility("hidden"))) int check_device(int handle_device, const char *noun);
 
+// Host memory the device writes and the host reads without a copy: `bytes` of mapped, coherent host memory in *host and the
+// same block as the device sees it in *dev -- or, on failure, nothing allocated and both NULL.  Freed with hipHostFree(*host).
+__attribute__((visibility("hidden"))) hipError_t mapped_alloc(size_t bytes, void **host, void **dev);
+
 // The one rule for per-stream reference ranges (rts_*_create_refs, rts_*_restart): len >= 1, first >= 0, [first, first +
 // len) inside the pool of n_ref_frames and, where `len_name` is given, len <= len_max (the handle's buffers were sized by
 // it).  `mask_host` (may be NULL) restricts the check to the selected streams.  Returns the largest length seen, or
@@ -111,8 +115,6 @@ __attribute__((visibility("hidden"))) int annot_select_enqueue(int B, const uint
                                                                const int32_t *frame0_host, int32_t *piece_dev,
                                                                int32_t *frame0_dev, hipStream_t s);
 __attribute__((visibility("hidden"))) int annot_live_enqueue(const rts_annot *a, const AnnotLive &g, hipStream_t s);
-// The path buffer of a WTW handle, [B][*path_cap][2] (rts_otw_device_views is the OTW counterpart).
-__attribute__((visibility("hidden"))) void wtw_path_view(const rts_wtw *h, const int32_t **path, int *path_cap);
 
 // The tail kernel of csrc/tempo.hip as the trackers and the live handle launch it: the regression window over the last
 // min(K, stored) points of every stream's own path (rts_otw_tempo in include/rtsync.h has the definition).  otw_tempo_view /

@@ -27,21 +27,21 @@
 //   live_level_kernel, live_gate_kernel   only after rts_live_gate(min_level > 0) (csrc/live_gate.h): the mean square of
 //                         every column's frame, then per stream the decision which columns its tracker gets, those
 //                         packed into a second buffer with their counts, and the meter words of rts_live_levels into a
-//                         third host-mapped block; the push below then takes that buffer and those counts
+//                         host-mapped block of its own; the push below then takes that buffer and those counts
 //   rts_otw_push | rts_wtw_push   the columns into the alignment state (insert semantics, column by column)
-//   rts_otw_path_cost     only after rts_live_watch(K > 0): the tracker's mean cell cost over its last K path points into a
-//                         second host-mapped block -- rts_live_confidence reads it like rts_live_poll reads the status words
-//   annot_live_kernel     only after rts_live_annotate with tables (csrc/annot.hip): beat and label of the reference frame of
-//                         every tracker's last path point into a fourth host-mapped block -- rts_live_beats reads it
-//   tempo_tail_kernel     only after rts_live_follow_tempo(K > 0) (csrc/tempo.hip): slope, position and beats per minute of the
-//                         last K points of every tracker's path into a fifth host-mapped block -- rts_live_tempo reads it
-//   ensemble_fuse_kernel  only after rts_live_follow_consensus with an ensemble and while annotations are on (csrc/ensemble.hip):
-//                         the median beat of every group of streams, each member's deviation, strikes and out into a sixth
-//                         host-mapped block -- rts_live_consensus reads it
-//   accomp_steer_kernel, rts_warp_run   only after rts_live_accompany with a plan (csrc/accomp.hip): the next anchor of every
-//                         armed stream's time map from the tail of its tracker's path, and the blocks that made due rendered
-//                         into this feed's chunk of a host-mapped ring, their words into a seventh host-mapped block --
-//                         rts_live_accompaniment reads both
+//   the publishers        (live_publishers_launch) each only after its enabling call, each into a host-mapped block of its own
+//                         that a non-blocking reader copies out like rts_live_poll the status words:
+//     rts_otw_path_cost     rts_live_watch(K > 0): the tracker's mean cell cost over its last K path points -- rts_live_confidence
+//     annot_live_kernel     rts_live_annotate with tables (csrc/annot.hip): beat and label of the reference frame of every
+//                           tracker's last path point -- rts_live_beats
+//     tempo_tail_kernel     rts_live_follow_tempo(K > 0) (csrc/tempo.hip): slope, position and beats per minute of the last K
+//                           points of every tracker's path -- rts_live_tempo
+//     ensemble_fuse_kernel  rts_live_follow_consensus with an ensemble, while annotations are on (csrc/ensemble.hip): the median
+//                           beat of every group of streams, each member's deviation, strikes and out -- rts_live_consensus
+//     accomp_steer_kernel, rts_warp_run   rts_live_accompany with a plan (csrc/accomp.hip): the next anchor of every armed
+//                           stream's time map from the tail of its tracker's path, and the blocks that made due rendered into
+//                           this feed's chunk of a host-mapped ring, their words into a block that accomp.hip keeps --
+//                           rts_live_accompaniment reads both
 //   live_compact_kernel   drop hop * n_frames consumed samples per stream (data = data[2048:], livenote_live.py:208),
 //                         and publish {status, live position, ref position, feed number} of every stream into
 //                         host-mapped memory -- rts_live_poll reads those words without touching the stream.
@@ -49,6 +49,11 @@
 // Commit (live_commit).  Once the last step has been enqueued the planned values become the mirror, and the slot ring
 // and the feed counter move on.  A chain that fails part-way commits nothing and marks the handle failed -- the device
 // may have run a part of it -- and every feed and restart is refused until rts_live_reset has zeroed both sides.
+//
+// The host-mapped blocks.  ONE table (csrc/live_pub.h) says where every word of the status, gate, confidence, beats, tempo
+// and consensus blocks lies and what an empty word holds; sizes, the kernels' and readers' pointers, the clears of
+// allocation, rts_live_reset, live_restart_kernel and live_import_kernel all come from it.  A new publisher adds a table
+// entry, an enabling call that ends in live_pub_alloc, a launch in live_publishers_launch and a reader made of live_word.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -57,11 +62,11 @@
 #include "accomp_plan.h"
 #include "common.h"
 #include "live_plan.h"
+#include "live_pub.h"
 
 namespace rts {
 
 constexpr int kLiveSlots = 4;
-constexpr int kLiveWords = 4;  // per stream in the mapped status block: status, live position, ref position, feed number
 constexpr int kLiveF = 12;     // pitch classes of a column (96 B in float64)
 
 struct LiveArgs {
@@ -74,38 +79,40 @@ struct LiveArgs {
     int B, cap, L, hop;
     const int32_t *state;        // alignment state of the streams, state_len ints each
     int state_len, st_status, st_live, st_ref;
-    int32_t *pub;                // host-mapped [B][kLiveWords]
-    int feed_no;
+    int feed_no;                 // (with state and the st_* words in one 64-byte line of the kernel arguments: measured)
+    PubSet pubs;                 // the host-mapped blocks (csrc/live_pub.h): status from create, the others when enabled
     // RTS_FEATURE_CHROMA_DIFF (all NULL in chroma mode)
     double *cols;                // [B][cols_stride][12] chroma columns of this feed
     double *dcols;               // [B][cols_stride][12] difference columns handed to the tracker
     double *carry;               // [B][12] last chroma column of every stream
     int32_t *has_carry, *n_cols; // [B]
     int cols_stride;             // rows per stream in cols / dcols: n_max of this feed
-    // rts_live_watch (NULL until its first call): host-mapped confidence words, republished by live_restart_kernel
-    double *conf_mean;           // [B]
-    int32_t *conf_n;             // [B]
-    // rts_live_annotate (NULL until its first call with tables): host-mapped beat words, republished by live_restart_kernel
-    double *ann_beat;            // [B]
-    int32_t *ann_label, *ann_ref;  // [B]
-    // rts_live_follow_tempo (NULL until its first call with K > 0): host-mapped tempo words, republished by live_restart_kernel
-    double *tempo_words;         // slope[B], pos[B], bpm[B]
-    int32_t *tempo_n;            // [B]
-    // rts_live_follow_consensus (NULL until its first call with an ensemble): the host-mapped per-stream words, republished
-    // by live_restart_kernel, and the bound ensemble's carried state on the device (NULL while consensus is off)
-    double *ens_dev;             // [B]
-    int32_t *ens_member;         // strikes[B], out[B]
-    int32_t *ens_state;          // strikes[B], out[B] of the ensemble handle
+    int32_t *ens_state;          // strikes[B], out[B] of the bound ensemble (NULL while consensus is off): a restart or an
+                                 // import clears the stream's
 };
 
-__device__ __forceinline__ void live_publish(const LiveArgs &g, int b) {
+// Status and positions of stream b from the tracker's state into the status block: every feed, restart and import.
+__device__ __forceinline__ void live_publish_status(const LiveArgs &g, int b) {
     const int32_t *st = g.state + (size_t)b * g.state_len;
-    volatile int32_t *p = g.pub + (size_t)b * kLiveWords;
-    p[0] = st[g.st_status];
-    p[1] = st[g.st_live];
-    p[2] = st[g.st_ref];
+    unsigned char *blk = g.pubs.dev[kPubStatus];
+    *(volatile int32_t *)pub_ptr<kPubStatus, kStatusStatus>(blk, g.B, b) = st[g.st_status];
+    *(volatile int32_t *)pub_ptr<kPubStatus, kStatusLive>(blk, g.B, b) = st[g.st_live];
+    *(volatile int32_t *)pub_ptr<kPubStatus, kStatusRef>(blk, g.B, b) = st[g.st_ref];
+}
+
+__device__ __forceinline__ void live_publish(const LiveArgs &g, int b) {
+    live_publish_status(g, b);
     __threadfence_system();
-    p[3] = g.feed_no;  // written last: a reader that sees feed k sees the three words of feed >= k
+    // written last: a reader that sees feed k sees the three words of feed >= k
+    *(volatile int32_t *)pub_ptr<kPubStatus, kStatusFeed>(g.pubs.dev[kPubStatus], g.B, b) = g.feed_no;
+}
+
+// A restarted or imported stream: the per-stream words of the allocated blocks among `blocks` (bit k: PubBlock k) hold
+// their empty values until the next feed.
+__device__ __forceinline__ void live_clear_published(const PubSet &s, unsigned blocks, int B, int b) {
+    RTS_PUB_UNROLL
+    for (int k = 0; k < kPubBlocks; k++)
+        if ((blocks >> k & 1) && s.dev[k]) pub_clear_stream((PubBlock)k, s.dev[k], B, b);
 }
 
 constexpr int kAppendSlices = 16;  // workgroups per stream in the append kernel (a 1-second buffer is 88 KB)
@@ -201,37 +208,19 @@ namespace rts {
 
 // rts_live_restart, after the bound tracker's own restart: the selected streams' pending samples are dropped and their
 // status / position words republished from the (now fresh) tracker state.  The feed number is left alone: the words
-// still reflect every feed submitted before the restart.  In diff mode the carried chroma column goes with the samples,
-// and once rts_live_gate has made its buffers (t.q != NULL) the stream's gate closes.
+// still reflect every feed submitted before the restart.  Every other block that exists holds the stream's empty words
+// until the next feed (the gate's meter words among them), and the bound ensemble forgets the member's strikes.  In diff
+// mode the carried chroma column goes with the samples, and once rts_live_gate has made its buffers (t.q != NULL) the
+// stream's gate closes.
 __global__ void live_restart_kernel(RestartSel sel, LiveArgs g, GateArgs t) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= sel.n) return;
     const int b = sel.idx[i];
     g.pending[b] = 0;
     if (g.has_carry) g.has_carry[b] = 0;
-    const int32_t *st = g.state + (size_t)b * g.state_len;
-    volatile int32_t *p = g.pub + (size_t)b * kLiveWords;
-    p[0] = st[g.st_status];
-    p[1] = st[g.st_live];
-    p[2] = st[g.st_ref];
-    if (g.conf_n) {  // a fresh stream has no path point yet
-        g.conf_n[b] = 0;
-        g.conf_mean[b] = __longlong_as_double(0x7ff8000000000000LL);
-    }
-    if (g.ann_beat) {  // nothing looked up yet
-        g.ann_beat[b] = __longlong_as_double(0x7ff8000000000000LL);
-        g.ann_label[b] = -1;
-        g.ann_ref[b] = -1;
-    }
-    if (g.tempo_words) {  // no window yet
-        for (int q = 0; q < 3; q++) g.tempo_words[(size_t)q * g.B + b] = __longlong_as_double(0x7ff8000000000000LL);
-        g.tempo_n[b] = 0;
-    }
+    live_publish_status(g, b);
     if (g.ens_state) g.ens_state[b] = g.ens_state[g.B + b] = 0;  // a fresh member: no strikes, heard again
-    if (g.ens_dev) {
-        g.ens_dev[b] = __longlong_as_double(0x7ff8000000000000LL);
-        g.ens_member[b] = g.ens_member[g.B + b] = 0;
-    }
+    live_clear_published(g.pubs, kPubRestartBlocks, g.B, b);
     if (t.q) live_gate_restart(t, b);
     __threadfence_system();
 }
@@ -243,8 +232,8 @@ struct rts_live {
     rts_otw *otw;
     rts_wtw *wtw;
     rts::LiveGeom geo;   // B, fft_len, hop, max_pending, diff mode, the resampler's ratio and in_cap
-    // what every launch takes, from create and rts_live_watch; a feed adds stage, sample_kind, feed_no, cols_stride to a copy.
-    // Every kernel gets every field: none may take a NULL field for the mode (live_restart_kernel's two tests are of buffers)
+    // what every launch takes, from create and the enabling calls; a feed adds stage, sample_kind, feed_no, cols_stride to a
+    // copy.  Every kernel gets every field: none may take a NULL field for the mode (live_restart_kernel's tests are of buffers)
     rts::LiveArgs args;
     int cols_cap, device;
     unsigned char *stage_host[rts::kLiveSlots];  // pinned
@@ -259,13 +248,13 @@ struct rts_live {
     rts::LiveMirror cur;
     rts::FeedPlan fp;
     int last_stride;     // rows per stream in the layout of the last submitted feed (rts_live_columns_view)
-    int32_t *pub_host;
+    // the host-mapped blocks as the host sees them, by PubBlock (csrc/live_pub.h has their layouts); NULL: never allocated.
+    // args.pubs holds the same blocks as the device sees them
+    unsigned char *pub_host[rts::kPubBlocks];
     int feeds;
     int failed;          // a feed's chain was enqueued in part: the mirror no longer describes the device (rts_live_reset)
-    // rts_live_watch: K path points per stream (0 = off) and the second host-mapped block, double mean[B] then int32 n[B],
-    // allocated by the first rts_live_watch(K > 0)
+    // rts_live_watch: K path points per stream (0 = off); the confidence block comes with the first rts_live_watch(K > 0)
     int watch_k;
-    unsigned char *conf_host;
     // rts_live_create_resampled (rs NULL otherwise): the plan, the input samples a stream carries (rs_T), the second
     // staging-layout device buffer the resampling launch writes and the append reads, tail [B][rs_T] and totals [B][2]
     // (input samples taken, output samples made) on the device
@@ -275,31 +264,23 @@ struct rts_live {
     float *rs_tail;  // [2][B][rs_T]: the copy feed k reads and the one it writes, alternating (rs_cur)
     int rs_cur;
     long long *rs_tot;
-    // rts_live_gate: on / off, what its two launches take (buffers from the first rts_live_gate(min_level > 0)), and the
-    // third host-mapped block, double level[B] then int32 {open, seen, passed}[B]
+    // rts_live_gate: on / off and what its two launches take; the buffers and the gate block come with the first
+    // rts_live_gate(min_level > 0)
     int gate_on;
     rts::GateArgs gate;
-    unsigned char *gate_host;
-    // rts_live_annotate: the tables in use (NULL = off), what its launch takes (the tracker's path and the two [B] device
-    // tables, from the first call with tables) and the fourth host-mapped block, double beat[B] then int32 label[B], ref_frame[B]
+    // rts_live_annotate: the tables in use (NULL = off) and the two [B] device tables, which come with the beats block in the
+    // first call with tables
     rts_annot *annot;
-    rts::AnnotLive ann;
     int32_t *ann_tables;  // piece[B] then frame0[B] on the device
-    unsigned char *ann_host;
-    // rts_live_follow_tempo: K points per stream (0 = off), what its launch takes (the tracker's view and the outputs, from
-    // the first call with K > 0) and the fifth host-mapped block, double slope[B], pos[B], bpm[B] then int32 n[B]
+    // rts_live_follow_tempo: K points per stream (0 = off) and how far ahead; the tempo block comes with the first call with K > 0
     int tempo_k;
-    rts::TempoTail tempo;
-    unsigned char *tempo_host;
-    // rts_live_follow_consensus: the ensemble in use (NULL = off), the groups of the one bound last, and the sixth
-    // host-mapped block, sized for B groups: double consensus[B], spread[B], dev[B] then int32 n_in[B], n_valid[B],
-    // strikes[B], out[B] (the group words use the first n_groups entries of theirs)
+    double tempo_ahead;
+    // rts_live_follow_consensus: the ensemble in use (NULL = off) and the groups of the one bound last; the consensus block,
+    // whose group words use the first n_groups entries of theirs, comes with the first call with an ensemble
     rts_ensemble *ens;
     int ens_groups;
-    unsigned char *ens_host;
-    rts::EnsembleOut ens_out;  // the block as the device sees it
     // rts_live_accompany: on / off, and everything it owns (csrc/accomp.hip), made by the first call with a plan: the streams'
-    // steering state on the device, the seventh host-mapped block and the ring of chunks
+    // steering state on the device, a host-mapped block of its own and the ring of chunks
     int acc_on;
     rts::Accomp *acc;
 };
@@ -315,81 +296,83 @@ static int live_usable(const rts_live *h) {
     return RTS_OK;
 }
 
-static void live_conf_clear(rts_live *h) {
-    double *mean = reinterpret_cast<double *>(h->conf_host);
-    int32_t *n = reinterpret_cast<int32_t *>(h->conf_host + sizeof(double) * (size_t)h->geo.B);
-    for (int b = 0; b < h->geo.B; b++) {
-        mean[b] = __builtin_nan("");
-        n[b] = 0;
+// Stream b's word of plane P of block K as the host reads it.
+template <PubBlock K, int P>
+static auto live_word(const rts_live *h, int b) {
+    auto *p = pub_ptr<K, P>(h->pub_host[K], h->geo.B, b);
+    return *const_cast<const volatile std::remove_pointer_t<decltype(p)> *>(p);
+}
+
+// Block k of the handle: nothing to do if it exists; else, with the handle's device current, mapped coherent host memory of
+// the table's size, every word empty, entered on both sides.  `who` names the public call in the one error message there is.
+static int live_pub_alloc(rts_live *h, PubBlock k, const char *who) {
+    if (h->pub_host[k]) return RTS_OK;
+    if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
+    void *host = nullptr, *dev = nullptr;
+    if (hipError_t e = mapped_alloc(pub_block_bytes(k, h->geo.B), &host, &dev); e != hipSuccess)
+        return set_error(RTS_ERR_HIP, "%s: host-mapped block %d: %s", who, (int)k, hipGetErrorString(e));
+    pub_clear_all(k, host, h->geo.B);
+    h->pub_host[k] = static_cast<unsigned char *>(host);
+    h->args.pubs.dev[k] = static_cast<unsigned char *>(dev);
+    return RTS_OK;
+}
+
+// The tracker as the publishers' kernels see it (state, path, reference lengths), fetched on every use and never kept in
+// the handle: nothing here rests on which of those pointers a restart may move.  Returns the tracker's longest reference.
+static int live_tracker_view(const rts_live *h, TempoTail *t) {
+    *t = TempoTail{};
+    return h->otw ? otw_tempo_view(h->otw, t) : wtw_tempo_view(h->wtw, t);
+}
+
+// The publishers of a feed, between the tracker push and live_compact_kernel: each reads what the push left in the tracker
+// and writes its own host-mapped block, and the compaction writes the feed number last, so a reader that sees feed k sees
+// every block's words of a feed >= k.  The order is watch (rts_otw_path_cost), beats, tempo, consensus, accompaniment (the
+// steering launch and one rts_warp_run; in the first feed after streams were armed also the launch that arms them); each is
+// skipped while it is off.  Tempo and consensus need the piece / frame0 tables of rts_live_annotate: the tempo launch
+// publishes NaN beats per minute without them or while annotations are off, the consensus launch is skipped while
+// annotations are off (rts_live_follow_consensus refuses a session that never had them).
+static int live_publishers_launch(rts_live *h, int feed_no, hipStream_t s) {
+    const int B = h->geo.B;
+    const PubSet &d = h->args.pubs;
+    const int32_t *piece = h->ann_tables, *frame0 = piece ? piece + B : nullptr;
+    TempoTail view;
+    (void)live_tracker_view(h, &view);
+    if (h->watch_k >= 1) {
+        if (int rc = rts_otw_path_cost(h->otw, h->watch_k, pub_ptr<kPubConf, kConfMean>(d.dev[kPubConf], B),
+                                       pub_ptr<kPubConf, kConfN>(d.dev[kPubConf], B), nullptr, s);
+            rc != RTS_OK)
+            return rc;
     }
-}
-
-// With watch on, one more launch per feed between the tracker push and live_compact_kernel: the path-cost kernel of
-// rts_otw_path_cost with its mean / n outputs in the mapped confidence block.  It precedes the compaction, which
-// writes the feed number last, so a reader that sees feed k sees confidence words of a feed >= k.
-static int live_watch_launch(rts_live *h, void *stream) {
-    if (h->watch_k < 1) return RTS_OK;
-    return rts_otw_path_cost(h->otw, h->watch_k, h->args.conf_mean, h->args.conf_n, nullptr, stream);
-}
-
-static void live_annot_clear(rts_live *h) {
-    double *beat = reinterpret_cast<double *>(h->ann_host);
-    int32_t *words = reinterpret_cast<int32_t *>(beat + h->geo.B);
-    for (int b = 0; b < h->geo.B; b++) beat[b] = __builtin_nan("");
-    for (int b = 0; b < 2 * h->geo.B; b++) words[b] = -1;
-}
-
-// With annotations on, one more launch per feed behind the watch launch and before live_compact_kernel, like the watch
-// launch and for the same reason: the compaction writes the feed number last.
-static int live_annot_launch(rts_live *h, hipStream_t s) {
-    if (!h->annot) return RTS_OK;
-    return annot_live_enqueue(h->annot, h->ann, s);
-}
-
-static void live_tempo_clear(rts_live *h) {
-    double *words = reinterpret_cast<double *>(h->tempo_host);
-    for (int b = 0; b < 3 * h->geo.B; b++) words[b] = __builtin_nan("");
-    memset(words + 3 * (size_t)h->geo.B, 0, sizeof(int32_t) * (size_t)h->geo.B);
-}
-
-// With tempo on, one more launch per feed behind the beat launch and before live_compact_kernel, for the same reason.
-// Beats per minute need what rts_live_annotate set up: the tables while they are on, piece and offset of every stream.
-static int live_tempo_launch(rts_live *h, hipStream_t s) {
-    if (h->tempo_k < 1) return RTS_OK;
-    TempoTail t = h->tempo;
-    t.piece = h->ann_tables;
-    t.frame0 = h->ann_tables ? h->ann_tables + h->geo.B : nullptr;
-    return tempo_tail_enqueue(t, h->annot, s);
-}
-
-static void live_ens_clear(rts_live *h) {
-    double *words = reinterpret_cast<double *>(h->ens_host);
-    for (int b = 0; b < 3 * h->geo.B; b++) words[b] = __builtin_nan("");
-    memset(words + 3 * (size_t)h->geo.B, 0, sizeof(int32_t) * 4 * (size_t)h->geo.B);
-}
-
-// With consensus on, one more launch per feed behind the beat and tempo launches and before live_compact_kernel, for the
-// same reason.  The member beat needs what rts_live_annotate set up: while annotations are off the launch is skipped.
-static int live_ens_launch(rts_live *h, hipStream_t s) {
-    if (!h->ens || !h->annot) return RTS_OK;
-    TempoTail view = {};
-    (void)(h->otw ? otw_tempo_view(h->otw, &view) : wtw_tempo_view(h->wtw, &view));
-    return ensemble_fuse_enqueue(h->ens, h->annot, view, h->ann_tables, h->ann_tables + h->geo.B, h->ens_out, s);
-}
-
-// With accompaniment on, behind the consensus launch and before live_compact_kernel, for the same reason: the steering launch
-// and one rts_warp_run (and, in the first feed after streams were armed, the launch that arms them).
-static int live_accomp_launch(rts_live *h, int feed_no, hipStream_t s) {
-    if (!h->acc_on) return RTS_OK;
-    TempoTail view = {};
-    (void)(h->otw ? otw_tempo_view(h->otw, &view) : wtw_tempo_view(h->wtw, &view));
-    return accomp_enqueue(h->acc, view, h->args.n_samples, h->args.pending, feed_no, s);
-}
-
-static void live_gate_clear(rts_live *h) {
-    double *level = reinterpret_cast<double *>(h->gate_host);
-    for (int b = 0; b < h->geo.B; b++) level[b] = __builtin_nan("");
-    memset(level + h->geo.B, 0, sizeof(int32_t) * kGateWords * (size_t)h->geo.B);
+    if (h->annot) {
+        unsigned char *blk = d.dev[kPubBeats];
+        const AnnotLive a = {view.state, view.state_len, view.st_n_path, view.path, view.path_cap, piece, frame0,
+                             pub_ptr<kPubBeats, kBeatsBeat>(blk, B), pub_ptr<kPubBeats, kBeatsLabel>(blk, B),
+                             pub_ptr<kPubBeats, kBeatsRef>(blk, B), B};
+        if (int rc = annot_live_enqueue(h->annot, a, s); rc != RTS_OK) return rc;
+    }
+    if (h->tempo_k >= 1) {
+        unsigned char *blk = d.dev[kPubTempo];
+        TempoTail t = view;
+        t.K = h->tempo_k;
+        t.ahead = h->tempo_ahead;
+        t.slope = pub_ptr<kPubTempo, kTempoSlope>(blk, B);
+        t.pos = pub_ptr<kPubTempo, kTempoPos>(blk, B);
+        t.bpm = pub_ptr<kPubTempo, kTempoBpm>(blk, B);
+        t.n_out = pub_ptr<kPubTempo, kTempoN>(blk, B);
+        t.piece = piece;
+        t.frame0 = frame0;
+        if (int rc = tempo_tail_enqueue(t, h->annot, s); rc != RTS_OK) return rc;
+    }
+    if (h->ens && h->annot) {
+        unsigned char *blk = d.dev[kPubEns];
+        const EnsembleOut o = {pub_ptr<kPubEns, kEnsConsensus>(blk, B), pub_ptr<kPubEns, kEnsSpread>(blk, B),
+                               pub_ptr<kPubEns, kEnsNIn>(blk, B),       pub_ptr<kPubEns, kEnsNValid>(blk, B),
+                               pub_ptr<kPubEns, kEnsDev>(blk, B),       pub_ptr<kPubEns, kEnsStrikes>(blk, B),
+                               pub_ptr<kPubEns, kEnsOut>(blk, B)};
+        if (int rc = ensemble_fuse_enqueue(h->ens, h->annot, view, piece, frame0, o, s); rc != RTS_OK) return rc;
+    }
+    if (h->acc_on) return accomp_enqueue(h->acc, view, h->args.n_samples, h->args.pending, feed_no, s);
+    return RTS_OK;
 }
 
 // With the gate on, two more launches per feed between the chroma (and difference) step and the tracker push, in a feed
@@ -422,10 +405,8 @@ static int live_refuse(const rts_live *h, LiveRefusal why, const FeedPlan &p, co
 // chroma column too: it writes the feed's n_cols); rts_chroma_frames_batch and rts_otw_push return at once when their
 // n_max is 0, rts_wtw_push after its entry check, which wtw.py:76-77 runs on every insert(), new column or not; in diff
 // mode the tracker is pushed only when some stream hands it a column (n_max_diff > 0; the rows still lie n_max apart);
-// the watch launch follows rts_live_watch, the two gate launches rts_live_gate: with the gate on the push takes the gated
-// buffer and its counts, and nothing else moves; the beat launch follows rts_live_annotate, the tempo launch
-// rts_live_follow_tempo, the consensus launch rts_live_follow_consensus, the steering launch and the rendering
-// rts_live_accompany.  The compaction and the publication end every feed.
+// the two gate launches follow rts_live_gate: with the gate on the push takes the gated buffer and its counts, and nothing
+// else moves; live_publishers_launch has the launches behind the push.  The compaction and the publication end every feed.
 static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, void *stream) {
     const int B = h->geo.B;
     hipStream_t s = (hipStream_t)stream;
@@ -472,11 +453,7 @@ static int live_enqueue(rts_live *h, const FeedPlan &p, int k, int sample_kind, 
                         : rts_wtw_push(h->wtw, cols, RTS_F64, n_push, n_new, 1, stream);
         rc != RTS_OK)
         return rc;
-    if (int rc = live_watch_launch(h, stream); rc != RTS_OK) return rc;
-    if (int rc = live_annot_launch(h, s); rc != RTS_OK) return rc;
-    if (int rc = live_tempo_launch(h, s); rc != RTS_OK) return rc;
-    if (int rc = live_ens_launch(h, s); rc != RTS_OK) return rc;
-    if (int rc = live_accomp_launch(h, g.feed_no, s); rc != RTS_OK) return rc;
+    if (int rc = live_publishers_launch(h, g.feed_no, s); rc != RTS_OK) return rc;
     hipLaunchKernelGGL(live_compact_kernel, dim3(B), dim3(1024), 0, s, g);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -492,14 +469,13 @@ static void live_commit(rts_live *h, const FeedPlan &p, int k) {
     h->last_stride = p.n_max;
 }
 
-// rts_live_poll / rts_live_confidence: `read(b)` under stream b's sequence word.  Returns the feeds whose results the
+// Every reader: `read(b)` under stream b's sequence word.  Returns the feeds whose results the
 // words read reflect for every stream.
 template <class Read>
 static int live_read_published(const rts_live *h, Read read) {
-    const volatile int32_t *p = h->pub_host;
     int fd = h->feeds;
     for (int b = 0; b < h->geo.B; b++) {
-        const int seq = p[(size_t)b * kLiveWords + 3];
+        const int seq = live_word<kPubStatus, kStatusFeed>(h, b);
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
         read(b);
         if (seq < fd) fd = seq;
@@ -534,12 +510,8 @@ int rts_live_destroy(rts_live *h) {
                    h->gate.passed, h->gate.ord, h->ann_tables};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    if (h->pub_host) (void)hipHostFree(h->pub_host);
-    if (h->conf_host) (void)hipHostFree(h->conf_host);
-    if (h->gate_host) (void)hipHostFree(h->gate_host);
-    if (h->ann_host) (void)hipHostFree(h->ann_host);
-    if (h->tempo_host) (void)hipHostFree(h->tempo_host);
-    if (h->ens_host) (void)hipHostFree(h->ens_host);
+    for (unsigned char *p : h->pub_host)
+        if (p) (void)hipHostFree(p);
     accomp_destroy(h->acc);
     free(h);  // the mirrors with it
     return RTS_OK;
@@ -628,14 +600,14 @@ static int live_create(rts_chroma *plan, rts_otw *otw, rts_wtw *wtw, int B, int 
         e = live_dev_zeroed(e, &h->rs_tail, 2 * nB * rs_T);
         e = live_dev_zeroed(e, &h->rs_tot, 4 * nB);
     }
-    if (e == hipSuccess)
-        e = hipHostMalloc((void **)&h->pub_host, sizeof(int32_t) * kLiveWords * nB, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&h->args.pub, h->pub_host, 0);
     if (e != hipSuccess) {
         rts_live_destroy(h);
         return set_error(RTS_ERR_HIP, "rts_live_create: %s", hipGetErrorString(e));
     }
-    memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * nB);
+    if (int rc = live_pub_alloc(h, kPubStatus, "rts_live_create"); rc != RTS_OK) {
+        rts_live_destroy(h);
+        return rc;
+    }
     int32_t *st = nullptr;
     const int rc = otw ? rts_otw_device_views(otw, nullptr, nullptr, &st) : rts_wtw_state_view(wtw, &st);
     h->args.state = st;
@@ -682,21 +654,17 @@ int rts_live_reset(rts_live *h, void *stream) {
         RTS_HIP(hipMemsetAsync(h->rs_tail, 0, sizeof(float) * 2 * nB * h->rs_T, (hipStream_t)stream));
         RTS_HIP(hipMemsetAsync(h->rs_tot, 0, sizeof(long long) * 4 * nB, (hipStream_t)stream));
     }
-    if (h->gate_host) {  // every stream closed and at ordinal 0 again; the setting stays
+    if (h->gate.q) {  // every stream closed and at ordinal 0 again; the setting stays
         RTS_HIP(hipMemsetD32Async((hipDeviceptr_t)h->gate.q, kGateClosed, nB, (hipStream_t)stream));
         for (int32_t *w : {h->gate.prev, h->gate.seen, h->gate.passed})
             RTS_HIP(hipMemsetAsync(w, 0, sizeof(int32_t) * nB, (hipStream_t)stream));
     }
     memset(h + 1, 0, kMirrorBytes * nB);
-    memset(h->pub_host, 0, sizeof(int32_t) * kLiveWords * nB);
-    if (h->conf_host) live_conf_clear(h);
-    if (h->gate_host) live_gate_clear(h);
-    if (h->ann_host) live_annot_clear(h);
-    if (h->tempo_host) live_tempo_clear(h);
+    for (int k = 0; k < kPubBlocks; k++)  // every block that exists: every word empty, the group words too
+        if (h->pub_host[k]) pub_clear_all((PubBlock)k, h->pub_host[k], h->geo.B);
     if (h->ens) {
         if (int rc = rts_ensemble_reset(h->ens, nullptr, stream); rc != RTS_OK) return rc;
     }
-    if (h->ens_host) live_ens_clear(h);
     if (h->acc) {  // every stream disarmed; on / off stays
         if (int rc = accomp_reset(h->acc, (hipStream_t)stream); rc != RTS_OK) return rc;
     }
@@ -801,12 +769,11 @@ int rts_live_feed(rts_live *h, const void *samples_host, int sample_kind, const 
 int rts_live_poll(rts_live *h, int32_t *status, int32_t *positions, int *feeds_done, int *feeds_submitted) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    const volatile int32_t *p = h->pub_host;
     const int fd = live_read_published(h, [=](int b) {
-        if (status) status[b] = p[(size_t)b * kLiveWords + 0];
+        if (status) status[b] = live_word<kPubStatus, kStatusStatus>(h, b);
         if (positions) {
-            positions[2 * b] = p[(size_t)b * kLiveWords + 1];
-            positions[2 * b + 1] = p[(size_t)b * kLiveWords + 2];
+            positions[2 * b] = live_word<kPubStatus, kStatusLive>(h, b);
+            positions[2 * b + 1] = live_word<kPubStatus, kStatusRef>(h, b);
         }
     });
     if (feeds_done) *feeds_done = fd;
@@ -821,19 +788,8 @@ int rts_live_watch(rts_live *h, int K) {
     if (!h->otw)
         return set_error(RTS_ERR_UNSUPPORTED, "rts_live_watch on a WTW tracker: there is no WTW path cost (its cosine cost is NaN "
                                               "on silent frames and its windows re-decide the path)");
-    if (K > 0 && !h->conf_host) {
-        if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
-        const size_t bytes = (sizeof(double) + sizeof(int32_t)) * (size_t)h->geo.B;
-        RTS_HIP(hipHostMalloc((void **)&h->conf_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-        void *dev = nullptr;
-        if (hipError_t e = hipHostGetDevicePointer(&dev, h->conf_host, 0); e != hipSuccess) {
-            (void)hipHostFree(h->conf_host);
-            h->conf_host = nullptr;
-            return set_error(RTS_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
-        }
-        h->args.conf_mean = reinterpret_cast<double *>(dev);
-        h->args.conf_n = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(dev) + sizeof(double) * (size_t)h->geo.B);
-        live_conf_clear(h);
+    if (K > 0) {
+        if (int rc = live_pub_alloc(h, kPubConf, "rts_live_watch"); rc != RTS_OK) return rc;
     }
     h->watch_k = K;
     return RTS_OK;
@@ -842,12 +798,10 @@ int rts_live_watch(rts_live *h, int K) {
 int rts_live_confidence(rts_live *h, double *mean_cost, int32_t *n_points, int *feeds_done) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (!h->conf_host) return set_error(RTS_ERR_INVALID, "rts_live_confidence before any rts_live_watch(K > 0)");
-    const volatile double *mean = reinterpret_cast<const volatile double *>(h->conf_host);
-    const volatile int32_t *n = reinterpret_cast<const volatile int32_t *>(h->conf_host + sizeof(double) * (size_t)h->geo.B);
+    if (!h->pub_host[kPubConf]) return set_error(RTS_ERR_INVALID, "rts_live_confidence before any rts_live_watch(K > 0)");
     const int fd = live_read_published(h, [=](int b) {
-        if (mean_cost) mean_cost[b] = mean[b];
-        if (n_points) n_points[b] = n[b];
+        if (mean_cost) mean_cost[b] = live_word<kPubConf, kConfMean>(h, b);
+        if (n_points) n_points[b] = live_word<kPubConf, kConfN>(h, b);
     });
     if (feeds_done) *feeds_done = fd;
     return RTS_OK;
@@ -873,46 +827,19 @@ int rts_live_annotate(rts_live *h, rts_annot *annot, const uint8_t *mask_host, c
             return set_error(RTS_ERR_INVALID, "stream %d: piece %d outside [0, %d)", b, piece_host[b], P);
         if (frame0_host && frame0_host[b] < 0) return set_error(RTS_ERR_INVALID, "stream %d: negative frame0 %d", b, frame0_host[b]);
     }
-    if (!h->ann_host) {
+    if (!h->ann_tables) {
         const size_t nB = (size_t)B;
         int32_t *tables = nullptr;
-        unsigned char *host = nullptr;
-        void *dev = nullptr;
         hipError_t e = hipMalloc((void **)&tables, sizeof(int32_t) * 2 * nB);
         if (e == hipSuccess) e = hipMemset(tables, 0xff, sizeof(int32_t) * nB);  // no piece
         if (e == hipSuccess) e = hipMemset(tables + nB, 0, sizeof(int32_t) * nB);
-        if (e == hipSuccess)
-            e = hipHostMalloc((void **)&host, (sizeof(double) + 2 * sizeof(int32_t)) * nB, hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) e = hipHostGetDevicePointer(&dev, host, 0);
-        if (e != hipSuccess) {
-            if (tables) (void)hipFree(tables);
-            if (host) (void)hipHostFree(host);
-            return set_error(RTS_ERR_HIP, "rts_live_annotate: %s", hipGetErrorString(e));
+        if (int rc = e == hipSuccess ? live_pub_alloc(h, kPubBeats, "rts_live_annotate")
+                                     : set_error(RTS_ERR_HIP, "rts_live_annotate: %s", hipGetErrorString(e));
+            rc != RTS_OK) {
+            if (tables) (void)hipFree(tables);  // nothing is left behind
+            return rc;
         }
-        AnnotLive a = {};
-        a.state = h->args.state;
-        a.state_len = h->args.state_len;
-        a.st_n_path = h->otw ? RTS_ST_N_PATH : RTS_WTW_ST_N_PATH;
-        if (h->otw) {
-            int32_t *path = nullptr;
-            (void)rts_otw_device_views(h->otw, &path, &a.path_cap, nullptr);
-            a.path = path;
-        } else {
-            wtw_path_view(h->wtw, &a.path, &a.path_cap);
-        }
-        a.piece = tables;
-        a.frame0 = tables + nB;
-        a.beat = reinterpret_cast<double *>(dev);
-        a.label = reinterpret_cast<int32_t *>(a.beat + nB);
-        a.ref_frame = a.label + nB;
-        a.B = B;
-        h->ann = a;
         h->ann_tables = tables;
-        h->ann_host = host;
-        h->args.ann_beat = a.beat;
-        h->args.ann_label = a.label;
-        h->args.ann_ref = a.ref_frame;
-        live_annot_clear(h);
     }
     if (int rc = annot_select_enqueue(B, mask_host, piece_host, frame0_host, h->ann_tables, h->ann_tables + B, (hipStream_t)stream);
         rc != RTS_OK)
@@ -924,14 +851,11 @@ int rts_live_annotate(rts_live *h, rts_annot *annot, const uint8_t *mask_host, c
 int rts_live_beats(rts_live *h, double *beat, int32_t *label, int32_t *ref_frame, int *feeds_done) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (!h->ann_host) return set_error(RTS_ERR_INVALID, "rts_live_beats before any rts_live_annotate with tables");
-    const volatile double *bt = reinterpret_cast<const volatile double *>(h->ann_host);
-    const volatile int32_t *w = reinterpret_cast<const volatile int32_t *>(h->ann_host + sizeof(double) * (size_t)h->geo.B);
-    const int B = h->geo.B;
+    if (!h->pub_host[kPubBeats]) return set_error(RTS_ERR_INVALID, "rts_live_beats before any rts_live_annotate with tables");
     const int fd = live_read_published(h, [=](int b) {
-        if (beat) beat[b] = bt[b];
-        if (label) label[b] = w[b];
-        if (ref_frame) ref_frame[b] = w[B + b];
+        if (beat) beat[b] = live_word<kPubBeats, kBeatsBeat>(h, b);
+        if (label) label[b] = live_word<kPubBeats, kBeatsLabel>(h, b);
+        if (ref_frame) ref_frame[b] = live_word<kPubBeats, kBeatsRef>(h, b);
     });
     if (feeds_done) *feeds_done = fd;
     return RTS_OK;
@@ -944,31 +868,10 @@ int rts_live_follow_tempo(rts_live *h, int K, double ahead) {
         h->tempo_k = 0;
         return RTS_OK;
     }
-    TempoTail t = {};
-    const int N_max = h->otw ? otw_tempo_view(h->otw, &t) : wtw_tempo_view(h->wtw, &t);
-    if (int rc = tempo_tail_check(K, ahead, N_max); rc != RTS_OK) return rc;
-    if (!h->tempo_host) {
-        if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
-        const size_t nB = (size_t)h->geo.B;
-        RTS_HIP(hipHostMalloc((void **)&h->tempo_host, (3 * sizeof(double) + sizeof(int32_t)) * nB,
-                              hipHostMallocMapped | hipHostMallocCoherent));
-        void *dev = nullptr;
-        if (hipError_t e = hipHostGetDevicePointer(&dev, h->tempo_host, 0); e != hipSuccess) {
-            (void)hipHostFree(h->tempo_host);
-            h->tempo_host = nullptr;
-            return set_error(RTS_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
-        }
-        h->args.tempo_words = reinterpret_cast<double *>(dev);
-        h->args.tempo_n = reinterpret_cast<int32_t *>(h->args.tempo_words + 3 * nB);
-        live_tempo_clear(h);
-    }
-    t.slope = h->args.tempo_words;
-    t.pos = t.slope + h->geo.B;
-    t.bpm = t.pos + h->geo.B;
-    t.n_out = h->args.tempo_n;
-    t.K = K;
-    t.ahead = ahead;
-    h->tempo = t;
+    TempoTail view;
+    if (int rc = tempo_tail_check(K, ahead, live_tracker_view(h, &view)); rc != RTS_OK) return rc;
+    if (int rc = live_pub_alloc(h, kPubTempo, "rts_live_follow_tempo"); rc != RTS_OK) return rc;
+    h->tempo_ahead = ahead;
     h->tempo_k = K;
     return RTS_OK;
 }
@@ -976,15 +879,12 @@ int rts_live_follow_tempo(rts_live *h, int K, double ahead) {
 int rts_live_tempo(rts_live *h, double *slope, double *pos, double *bpm, int32_t *n, int *feeds_done) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (!h->tempo_host) return set_error(RTS_ERR_INVALID, "rts_live_tempo before any rts_live_follow_tempo(K > 0)");
-    const int B = h->geo.B;
-    const volatile double *w = reinterpret_cast<const volatile double *>(h->tempo_host);
-    const volatile int32_t *cnt = reinterpret_cast<const volatile int32_t *>(h->tempo_host + 3 * sizeof(double) * (size_t)B);
+    if (!h->pub_host[kPubTempo]) return set_error(RTS_ERR_INVALID, "rts_live_tempo before any rts_live_follow_tempo(K > 0)");
     const int fd = live_read_published(h, [=](int b) {
-        if (slope) slope[b] = w[b];
-        if (pos) pos[b] = w[B + b];
-        if (bpm) bpm[b] = w[2 * B + b];
-        if (n) n[b] = cnt[b];
+        if (slope) slope[b] = live_word<kPubTempo, kTempoSlope>(h, b);
+        if (pos) pos[b] = live_word<kPubTempo, kTempoPos>(h, b);
+        if (bpm) bpm[b] = live_word<kPubTempo, kTempoBpm>(h, b);
+        if (n) n[b] = live_word<kPubTempo, kTempoN>(h, b);
     });
     if (feeds_done) *feeds_done = fd;
     return RTS_OK;
@@ -998,7 +898,7 @@ int rts_live_follow_consensus(rts_live *h, rts_ensemble *e) {
         h->args.ens_state = nullptr;
         return RTS_OK;
     }
-    if (!h->ann_host)
+    if (!h->ann_tables)
         return set_error(RTS_ERR_INVALID, "rts_live_follow_consensus before any rts_live_annotate with tables: the member beat "
                                           "needs every stream's piece and frame0");
     if (ensemble_batch(e) != h->geo.B)
@@ -1007,25 +907,7 @@ int rts_live_follow_consensus(rts_live *h, rts_ensemble *e) {
     if (ensemble_device(e) != h->device)
         return set_error(RTS_ERR_INVALID, "the ensemble e lives on device %d, the handle on device %d", ensemble_device(e),
                          h->device);
-    if (!h->ens_host) {
-        if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
-        const size_t nB = (size_t)h->geo.B;
-        RTS_HIP(hipHostMalloc((void **)&h->ens_host, (3 * sizeof(double) + 4 * sizeof(int32_t)) * nB,
-                              hipHostMallocMapped | hipHostMallocCoherent));
-        void *dev = nullptr;
-        if (hipError_t er = hipHostGetDevicePointer(&dev, h->ens_host, 0); er != hipSuccess) {
-            (void)hipHostFree(h->ens_host);
-            h->ens_host = nullptr;
-            return set_error(RTS_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(er));
-        }
-        double *w = reinterpret_cast<double *>(dev);
-        int32_t *n = reinterpret_cast<int32_t *>(w + 3 * nB);
-        const EnsembleOut o = {w, w + nB, n, n + nB, w + 2 * nB, n + 2 * nB, n + 3 * nB};
-        h->ens_out = o;
-        h->args.ens_dev = o.dev;
-        h->args.ens_member = o.strikes;
-        live_ens_clear(h);
-    }
+    if (int rc = live_pub_alloc(h, kPubEns, "rts_live_follow_consensus"); rc != RTS_OK) return rc;
     h->ens = e;
     h->ens_groups = ensemble_groups(e);
     h->args.ens_state = ensemble_state(e);
@@ -1036,20 +918,19 @@ int rts_live_consensus(rts_live *h, double *consensus, double *spread, int32_t *
                        int32_t *strikes, int32_t *out, int *feeds_done) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (!h->ens_host) return set_error(RTS_ERR_INVALID, "rts_live_consensus before any rts_live_follow_consensus with an ensemble");
-    const int B = h->geo.B, G = h->ens_groups;
-    const volatile double *w = reinterpret_cast<const volatile double *>(h->ens_host);
-    const volatile int32_t *n = reinterpret_cast<const volatile int32_t *>(h->ens_host + 3 * sizeof(double) * (size_t)B);
+    if (!h->pub_host[kPubEns])
+        return set_error(RTS_ERR_INVALID, "rts_live_consensus before any rts_live_follow_consensus with an ensemble");
+    const int G = h->ens_groups;
     const int fd = live_read_published(h, [=](int b) {
         if (b < G) {  // the group words ride under the sequence words of the first G streams: every stream's is written last
-            if (consensus) consensus[b] = w[b];
-            if (spread) spread[b] = w[B + b];
-            if (n_in) n_in[b] = n[b];
-            if (n_valid) n_valid[b] = n[B + b];
+            if (consensus) consensus[b] = live_word<kPubEns, kEnsConsensus>(h, b);
+            if (spread) spread[b] = live_word<kPubEns, kEnsSpread>(h, b);
+            if (n_in) n_in[b] = live_word<kPubEns, kEnsNIn>(h, b);
+            if (n_valid) n_valid[b] = live_word<kPubEns, kEnsNValid>(h, b);
         }
-        if (dev) dev[b] = w[2 * B + b];
-        if (strikes) strikes[b] = n[2 * B + b];
-        if (out) out[b] = n[3 * B + b];
+        if (dev) dev[b] = live_word<kPubEns, kEnsDev>(h, b);
+        if (strikes) strikes[b] = live_word<kPubEns, kEnsStrikes>(h, b);
+        if (out) out[b] = live_word<kPubEns, kEnsOut>(h, b);
     });
     if (feeds_done) *feeds_done = fd;
     return RTS_OK;
@@ -1066,13 +947,11 @@ int rts_live_gate(rts_live *h, double min_level, int hold) {
     if (h->feeds != 0)
         return set_error(RTS_ERR_INVALID, "rts_live_gate after %d feeds: the gate is set before the first feed after create or "
                                           "rts_live_reset, so that every ordinal counts from a closed stream", h->feeds);
-    if (min_level > 0.0 && !h->gate_host) {
+    if (min_level > 0.0 && !h->gate.q) {
         if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
         const size_t nB = (size_t)h->geo.B;
         GateArgs t = {};
         t.ord_len = h->otw ? otw_history(h->otw) : wtw_history(h->wtw);
-        unsigned char *host = nullptr;
-        void *dev = nullptr;
         hipError_t e = hipMalloc((void **)&t.lev, sizeof(double) * nB * h->cols_cap);
         if (e == hipSuccess) e = hipMalloc((void **)&t.gcols, sizeof(double) * kLiveF * nB * h->cols_cap);
         e = live_dev_zeroed(e, &t.n_gated, nB);
@@ -1082,22 +961,17 @@ int rts_live_gate(rts_live *h, double min_level, int hold) {
         e = live_dev_zeroed(e, &t.seen, nB);
         e = live_dev_zeroed(e, &t.passed, nB);
         e = live_dev_zeroed(e, &t.ord, nB * (size_t)t.ord_len);
-        if (e == hipSuccess)
-            e = hipHostMalloc((void **)&host, (sizeof(double) + sizeof(int32_t) * kGateWords) * nB,
-                              hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) e = hipHostGetDevicePointer(&dev, host, 0);
-        if (e != hipSuccess) {
+        if (int rc = e == hipSuccess ? live_pub_alloc(h, kPubGate, "rts_live_gate")
+                                     : set_error(RTS_ERR_HIP, "rts_live_gate: %s", hipGetErrorString(e));
+            rc != RTS_OK) {
             for (void *p : {(void *)t.lev, (void *)t.gcols, (void *)t.n_gated, (void *)t.q, (void *)t.prev, (void *)t.seen,
                             (void *)t.passed, (void *)t.ord})
-                if (p) (void)hipFree(p);
-            if (host) (void)hipHostFree(host);
-            return set_error(RTS_ERR_HIP, "rts_live_gate: %s", hipGetErrorString(e));
+                if (p) (void)hipFree(p);  // nothing is left behind
+            return rc;
         }
-        t.pub_level = reinterpret_cast<double *>(dev);
-        t.pub_words = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(dev) + sizeof(double) * nB);
+        t.pub_level = pub_ptr<kPubGate, kGateLevel>(h->args.pubs.dev[kPubGate], h->geo.B);
+        t.pub_words = pub_ptr<kPubGate, kGateOpen>(h->args.pubs.dev[kPubGate], h->geo.B);  // open, seen, passed interleaved
         h->gate = t;
-        h->gate_host = host;
-        live_gate_clear(h);
     }
     h->gate.min_level = min_level;
     h->gate.hold = hold;
@@ -1109,14 +983,12 @@ int rts_live_gate(rts_live *h, double min_level, int hold) {
 int rts_live_levels(rts_live *h, double *level, int32_t *open, int32_t *seen, int32_t *passed, int *feeds_done) {
     using namespace rts;
     if (!h) return set_error(RTS_ERR_INVALID, "handle is NULL");
-    if (!h->gate_host) return set_error(RTS_ERR_INVALID, "rts_live_levels before any rts_live_gate(min_level > 0)");
-    const volatile double *lv = reinterpret_cast<const volatile double *>(h->gate_host);
-    const volatile int32_t *w = reinterpret_cast<const volatile int32_t *>(h->gate_host + sizeof(double) * (size_t)h->geo.B);
+    if (!h->gate.q) return set_error(RTS_ERR_INVALID, "rts_live_levels before any rts_live_gate(min_level > 0)");
     const int fd = live_read_published(h, [=](int b) {
-        if (level) level[b] = lv[b];
-        if (open) open[b] = w[(size_t)b * kGateWords + 0];
-        if (seen) seen[b] = w[(size_t)b * kGateWords + 1];
-        if (passed) passed[b] = w[(size_t)b * kGateWords + 2];
+        if (level) level[b] = live_word<kPubGate, kGateLevel>(h, b);
+        if (open) open[b] = live_word<kPubGate, kGateOpen>(h, b);
+        if (seen) seen[b] = live_word<kPubGate, kGateSeen>(h, b);
+        if (passed) passed[b] = live_word<kPubGate, kGatePassed>(h, b);
     });
     if (feeds_done) *feeds_done = fd;
     return RTS_OK;
@@ -1125,7 +997,7 @@ int rts_live_levels(rts_live *h, double *level, int32_t *open, int32_t *seen, in
 int rts_live_gate_columns(rts_live *h, int b, int32_t *ordinals_host, int cap, int *n, void *stream) {
     using namespace rts;
     if (!h || !n) return set_error(RTS_ERR_INVALID, "NULL argument");
-    if (!h->gate_host) return set_error(RTS_ERR_INVALID, "rts_live_gate_columns before any rts_live_gate(min_level > 0)");
+    if (!h->gate.q) return set_error(RTS_ERR_INVALID, "rts_live_gate_columns before any rts_live_gate(min_level > 0)");
     if (b < 0 || b >= h->geo.B) return set_error(RTS_ERR_INVALID, "stream %d out of range [0, %d)", b, h->geo.B);
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -1183,9 +1055,8 @@ int rts_live_accompany(rts_live *h, rts_warp *warp_plan, const void *tracks_dev,
     if (h->geo.B > 65535) return set_error(RTS_ERR_INVALID, "B = %d: the renderer takes at most 65535 streams", h->geo.B);
     AccompGeom p;
     if (int rc = accomp_check(params, warp_plan, h->geo.hop, h->device, &p); rc != RTS_OK) return rc;
-    TempoTail view = {};
-    const int N_max = h->otw ? otw_tempo_view(h->otw, &view) : wtw_tempo_view(h->wtw, &view);
-    if (int rc = tempo_tail_check(p.K, 0.0, N_max); rc != RTS_OK) return rc;
+    TempoTail view;
+    if (int rc = tempo_tail_check(p.K, 0.0, live_tracker_view(h, &view)); rc != RTS_OK) return rc;
     if (int rc = accomp_tracks_check(h->geo.B, mask_host, first_host, len_host, origin_host); rc != RTS_OK) return rc;
     if (int rc = check_device(h->device, "handle"); rc != RTS_OK) return rc;
     if (h->acc && !accomp_same(h->acc, p, warp_plan, tracks_dev, track_dtype)) {

@@ -19,7 +19,6 @@ namespace rts {
 
 constexpr int kGateMaxHold = 65535;
 constexpr int kGateClosed = kGateMaxHold + 1;
-constexpr int kGateWords = 3;     // per stream in the mapped meter block behind level[B]: open, seen, passed
 constexpr int kGateBlock = 1024;  // columns decided, then copied, between two barriers of live_gate_kernel
 
 struct GateArgs {
@@ -31,8 +30,8 @@ struct GateArgs {
     int32_t *q, *prev, *seen, *passed;  // [B]
     int32_t *ord;        // [B][ord_len] ordinal (among the stream's chroma columns) of every column handed on
     int ord_len;         // the bound tracker's history length
-    double *pub_level;   // host-mapped [B]
-    int32_t *pub_words;  // host-mapped [B][kGateWords]
+    double *pub_level;   // host-mapped [B]                (the gate block of csrc/live_pub.h: plane kGateLevel and,
+    int32_t *pub_words;  // host-mapped [B][kGateWords]     interleaved from kGateOpen on, the three meter words)
 };
 
 // grid (n_max, B), one workgroup per column.  level = (sum_i (double)x[i] * (double)x[i]) / L over the L = fft_len
@@ -155,15 +154,13 @@ __global__ void __launch_bounds__(256) live_gate_kernel(LiveArgs g, GateArgs t) 
     }
 }
 
-// live_restart_kernel's share: the stream is closed again and has seen nothing.
+// live_restart_kernel's share: the stream is closed again and has seen nothing.  (Its meter words are emptied with every
+// other block's, through the table of csrc/live_pub.h.)
 __device__ __forceinline__ void live_gate_restart(const GateArgs &t, int b) {
     t.q[b] = kGateClosed;
     t.prev[b] = 0;
     t.seen[b] = 0;
     t.passed[b] = 0;
-    volatile int32_t *w = t.pub_words + (size_t)b * kGateWords;
-    *(volatile double *)(t.pub_level + b) = __longlong_as_double(0x7ff8000000000000LL);
-    w[0] = w[1] = w[2] = 0;
 }
 
 }  // namespace rts

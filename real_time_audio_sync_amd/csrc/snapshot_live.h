@@ -51,10 +51,10 @@ __global__ void __launch_bounds__(kLiveSnapThreads) live_export_kernel(snap::Sna
 // The same grid the other way round, behind the tracker's import on the same stream.  The count is clamped to the
 // buffer (the host has held the mirror words against max_pending before anything was enqueued).  Thread 0 of slice 0
 // stores the count and the carry flag and publishes like live_restart_kernel: status and position words from the
-// imported tracker state, confidence, beat and tempo words empty until the next feed, consensus strikes 0, the feed
-// number untouched.
-__global__ void __launch_bounds__(kLiveSnapThreads) live_import_kernel(snap::SnapSel sel, LiveArgs g, const unsigned char *blob,
-                                                                       long long rec_stride) {
+// imported tracker state, the per-stream words of `blocks` (bit k: PubBlock k of csrc/live_pub.h) empty until the next
+// feed, the bound ensemble's strikes 0, the feed number untouched.
+__global__ void __launch_bounds__(kLiveSnapThreads) live_import_kernel(snap::SnapSel sel, LiveArgs g, unsigned blocks,
+                                                                       const unsigned char *blob, long long rec_stride) {
     if ((int)blockIdx.y >= sel.n) return;
     const int b = sel.idx[blockIdx.y];
     const long long tail = snap::live_tail_bytes(g.cap), off_carry = tail - snap::kLiveCarryBytes;
@@ -81,32 +81,11 @@ __global__ void __launch_bounds__(kLiveSnapThreads) live_import_kernel(snap::Sna
         }
     }
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
     g.pending[b] = p;
     if (g.has_carry) g.has_carry[b] = has;
-    const int32_t *st = g.state + (size_t)b * g.state_len;
-    volatile int32_t *w = g.pub + (size_t)b * kLiveWords;
-    w[0] = st[g.st_status];
-    w[1] = st[g.st_live];
-    w[2] = st[g.st_ref];
-    if (g.conf_n) {
-        g.conf_n[b] = 0;
-        g.conf_mean[b] = qnan;
-    }
-    if (g.ann_beat) {
-        g.ann_beat[b] = qnan;
-        g.ann_label[b] = -1;
-        g.ann_ref[b] = -1;
-    }
-    if (g.tempo_words) {
-        for (int q = 0; q < 3; q++) g.tempo_words[(size_t)q * g.B + b] = qnan;
-        g.tempo_n[b] = 0;
-    }
+    live_publish_status(g, b);
     if (g.ens_state) g.ens_state[b] = g.ens_state[g.B + b] = 0;
-    if (g.ens_dev) {
-        g.ens_dev[b] = qnan;
-        g.ens_member[b] = g.ens_member[g.B + b] = 0;
-    }
+    live_clear_published(g.pubs, blocks, g.B, b);
     __threadfence_system();
 }
 
@@ -230,10 +209,13 @@ int rts_live_import(rts_live *h, const int32_t *slot_host, int n, const void *bl
                 return set_error(RTS_ERR_INVALID, "stream %d refused record %d (status %d): nothing was changed", slot_host[i], i, status[(size_t)i]);
     }
     const long long tail = snap::live_tail_bytes(h->geo.cap);
+    // What a restart empties, but not the gate block: an import is refused while the gate is on (live_snap_usable), and a
+    // gate that is off keeps its meter words with its queue and counters, which a record does not carry either.
+    const unsigned blocks = kPubRestartBlocks & ~(1u << kPubGate);
     snap::SnapSel sel;
     for (int pos = 0; snap::sel_next_chunk(n, slot_host, nullptr, nullptr, &pos, &sel) > 0;) {
         hipLaunchKernelGGL(live_import_kernel, dim3(live_snap_slices(tail), sel.n), dim3(kLiveSnapThreads), 0, (hipStream_t)stream, sel,
-                           h->args, static_cast<const unsigned char *>(blob_dev), rec_stride);
+                           h->args, blocks, static_cast<const unsigned char *>(blob_dev), rec_stride);
         if (hipGetLastError() != hipSuccess) {
             h->failed = 1;  // the tracker took the records, the session did not: the mirror no longer describes the device
             return set_error(RTS_ERR_HIP, "launch of live_import_kernel failed");

@@ -920,10 +920,6 @@ int wtw_tempo_view(const rts_wtw *h, TempoTail *t) {
     t->B = h->B;
     return h->args.M;
 }
-void wtw_path_view(const rts_wtw *h, const int32_t **path, int *path_cap) {
-    *path = h->args.path;
-    *path_cap = h->args.path_cap;
-}
 
 }  // namespace rts
 

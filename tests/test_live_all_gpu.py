@@ -364,3 +364,73 @@ def test_enable_order_does_not_matter():
         a.close()
         b.close()
         tab.close()
+
+
+def test_restart_across_launch_chunks_clears_every_block():
+    """A restart of 129 of 130 streams -- the selection reaches the device in launches of 128 and 1 (kRestartChunk) -- with
+    every publisher on: the restarted streams' words in every block are the empty values of csrc/live_pub.h bit for bit and
+    their status words a fresh tracker's, stream 64 and the consensus group words keep their bytes, feeds_done stays, and
+    the next feed fills the words again."""
+    from real_time_audio_sync_amd.annotate import AnnotationTables
+    from real_time_audio_sync_amd.live import LiveSession
+    B, KEPT = 130, 64
+    case = lam.Case()
+    case.kind, case.variant, case.euclid = "otw", "otw", False
+    ref = lam.reference(300, 0, False)
+    groups = [lam.GROUPS[b % len(lam.GROUPS)] for b in range(B)]
+    counts = (1500, 900, 1500)                                   # 8, 7 and (a fresh stream) 8 chroma columns
+    sounds = [lam.music(sum(counts), lam.RATE, 500 + s) for s in range(len(lam.GROUPS))]
+    audio = [sounds[b % len(sounds)] for b in range(B)]
+    tab = AnnotationTables(lam.synth_tables(1, 1.0, 17), frame_seconds=lam.FRAME_SECONDS, device=DEV)
+    sess = LiveSession([ref] * B, batch=B, c=lam.C, max_run_count=lam.MRC, variant="otw", fft_len=lam.L, hop_size=lam.HOP,
+                       fs=lam.RATE, max_pending=1 << 14, device=DEV)
+    try:
+        sess.gate(lam.MIN_DB, lam.HOLD)
+        sess.watch(lam.K_WATCH)
+        sess.annotate(tab, piece_of=[(ref, 0)])
+        sess.follow_tempo(lam.K_TEMPO, lam.AHEAD)
+        sess.follow_consensus(groups, lam.MAX_DEV, lam.PATIENCE)
+        at = 0
+        for n in counts[:2]:
+            sess.feed([x[at:at + n] for x in audio])
+            at += n
+        sess.sync()
+        before, done = read(sess, ALL)
+        assert set(done.values()) == {2}, done
+        # there is something to clear in every block, for every stream
+        assert (before["confidence"]["n"] > 0).all() and (before["tempo"]["n"] > 0).all() and (before["levels"]["seen"] > 0).all()
+        assert (before["beats"]["ref_frame"] >= 0).all() and (before["poll"]["positions"][:, 0] > 0).all()
+        assert np.isfinite(before["consensus"]["dev"]).any()
+        assert np.isfinite(before["consensus"]["consensus"]).all() and (before["consensus"]["n_in"] > 0).all()
+
+        gone = [b for b in range(B) if b != KEPT]
+        sess.restart(gone)
+        sess.sync()
+        got, done = read(sess, ALL)
+        assert set(done.values()) == {2}, done                   # feeds_done does not move
+        qnan = np.array([0x7FF8000000000000], dtype=np.uint64).view(np.float64)[0]
+        empty = dict(confidence=dict(mean=qnan, n=0), beats=dict(beat=qnan, label=-1, ref_frame=-1),
+                     tempo=dict(slope=qnan, pos=qnan, bpm=qnan, n=0), consensus=dict(dev=qnan, strikes=0, out=0),
+                     levels=dict(level=qnan, open=0, seen=0, passed=0))
+        for reader, words in empty.items():
+            for key, value in words.items():
+                v = np.asarray(got[reader][key])
+                assert same_bytes(v[gone], np.full(len(gone), value, dtype=v.dtype)), (reader, key, v[gone])
+        status, t, j = lam.Tracker(case, ref).position()         # a fresh tracker's
+        assert same_bytes(got["poll"]["status"][gone], np.full(len(gone), status, dtype=np.int32))
+        assert same_bytes(got["poll"]["positions"][gone], np.tile(np.array([t, j], dtype=np.int32), (len(gone), 1)))
+        group_words = ("consensus", "spread", "n_in", "n_valid")
+        for reader in got:
+            for key, v in got[reader].items():
+                keep = slice(None) if reader == "consensus" and key in group_words else [KEPT]
+                assert same_bytes(np.asarray(v)[keep], np.asarray(before[reader][key])[keep]), (reader, key)
+
+        sess.feed([x[at:at + counts[2]] for x in audio])
+        sess.sync()
+        got, done = read(sess, ALL)
+        assert set(done.values()) == {3}, done
+        assert (got["confidence"]["n"][gone] > 0).all() and (got["tempo"]["n"][gone] > 0).all()
+        assert (got["levels"]["seen"][gone] == 8).all() and got["levels"]["seen"][KEPT] == 8 + 7 + 12
+    finally:
+        sess.close()
+        tab.close()
