@@ -1522,6 +1522,64 @@ int rts_annot_transfer(rts_annot *h, const int32_t *path_dev /* [B][P_max][2] */
                        int rows_max, double *times_dev /* [B][rows_max] */, int32_t *n_rows_dev /* [B] */,
                        int32_t *status_dev /* [B] */, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Following a score: note lists to reference chroma.
+ * ------------------------------------------------------------------------------------------ */
+/* The reference follows recordings only; what a note list sounds like to the chroma chain is this project's definition, to
+ * the bit, like the resampler's and the renderer's.  tests/score_model.py holds it in plain numpy.
+ *
+ * A plan holds fft_len L (a power of two in [64, 8192], as a chroma plan), hop H in [1, 2^24], pad_left in [0, L] (L/2 for
+ * the reference's centred framing, chroma.py:44-65) and three host tables, copied at create:
+ *   T [128][12] float64   the chroma a steady tone of MIDI pitch p leaves
+ *   CW[L + 1]   float64   CW[0] = 0, CW[n] = CW[n-1] + w[n-1]^2: the window's cumulative energy, summed by the host
+ *   DK[K + 1]   float64   K in [0, 2^20]: the energy left k frames after the onset
+ * every entry finite and >= 0, CW[0] == 0 and CW not decreasing.
+ *
+ * Notes lie in one pool, piece by piece, each piece's notes in ascending onset order: onset and end (int64 samples, end
+ * exclusive), pitch (int32), energy (float64).  Piece p has notes [note_first[p], note_first[p] + note_len[p]) and writes
+ * frames [frame_first[p], frame_first[p] + n_frames[p]) of an output pool [n_pool_frames][12], the layout
+ * rts_otw_create_refs and rts_locate take.  Frame m of a piece, every float64 operation rounded on its own:
+ *   w0 = m H - pad_left
+ *   for every note n of the piece in ascending index, acc[0..11] starting at +0.0:
+ *       a = clamp(onset - w0, 0, L);  b = clamp(end - w0, 0, L);  if b <= a: the note takes no part
+ *       k = clamp(m - floor((onset + pad_left) / H), 0, K)
+ *       wgt = (energy * DK[k]) * (CW[b] - CW[a])
+ *       acc[c] = acc[c] + wgt * T[pitch][c]                        c = 0..11
+ *   s = sum of acc[c] * acc[c], c ascending, from +0.0;  len = sqrt(s)
+ *   if !normalize or len < 2.2250738585072014e-308: len = 1.0     (the rule of the chroma kernels)
+ *   out[c] = acc[c] / len                                          (float32 output: that value converted)
+ * in exact integers: no onset or end of 64 bits overflows a step of it.  A note takes no part in any frame when its pitch
+ * lies outside 0..127, onset < 0, end < onset, or its energy is negative or not finite; such notes are counted per piece
+ * in skipped_dev[p].  A piece without notes gives all-zero frames; a piece with n_frames < 1 writes nothing.
+ *
+ * Status of a piece, a sum of: */
+#define RTS_SCORE_OK 0
+#define RTS_SCORE_FRAMES 1 /* n_frames >= 1 and its frame range leaves the pool: nothing is written */
+#define RTS_SCORE_NOTES 2  /* its note range leaves [0, n_notes): nothing is written, no note is read, skipped is 0 */
+/* The result is a function of the notes and the tables alone, whatever order the notes have: the kernel leaves out notes
+ * that cannot reach a wave's frames by two per-piece tables that hold for any order (the largest end up to a note, the
+ * smallest onset from a note on), which a prepare kernel writes into the workspace, 24 bytes per note.  The note ranges of
+ * two pieces are either the same or disjoint.
+ *
+ * rts_score_chroma: asynchronous on `stream`, no allocation, no synchronisation (graph-capturable), two launches; writes
+ * the frames of the pieces, skipped_dev, status_dev and the workspace only, and no result depends on what they held.
+ *   RTS_ERR_UNSUPPORTED: fft_len no power of two in [64, 8192].
+ *   RTS_ERR_INVALID, naming the argument, before any GPU call: a NULL handle, table or pointer (the four note pointers
+ *   and the workspace may be NULL when n_notes == 0; skipped_dev and status_dev always), hop, pad_left or K outside their
+ *   limits, a table entry that breaks the rules above, n_notes outside [0, 2^31), P outside [1, 65535], n_pool_frames
+ *   outside [1, 2^31), out_dtype, a workspace below rts_score_workspace_bytes, another device current. */
+typedef struct rts_score rts_score;
+int rts_score_create(int fft_len, int hop, int pad_left, int K, const double *T_host /* [128][12] */,
+                     const double *CW_host /* [fft_len + 1] */, const double *DK_host /* [K + 1] */, rts_score **out);
+int rts_score_destroy(rts_score *h);
+int rts_score_workspace_bytes(long long n_notes, size_t *bytes);
+int rts_score_chroma(rts_score *h, const long long *onset_dev, const long long *end_dev, const int32_t *pitch_dev,
+                     const double *energy_dev, long long n_notes, const long long *note_first_dev /* [P] */,
+                     const int32_t *note_len_dev /* [P] */, const long long *frame_first_dev /* [P] */,
+                     const int32_t *n_frames_dev /* [P] */, int P, int normalize, void *out_dev /* [n_pool_frames][12] */,
+                     int out_dtype, long long n_pool_frames, int32_t *skipped_dev /* [P] or NULL */,
+                     int32_t *status_dev /* [P] or NULL */, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

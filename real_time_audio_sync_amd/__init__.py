@@ -26,4 +26,10 @@ def __getattr__(name):
     if name == "render":
         import importlib
         return importlib.import_module(".render", __name__)
+    if name == "score":
+        import importlib
+        return importlib.import_module(".score", __name__)
+    if name in ("Score", "ScorePlan"):
+        from . import score
+        return getattr(score, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

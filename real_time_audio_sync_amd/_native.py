@@ -234,6 +234,14 @@ PATHMAP_REASONS = ((PATHMAP_EMPTY, "no path point"), (PATHMAP_BACKWARD, "a colum
 _decl("rts_path_map", _i32, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp])
 _decl("rts_annot_transfer", _i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp])
 
+SCORE_OK, SCORE_FRAMES, SCORE_NOTES = 0, 1, 2  # RTS_SCORE_*
+SCORE_MAX_K = 1 << 20  # kScoreMaxK (csrc/score_plan.h)
+_decl("rts_score_create", _i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(_vp)])
+_decl("rts_score_destroy", _i32, [_vp])
+_decl("rts_score_workspace_bytes", _i32, [_i64, ctypes.POINTER(ctypes.c_size_t)])
+_decl("rts_score_chroma", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp,
+                                 ctypes.c_size_t, _vp])
+
 
 def check(rc):
     if rc != 0:
